@@ -11,6 +11,11 @@ A step is one frame: every rank renders its row slab from primitive arrays alrea
 a frame overlaps the render of the next one (two frames in flight).  Rank 0 prints ONE JSON line.
 ``value`` = frames/s of the whole job; tests/s = primitives x pixels x frames/s (algorithmic pairs, i.e.
 what the reference evaluates, whatever the kernel skips).  Total work is fixed as N grows -> "strong".
+
+A plain run does only what that line's headline needs: set-up, warm-up, the --steps timed frames, the line.  --full
+adds everything else the benchmark measures and checks (the bit-for-bit check of the timed frames, the CPU baseline,
+the half-frame schedule probe, the executed pair tests, the measured link rates).  --dump-outputs DIR writes the
+last timed frame's image and depth for output-for-output comparisons of two builds.
 """
 from __future__ import annotations
 
@@ -47,7 +52,7 @@ MIX_FILE = os.path.join(REPO, "profiles", "r03_valu_mix.json")      # tools/valu
 # (equal steady state, 2 % better over a 20-step region with the 105 us kernel, ratio 2.55).  With one-wave workgroups
 # and the typed 88 us kernel it is 30 % WORSE at config 5 (0.1068 against 0.0808 ms per frame, 400 steps; 0.1052 against
 # 0.0867 over 20 steps) -- and the probe sits at ratio 2.16-2.21, 4 % under the old threshold, so a slightly different
-# box would have flipped the default into it.  The probe is still taken and reported (config.schedule_probe);
+# box would have flipped the default into it.  The probe is still taken and reported with --full (config.schedule_probe);
 # --schedule stages remains for measurements.
 
 
@@ -127,11 +132,21 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: create the RCCL process group and use the multi-GPU frame collection even with "
                          "one rank (exercises the collective, stream and graph plumbing on a one-GPU box)")
-    ap.add_argument("--check", dest="check", action="store_true", default=True,
-                    help="(default) after the timed loop compare every output slot / collected frame on this rank, bit "
-                         "for bit, with a fresh eager render of the same rows and exit non-zero on a mismatch (stream / "
-                         "graph / collective ordering self-test; outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the benchmark measures and checks: the bit-for-bit "
+                         "check (--check), the CPU baseline, the half-frame schedule probe, the executed pair tests "
+                         "and, with several ranks, the measured link rates.  Off: only what the headline needs")
+    ap.add_argument("--check", dest="check", action="store_true", default=None,
+                    help="(default with --full) after the timed loop compare every output slot / collected frame on this "
+                         "rank, bit for bit, with a fresh eager render of the same rows and exit non-zero on a mismatch "
+                         "(stream / graph / collective ordering self-test; outside the timed region)")
     ap.add_argument("--no-check", dest="check", action="store_false")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed frame computed as DIR/image.npy (k, 3), "
+                         "DIR/depth.npy (k,) and DIR/hit.npy (k,: 1 hit, 0 nothing hit, where depth is then 0 instead "
+                         "of +inf), float32, at k pixels drawn with a fixed seed (at most 2^21, all of them for smaller "
+                         "frames), and their row-major pixel numbers as DIR/pixel_index.npy (float64); single-process "
+                         "runs")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="multi-GPU: when the default collection schedule fails its bit-for-bit check and the headline "
                          "falls back to the literal gather-to-rank-0 form, exit 0 anyway (the line still carries "
@@ -139,9 +154,12 @@ def parse():
     ap.add_argument("--warmup-ms", type=float, default=150.0,
                     help="after the --warmup steps keep submitting untimed frames until this much wall time has passed "
                          "since the first warm-up frame, so that a short run is timed at ramped clocks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--cpu-pixels", type=int, default=4096, help="pixels in the CPU-baseline sample (about 14 s of numpy)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.check is None:
+        args.check = args.full
+    return args
 
 
 def cpu_baseline(scene, prims, width, height, npix):
@@ -163,6 +181,29 @@ def cpu_baseline(scene, prims, width, height, npix):
             "host_cpus": os.cpu_count(),
             "sample": f"{npix} consecutive pixels around the middle of the image x {prims} discs ({tests:.3g} tests, "
                       f"{dt:.1f} s), oracle/np_oracle.py fp64, pixel tile 64; frames/s extrapolated"}
+
+
+DUMP_PIXELS = 1 << 21          # x (12 + 4 + 4 + 8) bytes: at most 59 MB of .npy files
+
+
+def dump_outputs(out_dir, slab, width, row0):
+    """--dump-outputs: what a caller of the timed path receives for one frame, the image (rows, W, 3) and depth (rows, W)
+    views of its output slab, at a fixed, seeded sample of the pixels (every pixel of a small frame).  The library's
+    depth is +inf where nothing is hit; the files hold only finite numbers, so that is written as hit = 0 and depth = 0
+    (a hit lies beyond the near clip, so 0 is no depth of a hit).  Anything else that is not finite stays as it is."""
+    from surf_renderer_amd.pipeline import slab_views
+    image, depth = slab_views(slab, width)
+    n = depth.numel()
+    idx = np.arange(n) if n <= DUMP_PIXELS else \
+        np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+    at = torch.from_numpy(idx).to(slab.device)
+    d = depth.reshape(n)[at].cpu().numpy()
+    miss = d == np.inf
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image.npy"), image.reshape(n, 3)[at].cpu().numpy())
+    np.save(os.path.join(out_dir, "depth.npy"), np.where(miss, np.float32(0), d))
+    np.save(os.path.join(out_dir, "hit.npy"), (~miss).astype(np.float32))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), (idx + row0 * width).astype(np.float64))   # row-major, whole frame
 
 
 def literal_root0_leg(args, buf, cam, device, rank, world, W, H):
@@ -679,7 +720,7 @@ def main():
         if schedule == "auto":
             # whole frames per stream (see the note at the top); one frame's halves are timed for the report only
             schedule = "frames"
-            if args.mode in ("auto", "binned") and graph_state["on"] and rotate == 1 and n_str >= 3 and \
+            if args.full and args.mode in ("auto", "binned") and graph_state["on"] and rotate == 1 and n_str >= 3 and \
                     (r0, r1) == (0, H):
                 try:                                   # the library refuses split frames that are not binned
                     bin_ms, render_ms = halves_ms()
@@ -737,6 +778,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
+    if args.dump_outputs and pipe is None:
+        raise SystemExit("--dump-outputs needs the single-process frame pipeline (no process group, no --batch-call on "
+                         "with --as-rank)")
     # capture every output slot's graph up front, before any collective is in flight (the single-process pipeline
     # has captured its own)
     if graph_state["on"] and use_dist and not owner:
@@ -797,7 +841,7 @@ def main():
                 break                                           # single process: stop on the clock
         warm_steps += done
     warm_ms = 1e3 * (time.perf_counter() - t_w)
-    if pipe is not None:
+    if pipe is not None and args.check:
         pipe.poison()                                           # the check below then proves the timed frames wrote their slabs
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -808,6 +852,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe.slabs[(pipe.count - 1) % pipe.n], W, r0)
 
     check_note = None
     # A multi-rank schedule (owner-weighted or batched all-to-all) whose frames fail the bit-for-bit check on ANY rank does
@@ -863,7 +909,8 @@ def main():
     if use_dist and not frames_par and not args.as_rank and \
             (os.environ.get("SRH_BENCH_BACKEND", "nccl") == "nccl" or os.environ.get("SRH_BENCH_LITERAL")):
         already_literal = not batched
-        link = measure_exchange(device, rank, world, W, H)
+        if args.full:
+            link = measure_exchange(device, rank, world, W, H)
         if not already_literal:
             literal = literal_root0_leg(args, buf, cam, device, rank, world, W, H)
 
@@ -972,7 +1019,7 @@ def main():
                 pass
         # the pairs the kernel really tests (bin lengths of one frame, read back outside the timed region) beside the
         # algorithmic primitives x pixels of `gtests_per_s` -- SURVEY 8 f2
-        if args.mode in ("auto", "binned") and not args.as_rank and world == 1:
+        if args.full and args.mode in ("auto", "binned") and not args.as_rank and world == 1:
             try:
                 st = renderer.bin_statistics(buf, cam)
                 out["executed_pair_tests"] = {"per_frame": st["executed_pair_tests"],
@@ -1005,10 +1052,12 @@ def main():
                 if out.get(key):
                     out[key]["note"] = "kernel time measured inside the schedule reported under other_schedule"
         if use_dist and literal is not None:
-            out["config"]["schedule_choice"] = "two schedules timed and checked in this run; the faster correct one is `value`"
+            out["config"]["schedule_choice"] = ("two schedules timed and checked in this run; the faster correct one is "
+                                                "`value`" if args.check else
+                                                "two schedules timed in this run (not checked); the faster one is `value`")
         if link is not None:
             out["links_measured"] = link
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, M, W, H, args.cpu_pixels)
         if collection_failed:
             # a schedule that RAN failed its check: the numbers above are the literal form's (which passed), but a

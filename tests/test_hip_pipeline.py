@@ -1,5 +1,5 @@
 """GPU: the frame pipeline bench.py times (surf_renderer_amd.pipeline.FramePipeline) -- hipGraph replays on three
-streams must give the eager frame bit for bit.  bench.py runs the same check after its timed loop; this test makes a
+streams must give the eager frame bit for bit.  bench.py --full runs the same check after its timed loop; this test makes a
 wrong graph (stale slot / scratch pairing, a dropped node) fail the suite instead of printing a fast number."""
 import numpy as np
 import pytest

@@ -4,7 +4,7 @@
 # then once per variant the secondary configs.
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { timeout -k 10 150 python bench.py --no-cpu-baseline $2 2>>$OUT/$1.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('[$1] $2', '-> ms/step', round(d['ms_per_step'],4), 'kernel_ms', round(d['roofline']['kernel_ms'],4), d['config']['check'][:14])" | tee -a $OUT/ab.txt; }
+run() { timeout -k 10 150 python bench.py --full --no-cpu-baseline $2 2>>$OUT/$1.err | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('[$1] $2', '-> ms/step', round(d['ms_per_step'],4), 'kernel_ms', round(d['roofline']['kernel_ms'],4), d['config']['check'][:14])" | tee -a $OUT/ab.txt; }
 for round in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then unset SRH_LIB; else export SRH_LIB=$PWD/build/abl/$v.so; fi

@@ -8,11 +8,11 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 if [ "$PART" != 2 ]; then
 echo "[profile] bench"
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench20.json 2> $OUT/bench20.err
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench20.json 2> $OUT/bench20.err
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 echo "[profile] kernel trace"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o r -- python3 bench.py --no-cpu-baseline > $OUT/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o r -- python3 bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1
 cp $OUT/trace/r_kernel_stats.csv $OUT/kernel_stats.csv
 echo "[profile] pmc"
 timeout -k 10 900 python3 tools/collect_pmc.py --commit $COMMIT --out $OUT/pmc.json > $OUT/pmc.log 2>&1; tail -2 $OUT/pmc.log | cut -c1-300
@@ -28,7 +28,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t
 cp $OUT/trace_bwd/r_kernel_stats.csv $OUT/bwd_shadow_kernel_stats.csv
 echo "[profile] rank rehearsal"
 { for P in 2 4 8; do for S in contiguous cost; do for R in $(seq 0 $((P/2-1))); do
-    timeout -k 10 120 python bench.py --no-cpu-baseline --as-rank $R/$P --slabs $S --batch-call on 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('P=$P slabs=$S rank $R:', round(d['ms_per_step']*1e3,1), 'us per frame')"
+    timeout -k 10 120 python bench.py --full --no-cpu-baseline --as-rank $R/$P --slabs $S --batch-call on 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('P=$P slabs=$S rank $R:', round(d['ms_per_step']*1e3,1), 'us per frame')"
   done; done; done; } > $OUT/ranks.txt 2>&1
 echo "[profile] views"
 timeout -k 10 300 python tools/bench_views.py --views 4 --streams 2 --calls 50 > $OUT/views.txt 2>&1

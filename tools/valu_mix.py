@@ -111,7 +111,7 @@ def main():
         total = float(pmc["SQ_INSTS_VALU"])
         entries = args.entries
         if entries is None:
-            raise SystemExit("--pmc needs --entries (bench.py prints executed_pair_tests; entries = that / 256)")
+            raise SystemExit("--pmc needs --entries (bench.py --full prints executed_pair_tests; entries = that / 256)")
         n_sweep = entries * sum(per_entry.values())
         n_rest = max(total - n_sweep, 0.0)
         cyc = (n_sweep * mean_cost(sweep_v) + n_rest * mean_cost(rest_v)) / total
