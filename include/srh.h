@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SRH_ABI_VERSION 10
+#define SRH_ABI_VERSION 11
 #define SRH_MAX_SEGMENTS 4
 #define SRH_MAX_LIGHTS 64
 
@@ -223,6 +223,24 @@ int srh_render_bwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
                    const float* grad_image, const float* grad_depth,
                    const int32_t* nearest, const float* depth,
                    const SrhGrads* grads, void* stream);
+
+/* srh_render_bwd with the upstream gradients of the forward's extra outputs as well (SRH_SHADING_TORCH):
+ * grad_normal and grad_pos (rows,W,3), dense like SrhParams.normal_out / pos_out, are d loss / d normal and
+ * d loss / d pos, where normal is the hit's unit normal n^ = n / sqrt(|n|^2 + 3e-10) before the double_sided flip
+ * (sphere: (p - c) likewise) and pos = origin + t d the hit point (per-pixel origin for orthographic cameras).  Any
+ * of grad_image, grad_depth, grad_normal and grad_pos may be NULL, but not all four.  Without grad_image the kernel
+ * differentiates the geometry alone (no light loops): light, colour and material gradients stay untouched.
+ * Difference from the reference by design: at pixels that hit nothing, the upstream gradients of normal and pos are
+ * ignored, as those of image and depth are (the reference gathers object 0's intersection there and differentiates
+ * it).  With SRH_SHADING_NUMPY grad_normal / grad_pos must be NULL (that backend has no such outputs) and grad_image
+ * is required.  Everything else is as for srh_render_bwd. */
+int srh_render_bwd_aux(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                       const SrhMaterials* materials, const SrhParams* params,
+                       void* workspace, size_t workspace_bytes,
+                       const float* grad_image, const float* grad_depth,
+                       const float* grad_normal, const float* grad_pos,
+                       const int32_t* nearest, const float* depth,
+                       const SrhGrads* grads, void* stream);
 
 /* Many views in one call: the batch axis of the reference's real callers, which render one view per
  * render() call in a Python loop (diffrend/torch/GAN/gan.py:325-378, torch/batch_render.py:36-53).  `cameras` is an

@@ -1216,16 +1216,18 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
   return e == hipSuccess ? SRH_OK : hip_fail(e, "shadow launch");
 }
 
-int srh_render_bwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
-                   const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
-                   const float* grad_image, const float* grad_depth, const int32_t* nearest, const float* depth,
-                   const SrhGrads* grads, void* stream) {
+// srh_render_bwd (grad_normal = grad_pos = NULL) and srh_render_bwd_aux; the callers have checked which upstream
+// gradients may be NULL
+static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                      const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                      const float* grad_image, const float* grad_depth, const float* grad_normal, const float* grad_pos,
+                      const int32_t* nearest, const float* depth, const SrhGrads* grads, void* stream) {
   FrameDev F;
   WsLayout L;
   int rc = setup_frame(camera, objects, lights, materials, params, workspace, workspace_bytes, &F, &L);
   if (rc) return rc;
-  if (!grad_image || !nearest || !depth || !grads)
-    return fail(SRH_E_NULL, "grad_image / nearest / depth / grads is NULL");
+  if (!nearest || !depth || !grads)
+    return fail(SRH_E_NULL, "nearest / depth / grads is NULL");
   if (F.ortho && params->shading != SRH_SHADING_TORCH)
     return fail(SRH_E_CAMERA, "orthographic projection exists only under SRH_SHADING_TORCH");
   GradsDev G;
@@ -1246,12 +1248,46 @@ int srh_render_bwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
   }
   const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
   if (params->ev_start) (void)hipEventRecord((hipEvent_t)params->ev_start, st);
-  if (tch) hipLaunchKernelGGL(k_render_bwd_tch, grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
-                              (const uint64_t*)params->visibility);
-  else hipLaunchKernelGGL(k_render_bwd, grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth);
+  const uint64_t* vis = (const uint64_t*)params->visibility;
+  const bool aux = grad_normal || grad_pos;
+  if (!tch) hipLaunchKernelGGL(k_render_bwd, grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth);
+  else if (!aux && grad_image)
+    hipLaunchKernelGGL((k_render_bwd_tch<false, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
+                       vis, nullptr, nullptr);
+  else if (grad_image)
+    hipLaunchKernelGGL((k_render_bwd_tch<true, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
+                       vis, grad_normal, grad_pos);
+  else          // geometry only; a depth-only call runs it too, with both aux pointers NULL
+    hipLaunchKernelGGL((k_render_bwd_tch<true, false>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
+                       vis, grad_normal, grad_pos);
   if (params->ev_stop) (void)hipEventRecord((hipEvent_t)params->ev_stop, st);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SRH_OK : hip_fail(e, "backward launch");
+}
+
+int srh_render_bwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                   const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                   const float* grad_image, const float* grad_depth, const int32_t* nearest, const float* depth,
+                   const SrhGrads* grads, void* stream) {
+  if (!grad_image) return fail(SRH_E_NULL, "grad_image / nearest / depth / grads is NULL");
+  return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
+                    nullptr, nullptr, nearest, depth, grads, stream);
+}
+
+int srh_render_bwd_aux(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                       const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                       const float* grad_image, const float* grad_depth, const float* grad_normal,
+                       const float* grad_pos, const int32_t* nearest, const float* depth, const SrhGrads* grads,
+                       void* stream) {
+  if (!grad_image && !grad_depth && !grad_normal && !grad_pos)
+    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_normal and grad_pos are all NULL");
+  if (params && params->shading != SRH_SHADING_TORCH) {
+    if (grad_normal || grad_pos)
+      return fail(SRH_E_TYPE, "normal / pos outputs exist only under SRH_SHADING_TORCH: grad_normal / grad_pos must be NULL");
+    if (!grad_image) return fail(SRH_E_NULL, "SRH_SHADING_NUMPY needs grad_image");
+  }
+  return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
+                    grad_normal, grad_pos, nearest, depth, grads, stream);
 }
 
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,

@@ -357,14 +357,24 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
 // multiply) and the nearest-hit selection.  torch.pow: 0^0 = 1, d/d exponent = 0 at base 0, d/d base = 0 at exponent 0.
 // Misses and the far + 1 background carry no gradient.
 // ---------------------------------------------------------------------------------------------------------------------
+// Two compile-time variants (srh_render_bwd_aux):
+//   kAux    the upstream gradients of the extra outputs normal = n^ (un-flipped: double_sided flips only inside the
+//           shading) and pos = origin + t d enter at hit pixels, added to d/d n^ and d/d p before the geometry chain.
+//           grad_normal / grad_pos are dense (rows,W,3) like the forward's normal_out / pos_out; either may be NULL.
+//   kImage  grad_image is read and the shading differentiated.  Without it both light loops and every light /
+//           material / colour accumulation drop out: a geometry-only backward for losses on normal / pos / depth.
+// <false, true> is srh_render_bwd's kernel (the two trailing arguments are unused there).
 #ifndef SRH_BWD_TCH_WAVES
 #define SRH_BWD_TCH_WAVES 3
 #endif
+template <bool kAux, bool kImage>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH_WAVES))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
                                                          const float* __restrict__ grad_depth,
                                                          const int32_t* __restrict__ nearest,
                                                          const float* __restrict__ depth,
-                                                         const uint64_t* __restrict__ visibility) {
+                                                         const uint64_t* __restrict__ visibility,
+                                                         const float* __restrict__ grad_normal,
+                                                         const float* __restrict__ grad_pos) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
   const int lane = threadIdx.x;
@@ -380,8 +390,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   float g_out[3] = {0, 0, 0}, g_dep = 0.0f;               // upstream gradients are fp32
   int win = 0;
   if (hit) {
-    const float* gi = grad_image + row * F.img_stride + 3 * (size_t)cc;
-    g_out[0] = gi[0]; g_out[1] = gi[1]; g_out[2] = gi[2];
+    if (kImage) {
+      const float* gi = grad_image + row * F.img_stride + 3 * (size_t)cc;
+      g_out[0] = gi[0]; g_out[1] = gi[1]; g_out[2] = gi[2];
+    }
     if (grad_depth) g_dep = grad_depth[row * F.depth_stride + cc];
     win = nearest[row * F.near_stride + cc];
   }
@@ -405,7 +417,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
     return ptr;
   };
   // light visibility of the forward pass (shadow rays): a constant 0 / 1 factor on each light's colour x albedo term
-  const uint64_t vis = (visibility && hit) ? visibility[row * (size_t)F.W + cc] : ~0ull;
+  const uint64_t vis = (kImage && visibility && hit) ? visibility[row * (size_t)F.W + cc] : ~0ull;
 
   // the pixel's ray: from the eye (perspective), or from its own origin eye + q0 on the image plane with the one
   // direction -z of the camera basis (orthographic, torch/utils.py:461-468); org is what the reference calls ray_orig
@@ -456,6 +468,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   const double cdotn = (cdir[0] * n[0] + cdir[1] * n[1]) + cdir[2] * n[2];
   const double sgn = F.double_sided ? ((cdotn > 0.0) ? 1.0 : ((cdotn < 0.0) ? -1.0 : 0.0)) : 1.0;
   const int pw = F.use_quartic ? 4 : 2;
+  const int nlights = kImage ? F.nlights : 0;              // geometry-only variant: no light loop at all
 
   // per-light forward terms, evaluated twice (image first: its value gates the clip / tonemap derivative).
   // The light loops run in fp32: the hit point, the normal and the view direction come out of the fp64 geometry above and
@@ -491,7 +504,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   auto spec_pow = [&](float rdotc) { return (rdotc == 0.0f && cf[2] == 0.0f) ? 1.0f : powf(rdotc, cf[2]); };
 
   float im[3] = {0, 0, 0};
-  for (int l = 0; l < F.nlights; ++l) {
+  for (int l = 0; l < nlights; ++l) {
     LightTerms T;
     light_terms(l, T);
     const float w = (cf[0] * fmaxf(T.nd, 0.0f) + cf[1] * spec_pow(fmaxf(T.rd, 0.0f))) * (float)((vis >> l) & 1ull);
@@ -510,7 +523,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   float g_nf[3] = {0, 0, 0}, g_pf[3] = {0, 0, 0};
   float g_alb[3] = {0, 0, 0}, g_cf[3] = {0, 0, 0}, g_amb[3] = {0, 0, 0};     // leave as fp32 atomics: summed in fp32
   float g_cdf[3] = {0, 0, 0}, g_cdotnf = 0.0f;
-  for (int l = 0; l < F.nlights; ++l) {
+  for (int l = 0; l < nlights; ++l) {
     LightTerms T;
     light_terms(l, T);
     const float ndotl = fmaxf(T.nd, 0.0f), rdotc = fmaxf(T.rd, 0.0f);
@@ -583,14 +596,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   double g_n[3] = {(double)g_nf[0], (double)g_nf[1], (double)g_nf[2]}, g_p[3] = {(double)g_pf[0], (double)g_pf[1], (double)g_pf[2]};
   double g_cdir[3] = {(double)g_cdf[0], (double)g_cdf[1], (double)g_cdf[2]};
   const double g_cdotn = (double)g_cdotnf;
-  if (G.ambient) {
+  // the extra outputs' upstream gradients, read here rather than at the top: nothing holds them across the light loops
+  if (kAux && hit) {
+    const size_t a = (row * (size_t)F.W + (size_t)cc) * 3;
+    if (grad_normal) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g_n[k] += (double)grad_normal[a + k];
+    }
+    if (grad_pos) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g_p[k] += (double)grad_pos[a + k];
+    }
+  }
+  if (kImage && G.ambient) {
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float sum = wave_sum((float)g_amb[ch]);
       if (lane == 0 && sum != 0.0f) atomicAdd(G.ambient + ch, sum);
     }
   }
-  {
+  if (kImage) {
     // one material for the whole wave (the common case) -> one atomic per component; otherwise per lane
     const int m0 = __builtin_amdgcn_readfirstlane(m);
     const bool uniform = __builtin_amdgcn_ballot_w64(hit && m != m0) == 0ull;
@@ -619,7 +644,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH
   }
   // ---- view direction and geometry: every lane takes part (run reduction below); lanes without a hit carry zeros ------
   double gA[3] = {0, 0, 0}, gB[3] = {0, 0, 0}, g_r = 0.0;
-  if (hit) {
+  if (kImage && hit) {
     // c^ . n^ and c^ = u / sqrt(|u|^2 + eps), u = o - p
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g_cdir[k] += g_cdotn * n[k]; g_n[k] += g_cdotn * cdir[k]; }

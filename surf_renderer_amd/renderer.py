@@ -529,13 +529,19 @@ def shadow_pass(buf: SceneBuffers, cam: _lib.SrhCamera, rows, image: torch.Tenso
 class _RenderFunction(torch.autograd.Function):
     """render_buffers with the analytic backward of libsrh (srh_render_bwd).  Gradient semantics are those of
     autograd through the reference's torch backend (SURVEY.md section 8, row a-B): selection and masks are piecewise
-    constant; a disc's radius and a triangle's vertices 1, 2 receive zero gradient."""
+    constant; a disc's radius and a triangle's vertices 1, 2 receive zero gradient.  With shade[4] (torch shading only)
+    the outputs are image, depth, nearest, normal, pos, and upstream gradients of normal / pos go to
+    srh_render_bwd_aux."""
 
     @staticmethod
     def forward(ctx, buf, cam, rows, mode, shade, *inputs):
-        # shade = (shading, double_sided, use_quartic, shadow)
+        # shade = (shading, double_sided, use_quartic, shadow, aux)
+        aux = None
+        if shade[4]:
+            aux = _aux_buffers(cam, rows, buf.device)
+            ctx.set_materialize_grads(False)            # an unused normal / pos must arrive as None, not as zeros
         image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode, shading=shade[0],
-                                               double_sided=shade[1], use_quartic=shade[2])
+                                               double_sided=shade[1], use_quartic=shade[2], aux=aux)
         vis = shadow_pass(buf, cam, rows, image, depth, nearest, shade[1], shade[2]) if shade[3] else None
         ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade = buf, cam, rows, mode, shade
         ctx.has_vis = vis is not None
@@ -544,25 +550,30 @@ class _RenderFunction(torch.autograd.Function):
         else:
             ctx.save_for_backward(depth, nearest)
         ctx.mark_non_differentiable(nearest)
+        if aux is not None:
+            return image, depth, nearest, aux[0], aux[1]
         return image, depth, nearest
 
     @staticmethod
-    def backward(ctx, g_image, g_depth, _g_nearest):
+    def backward(ctx, g_image, g_depth, _g_nearest, g_normal=None, g_pos=None):
         if ctx.has_vis:
             depth, nearest, vis = ctx.saved_tensors
         else:
             (depth, nearest), vis = ctx.saved_tensors, None
         keys = _float_keys(ctx.buf, ctx.shade[0])
         grads = _render_backward(ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade, depth, nearest, vis, g_image, g_depth,
-                                 ctx.needs_input_grad[5:])
+                                 ctx.needs_input_grad[5:], g_normal, g_pos)
         return (None, None, None, None, None) + tuple(grads.get(k) for k in keys)
 
 
 def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade, depth: torch.Tensor,
                      nearest: torch.Tensor, vis: Optional[torch.Tensor], g_image: Optional[torch.Tensor],
-                     g_depth: Optional[torch.Tensor], need: Sequence[bool]) -> Dict[str, torch.Tensor]:
+                     g_depth: Optional[torch.Tensor], need: Sequence[bool], g_normal: Optional[torch.Tensor] = None,
+                     g_pos: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """srh_render_bwd: gradients of the inputs named by ``_float_keys`` (those with ``need``) for the upstream gradients
-    of image and depth, from the winners the forward pass saved.  Everything is enqueued on the current stream."""
+    of image and depth, from the winners the forward pass saved.  Everything is enqueued on the current stream.
+    With an upstream gradient of the torch shading's ``normal`` or ``pos`` output the call is srh_render_bwd_aux
+    instead; there a missing ``g_image`` is passed as NULL (the geometry-only kernel) rather than as zeros."""
     lib = _lib.load()
     width, height = frame_size(cam)
     r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
@@ -592,9 +603,12 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
             if name == "radius" and kind == "disk":
                 continue                      # identically zero (numpy/renderer.py:88: the radius only feeds a mask)
             getattr(sg, name)[s] = g.data_ptr()
+    aux = g_normal is not None or g_pos is not None
     g_image = g_image.to(torch.float32).contiguous() if g_image is not None else \
-        torch.zeros((r1 - r0, width, 3), dtype=torch.float32, device=buf.device)
+        (None if aux else torch.zeros((r1 - r0, width, 3), dtype=torch.float32, device=buf.device))
     g_depth = g_depth.to(torch.float32).contiguous() if g_depth is not None else None
+    g_normal = g_normal.to(torch.float32).contiguous() if g_normal is not None else None
+    g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
     params = _lib.SrhParams(row0=r0, row1=r1, mode=_lib.MODES[mode],
                             tonemap_gamma=0 if buf.gamma is None else 1,
                             gamma=1.0 if buf.gamma is None else buf.gamma,
@@ -602,11 +616,20 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
                             use_quartic=int(bool(shade[2])),
                             visibility=vis.data_ptr() if vis is not None else None)
     workspace = buf.ensure_workspace(width, height)
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
     with torch.cuda.device(buf.device):
-        rc = lib.srh_render_bwd(C.byref(cam), C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials),
-                                C.byref(params), workspace.data_ptr(), workspace.numel(),
-                                g_image.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
-                                nearest.data_ptr(), depth.data_ptr(), C.byref(sg), _stream_ptr(buf.device))
+        if aux:
+            rc = lib.srh_render_bwd_aux(C.byref(cam), C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials),
+                                        C.byref(params), workspace.data_ptr(), workspace.numel(), ptr(g_image),
+                                        ptr(g_depth), ptr(g_normal), ptr(g_pos), nearest.data_ptr(), depth.data_ptr(),
+                                        C.byref(sg), _stream_ptr(buf.device))
+        else:
+            rc = lib.srh_render_bwd(C.byref(cam), C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials),
+                                    C.byref(params), workspace.data_ptr(), workspace.numel(),
+                                    g_image.data_ptr(), g_depth.data_ptr() if g_depth is not None else None,
+                                    nearest.data_ptr(), depth.data_ptr(), C.byref(sg), _stream_ptr(buf.device))
     _lib.check(rc)
     return grads
 
@@ -865,12 +888,18 @@ class ResidentScene:
         rs = ResidentScene(scene, shading='torch')        # leaves with requires_grad=True stay attached
         for _ in range(steps):
             opt.zero_grad(); loss(rs.render()['image']).backward(); opt.step()
+
+    ``aux=True`` (``shading='torch'`` only) adds the torch backend's ``normal`` and ``pos`` outputs to ``render()``,
+    differentiable like ``image`` and ``depth``, and lets a ``capture_step`` loss use them.  It is off by default:
+    writing them costs 24 bytes per pixel and frame.
     """
 
     def __init__(self, scene: Dict[str, Any], device="cuda", shading: str = "numpy", mode: str = "auto",
-                 double_sided: bool = False, use_quartic: bool = False, validate: bool = True):
+                 double_sided: bool = False, use_quartic: bool = False, validate: bool = True, aux: bool = False):
         if shading not in _lib.SHADING:
             raise ValueError(f"shading must be 'numpy' or 'torch', got {shading!r}")
+        if aux and shading != "torch":
+            raise ValueError("normal / pos outputs exist only in the torch backend's semantics: shading='torch'")
         self.device = torch.device(device)
         self.buf = flatten_scene(scene, self.device, validate=validate, keep_graph=True)
         self.shading, self.mode = shading, mode
@@ -878,7 +907,8 @@ class ResidentScene:
         self.cam = camera_struct(scene["camera"], shading)
         if self.cam.ortho and shading != "torch":
             raise ValueError("orthographic projection exists only in the torch backend's semantics: shading='torch'")
-        self.shade = (shading, bool(double_sided), bool(use_quartic), False)
+        self.aux = bool(aux)
+        self.shade = (shading, bool(double_sided), bool(use_quartic), False, self.aux)
         self.inputs = [self.buf.tensors[k] for k in _float_keys(self.buf, shading)]
         self.differentiable = any(t.requires_grad for t in self.inputs)
         # "In place" has to be true for every leaf that is being optimised: a float64, CPU or non-contiguous leaf is
@@ -903,12 +933,19 @@ class ResidentScene:
         self.cam = camera_struct(camera, self.shading)
 
     def render(self, rows: Optional[Tuple[int, int]] = None) -> "RenderResult":
+        extra = {}
         if self.differentiable and torch.is_grad_enabled():
-            image, depth, nearest = _RenderFunction.apply(self.buf, self.cam, rows, self.mode, self.shade, *self.inputs)
+            out = _RenderFunction.apply(self.buf, self.cam, rows, self.mode, self.shade, *self.inputs)
+            image, depth, nearest = out[:3]
+            if self.aux:
+                extra = {"normal": out[3], "pos": out[4]}
         else:
+            aux = _aux_buffers(self.cam, rows, self.device) if self.aux else None
             image, depth, nearest = render_buffers(self.buf, self.cam, rows=rows, mode=self.mode, shading=self.shading,
-                                                   double_sided=self.shade[1], use_quartic=self.shade[2])
-        return RenderResult(self._camera, self.device, image=image, depth=depth, nearest=nearest)
+                                                   double_sided=self.shade[1], use_quartic=self.shade[2], aux=aux)
+            if aux is not None:
+                extra = {"normal": aux[0], "pos": aux[1]}
+        return RenderResult(self._camera, self.device, image=image, depth=depth, nearest=nearest, **extra)
 
     def capture_step(self, loss_fn, warmup: int = 3) -> "CapturedStep":
         """One optimisation step's GPU work -- render, ``loss_fn(result)``, backward -- captured as ONE hipGraph and
@@ -921,8 +958,9 @@ class CapturedStep:
     """``step = rs.capture_step(loss_fn)``; then per iteration ``loss = step.replay(); optimiser.step()``.
 
     The whole-step capture recipe of torch.cuda.graphs: a few eager iterations on a side stream, then one iteration
-    recorded into a graph -- the library's forward, ``loss_fn`` on the rendered image and depth, torch's own backward of
-    the loss down to image and depth, and the library's backward from there to the leaves, called directly.  (Letting
+    recorded into a graph -- the library's forward, ``loss_fn`` on the rendered image and depth (and normal and pos
+    with ``ResidentScene(aux=True)``), torch's own backward of the loss down to those outputs, and the library's
+    backward from there to the leaves, called directly.  (Letting
     the autograd engine run the renderer's autograd.Function inside a capture ends in a segmentation fault in
     hipStreamEndCapture on ROCm 7.2 -- tools/diag_capture.py; each of the pieces used here captures fine.)  The
     leaves' ``.grad`` tensors are static: every replay overwrites them (they do not accumulate), ``loss`` and
@@ -956,13 +994,19 @@ class CapturedStep:
         need = [k in rs.leaves for k in keys]
         with torch.cuda.graph(self.graph):
             with torch.no_grad():
+                aux = _aux_buffers(rs.cam, None, rs.device) if rs.aux else None
                 image, depth, nearest = render_buffers(rs.buf, rs.cam, mode=rs.mode, shading=rs.shading,
-                                                       double_sided=rs.shade[1], use_quartic=rs.shade[2])
-            img, dep = image.requires_grad_(), depth.requires_grad_()
-            self.result = RenderResult(rs._camera, rs.device, image=img, depth=dep, nearest=nearest)
+                                                       double_sided=rs.shade[1], use_quartic=rs.shade[2], aux=aux)
+            outs = [image.requires_grad_(), depth.requires_grad_()]
+            extra = {}
+            if aux is not None:
+                outs += [aux[0].requires_grad_(), aux[1].requires_grad_()]
+                extra = {"normal": outs[2], "pos": outs[3]}
+            self.result = RenderResult(rs._camera, rs.device, image=outs[0], depth=outs[1], nearest=nearest, **extra)
             self.loss = loss_fn(self.result)
-            g_img, g_dep = torch.autograd.grad(self.loss, [img, dep], allow_unused=True)
-            got = _render_backward(rs.buf, rs.cam, None, rs.mode, rs.shade, depth, nearest, None, g_img, g_dep, need)
+            g = list(torch.autograd.grad(self.loss, outs, allow_unused=True)) + [None, None]
+            got = _render_backward(rs.buf, rs.cam, None, rs.mode, rs.shade, depth, nearest, None, g[0], g[1], need,
+                                   g[2], g[3])
         # the static gradient tensors every replay writes, in the order of self.leaves and in the leaves' own shapes
         self.grads = [(got[k] if k in got else torch.zeros_like(rs.buf.tensors[k])).view(leaf.shape)
                       for k, leaf in zip(self.keys, self.leaves)]
@@ -974,6 +1018,14 @@ class CapturedStep:
         for t, g in zip(self.leaves, self.grads):          # whatever happened to .grad in between (zero_grad(set_to_none))
             t.grad = g
         return self.loss
+
+
+def _aux_buffers(cam: _lib.SrhCamera, rows, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The (rows, W, 3) float32 ``normal`` and ``pos`` outputs of a torch-shading frame (or slab)."""
+    width, height = frame_size(cam)
+    h = height if rows is None else int(rows[1]) - int(rows[0])
+    return (torch.empty((h, width, 3), dtype=torch.float32, device=device),
+            torch.empty((h, width, 3), dtype=torch.float32, device=device))
 
 
 def _norm_depth_image(depth: torch.Tensor, far: float) -> torch.Tensor:
@@ -1031,7 +1083,9 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
     ``validate`` (host-side index / w checks), ``shading`` ('numpy' | 'torch').  With ``shading='torch'`` the call
     follows ``diffrend.torch.renderer.render`` instead (Phong shading with lights.attenuation / lights.ambient /
     materials.coeffs, ``double_sided``, ``use_quartic``, orthonormal camera basis, far+1 background, extra outputs
-    ``normal`` and ``pos``; ``shadow=True`` adds the all-pairs shadow-ray pass and a ``light_visibility`` bit field;
+    ``normal`` and ``pos`` -- differentiable like ``image`` and ``depth`` when a leaf requires grad (see
+    ``_RenderFunction``; their upstream gradients at pixels that hit nothing are ignored, as image's and depth's are);
+    ``shadow=True`` adds the all-pairs shadow-ray pass and a ``light_visibility`` bit field;
     ``camera.proj_type = 'ortho'``; ``norm_depth_image_only=True`` returns the normalised depth as ``image``).  The
     torch backend's remaining kwargs are accepted where they change no output of the reference (``tiled``,
     ``tile_size``, ``backface_culling`` -- see ``_TORCH_ONLY_KWARGS``); ``vis_stat=True`` raises as it does there.
@@ -1063,11 +1117,14 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
         # the torch backend's semantics
         shade = ("torch", bool(params.get("double_sided", False)), bool(params.get("use_quartic", False)), shadow)
         if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
-            # differentiable call (no normal / pos outputs on this path)
-            image, depth, nearest = _RenderFunction.apply(buf, cam, rows, mode, shade, *inputs)
+            # differentiable call; norm_depth_image_only returns no normal / pos (torch/renderer.py:245-260)
+            out = _RenderFunction.apply(buf, cam, rows, mode, shade + (not norm_depth,), *inputs)
+            image, depth, nearest = out[:3]
             if norm_depth:
-                image = _norm_depth_image(depth, cam.far_clip)
-            return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64))
+                return RenderResult(scene["camera"], device, image=_norm_depth_image(depth, cam.far_clip), depth=depth,
+                                    nearest=nearest.to(torch.int64))
+            return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64),
+                                normal=out[3], pos=out[4])
         width, height = frame_size(cam)
         r0, r1 = (0, height) if rows is None else rows
         normal = torch.empty((r1 - r0, width, 3), dtype=torch.float32, device=device)
@@ -1086,7 +1143,8 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
                             normal=normal, pos=pos, **extra)
     if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
         # differentiable call: image and depth carry a grad_fn backed by the analytic HIP backward
-        image, depth, nearest = _RenderFunction.apply(buf, cam, rows, mode, ("numpy", False, False, False), *inputs)
+        image, depth, nearest = _RenderFunction.apply(buf, cam, rows, mode, ("numpy", False, False, False, False),
+                                                      *inputs)
     else:
         image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode,
                                                waves_per_tile=params.get("waves_per_tile", 0))
