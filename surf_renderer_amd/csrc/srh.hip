@@ -126,7 +126,7 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
   float Q[N32];
   const PixelBasis B = pixel_basis(F);
   const bool near_pos = F.near_clip > 0.0;
-  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, Q);
+  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q);
   else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q);
   else if (TYPE == SRH_PRIM_TRIANGLE) triangle_reject_record(R, F.o, B, F.W, F.H, near_pos, Q);
   else plane_reject_record(R, B, F.W, F.H, Q);

@@ -407,9 +407,11 @@ __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __buil
 // SCALE = false leaves out the factor 1 / |D|: the value is then den = inv |D|, which orders the candidates of ONE pixel
 // exactly as inv does -- the typed kernels of planar primitives track their keys in that unit (kDenKeys) and convert at
 // the few places that compare a key with a depth.
+// `qout` (discs and spheres): the quadratic form's value per pixel pair, for the occlusion cull's certain-hit test.
 template <int TYPE, bool PRETEST, bool SCALE = true>
 __device__ __forceinline__ void pair_bounds(const RejectRecord<TYPE>& R, const f32x2 (&cf)[2], float rf,
-                                            const f32x2 (&rlen)[2], int32_t (&sel)[4], f32x2 (&inv)[2]) {
+                                            const f32x2 (&rlen)[2], int32_t (&sel)[4], f32x2 (&inv)[2],
+                                            f32x2* qout = nullptr) {
   f32x2 den[2];
   if (TYPE == SRH_PRIM_DISK || TYPE == SRH_PRIM_SPHERE) {
     // candidate iff q <= 0; tested as q - 2^-22 < 0 (a superset) so that the sign bit decides
@@ -428,6 +430,7 @@ __device__ __forceinline__ void pair_bounds(const RejectRecord<TYPE>& R, const f
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) sel[j] = __float_as_int(q[j >> 1][j & 1]) >> 31;
+    if (qout) { qout[0] = q[0]; qout[1] = q[1]; }
     if (TYPE == SRH_PRIM_DISK) {
       // a multiply and an add (2.5 cycles each, one scalar operand each) instead of one fma, which would need a v_mov
       // for its second scalar operand (one constant-bus read per instruction) and costs 4.7 cycles itself
@@ -709,9 +712,15 @@ __device__ __forceinline__ void sweep_tile(const FrameDev& F, int tile, QuadStat
 }
 
 // Global primitive index of the entry with ordinal `ord` (per lane) in the tile's lists; -1 if out of range.
+// `sorted` (wave-uniform; null: the lists' own order): the front-to-back order of the occlusion cull, in LDS.
 template <int BATCH = -1>
-__device__ __forceinline__ int ordinal_to_global(const FrameDev& F, int tile, uint32_t ord) {
+__device__ __forceinline__ int ordinal_to_global(const FrameDev& F, int tile, uint32_t ord,
+                                                 const int32_t* sorted = nullptr) {
   const TileLists L{F, tile};
+  if (sorted) {
+    const uint32_t n = L.count(0, 1);
+    return ord < n ? sorted[min(ord, n - 1)] : -1;
+  }
   if (((BATCH >= 0) || F.nseg == 1) && L.count(0, 0) == 0) {          // one batch, nothing frame-wide: the ordinal is the bin-list position
     const uint32_t n = L.count(0, 1);
     return ord < n ? (int)L.list(0, 1)[min(ord, n - 1)] : -1;
@@ -727,6 +736,174 @@ __device__ __forceinline__ int ordinal_to_global(const FrameDev& F, int tile, ui
     }
   }
   return g;
+}
+
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- front-to-back occlusion cull (one-batch disc kernel, one wave per tile) ----------------------------------------
+// Most entries of a busy tile cannot win: the tile is covered by nearer discs.  So the tile's list is sorted by each
+// disc's upper bound U of 1 / t (rec32[8], k_prep) -- nearest possible first -- and swept in that order while every
+// pixel tracks L(p), the largest LOWER bound of 1 / t over the discs that CERTAINLY hit it (rec32[11], conic_record's
+// sure_in; the depth through den shifted down, below).  Every kOcclGroup entries the wave takes T = min over the
+// tile's pixels of L(p); the sweep stops at the first sorted entry with U < T.  Such an entry's valid hits all have
+// t > 1 / T >= the certain hit's t at EVERY pixel of the tile: strictly behind the confirmed winner, so it can neither
+// win nor tie resolve_lex, and leaving it out of the keys changes nothing (the slow path and the re-sweep still walk
+// the full lists).  A pixel without a certain hit keeps L = 0, T = 0, and nothing is skipped.
+// The key fields hold the SORTED position; ordinal_to_global maps them through the sorted copy in LDS.
+#ifndef SRH_OCCLUSION_CULL
+#define SRH_OCCLUSION_CULL 1
+#endif
+#ifndef SRH_OCCL_GROUP
+#define SRH_OCCL_GROUP 8
+#endif
+constexpr uint32_t kOcclGroup = SRH_OCCL_GROUP;     // entries between two thresholds (even: the sweep goes in pairs)
+static_assert(kOcclGroup % 2 == 0 && kOcclGroup >= 2, "SRH_OCCL_GROUP");
+constexpr uint32_t kSortCap = 128;                  // entries one wave sorts (two per lane); longer lists: the plain sweep
+constexpr uint32_t kSortLow = 0x7Fu;                // low key bits: the list position
+// den - 3 E / K <= s (n^.D) / K for the fp32 den of the vector path AND the fp64 path's own n^.d (plane_estimate_record:
+// den carries less than E / K of error and is shifted up by E / K; E covers the fp64 side too), with E / K read off
+// lo_u = 1025 E / K (rounded up there) -- the factor is 3 / 1025 rounded up by 2.4e-6.
+constexpr float kDenShiftPerLoU = 0.0029269f;
+// L (p) rlen_lo (1 - 2^-18) <= 1 / t: the (1 - 2^-20) of K, the fp32 1 / |D|, the subtraction and two products
+constexpr float kSureRound = 0.99999619f;
+
+// Bitonic sort, DESCENDING, of NR x 64 distinct signed keys across the wave: element i = lane + 64 h is register h of
+// lane `lane`.  Stage (k, j) compares i with i ^ j; blocks of size k with (i & k) == 0 run descending, the others
+// ascending, so that each merge sees a bitonic sequence.
+template <int NR>
+__device__ __forceinline__ void wave_sort_desc(int32_t (&v)[NR], int lane) {
+  constexpr int N = 64 * NR;
+#pragma unroll
+  for (int k = 2; k <= N; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      if (j == 64) {                                  // k = 128: partner in the lane's other register, all descending
+        const int32_t a = v[0], b = v[NR - 1];
+        v[0] = max(a, b);
+        v[NR - 1] = min(a, b);
+      } else {
+#pragma unroll
+        for (int h = 0; h < NR; ++h) {
+          const int i = lane + 64 * h;
+          const int32_t p = __shfl_xor(v[h], j);
+          v[h] = (((i & j) == 0) == ((i & k) == 0)) ? max(v[h], p) : min(v[h], p);
+        }
+      }
+    }
+  }
+}
+
+// Sort the tile's bin list (n <= kSortCap entries) front to back.  Leaves the sorted global indices in sg[] (LDS) and
+// in gs[] (register h of lane l: sorted entry l + 64 h), the sorted keys with their low bits SET -- upper bounds of
+// 1 / t, positive floats compared as integers -- in su[] (-1 past the end).
+template <int NR>
+__device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __restrict__ list, uint32_t n, int lane,
+                                          int32_t* sg, int32_t* su, int32_t (&gs)[2]) {
+  int32_t key[NR], g[NR];
+#pragma unroll
+  for (int h = 0; h < NR; ++h) {
+    const uint32_t i = (uint32_t)lane + 64u * h;
+    g[h] = i < n ? (int32_t)list[i] : S.first;
+    const float u = S.rec32[(size_t)(g[h] - S.first) * kRec32Stride[SRH_PRIM_DISK] + 8];
+    key[h] = i < n ? (int32_t)((__float_as_uint(u) & ~kSortLow) | i) : -1;   // U > 0: keys of real entries are >= 0
+  }
+  wave_sort_desc<NR>(key, lane);
+#pragma unroll
+  for (int h = 0; h < NR; ++h) sg[lane + 64 * h] = g[h];          // list order ...
+  wave_lds_fence();
+#pragma unroll
+  for (int h = 0; h < NR; ++h) gs[h] = sg[key[h] & kSortLow];    // ... gathered into sorted order
+  wave_lds_fence();
+#pragma unroll
+  for (int h = 0; h < NR; ++h) {
+    sg[lane + 64 * h] = gs[h];
+    su[lane + 64 * h] = key[h] | (int32_t)kSortLow;
+  }
+  if (NR == 1) gs[1] = gs[0];
+  wave_lds_fence();
+}
+
+// The sweep of a sorted list: stream_list's pipelined pairs (records by scalar loads from wave-uniform addresses), the
+// list words by v_readlane from gs[], the key update of sweep_entry, and per pixel
+//   L = max(L, bits(den - shift) & (q < s_in ? ~0 : 0))      (a negative lower bound never beats the initial 0)
+// Returns the number of entries swept.
+// `rlen_lo` <= 1 / |D| at every pixel of the tile (the disc kernel's Q.rlen is 1: its keys are in den units).
+template <int NR>
+__device__ __forceinline__ uint32_t sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
+                                                 const int32_t* su, int lane, float rlen_lo, QuadState& Q) {
+  constexpr int TYPE = SRH_PRIM_DISK;
+  const char* base_c = reinterpret_cast<const char*>(S.rec32) - (size_t)S.first * (size_t)(4 * kRec32Stride[TYPE]);
+  auto record = [&](int g) {
+    return reinterpret_cast<const float*>(base_c + (uint32_t)g * (uint32_t)(4 * kRec32Stride[TYPE]));
+  };
+  auto entry = [&](uint32_t k) {
+    k = min(k, n - 1);
+    return (NR == 1 || k < 64) ? __builtin_amdgcn_readlane(gs[0], (int)k) : __builtin_amdgcn_readlane(gs[1], (int)(k - 64));
+  };
+  int32_t L[4] = {0, 0, 0, 0};
+  const uint32_t keep = ~Q.ordmask;
+  auto op = [&](const RejectRecord<TYPE>& R, uint32_t k) {
+    int32_t sel[4];
+    f32x2 den[2], q[2];
+    pair_bounds<TYPE, true, false>(R, Q.cf, Q.rf, Q.rlen, sel, den, q);
+    const uint32_t field = k + 1u;                    // n + 1 <= ordmask: never saturated
+    const float shift = R[9] * kDenShiftPerLoU;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const f32x2 qi = q[p] - splat2(R[11]);
+      const f32x2 lo = den[p] - splat2(shift);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = 2 * p + h;
+        const int32_t key = pack_key(den[p][h], field, keep) & sel[j];
+        if (kKeys == 4) Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
+        Q.k3[j] = imed3(Q.k2[j], key, Q.k3[j]);
+        Q.k2[j] = imed3(Q.k1[j], key, Q.k2[j]);
+        Q.k1[j] = max(Q.k1[j], key);
+        L[j] = max(L[j], __float_as_int(lo[h]) & (__float_as_int(qi[h]) >> 31));
+      }
+    }
+  };
+  // first sorted position whose U lies below the tile's certain inverse depth (n if none)
+  auto stop_at = [&]() -> uint32_t {
+    const float m0 = __int_as_float(min(min(L[0], L[1]), min(L[2], L[3])));
+    float m = m0 * rlen_lo * kSureRound;
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) m = fminf(m, __shfl_xor(m, x));
+    const int32_t T = __builtin_amdgcn_readfirstlane(__float_as_int(m));
+    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(su[lane] < T);
+    if (b0) return (uint32_t)__builtin_ctzll(b0);
+    if (NR == 2) {
+      const unsigned long long b1 = __builtin_amdgcn_ballot_w64(su[lane + 64] < T);
+      if (b1) return 64u + (uint32_t)__builtin_ctzll(b1);
+    }
+    return n;
+  };
+  RejectRecord<TYPE> A, B;
+  uint32_t stop = n;
+  int gA = entry(0);
+  int gB = entry(1);
+  A.load(record(gA));
+  uint32_t i = 0;
+  for (; i < stop; i += 2) {
+    B.load(record(gB));
+    gA = entry(i + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    op(A, i);
+    if (i + 1 >= stop) { i += 1; break; }
+    __builtin_amdgcn_sched_barrier(0);
+    A.load(record(gA));
+    gB = entry(i + 3);
+    __builtin_amdgcn_sched_barrier(0);
+    op(B, i + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if ((i + 2) % kOcclGroup == 0 && i + 2 < stop) stop = min(stop, stop_at());
+  }
+  return min(i, n);
 }
 
 // Resolve the pixel of lane `src` on the slow path with the whole wave; returns the merged (t, index) minimum of
@@ -851,12 +1028,6 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The finish phase is COMPACTED: after the sweep the tile's pixels that have at least one candidate are queued
 // (row-major) in LDS and handed out 64 at a time, so a tile that is 40 % covered costs two fp64 rounds instead
 // of four; pixels without a candidate are background and stored straight away.
@@ -911,6 +1082,8 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   __shared__ Parked park[kWaves][4][64];      // [wave][pixel of the quad][lane]: conflict-free 16-byte writes
   __shared__ int32_t front[kWaves][4][64];    // global index of each pixel's front candidate (-1: none / saturated)
   __shared__ uint8_t queue[kWaves][256];      // [wave]: ids j * 64 + lane of the pixels with a candidate, row-major
+  __shared__ int32_t occl_g[kWaves][kSortCap];  // occlusion cull: the tile's list in front-to-back order ...
+  __shared__ int32_t occl_u[kWaves][kSortCap];  // ... and its inverse-depth bounds (sweep_sorted)
   const int wave = kWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   int tx, ty;
@@ -940,7 +1113,22 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   // low key bits that hold a candidate's list position (ord_mask_for); the matrix-core measurement build packs its
   // keys with the full 12 bits, so it keeps them everywhere
   const uint32_t ordmask = SRH_MFMA ? kOrdMask : ord_mask_for(listed);
+  bool sorted = false;                        // the keys' fields are positions in occl_g (front-to-back order)
+  uint32_t swept = listed;                    // entries the sweep evaluated (measurement builds report it)
   if (listed) {
+    // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
+    // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
+    int32_t gs[2] = {0, 0};
+#if SRH_OCCLUSION_CULL
+    if (WPT == 1 && BATCH == SRH_PRIM_DISK && !SRH_MFMA && pretest) {
+      const TileLists L{F, tile};
+      if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
+        if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], occl_u[wave], gs);
+        else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], occl_u[wave], gs);
+        sorted = true;
+      }
+    }
+#endif
     const int r = min(r_raw, F.row1 - 1);
     QuadState Q;
     Q.ordmask = ordmask;
@@ -991,7 +1179,17 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       matrix = n_wide + n_bin + 1u <= kOrdMask;
     }
     const int passes = matrix ? (n_wide ? 1 : 0) : 3;
-    if (passes) {
+    if (sorted) {
+      // 1 / |D| is smallest where |D| is largest: |D| is convex in the pixel coordinates, so at a corner of the tile
+      const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
+      const double m2 = fmax(fmax(pixel_len2(F, ca, ra), pixel_len2(F, cb, ra)),
+                             fmax(pixel_len2(F, ca, rb), pixel_len2(F, cb, rb)));
+      float rl = (float)(1.0 / sqrt(m2));
+      rl = (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;           // (0: T = 0, nothing is skipped)
+      const float rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rl)));
+      swept = listed <= 64 ? sweep_sorted<1>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q)
+                           : sweep_sorted<2>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
+    } else if (passes) {
       if (pretest) sweep_tile<true, WPT, BATCH>(F, tile, Q, part, lane, passes);
       else sweep_tile<false, WPT, BATCH>(F, tile, Q, part, lane, passes);
     }
@@ -1070,7 +1268,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       front[wave][j][lane] =
-          (((has >> j) & 1u) && !key_saturated(Q.k1[j], ordmask)) ? ordinal_to_global<BATCH>(F, tile, key_ordinal(Q.k1[j], ordmask)) : -1;
+          (((has >> j) & 1u) && !key_saturated(Q.k1[j], ordmask)) ? ordinal_to_global<BATCH>(F, tile, key_ordinal(Q.k1[j], ordmask), sorted ? occl_g[wave] : nullptr) : -1;
     }
   }
 
@@ -1166,7 +1364,8 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
             if (key_saturated(key, ordmask)) {
               saturated = true;
             } else {
-              const int g = (q == 0) ? gfront : ordinal_to_global<BATCH>(F, tile, key_ordinal(key, ordmask));
+              const int g = (q == 0) ? gfront : ordinal_to_global<BATCH>(F, tile, key_ordinal(key, ordmask),
+                                                                           sorted ? occl_g[wave] : nullptr);
               if (q == 0) g1 = g;
               if (q == 1) g2 = g;
               if (q == 0) resolve_lex(F, fr.hit(F, d), g, best, besti);
@@ -1224,6 +1423,15 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       }
     }
   }
+#ifdef SRH_DIAG_SWEPT   // measurement build: entries swept and listed, in `nearest` at the tile's first two pixels
+  if (nearest && lane == 0 && WPT == 1 && py0 < F.row1) {
+    int32_t* nr = nearest + (size_t)(py0 - F.row0) * F.near_stride + px0;
+    nr[0] = (int32_t)swept;
+    if (px0 + 1 < F.W) nr[1] = (int32_t)listed;
+  }
+#else
+  (void)swept;
+#endif
   // Leave the counters as the next frame's binning needs them: zero -- a frame is then prep-and-bin + render, without a
   // clearing launch in front (SrhParams.counters_clean).  A tile's own bin counters were read by nobody else.  The
   // frame-wide list lengths are read by every tile until the kernel ends: tile 0 zeroes the OTHER set and makes it the

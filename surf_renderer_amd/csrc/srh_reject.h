@@ -13,10 +13,11 @@
 // direction is affine in them:  D(c, r) = D0 + c*Dc + r*Dr   (numpy/renderer.py:152-164).
 //
 // rec32 layouts (floats)
-//   disc (12)      [0] c0 [1] r0 [2] A11 [3] 2*A12 [4] A22 [8], [11] 0 : candidate iff
+//   disc (12)      [0] c0 [1] r0 [2] A11 [3] 2*A12 [4] A22 : candidate iff
 //                  dc*(A11*dc + 2A12*dr) + A22*dr*dr - 1 <= 0,  dc = c - c0, dr = r - r0
 //                  (A = 0: "always a candidate" -- the disc's image is not an ellipse, etc.)
 //                  [5..7] u0 u1 u2 [9] lo_u [10] hi_u : depth estimate, see plane_estimate_record
+//                  [8] U [11] s_in : occlusion fields, see disk_reject_record
 //   sphere (12)    [0..4] as the disc; [5] upper bound of 1 / t for the whole sphere (1e30: none)
 //   triangle (16)  {a_i, b_i, g_i} at [4i..4i+2], i < 3: candidate iff min_i(a_i*c + b_i*r + g_i) >= 0
 //                  [3] u0 [7] u1 [11] u2 [13] lo_u [14] hi_u
@@ -112,8 +113,15 @@ __device__ inline void plane_estimate_record(const double n[3], double k, const 
 // Tm = A11 X^2 + 2|A12| X Y + A22 Y^2 + 1 with X = hc + 34, Y = hr + 34 (hc, hr = half extents of the box) bounds the
 // sum of the absolute terms of either evaluation; each commits at most 2.6 * 2^-20 Tm, `rel` is 2^-18 Tm.  A point
 // inside the true ellipse has A d.d <= 1, hence value <= 1 / thr - 1 <= -rel / (1 + rel) after the inflation.
+//
+// `sure_in` (optional) receives the INWARD counterpart: an fp32 value q < sure_in of the kernel's evaluation (with its
+// -1.00000024, pair_bounds) proves that the pixel lies inside the ellipse with room to spare -- the value carries at most
+// rel + 2^-22 of evaluation error, the centre moves by at most delta, and what is left shrinks the radius by another
+// (grow - 1) + 2^-10 of itself for the fp64 path's own roundings (twice the position slack the outward margin grants
+// them, plus 2^-10).  -1e30 when nothing is provably inside.
 __device__ inline double conic_record(double T00, double T01, double T02, double T11, double T12, double T22,
-                                      int W, int H, float* out) {
+                                      int W, int H, float* out, double* sure_in = nullptr) {
+  if (sure_in) *sure_in = -1.0e30;
   rec_zero(out, 5);
   out[11] = 0.0f;
   const double det = T11 * T22 - T12 * T12;
@@ -151,6 +159,8 @@ __device__ inline double conic_record(double T00, double T01, double T02, double
   out[2] = (float)(A11 * it);
   out[3] = (float)(2.0 * A12 * it);
   out[4] = (float)(A22 * it);
+  const double shrink = 1.0 - 2.0 * (grow - 1.0) - 9.765625e-4;
+  if (sure_in && shrink > 0.0) *sure_in = shrink * shrink * it - 1.0 - rel - 4.76837158203125e-7;
   return smax * sqrt(thr);
 }
 
@@ -202,8 +212,13 @@ __device__ inline void sphere_conic_record(const double oc[3], double cq, double
 }
 
 // disc: | oc (n.D) + k D |^2 <= r^2 (n.D)^2   (numpy/renderer.py:69,85-88 with t = k / (n.D))
+// Occlusion fields (the front-to-back sweep of the binned disc kernel, srh_binned.h):
+//   [8]  U = upper bound of 1 / t over every valid hit (ball_inverse_depth_bound; 1e30: none)
+//   [11] s_in: a pixel whose fp32 value q (pair_bounds) is < s_in is a CERTAIN valid hit (conic_record's sure_in) --
+//        only for a trusted, non-degenerate ellipse with finite, moderate coefficients whose whole ball lies inside
+//        [near, far] with margin; -1e30 (never) otherwise.  Its depth is then bounded through den (see sure_den_shift).
 __device__ inline void disk_reject_record(const double* R, const double o[3], const PixelBasis& B, int W, int H,
-                                          float* out) {
+                                          double near_clip, double far_clip, float* out) {
   const double* n = R;
   const double k = R[3];
   const double oc[3] = {o[0] - R[4], o[1] - R[5], o[2] - R[6]};
@@ -239,7 +254,9 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
       }
   }
   bool degenerate = true;
-  if (conic_trusted(tmax, emax)) degenerate = conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out) < 0.0;
+  double sure_in = -1.0e30;
+  if (conic_trusted(tmax, emax))
+    degenerate = conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out, &sure_in) < 0.0;
   if (degenerate) {
     // The disc's own image is not a usable ellipse (seen edge-on: axis ratio beyond 512, parameters are noise).
     // Every hit lies on the disc, hence inside the sphere around its centre with its radius, and that sphere's
@@ -263,6 +280,16 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
     out[5] = (u < 1.0e30 && isfinite(u)) ? (float)u * 1.0000002f : 1.0e30f;
     out[6] = out[7] = 0.0f; out[9] = 3.0e38f; out[10] = -3.0e38f;
   }
+  const double r = sqrt(r2);
+  out[8] = ball_inverse_depth_bound(oc, r);
+  // certain hits: every point of the ball (hence every fp64 hit, whose distance ball_inverse_depth_bound's 2^-22 covers)
+  // lies in [near, far], and the record's values stay finite at every pixel (no inf - inf, no NaN sign bit to read)
+  const double l = sqrt(dot3(oc, oc)), slack = 9.5367431640625e-7 * (l + r);
+  bool sure = !degenerate && near_clip > 0.0 && (l - r) - slack > near_clip && (l + r) + slack < far_clip &&
+              sure_in > -1.0 && out[9] < 1.0e30f;
+  for (int i = 0; i < 11; ++i) sure = sure && fabsf(out[i]) < 1.0e30f;
+  sure = sure && fabsf(out[2]) < 1.0e6f && fabsf(out[3]) < 1.0e6f && fabsf(out[4]) < 1.0e6f;
+  out[11] = sure ? (float)sure_in : -1.0e30f;
 }
 
 // sphere: the ray's line meets it iff (oc.D)^2 - |D|^2 (|oc|^2 - r^2) >= 0   (numpy/renderer.py:20-25).
