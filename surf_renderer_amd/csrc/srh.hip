@@ -178,11 +178,7 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
       F.neardist[S.first + i] = nd;
     }
     const TileBox box = bin_primitive(F, s, TYPE, Q, S.first + i, set, near_eye);
-#if SRH_FUSE_BIN
-    if (box.tx0 <= box.tx1) bin_place<1>(F, s, TYPE, S.first, Q, S.first + i, 0, box.tx0, box.ty0, box.tx1, box.ty1, set);
-#else
-    (void)box;
-#endif
+    if (box.tx0 <= box.tx1) bin_place(F, s, TYPE, S.first, Q, S.first + i, box.tx0, box.ty0, box.tx1, box.ty1, set);
   }
 }
 
@@ -190,12 +186,9 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
 // the disc instantiation once the fp64 trust terms of srh_reject.h went in, three waves per SIMD -- and the prep waves of
 // the frames in flight then hold their slots longer beside the render waves: config 5 went from 0.078 to 0.093 ms per
 // frame on that alone.  At 128 the compiler needs no spills.
-#ifndef SRH_PREP_WAVES
-#define SRH_PREP_WAVES 4
-#endif
-#define SRH_PREP_ATTR __attribute__((amdgpu_waves_per_eu(SRH_PREP_WAVES)))
+constexpr int kPrepWaves = 4;
 template <int TYPE>
-__global__ __launch_bounds__(kBinBlock) SRH_PREP_ATTR void k_prep(FrameDev F, int s, double* rec64, float* rec32) {
+__global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrepWaves))) void k_prep(FrameDev F, int s, double* rec64, float* rec32) {
   // the frame's constants into the workspace, where the render kernel reads them (FrameDev::self; srh_binned.h)
   if (F.self && s == 0 && blockIdx.x == 0) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&F);
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(kBinBlock) SRH_PREP_ATTR void k_prep(FrameDev F, in
 }
 
 template <int TYPE>
-__global__ __launch_bounds__(kBinBlock) SRH_PREP_ATTR void k_prep_views(const FrameDev* __restrict__ Fs, int s) {
+__global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrepWaves))) void k_prep_views(const FrameDev* __restrict__ Fs, int s) {
   const FrameDev& F = Fs[blockIdx.y];
   prep_body<TYPE>(F, s, const_cast<double*>(F.seg[s].rec64), const_cast<float*>(F.seg[s].rec32));
 }
@@ -607,9 +600,6 @@ WsLayout layout_for(const SrhObjects* ob, int width, int height) {
   const size_t ntiles = ((size_t)L.tiles_x * L.tiles_y_max + 3) / 4 * 4;
   L.tilerange = off;
   off = align_up(off + total * 4 * sizeof(uint16_t));
-#ifdef SRH_WS_SHIFT      // measurement build: extra bytes in front of the counters / lists (the layout moves the frame time)
-  off = align_up(off + (size_t)(SRH_WS_SHIFT));
-#endif
   L.counters = off;
   L.counters_bytes = (kCounterPad + SRH_MAX_SEGMENTS * ntiles) * sizeof(uint32_t);
   off = align_up(off + L.counters_bytes);
@@ -668,9 +658,6 @@ int camera_to_frame(const SrhCamera* cam, FrameDev* F, bool orthonormal = false)
   bool ok = ordinary(F->half_w) && F->half_w != 0.0 && ordinary(F->half_h) && F->half_h != 0.0 &&
             ordinary(F->focal) && F->focal != 0.0;
   for (int i = 0; i < 3; ++i) ok = ok && ordinary(F->bx[i]) && ordinary(F->by[i]) && ordinary(F->bz[i]);
-#ifdef SRH_ABL_NODIVSHARE
-  ok = false;
-#endif
   F->div_shared = ok ? 1 : 0;
   F->ortho = cam->ortho ? 1 : 0;
   return SRH_OK;
@@ -841,18 +828,12 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
   if (stages & ~(SRH_STAGE_BIN | SRH_STAGE_RENDER | SRH_STAGE_KEEP_BINS)) return fail(SRH_E_TYPE, "unknown stages mask %d", params->stages);
   if ((stages & (SRH_STAGE_BIN | SRH_STAGE_RENDER)) != (SRH_STAGE_BIN | SRH_STAGE_RENDER) && mode != SRH_MODE_BINNED)
     return fail(SRH_E_TYPE, "SrhParams.stages splits binned frames only");
-  const bool abl_skip_binning = !(stages & SRH_STAGE_BIN), abl_skip_render = !(stages & SRH_STAGE_RENDER);
+  const bool run_binning = (stages & SRH_STAGE_BIN) != 0, run_render = (stages & SRH_STAGE_RENDER) != 0;
   if (mode == SRH_MODE_BINNED) setup_binning(F, L, workspace);
   F.keep_bins = (stages & SRH_STAGE_KEEP_BINS) ? 1 : 0;
-#if SRH_FRAME_MEM
   if (mode == SRH_MODE_BINNED) F.self = (FrameDev*)((char*)workspace + L.frame);
-#endif
-#ifdef SRH_ALWAYS_ZERO      // measurement build: the clearing launch of every frame, as before ABI 10
-  const bool counters_clean = false;
-#else
   const bool counters_clean = params->counters_clean != 0;
-#endif
-  if (mode == SRH_MODE_BINNED && !abl_skip_binning && !counters_clean) {
+  if (mode == SRH_MODE_BINNED && run_binning && !counters_clean) {
     // The bin counters start every frame at zero.  The render kernel leaves them that way (render_binned_body), so
     // a workspace that goes from frame to frame needs this launch only the first time (SrhParams.counters_clean).
     // A kernel, not hipMemsetAsync: captured into a hipGraph and replayed beside a live RCCL process group a memset
@@ -861,42 +842,30 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
     hipLaunchKernelGGL(k_zero_counters, dim3((unsigned)((ncount + 1023) / 1024)), dim3(256), 0, st, F.counters, (uint32_t)ncount);
   }
 
-  for (int s = 0; s < F.nseg && !abl_skip_binning; ++s) {
+  for (int s = 0; s < F.nseg && run_binning; ++s) {
     launch_prep(F, s, st);
   }
-  if (mode == SRH_MODE_BINNED && !abl_skip_binning) {
-#if !SRH_FUSE_BIN
-    hipLaunchKernelGGL(k_bin_count, dim3((unsigned)(((size_t)F.total * kCountLanes + kBinBlock - 1) / kBinBlock)), dim3(kBinBlock), 0, st, F);
-#endif
-  }
   if (params->ev_start) (void)hipEventRecord((hipEvent_t)params->ev_start, st);
-  if (abl_skip_render) {
+  if (!run_render) {
   } else if (mode == SRH_MODE_BINNED) {
-    const unsigned groups = binned_grid(F);   // whole regions of tiles, a multiple of 8 of them (see k_render_binned)
+    const unsigned groups = binned_grid(F);   // whole regions of tiles, a multiple of 8 of them (see binned_grid)
     // one wave per tile while that still gives every SIMD several waves; four waves per tile for small frames / slabs
     const bool split = (params->waves_per_tile == 1 || params->waves_per_tile == 4) ? params->waves_per_tile == 4
                                                                                    : binned_waves_per_tile(F) == 4;
-    const dim3 g4(groups * 4), b4(256), g1(groups * (4 / kWavesPerGroup1)), b1(64 * kWavesPerGroup1);
+    const dim3 g4(groups * 4), b4(256), g1(groups * 4), b1(64);
     // one object batch of a known type: the instantiation without per-batch generality and without the other types' code
     const int batch = F.nseg == 1 ? F.seg[0].type : -1;
-#if SRH_FRAME_MEM
     // the render kernel reads the frame's constants from the workspace: k_prep of batch 0 put them there, unless this
     // call renders from bins an earlier call made
-    if (abl_skip_binning) hipLaunchKernelGGL(k_put_frame, dim3(1), dim3(64), 0, st, F);
+    if (!run_binning) hipLaunchKernelGGL(k_put_frame, dim3(1), dim3(64), 0, st, F);
     const FrameConstPtr Fc = (FrameConstPtr)F.self;
-#define SRH_RENDER_KERNEL k_render_binned_mem
-#define SRH_RENDER_FRAME Fc
-#else
-#define SRH_RENDER_KERNEL k_render_binned
-#define SRH_RENDER_FRAME F
-#endif
 #define SRH_LAUNCH_BINNED(TCH_, WPT_, G_, B_)                                                                          \
     switch (batch) {                                                                                                   \
-      case SRH_PRIM_DISK: hipLaunchKernelGGL((SRH_RENDER_KERNEL<TCH_, WPT_, SRH_PRIM_DISK>), G_, B_, 0, st, SRH_RENDER_FRAME, image, depth, nearest); break;       \
-      case SRH_PRIM_PLANE: hipLaunchKernelGGL((SRH_RENDER_KERNEL<TCH_, WPT_, SRH_PRIM_PLANE>), G_, B_, 0, st, SRH_RENDER_FRAME, image, depth, nearest); break;     \
-      case SRH_PRIM_SPHERE: hipLaunchKernelGGL((SRH_RENDER_KERNEL<TCH_, WPT_, SRH_PRIM_SPHERE>), G_, B_, 0, st, SRH_RENDER_FRAME, image, depth, nearest); break;   \
-      case SRH_PRIM_TRIANGLE: hipLaunchKernelGGL((SRH_RENDER_KERNEL<TCH_, WPT_, SRH_PRIM_TRIANGLE>), G_, B_, 0, st, SRH_RENDER_FRAME, image, depth, nearest); break; \
-      default: hipLaunchKernelGGL((SRH_RENDER_KERNEL<TCH_, WPT_, -1>), G_, B_, 0, st, SRH_RENDER_FRAME, image, depth, nearest); break;  \
+      case SRH_PRIM_DISK: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_DISK>), G_, B_, 0, st, Fc, image, depth, nearest); break;       \
+      case SRH_PRIM_PLANE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_PLANE>), G_, B_, 0, st, Fc, image, depth, nearest); break;     \
+      case SRH_PRIM_SPHERE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_SPHERE>), G_, B_, 0, st, Fc, image, depth, nearest); break;   \
+      case SRH_PRIM_TRIANGLE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_TRIANGLE>), G_, B_, 0, st, Fc, image, depth, nearest); break; \
+      default: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, -1>), G_, B_, 0, st, Fc, image, depth, nearest); break;  \
     }
     if (F.shading) {
       if (split) { SRH_LAUNCH_BINNED(true, 4, g4, b4) } else { SRH_LAUNCH_BINNED(true, 1, g1, b1) }
@@ -904,8 +873,6 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
       if (split) { SRH_LAUNCH_BINNED(false, 4, g4, b4) } else { SRH_LAUNCH_BINNED(false, 1, g1, b1) }
     }
 #undef SRH_LAUNCH_BINNED
-#undef SRH_RENDER_KERNEL
-#undef SRH_RENDER_FRAME
   } else if (mode == SRH_MODE_EXACT) {
     const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
     if (F.ortho) hipLaunchKernelGGL(k_render_ortho, grid, block, 0, st, F, image, depth, nearest);
@@ -1083,15 +1050,12 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     hipLaunchKernelGGL(k_views_zero, dim3((unsigned)((ncount + 255) / 256), V), dim3(256), 0, st, Fs);
   for (int s = 0; s < F0.nseg; ++s)
     launch_prep_views(F0, Fs, s, V, st);
-#if !SRH_FUSE_BIN
-  hipLaunchKernelGGL(k_bin_count_views, dim3((unsigned)(((size_t)F0.total * kCountLanes + kBinBlock - 1) / kBinBlock), V), dim3(kBinBlock), 0, st, Fs);
-#endif
   const unsigned groups = binned_grid(F0);
   // all views share the GPU, so the batch as a whole decides the launch shape
   const bool split = (params->waves_per_tile == 1 || params->waves_per_tile == 4)
-                         ? params->waves_per_tile == 4 : (size_t)F0.ntiles * V < (size_t)SRH_SPLIT_TILES;
+                         ? params->waves_per_tile == 4 : (size_t)F0.ntiles * V < (size_t)kSplitTiles;
   {
-    const dim3 g4(groups * 4, V), b4(256), g1(groups * (4 / kWavesPerGroup1), V), b1(64 * kWavesPerGroup1);
+    const dim3 g4(groups * 4, V), b4(256), g1(groups * 4, V), b1(64);
     const int batch = F0.nseg == 1 ? F0.seg[0].type : -1;        // as in srh_render_fwd: the typed instantiation
 #define SRH_LAUNCH_VIEWS(TCH_, WPT_, G_, B_)                                                                            \
     switch (batch) {                                                                                                   \
@@ -1208,9 +1172,6 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
   hipLaunchKernelGGL(k_views_zero, dim3((unsigned)((ncount + 255) / 256), V), dim3(256), 0, st, frames);
   for (int s = 0; s < T.nseg; ++s)
     launch_prep_views(T, frames, s, V, st);
-#if !SRH_FUSE_BIN
-  hipLaunchKernelGGL(k_bin_count_views, dim3((unsigned)(((size_t)T.total * kCountLanes + kBinBlock - 1) / kBinBlock), V), dim3(kBinBlock), 0, st, frames);
-#endif
   hipLaunchKernelGGL(k_shadow_shade_binned, grid, block, 0, st, F, frames, image, depth, nearest, visibility);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SRH_OK : hip_fail(e, "shadow launch");

@@ -364,11 +364,9 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
 //   kImage  grad_image is read and the shading differentiated.  Without it both light loops and every light /
 //           material / colour accumulation drop out: a geometry-only backward for losses on normal / pos / depth.
 // <false, true> is srh_render_bwd's kernel (the two trailing arguments are unused there).
-#ifndef SRH_BWD_TCH_WAVES
-#define SRH_BWD_TCH_WAVES 3
-#endif
+constexpr int kBwdTchWaves = 3;
 template <bool kAux, bool kImage>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SRH_BWD_TCH_WAVES))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
                                                          const float* __restrict__ grad_depth,
                                                          const int32_t* __restrict__ nearest,
                                                          const float* __restrict__ depth,

@@ -5,8 +5,7 @@
 //                      the bin's counter claims a slot of the bin's fixed-capacity list and the index goes there
 //                      (bin_place).  One pass over the primitives, no count / scan / fill.  A bin that is full sends
 //                      the primitive to the `large` list instead, which every tile tests.
-//   k_bin_count        the placement as a kernel of its own, two lanes per primitive (build switch SRH_FUSE_BIN=0)
-//   k_render_binned    per tile: sweep the tile's primitives, confirm the front one per pixel, shade, store
+//   k_render_binned_mem  per tile: sweep the tile's primitives, confirm the front one per pixel, shade, store
 //
 // A bin is (object batch, tile): every list the render kernel walks holds primitives of ONE type, so its
 // loops are specialised per type and the primitive stream is wave-uniform -- list entries and reject records
@@ -62,50 +61,26 @@ __device__ inline TileBox bin_primitive(const FrameDev& F, int seg, int type, co
   return TileBox{tx0, ty0, tx1, ty1};
 }
 
-__device__ __forceinline__ int rec32_stride(int type) {
-  return type == SRH_PRIM_DISK ? kRec32Stride[0] : type == SRH_PRIM_PLANE ? kRec32Stride[1]
-       : type == SRH_PRIM_SPHERE ? kRec32Stride[2] : kRec32Stride[3];
-}
+// Workgroup size of the per-primitive kernel (k_prep): ONE wave.  It runs beside other frames' render kernels, whose
+// single-wave workgroups refill every slot the moment it is free; a four-wave workgroup would wait for four free slots
+// on one CU and starve.  (Measured together with the render kernel's workgroup size below: 256/4 0.0850 ms per frame
+// at config 5, 256/1 0.0948-0.0980, 64/1 0.0816.)
+constexpr int kBinBlock = 64;
 
-// Workgroup size of the per-primitive kernels (prep, count): ONE wave.  They run beside other frames' render
-// kernels, whose single-wave workgroups refill every slot the moment it is free; a four-wave workgroup would wait for
-// four free slots on one CU and starve.  (Measured together with SRH_GROUP_WAVES below: 256/4 0.0850 ms per frame at
-// config 5, 256/1 0.0948-0.0980, 64/1 0.0816.)
-#ifndef SRH_BIN_BLOCK
-#define SRH_BIN_BLOCK 64
-#endif
-constexpr int kBinBlock = SRH_BIN_BLOCK;
-// Place the primitive from k_prep itself (a thread per primitive walks its box right after it built the record): no
-// count kernel, and nobody reads the reject record back from another XCD.
-#ifndef SRH_FUSE_BIN
-#define SRH_FUSE_BIN 1
-#endif
-#ifndef SRH_COUNT_LANES
-#define SRH_COUNT_LANES 2
-#endif
-constexpr int kCountLanes = SRH_COUNT_LANES;
-
-// ---- count: kCountLanes lanes per primitive, one tile of its box per lane and step ------------------------------
-// Of the (at most 64) tiles of the box keep those the reject shape really reaches and that are not provably behind
-// the eye; bit k of the primitive's tile mask = k-th tile of the box, row-major.  k_prep leaves this to a kernel of
-// its own because a thread per primitive walking up to 64 tiles in fp64 is a long serial chain on a launch that
-// has only a wave or two per SIMD.
-// The tiles of primitive gidx's box that its reject shape really reaches: kLanes lanes share the box (lane `sub` takes
-// tiles sub, sub + kLanes, ...).
-#ifndef SRH_BIN_CLAIMS
-#define SRH_BIN_CLAIMS 4
-#endif
-constexpr int kClaims = SRH_BIN_CLAIMS;
-template <int kLanes>
+// ---- placement: the thread of k_prep that built a primitive's record walks its box of tiles ---------------------
+// No count kernel, and nobody reads the reject record back from another XCD.  Of the (at most 64) tiles of the box
+// keep those the reject shape really reaches and that are not provably behind the eye; bit k of the primitive's tile
+// mask = k-th tile of the box, row-major.
+constexpr int kClaims = 4;
 __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, int first, const float* rec32, int gidx,
-                                          int sub, int tx0, int ty0, int tx1, int ty1, uint32_t set) {
+                                          int tx0, int ty0, int tx1, int ty1, uint32_t set) {
   uint32_t* count = F.counters + kCounterPad + seg * F.ntiles_pad;
   const int nx = tx1 - tx0 + 1, n = nx * (ty1 - ty0 + 1);
   const RectTest T(type, rec32, F.near_clip > 0.0);
   // pass 1, arithmetic only: bit k of `mask` = tile k of the box (row-major) is reached
   const uint32_t inv_nx = 65536u / (uint32_t)nx + 1u;            // k / nx == (k * inv_nx) >> 16 for k < 64, nx <= 64
   uint64_t mask = 0;
-  for (int k = sub; k < n; k += kLanes) {
+  for (int k = 0; k < n; ++k) {
     const int dy = (int)(((uint32_t)k * inv_nx) >> 16);
     const int tx = tx0 + (k - dy * nx), ty = ty0 + dy;
     const double pc0 = tx * kTile - F.bin_pad, pr0 = F.row0 + ty * kTile - F.bin_pad;
@@ -140,29 +115,10 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
   }
   // a full bin: the primitive joins the batch's `large` list (tested by every tile) -- once, whatever the number of
   // full bins; the bins that did take it keep it, a duplicate candidate changes no result
-#pragma unroll
-  for (int m = 1; m < kLanes; m <<= 1) over |= __shfl_xor(over, m);
-  if (sub == 0 && over) {
+  if (over) {
     const uint32_t at = atomicAdd(&F.counters[4u * set + seg], 1u);
     if (at < (uint32_t)F.seg[seg].count) F.large[first + at] = (uint32_t)gidx;
   }
-}
-
-__device__ __forceinline__ void bin_count_body(const FrameDev& F) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int gidx = t / kCountLanes, sub = t % kCountLanes;
-  if (gidx >= F.total) return;                                  // whole lane groups leave together
-  const uint16_t* tr = F.tilerange + 4 * (size_t)gidx;
-  const int tx0 = tr[0], ty0 = tr[1], tx1 = tr[2], ty1 = tr[3];
-  if (tx0 > tx1) return;
-  const int seg = segment_of(F, gidx);
-  int type = F.seg[0].type, first = F.seg[0].first;
-  const float* base = F.seg[0].rec32;
-#pragma unroll
-  for (int i = 1; i < SRH_MAX_SEGMENTS; ++i)
-    if (seg == i) { type = F.seg[i].type; first = F.seg[i].first; base = F.seg[i].rec32; }
-  const float* rec32 = base + (size_t)(gidx - first) * rec32_stride(type);
-  bin_place<kCountLanes>(F, seg, type, first, rec32, gidx, sub, tx0, ty0, tx1, ty1, F.counters[kLargeNext] & 1u);
 }
 
 // the bin's list and its length (bin = seg * ntiles_pad + tile)
@@ -177,8 +133,6 @@ __device__ __forceinline__ uint32_t bin_length(const FrameDev& F, int bin) {
 __device__ __forceinline__ uint32_t large_length(const FrameDev& F, int s) {
   return min(F.counters[4u * (F.counters[kLargeNow] & 1u) + s], (uint32_t)F.seg[s].count);
 }
-
-__global__ __launch_bounds__(kBinBlock) void k_bin_count(FrameDev F) { bin_count_body(F); }
 
 // counters <- 0 (four words per thread)
 __global__ __launch_bounds__(256) void k_zero_counters(uint32_t* __restrict__ counters, uint32_t n) {
@@ -222,14 +176,8 @@ __global__ __launch_bounds__(256) void k_zero_counters(uint32_t* __restrict__ co
 constexpr uint32_t kOrdMask = 0xFFFu;
 constexpr int32_t kNoKey = 0;
 constexpr float kNoEstimate = 1.0e30f;
-#ifndef SRH_SERIAL_SLOW_MAX
-#define SRH_SERIAL_SLOW_MAX 2
-#endif
-constexpr int kSerialSlowMax = SRH_SERIAL_SLOW_MAX;   // more undecided pixels than this in a round: lane-parallel re-sweep
-#ifndef SRH_KEYS
-#define SRH_KEYS 4
-#endif
-constexpr int kKeys = SRH_KEYS;             // keys tracked per pixel: kKeys - 1 are confirmed in fp64, the last is a bound only
+constexpr int kSerialSlowMax = 2;           // more undecided pixels than this in a round: lane-parallel re-sweep
+constexpr int kKeys = 4;                    // keys tracked per pixel: kKeys - 1 are confirmed in fp64, the last is a bound only
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -480,7 +428,7 @@ __device__ __forceinline__ void sweep_entry(const RejectRecord<TYPE>& R, uint32_
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int32_t key = pack_key(inv[j >> 1][j & 1], field, keep) & sel[j];
-    if (kKeys == 4) Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
+    Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
     Q.k3[j] = imed3(Q.k2[j], key, Q.k3[j]);
     Q.k2[j] = imed3(Q.k1[j], key, Q.k2[j]);
     Q.k1[j] = max(Q.k1[j], key);
@@ -531,69 +479,16 @@ __device__ __forceinline__ void stream_list(const SegDev& S, const uint32_t* __r
   }
 }
 
-// The same stream fed by VECTOR loads: lane l fetches list entry l of a 64-entry chunk and that entry's record
-// (one coalesced list load, then kQuads 16-byte gathers per lane -- 64 records in flight at once, and the next chunk's
-// while this one is evaluated); entry e's record then reaches the scalar registers by v_readlane.  Costs one readlane
-// per record word instead of the scalar loads, but a record's latency is paid once per chunk, not once per entry.
-#ifndef SRH_SWEEP_VEC
-#define SRH_SWEEP_VEC 0
-#endif
-template <int TYPE, int WPT, class Op>
-__device__ __forceinline__ void stream_list_vec(const SegDev& S, const uint32_t* __restrict__ list, uint32_t n_all,
-                                                uint32_t ord0, uint32_t part, int lane, Op&& op, uint32_t ordmask = kOrdMask) {
-  if (n_all <= part) return;
-  constexpr int kQuads = kRec32Stride[TYPE] / 4;
-  const uint32_t n = (n_all - part + WPT - 1) / WPT;
-  const float4* base = reinterpret_cast<const float4*>(S.rec32);
-  const int first = S.first;
-  float4 cur[kQuads], nxt[kQuads];
-  auto fetch = [&](uint32_t c0, float4 (&dst)[kQuads]) {
-    const uint32_t k = min(c0 + (uint32_t)lane, n - 1);          // clamped: the spare lanes reload a valid record
-    const int g = (int)list[k * WPT + part];
-    const float4* r = base + (size_t)(g - first) * kQuads;
-#pragma unroll
-    for (int q = 0; q < kQuads; ++q) dst[q] = r[q];
-  };
-  fetch(0, cur);
-  for (uint32_t c0 = 0; c0 < n; c0 += 64) {
-    const bool more = c0 + 64 < n;
-    if (more) fetch(c0 + 64, nxt);
-    const uint32_t m = min(64u, n - c0);
-#pragma unroll 1
-    for (uint32_t e = 0; e < m; ++e) {
-      RejectRecord<TYPE> A;
-#pragma unroll
-      for (int q = 0; q < kQuads; ++q) {
-        A.v[4 * q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur[q].x), (int)e));
-        A.v[4 * q + 1] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur[q].y), (int)e));
-        A.v[4 * q + 2] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur[q].z), (int)e));
-        A.v[4 * q + 3] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur[q].w), (int)e));
-      }
-      op(A, 0, min(ord0 + (c0 + e) * WPT + part + 1, ordmask));
-    }
-    if (more) {
-#pragma unroll
-      for (int q = 0; q < kQuads; ++q) cur[q] = nxt[q];
-    }
-  }
-}
-
 template <int TYPE, bool PRETEST, int WPT, bool DENKEYS>
 __device__ __forceinline__ void sweep_list(const SegDev& S, const uint32_t* __restrict__ list, uint32_t n_all,
-                                           uint32_t ord0, QuadState& Q, uint32_t part, int lane) {
-#if SRH_SWEEP_VEC
-  stream_list_vec<TYPE, WPT>(S, list, n_all, ord0, part, lane, [&](const RejectRecord<TYPE>& R, int, uint32_t field) {
-    sweep_entry<TYPE, PRETEST, DENKEYS>(R, field, Q);
-  }, Q.ordmask);
-#else
+                                           uint32_t ord0, QuadState& Q, uint32_t part) {
   stream_list<TYPE, WPT>(S, list, n_all, ord0, part, [&](const RejectRecord<TYPE>& R, int, uint32_t field) {
     sweep_entry<TYPE, PRETEST, DENKEYS>(R, field, Q);
   }, Q.ordmask);
-#endif
 }
 
 // Keys of the one-batch kernels of PLANAR primitives hold den = inv |D| instead of inv (see pair_bounds): one packed
-// multiply per entry less, and it is the unit the matrix path produces.  Spheres carry a per-sphere inverse depth, and
+// multiply per entry less.  Spheres carry a per-sphere inverse depth, and
 // the all-types kernel mixes them with the others: those keep inv.
 __host__ __device__ constexpr bool den_keys(int batch) {
   return batch == SRH_PRIM_DISK || batch == SRH_PRIM_TRIANGLE || batch == SRH_PRIM_PLANE;
@@ -677,19 +572,13 @@ struct TileLists {
     return pass == 0 ? F.large + F.seg[s].first : bin_list(F, s * F.ntiles_pad + tile);
   }
   __device__ __forceinline__ uint32_t count(int s, int pass) const {
-#ifdef SRH_ABL_NOLOOP
-    return 0;
-#else
     const int bin = s * F.ntiles_pad + tile;
     return pass == 0 ? large_length(F, s) : bin_length(F, bin);
-#endif
   }
 };
 
-// `passes`: bit 0 = the frame-wide lists, bit 1 = the tile's bins (a list that is left out still counts its ordinals)
 template <bool PRETEST, int WPT, int BATCH = -1>
-__device__ __forceinline__ void sweep_tile(const FrameDev& F, int tile, QuadState& Q, uint32_t part, int lane,
-                                           int passes = 3) {
+__device__ __forceinline__ void sweep_tile(const FrameDev& F, int tile, QuadState& Q, uint32_t part) {
   const TileLists L{F, tile};
   uint32_t ord0 = 0;
   for (int s = 0; s < ((BATCH >= 0) ? 1 : F.nseg); ++s) {
@@ -698,13 +587,12 @@ __device__ __forceinline__ void sweep_tile(const FrameDev& F, int tile, QuadStat
     for (int pass = 0; pass < 2; ++pass) {
       const uint32_t* list = L.list(s, pass);
       const uint32_t n = L.count(s, pass);
-      if (!((passes >> pass) & 1)) { ord0 += n; continue; }
       constexpr bool DK = den_keys(BATCH);
       switch (BATCH >= 0 ? BATCH : S.type) {
-        case SRH_PRIM_DISK: sweep_list<SRH_PRIM_DISK, PRETEST, WPT, DK>(S, list, n, ord0, Q, part, lane); break;
-        case SRH_PRIM_PLANE: sweep_list<SRH_PRIM_PLANE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part, lane); break;
-        case SRH_PRIM_SPHERE: sweep_list<SRH_PRIM_SPHERE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part, lane); break;
-        default: sweep_list<SRH_PRIM_TRIANGLE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part, lane); break;
+        case SRH_PRIM_DISK: sweep_list<SRH_PRIM_DISK, PRETEST, WPT, DK>(S, list, n, ord0, Q, part); break;
+        case SRH_PRIM_PLANE: sweep_list<SRH_PRIM_PLANE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part); break;
+        case SRH_PRIM_SPHERE: sweep_list<SRH_PRIM_SPHERE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part); break;
+        default: sweep_list<SRH_PRIM_TRIANGLE, PRETEST, WPT, DK>(S, list, n, ord0, Q, part); break;
       }
       ord0 += n;
     }
@@ -757,11 +645,7 @@ __device__ __forceinline__ void wave_lds_fence() {
 #ifndef SRH_OCCLUSION_CULL
 #define SRH_OCCLUSION_CULL 1
 #endif
-#ifndef SRH_OCCL_GROUP
-#define SRH_OCCL_GROUP 8
-#endif
-constexpr uint32_t kOcclGroup = SRH_OCCL_GROUP;     // entries between two thresholds (even: the sweep goes in pairs)
-static_assert(kOcclGroup % 2 == 0 && kOcclGroup >= 2, "SRH_OCCL_GROUP");
+constexpr uint32_t kOcclGroup = 8;                  // entries between two thresholds (even: the sweep goes in pairs)
 constexpr uint32_t kSortCap = 128;                  // entries one wave sorts (two per lane); longer lists: the plain sweep
 constexpr uint32_t kSortLow = 0x7Fu;                // low key bits: the list position
 // den - 3 E / K <= s (n^.D) / K for the fp32 den of the vector path AND the fp64 path's own n^.d (plane_estimate_record:
@@ -830,10 +714,9 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
 // The sweep of a sorted list: stream_list's pipelined pairs (records by scalar loads from wave-uniform addresses), the
 // list words by v_readlane from gs[], the key update of sweep_entry, and per pixel
 //   L = max(L, bits(den - shift) & (q < s_in ? ~0 : 0))      (a negative lower bound never beats the initial 0)
-// Returns the number of entries swept.
 // `rlen_lo` <= 1 / |D| at every pixel of the tile (the disc kernel's Q.rlen is 1: its keys are in den units).
 template <int NR>
-__device__ __forceinline__ uint32_t sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
+__device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
                                                  const int32_t* su, int lane, float rlen_lo, QuadState& Q) {
   constexpr int TYPE = SRH_PRIM_DISK;
   const char* base_c = reinterpret_cast<const char*>(S.rec32) - (size_t)S.first * (size_t)(4 * kRec32Stride[TYPE]);
@@ -860,7 +743,7 @@ __device__ __forceinline__ uint32_t sweep_sorted(const SegDev& S, uint32_t n, co
       for (int h = 0; h < 2; ++h) {
         const int j = 2 * p + h;
         const int32_t key = pack_key(den[p][h], field, keep) & sel[j];
-        if (kKeys == 4) Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
+        Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
         Q.k3[j] = imed3(Q.k2[j], key, Q.k3[j]);
         Q.k2[j] = imed3(Q.k1[j], key, Q.k2[j]);
         Q.k1[j] = max(Q.k1[j], key);
@@ -888,13 +771,12 @@ __device__ __forceinline__ uint32_t sweep_sorted(const SegDev& S, uint32_t n, co
   int gA = entry(0);
   int gB = entry(1);
   A.load(record(gA));
-  uint32_t i = 0;
-  for (; i < stop; i += 2) {
+  for (uint32_t i = 0; i < stop; i += 2) {
     B.load(record(gB));
     gA = entry(i + 2);
     __builtin_amdgcn_sched_barrier(0);
     op(A, i);
-    if (i + 1 >= stop) { i += 1; break; }
+    if (i + 1 >= stop) break;
     __builtin_amdgcn_sched_barrier(0);
     A.load(record(gA));
     gB = entry(i + 3);
@@ -903,7 +785,6 @@ __device__ __forceinline__ uint32_t sweep_sorted(const SegDev& S, uint32_t n, co
     __builtin_amdgcn_sched_barrier(0);
     if ((i + 2) % kOcclGroup == 0 && i + 2 < stop) stop = min(stop, stop_at());
   }
-  return min(i, n);
 }
 
 // Resolve the pixel of lane `src` on the slow path with the whole wave; returns the merged (t, index) minimum of
@@ -976,24 +857,14 @@ struct alignas(16) Parked {
   int32_t k1, k2, k3, k4;
 };
 
-}  // namespace srh
-#include "srh_mfma.h"
-namespace srh {
-
-// Workgroup -> tiles.  A workgroup renders 4 tiles that are neighbours in x (one per wave).  Workgroups are dealt to
+// Workgroup -> tiles.  Four consecutive workgroups on one XCD render 4 tiles that are neighbours in x.  Workgroups are dealt to
 // the 8 XCDs round-robin by the hardware, and each XCD has its own L2; a primitive overlaps neighbouring tiles, so
 // the image is cut into REGIONS of kRegionW x kRegionH workgroups and whole regions are dealt to the XCDs in turn:
 // a primitive's records are then fetched into one or two L2s instead of all eight.  The regions are small and the
 // deal is rotated from one row of regions to the next (no XCD owns a vertical stripe), so every XCD gets an equal
 // share of the busy parts of the image -- measured at 2048^2 x 100k discs: linear order 188 us, 128 x 64-pixel regions
 // 152 us, unrotated 256-pixel stripes 190 us.
-#ifndef SRH_REGION_W
-#define SRH_REGION_W 2
-#endif
-#ifndef SRH_REGION_H
-#define SRH_REGION_H 4
-#endif
-constexpr unsigned kRegionW = SRH_REGION_W, kRegionH = SRH_REGION_H;
+constexpr unsigned kRegionW = 2, kRegionH = 4;
 
 __host__ __device__ inline unsigned binned_regions_x(const FrameDev& F) {
   return (((unsigned)F.tiles_x + 3u) / 4u + kRegionW - 1u) / kRegionW;
@@ -1006,32 +877,21 @@ __host__ inline unsigned binned_grid(const FrameDev& F) {
   return ((regions + 7u) & ~7u) * (kRegionW * kRegionH);
 }
 
-#ifndef SRH_SPLIT_TILES
-#define SRH_SPLIT_TILES 3072
-#endif
-// Workgroup size of the one-wave-per-tile kernel.  Its waves never meet at a barrier, and tiles differ a lot in cost
+// Workgroup size of the one-wave-per-tile kernel: one wave.  Its waves never meet at a barrier, and tiles differ a lot in cost
 // (10th / 50th / 90th percentile of a wave's life at config 5: 3 / 29 / 50 us): with four waves per workgroup a
 // finished wave's slot stays empty until the workgroup's slowest wave is done and four slots are free together --
 // measured 3.0 resident waves per SIMD of the 4 the registers allow.  One wave per workgroup: a slot is refilled
 // as soon as its wave ends.  That only pays when the per-primitive kernels of the frames in flight use one-wave
-// workgroups too (SRH_BIN_BLOCK above), or they starve behind the render waves.
-#ifndef SRH_GROUP_WAVES
-#define SRH_GROUP_WAVES 1
-#endif
-constexpr int kWavesPerGroup1 = SRH_GROUP_WAVES;   // 1 or 4
-static_assert(kWavesPerGroup1 == 1 || kWavesPerGroup1 == 4, "SRH_GROUP_WAVES");
-// waves per tile of the render kernel (see k_render_binned): 4 below SRH_SPLIT_TILES tiles, else 1
-__host__ inline int binned_waves_per_tile(const FrameDev& F) { return F.ntiles < SRH_SPLIT_TILES ? 4 : 1; }
+// workgroups too (kBinBlock above), or they starve behind the render waves.
 
-// lanes below this one in a ballot mask
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+// waves per tile of the render kernel (see render_binned_body): 4 below kSplitTiles tiles, else 1
+constexpr int kSplitTiles = 3072;
+__host__ inline int binned_waves_per_tile(const FrameDev& F) { return F.ntiles < kSplitTiles ? 4 : 1; }
 
 // The finish phase is COMPACTED: after the sweep the tile's pixels that have at least one candidate are queued
 // (row-major) in LDS and handed out 64 at a time, so a tile that is 40 % covered costs two fp64 rounds instead
 // of four; pixels without a candidate are background and stored straight away.
-// WPT = waves per tile.  1: a workgroup renders four tiles, one per wave (most work per launched wave).  4: a
+// WPT = waves per tile = waves per workgroup.  1: a workgroup renders one tile (most work per launched wave).  4: a
 // workgroup renders ONE tile -- each wave sweeps a quarter of the tile's entries for all 256 pixels, the per-pixel
 // keys are merged through LDS, and each wave finishes a quarter of the pixels.  Same arithmetic, a quarter of the
 // latency per tile and four times the waves: for frames (or row slabs of a multi-GPU job) with too few tiles to
@@ -1040,33 +900,19 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {
 // of this function touches it every store would force the frame constants to be read again
 // image / depth stores: written once and never read again by the GPU -> nontemporal (config 5: -1 % job time;
 // sc1 write-through stores cost +6 %)
-#ifndef SRH_OUT_NT
-#define SRH_OUT_NT 1
-#endif
 typedef float vf4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void out_store(float* p, float v) {
-#if SRH_OUT_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void out_store(float* p, float v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ void out_store4(float* p, float4 v) {
-#if SRH_OUT_NT
   const vf4 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, reinterpret_cast<vf4*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 
-// Tile of a wave of the binned render grid (see "Workgroup -> tiles" above).  kWaves = waves of the workgroup.
-template <int WPT, int kWaves>
-__device__ __forceinline__ void binned_tile_of(const FrameDev& F, int wave, int& tx, int& ty) {
-    // `group` = four tiles that are neighbours in x: one workgroup (WPT 1) or four consecutive ones on the same XCD
+// Tile of a workgroup of the binned render grid (see "Workgroup -> tiles" above).
+__device__ __forceinline__ void binned_tile_of(const FrameDev& F, int& tx, int& ty) {
+    // four consecutive workgroups on the same XCD render four tiles that are neighbours in x
     const unsigned seq = blockIdx.x >> 3, xcd = blockIdx.x & 7u;
-    const unsigned idx = kWaves == 4 && WPT == 1 ? seq : seq >> 2;
-    const unsigned sub = kWaves == 4 && WPT == 1 ? (unsigned)wave : (seq & 3u);
+    const unsigned idx = seq >> 2;
+    const unsigned sub = seq & 3u;
     const unsigned q = idx / (kRegionW * kRegionH), within = idx % (kRegionW * kRegionH);
     const unsigned nrx = binned_regions_x(F);
     const unsigned region = q * 8u + ((xcd + 3u * ((q * 8u) / nrx)) & 7u);   // rotate the deal from one region row to the next
@@ -1078,7 +924,7 @@ __device__ __forceinline__ void binned_tile_of(const FrameDev& F, int wave, int&
 template <bool TCH, int WPT, int BATCH = -1>
 __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ F, float* __restrict__ image,
                                                    float* __restrict__ depth, int32_t* __restrict__ nearest) {
-  constexpr int kWaves = WPT == 1 ? kWavesPerGroup1 : 4;   // waves of the workgroup
+  constexpr int kWaves = WPT;                 // waves of the workgroup
   __shared__ Parked park[kWaves][4][64];      // [wave][pixel of the quad][lane]: conflict-free 16-byte writes
   __shared__ int32_t front[kWaves][4][64];    // global index of each pixel's front candidate (-1: none / saturated)
   __shared__ uint8_t queue[kWaves][256];      // [wave]: ids j * 64 + lane of the pixels with a candidate, row-major
@@ -1087,7 +933,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   const int wave = kWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   int tx, ty;
-  binned_tile_of<WPT, kWaves>(F, wave, tx, ty);
+  binned_tile_of(F, tx, ty);
   // WPT 1: waves are independent, no block barrier below.  WPT 4: the whole workgroup shares the tile and leaves together.
   if (tx >= F.tiles_x || ty >= F.tiles_y) return;
   const int tile = ty * F.tiles_x + tx;
@@ -1095,11 +941,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   const int c0 = px0 + 4 * (lane & 3);
   const int r_raw = py0 + (lane >> 2);
   const bool row_live = r_raw < F.row1;
-#ifdef SRH_ABL_NOPRETEST
-  const bool pretest = false;
-#else
   const bool pretest = F.near_clip > 0.0;     // with near <= 0 a negative t can be valid: confirm every candidate
-#endif
   const bool want_aux = F.normal_out || F.pos_out;
   const uint32_t mine = WPT == 1 ? 0xFu : (1u << wave);   // pixels of the quad this wave finishes
   uint32_t has = 0;                           // bit j: pixel j of the quad exists, is mine and has a candidate
@@ -1110,17 +952,14 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     const TileLists L{F, tile};
     for (int s = 0; s < ((BATCH >= 0) ? 1 : F.nseg); ++s) listed += L.count(s, 0) + L.count(s, 1);
   }
-  // low key bits that hold a candidate's list position (ord_mask_for); the matrix-core measurement build packs its
-  // keys with the full 12 bits, so it keeps them everywhere
-  const uint32_t ordmask = SRH_MFMA ? kOrdMask : ord_mask_for(listed);
+  const uint32_t ordmask = ord_mask_for(listed);   // low key bits that hold a candidate's list position
   bool sorted = false;                        // the keys' fields are positions in occl_g (front-to-back order)
-  uint32_t swept = listed;                    // entries the sweep evaluated (measurement builds report it)
   if (listed) {
     // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
     // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
     int32_t gs[2] = {0, 0};
 #if SRH_OCCLUSION_CULL
-    if (WPT == 1 && BATCH == SRH_PRIM_DISK && !SRH_MFMA && pretest) {
+    if (WPT == 1 && BATCH == SRH_PRIM_DISK && pretest) {
       const TileLists L{F, tile};
       if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
         if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], occl_u[wave], gs);
@@ -1137,11 +976,6 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     // B = 2 D(c0).Dc, C = |Dc|^2 -- one fp64 ray instead of four (equal to ~1e-16 relative; only the fp32 bound uses it)
     double len2[4] = {1.0, 1.0, 1.0, 1.0};
     if (!den_keys(BATCH)) {
-#ifdef SRH_ABL_LEN2_EACH
-#pragma unroll
-    for (int j = 0; j < 4; ++j) len2[j] = pixel_len2(F, min(c0 + j, F.W - 1), r);
-#else
-    {
       const double xs = c0 * F.step_x + -1.0, ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
       const double X = xs * F.half_w, Y = ys * F.half_h, sx = F.step_x * F.half_w;
       double A = 0.0, B = 0.0, C = 0.0;
@@ -1155,8 +989,6 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
 #pragma unroll
       for (int j = 0; j < 4; ++j) len2[j] = __builtin_fma((double)j, __builtin_fma((double)j, C, 2.0 * B), A);
     }
-#endif
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = min(c0 + j, F.W - 1);
@@ -1167,18 +999,6 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       Q.k1[j] = Q.k2[j] = Q.k3[j] = Q.k4[j] = kNoKey;
     }
     const uint32_t part = WPT == 1 ? 0u : (uint32_t)wave;     // which share of the tile's entries this wave sweeps
-    // Disc bins go through the matrix cores (srh_mfma.h) unless the tile's lists are too long for an unsaturated key
-    // field; the frame-wide list (huge discs, overflowing bins: usually empty) stays on the vector path, whose
-    // centre-relative evaluation does not care how far the tile is from the ellipse.
-    uint32_t n_wide = 0, n_bin = 0;
-    bool matrix = false;
-    if (SRH_MFMA && BATCH == SRH_PRIM_DISK) {
-      const TileLists L{F, tile};
-      n_wide = L.count(0, 0);
-      n_bin = L.count(0, 1);
-      matrix = n_wide + n_bin + 1u <= kOrdMask;
-    }
-    const int passes = matrix ? (n_wide ? 1 : 0) : 3;
     if (sorted) {
       // 1 / |D| is smallest where |D| is largest: |D| is convex in the pixel coordinates, so at a corner of the tile
       const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
@@ -1187,54 +1007,18 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       float rl = (float)(1.0 / sqrt(m2));
       rl = (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;           // (0: T = 0, nothing is skipped)
       const float rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rl)));
-      swept = listed <= 64 ? sweep_sorted<1>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q)
-                           : sweep_sorted<2>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
-    } else if (passes) {
-      if (pretest) sweep_tile<true, WPT, BATCH>(F, tile, Q, part, lane, passes);
-      else sweep_tile<false, WPT, BATCH>(F, tile, Q, part, lane, passes);
+      if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
+      else sweep_sorted<2>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
+    } else if (pretest) {
+      sweep_tile<true, WPT, BATCH>(F, tile, Q, part);
+    } else {
+      sweep_tile<false, WPT, BATCH>(F, tile, Q, part);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       Parked p;
       p.k1 = Q.k1[j]; p.k2 = Q.k2[j]; p.k3 = Q.k3[j]; p.k4 = Q.k4[j];
       park[wave][j][lane] = p;
-    }
-    if (SRH_MFMA && BATCH == SRH_PRIM_DISK && matrix && n_bin > part) {
-      int32_t K[8][4];
-#pragma unroll
-      for (int g = 0; g < 8; ++g)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) K[g][q] = kNoKey;
-      const TileLists L{F, tile};
-      if (pretest) sweep_bin_mfma<true, WPT>(F.seg[0], L.list(0, 1), n_bin, n_wide, part, lane, px0, py0, K);
-      else sweep_bin_mfma<false, WPT>(F.seg[0], L.list(0, 1), n_bin, n_wide, part, lane, px0, py0, K);
-      mfma_merge_keys<WPT>(lane, K);
-      // both lanes of a pixel now hold its keys: lanes 0-31 file the even groups, lanes 32-63 the odd ones, into the
-      // (row quad, lane) slots of the vector layout, on top of whatever the frame-wide list left there
-      wave_lds_fence();
-      const bool upper = lane >= 32;
-      const int col = lane & 31, x = col & 15;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int y = 2 * (2 * i + (upper ? 1 : 0)) + (col >> 4);
-        Parked& slot = park[wave][x & 3][y * 4 + (x >> 2)];
-        Parked p = slot;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int32_t key = upper ? K[2 * i + 1][q] : K[2 * i][q];
-          if (kKeys == 4) p.k4 = imed3(p.k3, key, p.k4);
-          p.k3 = imed3(p.k2, key, p.k3);
-          p.k2 = imed3(p.k1, key, p.k2);
-          p.k1 = max(p.k1, key);
-        }
-        slot = p;
-      }
-      wave_lds_fence();
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const Parked p = park[wave][j][lane];
-        Q.k1[j] = p.k1; Q.k2[j] = p.k2; Q.k3[j] = p.k3; Q.k4[j] = p.k4;
-      }
     }
     if (WPT > 1) {
       // merge: pixel j = wave of every lane collects the keys the four waves found for it
@@ -1247,7 +1031,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
         const int32_t keys[4] = {o.k1, o.k2, o.k3, o.k4};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          if (kKeys == 4) m4 = imed3(m3, keys[t], m4);
+          m4 = imed3(m3, keys[t], m4);
           m3 = imed3(m2, keys[t], m3);
           m2 = imed3(m1, keys[t], m2);
           m1 = max(m1, keys[t]);
@@ -1342,13 +1126,12 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       float bound = __builtin_inff();
       int g1 = -1, g2 = -1;
       bool slow = false;
-#ifndef SRH_ABL_NOCONFIRM
       if (live) {
         // Confirm the front candidates in key order while their bound still reaches the confirmed depth (the
         // first one always; the next ones after a near miss at an ellipse edge or for nearly coplanar primitives).
         // A saturated ordinal does not identify its primitive: such a pixel confirms everything on the slow path.
         const int32_t keys[3] = {p.k1, p.k2, p.k3};
-        const int32_t sentinel = kKeys == 4 ? p.k4 : p.k3;
+        const int32_t sentinel = p.k4;
         bool saturated = false;
         // a key still "reaches" the confirmed depth iff its inverse-depth bound is >= reach_of(bound)
         // (one reciprocal per confirmation instead of one per key; 0 while nothing is confirmed).  Keys in den units
@@ -1379,8 +1162,6 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
         slow = saturated || (sentinel != kNoKey && key_inv(sentinel, ordmask) >= reach);
         if (slow) { g1 = g2 = -1; }           // the slow path re-confirms; cheaper than excluding three indices
       }
-#endif
-#ifndef SRH_ABL_NORESWEEP
       unsigned long long todo = __builtin_amdgcn_ballot_w64(slow);
       if (__popcll(todo) > kSerialSlowMax) {      // several undecided pixels: all of them at once, lane-parallel
         if (slow) { best = __builtin_inf(); besti = 0x7fffffff; bound = __builtin_inff(); }   // confirm everything that passes
@@ -1400,38 +1181,20 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
           besti = si;
         }
       }
-#endif
       if (live) {
         if (besti == 0x7fffffff) besti = 0;   // nothing hit: np.argmin of an all-inf column
         float rgb[3], aux[6];
-#ifdef SRH_ABL_NOSHADE
-        rgb[0] = rgb[1] = rgb[2] = (float)d[0] + __int_as_float(p.k1);
-#else
         const ShadeHint hint = fr.hint();
         shade_pixel_t<TCH, BATCH>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint);
-#endif
         const size_t row = (size_t)(r - F.row0);
         float* px = image + row * F.img_stride + 3 * (size_t)c;
         out_store(px, rgb[0]); out_store(px + 1, rgb[1]); out_store(px + 2, rgb[2]);
         out_store(depth + row * F.depth_stride + c, background_depth(F, best));
         if (want_aux) store_aux(F, row, c, aux);
-#ifdef SRH_DIAG_AGAIN   // diagnostic build: did this pixel take the slow path
-        if (nearest) nearest[row * F.near_stride + c] = slow ? 1 : 0;
-#else
         if (nearest) nearest[row * F.near_stride + c] = besti;
-#endif
       }
     }
   }
-#ifdef SRH_DIAG_SWEPT   // measurement build: entries swept and listed, in `nearest` at the tile's first two pixels
-  if (nearest && lane == 0 && WPT == 1 && py0 < F.row1) {
-    int32_t* nr = nearest + (size_t)(py0 - F.row0) * F.near_stride + px0;
-    nr[0] = (int32_t)swept;
-    if (px0 + 1 < F.W) nr[1] = (int32_t)listed;
-  }
-#else
-  (void)swept;
-#endif
   // Leave the counters as the next frame's binning needs them: zero -- a frame is then prep-and-bin + render, without a
   // clearing launch in front (SrhParams.counters_clean).  A tile's own bin counters were read by nobody else.  The
   // frame-wide list lengths are read by every tile until the kernel ends: tile 0 zeroes the OTHER set and makes it the
@@ -1455,32 +1218,19 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
 // kernel would spill 10 at 5 waves and is slower there (config 4: 0.0553 -> 0.0562 ms), so it stays at 4.  With 5
 // waves per SIMD config 5 goes from 0.0927 to 0.0852 ms per frame (stand-alone kernel 90.5 -> 88.0 us): the extra
 // slot is what the other frames' binning waves need beside the render waves.
-#ifndef SRH_TYPED_WAVES
-#define SRH_TYPED_WAVES 0
-#endif
 constexpr int typed_waves(bool tch, int batch) {      // the Phong fragment stage needs more registers: 4 waves as before
-  return (batch < 0 || tch) ? 4 : SRH_TYPED_WAVES ? SRH_TYPED_WAVES
-       : batch == SRH_PRIM_TRIANGLE ? 4 : batch == SRH_PRIM_PLANE ? 6 : 5;
-}
-template <bool TCH, int WPT, int BATCH = -1>
-__global__ __launch_bounds__(WPT == 1 ? 64 * kWavesPerGroup1 : 256)
-__attribute__((amdgpu_waves_per_eu(typed_waves(TCH, BATCH)))) void k_render_binned(
-    FrameDev F, float* __restrict__ image, float* __restrict__ depth, int32_t* __restrict__ nearest) {
-  render_binned_body<TCH, WPT, BATCH>(F, image, depth, nearest);
+  return (batch < 0 || tch) ? 4 : batch == SRH_PRIM_TRIANGLE ? 4 : batch == SRH_PRIM_PLANE ? 6 : 5;
 }
 
-// The product form of the same kernel reads its frame constants from MEMORY in the constant address space -- the copy
-// k_prep (or k_put_frame) left in the workspace, FrameDev::self -- instead of from by-value kernel arguments: the loads
-// are invariant scalar loads that hipcc re-materialises where the values are used, where the by-value form keeps ~150
-// scalars alive across the sweep and spills them into vector-register lanes, and every v_writelane / v_readlane of
-// those is a VECTOR instruction (disc kernel: 219 of them in the by-value form, 56 here; 52 -> 22 spilled scalars,
-// 96 -> 93 vector registers).  -DSRH_FRAME_MEM=0 builds the by-value launch for comparison.
-#ifndef SRH_FRAME_MEM
-#define SRH_FRAME_MEM 1
-#endif
+// The kernel reads its frame constants from MEMORY in the constant address space -- the copy k_prep (or k_put_frame)
+// left in the workspace, FrameDev::self -- instead of from by-value kernel arguments: the loads are invariant scalar
+// loads that hipcc re-materialises where the values are used, where a by-value FrameDev keeps ~150 scalars alive across
+// the sweep and spills them into vector-register lanes, and every v_writelane / v_readlane of those is a VECTOR
+// instruction (disc kernel, measured: 219 of them by value, 56 here; 52 -> 22 spilled scalars, 96 -> 93 vector
+// registers).
 typedef const __attribute__((address_space(4))) FrameDev* FrameConstPtr;
 template <bool TCH, int WPT, int BATCH = -1>
-__global__ __launch_bounds__(WPT == 1 ? 64 * kWavesPerGroup1 : 256)
+__global__ __launch_bounds__(64 * WPT)
 __attribute__((amdgpu_waves_per_eu(typed_waves(TCH, BATCH)))) void k_render_binned_mem(
     FrameConstPtr Fp, float* __restrict__ image, float* __restrict__ depth, int32_t* __restrict__ nearest) {
   render_binned_body<TCH, WPT, BATCH>(*(const FrameDev*)Fp, image, depth, nearest);
@@ -1501,7 +1251,6 @@ __global__ __launch_bounds__(256) void k_views_zero(const FrameDev* __restrict__
   const size_t n = (size_t)kCounterPad + (size_t)F.nbins;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) F.counters[i] = 0u;
 }
-__global__ __launch_bounds__(kBinBlock) void k_bin_count_views(const FrameDev* __restrict__ Fs) { bin_count_body(Fs[blockIdx.y]); }
 
 // The render kernel reads its view's frame constants from CONSTANT memory: loads from there are invariant, so hipcc
 // re-materialises them where they are used (as it does with a by-value kernel argument) instead of keeping 140 SGPRs
@@ -1512,7 +1261,7 @@ constexpr int kViewRing = 4;                       // batches in flight before t
 __constant__ FrameDev g_view_frames[kViewRing * kMaxViewsPerCall];
 
 template <bool TCH, int WPT, int BATCH = -1>
-__global__ __launch_bounds__(WPT == 1 ? 64 * kWavesPerGroup1 : 256)
+__global__ __launch_bounds__(64 * WPT)
 __attribute__((amdgpu_waves_per_eu(typed_waves(TCH, BATCH)))) void k_render_binned_views(
     int base, float* __restrict__ image, float* __restrict__ depth, int32_t* __restrict__ nearest) {
   const FrameDev& F = g_view_frames[base + blockIdx.y];

@@ -58,9 +58,10 @@ __device__ inline void rec_zero(float* out, int n) {
 //   u_j = w_j / K  with  w0 = s v0 + E, w1 = s v1, w2 = s v2,  s = sign(k),  K = |k| (1 - 2^-20),  and lo_u, hi_u.
 // The kernel evaluates den = u0 + c u1 + r u2 = (s (n^.D) + E) / K up to an fp32 error below E / K, where
 //   E = 2^-19 (|v0| + W |v1| + H |v2|)  covers the three rounded coefficients and the two fmas of the vector path
-// (5 x 2^-24) and, with 2x slack, the matrix path (sweep_bin_mfma): the constant moved to the tile origin by two more
-// fmas, every coefficient split into three bfloat16 parts (2^-24 of itself left over) and nine exact products summed
-// in fp32 (at most 16 x 2^-24 together) -- so s (n^.D) / K <= den always.  A valid hit with near > 0 has s (n^.D) > 0 and ray distance
+// (5 x 2^-24) and, with 2x slack, the matrix-core sweep that was measured and dropped (DESIGN.md Part II A.2; the
+// margin still covers it): the constant moved to the tile origin by two more fmas, every coefficient split into three
+// bfloat16 parts (2^-24 of itself left over) and nine exact products summed in fp32 (at most 16 x 2^-24 together) --
+// so s (n^.D) / K <= den always.  A valid hit with near > 0 has s (n^.D) > 0 and ray distance
 //   t = |k| |D| / (s n^.D) >= |D| / ((1 - 2^-20) max(den, lo_u))      for ANY lo_u > 0
 // (the 2^-20 absorbs the roundings of |D|, the reciprocal and the product).  The kernel uses exactly that,
 //   lower bound = |D| rcp(max(den, lo_u)),   lo_u = 1025 E / K:
@@ -105,8 +106,8 @@ __device__ inline void plane_estimate_record(const double n[3], double k, const 
 // evaluated in two ways, and the inflation `thr` covers both:
 //   vector path   centre-relative in fp32 (pair_bounds, ellipse_reject): three rounded coefficients and five rounded
 //                 operations on terms up to Tm near the boundary;
-//   matrix path   (sweep_bin_mfma) as the polynomial a0 + a1 x + a2 y + a3 x^2 + a4 x y + a5 y^2 in TILE-LOCAL pixel
-//                 coordinates x, y in [0, 15]: coefficients moved to the tile origin in fp32 (six rounded operations),
+//   matrix path   (measured and dropped, DESIGN.md Part II A.2; the inflation still covers it) as the polynomial
+//                 a0 + a1 x + a2 y + a3 x^2 + a4 x y + a5 y^2 in TILE-LOCAL pixel coordinates x, y in [0, 15]: coefficients moved to the tile origin in fp32 (six rounded operations),
 //                 each split into two float16 parts (2^-22 of itself left over), twelve exact products summed in fp32.
 //                 Its terms reach the form's value, with absolute values, 15 pixels beyond the tile origin; a binned
 //                 tile starts at most 17 pixels outside the ellipse's box.

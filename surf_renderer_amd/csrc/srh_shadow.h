@@ -37,10 +37,7 @@ namespace srh {
 // alone: config 5 (100 k discs of radius 0.02) 3.91 ms at 2048, 2.87 at 4096, 3.90 at 8192; bunny.obj at 512^2
 // 0.60 / 1.31 / 18.9 ms.  So every light picks its own resolution, 2048 or 4096, from the mean size of the scene's
 // primitives (k_scene_bounds): the finer one while a mean primitive stays within ~3 tiles across.
-#ifndef SRH_SHADOW_RES
-#define SRH_SHADOW_RES 4096
-#endif
-constexpr int kShadowRes = SRH_SHADOW_RES;        // the largest view: workspace slices are sized for it
+constexpr int kShadowRes = 4096;                  // the largest view: workspace slices are sized for it
 constexpr int kShadowResCoarse = 2048;
 constexpr double kShadowFineMaxTiles = 3.2;       // mean primitive diameter, in tiles, up to which the fine view is taken
 
