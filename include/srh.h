@@ -286,6 +286,76 @@ int srh_event_create(void** event);
 int srh_event_destroy(void* event);
 int srh_event_elapsed_ms(void* start, void* stop, float* ms);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's splat renderer, render_splats_along_ray (diffrend/torch/renderer.py:537-751): one splat per pixel of a
+ * W x H grid, given by its camera-space depth z, shaded in camera coordinates with the torch backend's Phong model
+ * (double_sided off, no tonemap, relu over the light sum).  Normals are given or estimated by the reference's plane fit
+ * over the reflected 3x3 stencil; samples K > 1 shades K x K sub-rays per splat on the splat's plane.  Many views per
+ * call: z, normals, light_vis, the eye and the light positions may differ per view (the GAN's batch), everything else is
+ * shared.  These entry points were added without an ABI version change: no existing struct or signature changed.
+ * Conventions as above: caller-owned device buffers, enqueue only, no synchronisation or allocation, argument checks
+ * before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhSplatParams {
+  int32_t n_views;              /* B >= 1 */
+  int32_t width, height;        /* base grid W x H (camera viewport); >= 2 each when normals are estimated */
+  int32_t samples;              /* K in 1..8: outputs are (B, K H, K W, ...) */
+  int32_t pos_cols;             /* 1: pos holds z (N); 3: pos is (N,3) and only column 2 (z) is read */
+  int32_t use_quartic;          /* attenuation uses d^4 instead of d^2 */
+  int32_t shade;                /* 1: shade the image; 0: geometry only (depth, pos, normal; norm_depth_image_only) */
+  int32_t reserved;
+  double fovy, focal_length;    /* radians; f > 0 */
+  double at[3], up[3];          /* camera.at / camera.up (shared by all views; w dropped as the reference does) */
+} SrhSplatParams;
+
+/* Device inputs; N = W * H.  A view stride of 0 shares the array between all views. */
+typedef struct SrhSplatInputs {
+  const float* pos;             /* (B, N, pos_cols) with pos_view_stride elements between views */
+  int64_t pos_view_stride;
+  const float* normal;          /* (N,3) per view, used as given; NULL: estimate (plane fit) */
+  int64_t normal_view_stride;
+  const float* light_vis;       /* (n_lights, N) per view, multiplies colour x albedo; NULL: all lights visible */
+  int64_t light_vis_view_stride;
+  const float* eye;             /* (3) per view: camera.eye[:3] */
+  int64_t eye_view_stride;
+  int64_t lights_pos_view_stride; /* SrhLights.pos is (n_lights,4) per view with this stride */
+  const int32_t* material_idx;  /* (N) shared; NULL: material 0 everywhere */
+} SrhSplatInputs;
+
+/* Gradients.  pos, normal and light_vis are WRITTEN (dense per view, no atomics: identical from run to run):
+ * pos (B, N, pos_cols) with zeros outside column pos_cols - 1, normal (B, N, 3) (given normals only), light_vis
+ * (B, n_lights, N).  The scene parameters are ADDED with fp32 atomics (zero-fill them first) in their input layouts:
+ * lights_pos (n_lights,4) per view at lights_pos_view_stride, colors, attenuation, ambient, albedo, coeffs.
+ * NULL = not wanted.  The camera has no gradient.  A geometry-only frame (shade = 0) depends on none of light_vis,
+ * the lights, colours and materials: srh_splat_bwd refuses those gradient buffers then (SRH_E_TYPE). */
+typedef struct SrhSplatGrads {
+  float* pos;
+  float* normal;
+  float* light_vis;
+  float* lights_pos;
+  float* colors;
+  float* attenuation;
+  float* ambient;
+  float* albedo;
+  float* coeffs;
+} SrhSplatGrads;
+
+/* bytes of device scratch srh_splat_bwd needs (8-byte aligned; 0 for given normals); 0 and srh_last_error on bad input */
+size_t srh_splat_workspace_bytes(const SrhSplatParams* params, const SrhSplatInputs* inputs);
+
+/* image (B,KH,KW,3) (may be NULL when params->shade == 0), depth (B,KH,KW), pos (B,KH,KW,3), normal (B,KH,KW,3).
+ * lights / materials as for SRH_SHADING_TORCH (attenuation, ambient and coeffs optional). */
+int srh_splat_fwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, float* image, float* depth, float* pos, float* normal, void* stream);
+
+/* Vector-Jacobian product of srh_splat_fwd for the upstream gradients of its four outputs (same layouts; any may be
+ * NULL, grad_image must be NULL when shade = 0).  Relus and the z >= 0 clamp are constants (no gradient through them); at a point at the origin the depth
+ * has no gradient. */
+int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
+                  const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
+                  const SrhSplatGrads* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,9 @@ import importlib
 _RENDERER = ("render", "render_views", "ResidentScene", "CapturedStep", "ViewScenes", "flatten_scene", "render_buffers", "camera_struct",
              "generate_rays")
 _SCENE = ("load_scene", "load_model", "load_obj", "load_splat", "obj_to_triangle_spec")
+_SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
 
-__all__ = [*_RENDERER, *_SCENE]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS]
 
 
 def __getattr__(name):
@@ -21,6 +22,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".renderer", __name__), name)
     if name in _SCENE:
         return getattr(importlib.import_module(".scene", __name__), name)
+    if name in _SPLATS:
+        return getattr(importlib.import_module(".splats", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

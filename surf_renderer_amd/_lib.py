@@ -69,10 +69,29 @@ class SrhGrads(C.Structure):
                 ("coeffs", C.c_void_p), ("attenuation", C.c_void_p), ("ambient", C.c_void_p)]
 
 
+class SrhSplatParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32),
+                ("pos_cols", C.c_int32), ("use_quartic", C.c_int32), ("shade", C.c_int32), ("reserved", C.c_int32),
+                ("fovy", C.c_double), ("focal_length", C.c_double), ("at", C.c_double * 3), ("up", C.c_double * 3)]
+
+
+class SrhSplatInputs(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("pos_view_stride", C.c_int64), ("normal", C.c_void_p),
+                ("normal_view_stride", C.c_int64), ("light_vis", C.c_void_p), ("light_vis_view_stride", C.c_int64),
+                ("eye", C.c_void_p), ("eye_view_stride", C.c_int64), ("lights_pos_view_stride", C.c_int64),
+                ("material_idx", C.c_void_p)]
+
+
+class SrhSplatGrads(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pos", "normal", "light_vis", "lights_pos", "colors", "attenuation",
+                                          "ambient", "albedo", "coeffs")]
+
+
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
            "srh_render_bwd", "srh_render_bwd_aux", "srh_workspace_bytes_views", "srh_render_views", "srh_shadow_shade",
            "srh_shadow_workspace_bytes", "srh_bin_counters",
-           "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms")
+           "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
+           "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd")
 
 _lib: Optional[C.CDLL] = None
 
@@ -149,6 +168,15 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib.srh_event_destroy.argtypes = [C.c_void_p]
     lib.srh_event_elapsed_ms.restype = C.c_int
     lib.srh_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    lib.srh_splat_workspace_bytes.restype = C.c_size_t
+    lib.srh_splat_workspace_bytes.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs)]
+    lib.srh_splat_fwd.restype = C.c_int
+    lib.srh_splat_fwd.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs), C.POINTER(SrhLights),
+                                  C.POINTER(SrhMaterials), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.srh_splat_bwd.restype = C.c_int
+    lib.srh_splat_bwd.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs), C.POINTER(SrhLights),
+                                  C.POINTER(SrhMaterials), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(SrhSplatGrads), C.c_void_p]
     got = lib.srh_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {got}, this package expects {ABI_VERSION}; rebuild it")

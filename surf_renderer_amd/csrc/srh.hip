@@ -21,6 +21,7 @@
 #include "srh_binned.h"
 #include "srh_backward.h"
 #include "srh_shadow.h"
+#include "srh_splat.h"
 
 using namespace srh;
 
@@ -741,6 +742,139 @@ int setup_frame(const SrhCamera* camera, const SrhObjects* objects, const SrhLig
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// the splat renderer (srh_splat.h)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kSplatMaxSamples = 8;
+
+// argument checks (no HIP call) and the device view of a splat launch
+int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLights* lights, const SrhMaterials* mats,
+                SplatDev* S) {
+  if (!p || !in) return fail(SRH_E_NULL, "params / inputs is NULL");
+  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
+  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
+    return fail(SRH_E_RANGE, "grid %d x %d out of range", p->width, p->height);
+  if (p->samples < 1 || p->samples > kSplatMaxSamples)
+    return fail(SRH_E_RANGE, "samples = %d, expected 1..%d", p->samples, kSplatMaxSamples);
+  if (p->pos_cols != 1 && p->pos_cols != 3) return fail(SRH_E_RANGE, "pos_cols = %d, expected 1 or 3", p->pos_cols);
+  if (!(p->focal_length > 0.0) || !(p->fovy > 0.0) || !(p->fovy < M_PI))
+    return fail(SRH_E_RANGE, "focal_length must be > 0 and fovy in (0, pi)");
+  if (!in->pos || !in->eye) return fail(SRH_E_NULL, "inputs.pos / inputs.eye is NULL");
+  if (!in->normal && (p->width < 2 || p->height < 2))
+    return fail(SRH_E_RANGE, "normal estimation needs a grid of at least 2 x 2 (got %d x %d)", p->width, p->height);
+  if (in->pos_view_stride < 0 || in->normal_view_stride < 0 || in->light_vis_view_stride < 0 ||
+      in->eye_view_stride < 0 || in->lights_pos_view_stride < 0)
+    return fail(SRH_E_RANGE, "negative view stride");
+  if (!lights || !mats) return fail(SRH_E_NULL, "lights / materials is NULL");
+  if (p->shade) {
+    if (lights->n_lights < 0 || lights->n_lights > SRH_MAX_LIGHTS)
+      return fail(SRH_E_RANGE, "n_lights = %d, expected 0..%d", lights->n_lights, SRH_MAX_LIGHTS);
+    if (lights->n_lights > 0 && (!lights->pos || !lights->color_idx || !lights->colors || lights->n_colors < 1))
+      return fail(SRH_E_NULL, "lights arrays missing");
+    if (mats->n_materials < 1 || !mats->albedo) return fail(SRH_E_NULL, "materials.albedo missing");
+  }
+  const double up2 = p->up[0] * p->up[0] + p->up[1] * p->up[1] + p->up[2] * p->up[2];
+  if (!(up2 > 0.0)) return fail(SRH_E_CAMERA, "camera.up is zero");
+  memset(S, 0, sizeof(*S));
+  S->B = p->n_views; S->W = p->width; S->H = p->height; S->K = p->samples; S->N = p->width * p->height;
+  S->pos_cols = p->pos_cols; S->use_quartic = p->use_quartic != 0; S->shade = p->shade != 0;
+  S->estimate = in->normal == nullptr;
+  S->nlights = p->shade ? lights->n_lights : 0;
+  S->ncolors = lights->n_colors; S->nmat = mats->n_materials;
+  // h = 2 f tan(fovy / 2), w = h W / H, in the reference's order of operations
+  const double h = tan(p->fovy / 2) * 2 * p->focal_length, w = h * ((double)p->width / (double)p->height);
+  S->f = p->focal_length; S->half_w = w / 2; S->half_h = h / 2;
+  S->step_x = p->width > 1 ? 2.0 / (p->width - 1) : 0.0;
+  S->step_y = p->height > 1 ? -2.0 / (p->height - 1) : 0.0;
+  S->sub_dx = p->samples > 1 ? w / (p->samples * p->width - 1) : 0.0;
+  S->sub_dy = p->samples > 1 ? h / (p->samples * p->height - 1) : 0.0;
+  S->sub_step = p->samples > 1 ? 2.0 / (p->samples - 1) : 0.0;
+  const double ui = 1.0 / sqrt(((p->up[0] * p->up[0] + 1e-10) + (p->up[1] * p->up[1] + 1e-10)) + (p->up[2] * p->up[2] + 1e-10));
+  for (int k = 0; k < 3; ++k) { S->at[k] = p->at[k]; S->up[k] = p->up[k] * ui; }
+  S->pos = in->pos; S->pos_vs = in->pos_view_stride;
+  S->normal = in->normal; S->nrm_vs = in->normal_view_stride;
+  S->vis = in->light_vis; S->vis_vs = in->light_vis_view_stride;
+  S->eye = in->eye; S->eye_vs = in->eye_view_stride;
+  S->lpos = lights->pos; S->lpos_vs = in->lights_pos_view_stride;
+  S->lcidx = lights->color_idx; S->colors = lights->colors; S->latt = lights->attenuation; S->amb = lights->ambient;
+  S->mat = in->material_idx; S->albedo = mats->albedo; S->coeffs = mats->coeffs;
+  return SRH_OK;
+}
+
+size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N * 9 * sizeof(double) : 0; }
+
+}  // namespace
+
+extern "C" {
+
+size_t srh_splat_workspace_bytes(const SrhSplatParams* params, const SrhSplatInputs* inputs) {
+  SrhLights L;
+  SrhMaterials M;
+  memset(&L, 0, sizeof(L));
+  memset(&M, 0, sizeof(M));
+  SrhSplatParams p;
+  if (!params) { fail(SRH_E_NULL, "params is NULL"); return 0; }
+  p = *params;
+  p.shade = 0;                                           // the size does not depend on the lights
+  SplatDev S;
+  if (splat_setup(&p, inputs, &L, &M, &S)) return 0;
+  return splat_ws_bytes(S);
+}
+
+int srh_splat_fwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, float* image, float* depth, float* pos, float* normal, void* stream) {
+  SplatDev S;
+  int rc = splat_setup(params, inputs, lights, materials, &S);
+  if (rc) return rc;
+  if (!depth || !pos || !normal || (S.shade && !image)) return fail(SRH_E_NULL, "an output buffer is NULL");
+  const dim3 grid((S.N + 255) / 256, S.B);
+  hipLaunchKernelGGL(k_splat_fwd, grid, dim3(256), 0, (hipStream_t)stream, S, image, depth, pos, normal);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SRH_OK : hip_fail(e, "k_splat_fwd launch");
+}
+
+int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
+                  const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
+                  const SrhSplatGrads* grads, void* stream) {
+  SplatDev S;
+  int rc = splat_setup(params, inputs, lights, materials, &S);
+  if (rc) return rc;
+  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
+  if (!grad_image && !grad_depth && !grad_pos && !grad_normal)
+    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_pos and grad_normal are all NULL");
+  if (!S.shade && (grad_image || grads->light_vis || grads->lights_pos || grads->colors || grads->attenuation ||
+                   grads->ambient || grads->albedo || grads->coeffs))
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
+  if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
+  if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
+  const size_t need = splat_ws_bytes(S);
+  const bool gather = S.estimate && grads->pos;
+  if (gather && (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double))))
+    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
+                workspace);
+  SplatGradsDev G;
+  G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
+  G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
+  G.coeffs = grads->coeffs;
+  if (S.estimate && !gather) {
+    G.pos = nullptr;
+    if (!G.vis && !G.lpos && !G.colors && !G.latt && !G.amb && !G.albedo && !G.coeffs) return SRH_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((S.N + 255) / 256, S.B);
+  // without z gradients the stencil slots are not wanted: k_splat_bwd then needs no workspace
+  double* ws = gather ? (double*)workspace : nullptr;
+  hipLaunchKernelGGL(k_splat_bwd, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws);
+  if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SRH_OK : hip_fail(e, "splat backward launch");
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
