@@ -655,38 +655,101 @@ constexpr float kDenShiftPerLoU = 0.0029269f;
 // L (p) rlen_lo (1 - 2^-18) <= 1 / t: the (1 - 2^-20) of K, the fp32 1 / |D|, the subtraction and two products
 constexpr float kSureRound = 0.99999619f;
 
+// ---- cross-lane exchanges in registers (no LDS round trip) -------------------------------------------------------
+// __shfl_xor is a ds_bpermute: an LDS instruction, a wait for its result and ~4 vector instructions of address
+// arithmetic.  For the partner lane ^ J gfx950 has register paths: DPP (quad_perm for 1 and 2, row_ror:8 for 8, a pair
+// of bank-masked row shifts for 4) and v_permlane16/32_swap for 16 and 32.  A swap of a register with itself leaves the
+// even rows (lower half) of every row pair (half pair) in one result and the odd rows (upper half) in the other, so the
+// pair's max and min come out in both lanes without picking the partner first.  (hipcc puts the wait states the swaps
+// need after a vector write of their operand.)
+__device__ constexpr uint64_t lanes_bit_clear(int j) {          // lanes whose bit j (a power of two, <= 32) is 0
+  return j == 1 ? 0x5555555555555555ull : j == 2 ? 0x3333333333333333ull : j == 4 ? 0x0F0F0F0F0F0F0F0Full
+       : j == 8 ? 0x00FF00FF00FF00FFull : j == 16 ? 0x0000FFFF0000FFFFull : 0x00000000FFFFFFFFull;
+}
+
+// mask bit l set: lane l takes `if_set`.  The mask is a wave-uniform constant in SGPRs; hipcc would otherwise rebuild
+// the per-lane condition from the lane index with vector instructions at every stage.
+__device__ __forceinline__ int32_t lane_select(uint64_t mask, int32_t if_set, int32_t if_clear) {
+  int32_t r;
+  asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(if_clear), "v"(if_set), "s"(mask));
+  return r;
+}
+
+// (max, min) of the values of lanes l and l ^ J, in both lanes
+template <int J>
+__device__ __forceinline__ void xor_pair_maxmin(int32_t v, int32_t& hi, int32_t& lo) {
+  static_assert(J == 1 || J == 2 || J == 4 || J == 8 || J == 16 || J == 32, "partner distance");
+  if constexpr (J == 16 || J == 32) {
+    const auto s = J == 16 ? __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false)
+                           : __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
+    hi = max((int32_t)s[0], (int32_t)s[1]);
+    lo = min((int32_t)s[0], (int32_t)s[1]);
+  } else {
+    int32_t p;
+    if constexpr (J == 4) {                 // banks 0 and 2 of a row (lanes 0-3, 8-11) read l + 4, banks 1 and 3 l - 4
+      p = __builtin_amdgcn_update_dpp(v, v, 0x104 /* row_shl:4 */, 0xF, 0x5, false);
+      p = __builtin_amdgcn_update_dpp(p, v, 0x114 /* row_shr:4 */, 0xF, 0xA, false);
+    } else {
+      p = __builtin_amdgcn_mov_dpp(v, J == 1 ? 0xB1 /* quad_perm [1,0,3,2] */ : J == 2 ? 0x4E /* quad_perm [2,3,0,1] */
+                                                                       : 0x128 /* row_ror:8 */, 0xF, 0xF, true);
+    }
+    hi = max(v, p);
+    lo = min(v, p);
+  }
+}
+
+// fminf over the wave, valid in every lane (fminf is commutative and associative: the order of the steps does not
+// change the result)
+template <int CTRL>
+__device__ __forceinline__ float dpp_min_f32(float m) {
+  return fminf(m, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m), CTRL, 0xF, 0xF, true)));
+}
+__device__ __forceinline__ float wave_min_f32(float m) {
+  m = dpp_min_f32<0xB1>(m);                 // quad_perm [1,0,3,2]
+  m = dpp_min_f32<0x4E>(m);                 // quad_perm [2,3,0,1]: the quad's minimum in each lane
+  m = dpp_min_f32<0x124>(m);                // row_ror:4
+  m = dpp_min_f32<0x128>(m);                // row_ror:8: the row's minimum
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+  m = fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+  return fminf(__uint_as_float(h[0]), __uint_as_float(h[1]));
+}
+
 // Bitonic sort, DESCENDING, of NR x 64 distinct signed keys across the wave: element i = lane + 64 h is register h of
 // lane `lane`.  Stage (k, j) compares i with i ^ j; blocks of size k with (i & k) == 0 run descending, the others
-// ascending, so that each merge sees a bitonic sequence.
-template <int NR>
-__device__ __forceinline__ void wave_sort_desc(int32_t (&v)[NR], int lane) {
-  constexpr int N = 64 * NR;
+// ascending, so that each merge sees a bitonic sequence.  Element i keeps the pair's maximum iff
+// ((i & j) == 0) == ((i & k) == 0): per register h and stage a constant lane mask.
+template <int NR, int K, int J>
+__device__ __forceinline__ void sort_stage(int32_t (&v)[NR]) {
+  if constexpr (J == 64) {                            // K = 128: partner in the lane's other register, all descending
+    const int32_t a = v[0], b = v[NR - 1];
+    v[0] = max(a, b);
+    v[NR - 1] = min(a, b);
+  } else {
 #pragma unroll
-  for (int k = 2; k <= N; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      if (j == 64) {                                  // k = 128: partner in the lane's other register, all descending
-        const int32_t a = v[0], b = v[NR - 1];
-        v[0] = max(a, b);
-        v[NR - 1] = min(a, b);
-      } else {
-#pragma unroll
-        for (int h = 0; h < NR; ++h) {
-          const int i = lane + 64 * h;
-          const int32_t p = __shfl_xor(v[h], j);
-          v[h] = (((i & j) == 0) == ((i & k) == 0)) ? max(v[h], p) : min(v[h], p);
-        }
-      }
+    for (int h = 0; h < NR; ++h) {
+      // lanes whose element has bit K clear: K <= 32 by the lane, K = 64 by the register, K = 128 every element
+      const uint64_t k_clear = K <= 32 ? lanes_bit_clear(K) : (K == 64 && h == 1) ? 0ull : ~0ull;
+      int32_t hi, lo;
+      xor_pair_maxmin<J>(v[h], hi, lo);
+      v[h] = lane_select(~(lanes_bit_clear(J) ^ k_clear), hi, lo);
     }
   }
+  if constexpr (J > 1) sort_stage<NR, K, J / 2>(v);
+  else if constexpr (K < 64 * NR) sort_stage<NR, 2 * K, K>(v);
+}
+
+template <int NR>
+__device__ __forceinline__ void wave_sort_desc(int32_t (&v)[NR]) {
+  sort_stage<NR, 2, 1>(v);
 }
 
 // Sort the tile's bin list (n <= kSortCap entries) front to back.  Leaves the sorted global indices in sg[] (LDS) and
 // in gs[] (register h of lane l: sorted entry l + 64 h), the sorted keys with their low bits SET -- upper bounds of
-// 1 / t, positive floats compared as integers -- in su[] (-1 past the end).
+// 1 / t, positive floats compared as integers -- in us[] (same layout; -1 past the end).
 template <int NR>
 __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __restrict__ list, uint32_t n, int lane,
-                                          int32_t* sg, int32_t* su, int32_t (&gs)[2]) {
+                                          int32_t* sg, int32_t (&gs)[2], int32_t (&us)[2]) {
   int32_t key[NR], g[NR];
 #pragma unroll
   for (int h = 0; h < NR; ++h) {
@@ -695,7 +758,7 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
     const float u = S.rec32[(size_t)(g[h] - S.first) * kRec32Stride[SRH_PRIM_DISK] + 8];
     key[h] = i < n ? (int32_t)((__float_as_uint(u) & ~kSortLow) | i) : -1;   // U > 0: keys of real entries are >= 0
   }
-  wave_sort_desc<NR>(key, lane);
+  wave_sort_desc<NR>(key);
 #pragma unroll
   for (int h = 0; h < NR; ++h) sg[lane + 64 * h] = g[h];          // list order ...
   wave_lds_fence();
@@ -705,9 +768,9 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
 #pragma unroll
   for (int h = 0; h < NR; ++h) {
     sg[lane + 64 * h] = gs[h];
-    su[lane + 64 * h] = key[h] | (int32_t)kSortLow;
+    us[h] = key[h] | (int32_t)kSortLow;
   }
-  if (NR == 1) gs[1] = gs[0];
+  if (NR == 1) { gs[1] = gs[0]; us[1] = -1; }
   wave_lds_fence();
 }
 
@@ -717,7 +780,7 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
 // `rlen_lo` <= 1 / |D| at every pixel of the tile (the disc kernel's Q.rlen is 1: its keys are in den units).
 template <int NR>
 __device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
-                                                 const int32_t* su, int lane, float rlen_lo, QuadState& Q) {
+                                                 const int32_t (&us)[2], float rlen_lo, QuadState& Q) {
   constexpr int TYPE = SRH_PRIM_DISK;
   const char* base_c = reinterpret_cast<const char*>(S.rec32) - (size_t)S.first * (size_t)(4 * kRec32Stride[TYPE]);
   auto record = [&](int g) {
@@ -754,14 +817,12 @@ __device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const 
   // first sorted position whose U lies below the tile's certain inverse depth (n if none)
   auto stop_at = [&]() -> uint32_t {
     const float m0 = __int_as_float(min(min(L[0], L[1]), min(L[2], L[3])));
-    float m = m0 * rlen_lo * kSureRound;
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) m = fminf(m, __shfl_xor(m, x));
+    const float m = wave_min_f32(m0 * rlen_lo * kSureRound);
     const int32_t T = __builtin_amdgcn_readfirstlane(__float_as_int(m));
-    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(su[lane] < T);
+    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(us[0] < T);
     if (b0) return (uint32_t)__builtin_ctzll(b0);
     if (NR == 2) {
-      const unsigned long long b1 = __builtin_amdgcn_ballot_w64(su[lane + 64] < T);
+      const unsigned long long b1 = __builtin_amdgcn_ballot_w64(us[1] < T);
       if (b1) return 64u + (uint32_t)__builtin_ctzll(b1);
     }
     return n;
@@ -921,15 +982,32 @@ __device__ __forceinline__ void binned_tile_of(const FrameDev& F, int& tx, int& 
     ty = (int)(ry * kRegionH + within / kRegionW);
 }
 
+// The frame constants of one finish round.  F lives in the constant address space, so a field can be loaded again
+// wherever it is used; but hipcc hoists the loads -- and what it derives from them, as 64-bit lane masks -- out of the
+// round loop, where they stay live for the whole loop and end up spilled into vector-register lanes (one v_readlane
+// per use, a vector instruction).  The frame's address passed through an empty asm statement is a new value every
+// round: the round's loads stay in the round, as scalar loads.  Only for the one-wave-per-tile kernels (RELOAD), which
+// are bound by vector-instruction issue; the four-wave kernels render small, latency-bound frames and keep the hoisted
+// constants (one run with them reloaded gave config 2 pipelined 0.0173 ms against 0.0146, not clearly outside the
+// spread of that figure, so it is left as it was).
+template <bool RELOAD>
+__device__ __forceinline__ const FrameDev& round_frame(const FrameDev& F) {
+  if constexpr (!RELOAD) return F;
+  typedef const __attribute__((address_space(4))) FrameDev* P;
+  P p = (P)&F;
+  asm volatile("" : "+s"(p));
+  return *(const FrameDev*)p;
+}
+
 template <bool TCH, int WPT, int BATCH = -1>
 __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ F, float* __restrict__ image,
                                                    float* __restrict__ depth, int32_t* __restrict__ nearest) {
+  const FrameDev& F0 = F;
   constexpr int kWaves = WPT;                 // waves of the workgroup
   __shared__ Parked park[kWaves][4][64];      // [wave][pixel of the quad][lane]: conflict-free 16-byte writes
   __shared__ int32_t front[kWaves][4][64];    // global index of each pixel's front candidate (-1: none / saturated)
   __shared__ uint8_t queue[kWaves][256];      // [wave]: ids j * 64 + lane of the pixels with a candidate, row-major
-  __shared__ int32_t occl_g[kWaves][kSortCap];  // occlusion cull: the tile's list in front-to-back order ...
-  __shared__ int32_t occl_u[kWaves][kSortCap];  // ... and its inverse-depth bounds (sweep_sorted)
+  __shared__ int32_t occl_g[kWaves][kSortCap];  // occlusion cull: the tile's list in front-to-back order
   const int wave = kWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   int tx, ty;
@@ -957,13 +1035,13 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   if (listed) {
     // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
     // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
-    int32_t gs[2] = {0, 0};
+    int32_t gs[2] = {0, 0}, us[2] = {-1, -1};   // sorted entries and their bounds (occl_sort)
 #if SRH_OCCLUSION_CULL
     if (WPT == 1 && BATCH == SRH_PRIM_DISK && pretest) {
       const TileLists L{F, tile};
       if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
-        if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], occl_u[wave], gs);
-        else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], occl_u[wave], gs);
+        if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
+        else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         sorted = true;
       }
     }
@@ -1007,8 +1085,8 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       float rl = (float)(1.0 / sqrt(m2));
       rl = (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;           // (0: T = 0, nothing is skipped)
       const float rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rl)));
-      if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
-      else sweep_sorted<2>(F.seg[0], listed, gs, occl_u[wave], lane, rlen_lo, Q);
+      if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, rlen_lo, Q);
+      else sweep_sorted<2>(F.seg[0], listed, gs, us, rlen_lo, Q);
     } else if (pretest) {
       sweep_tile<true, WPT, BATCH>(F, tile, Q, part);
     } else {
@@ -1109,6 +1187,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
 #pragma unroll 1
   for (int base = 0; base < n1; base += 64) {
     {
+      const FrameDev& F = round_frame<WPT == 1>(F0);
       const bool live = base + lane < n1;
       const int id = live ? (int)queue[wave][base + lane] : 0;
       const int j = id >> 6, src = id & 63;
