@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -160,6 +160,28 @@ class SceneBuffers:
         return sum(t.numel() * t.element_size() for t in self.tensors.values())
 
 
+class _Leaf(NamedTuple):
+    """A scene leaf outside scene['objects'].  Its field in the descriptor is named like the last step of its path."""
+    path: Tuple[str, ...]               # where it sits in the scene dict
+    struct: str                         # the descriptor that points at it: "lights" (SrhLights), "materials" (SrhMaterials)
+    grad: Optional[str]                 # its SrhGrads field; None: an index array, not differentiable
+    shape: Tuple[int, ...]              # its shape in SceneBuffers.tensors
+    torch_only: bool = False            # an optional input of the torch backend's shading model (the numpy one ignores
+                                        # it, numpy/renderer.py:234-255)
+
+
+# the scene's leaves outside scene['objects'] under their SceneBuffers.tensors keys, in the order of _float_keys
+_SCENE_LEAVES = {
+    "lights.pos": _Leaf(("lights", "pos"), "lights", "lights_pos", (-1, 4)),
+    "lights.color_idx": _Leaf(("lights", "color_idx"), "lights", None, (-1,)),
+    "colors": _Leaf(("colors",), "lights", "colors", (-1, 3)),
+    "materials.albedo": _Leaf(("materials", "albedo"), "materials", "albedo", (-1, 3)),
+    "materials.coeffs": _Leaf(("materials", "coeffs"), "materials", "coeffs", (-1, 3), True),
+    "lights.attenuation": _Leaf(("lights", "attenuation"), "lights", "attenuation", (-1, 3), True),
+    "lights.ambient": _Leaf(("lights", "ambient"), "lights", "ambient", (3,), True),
+}
+
+
 def _check_w(name: str, arr: Optional[np.ndarray], want: float) -> None:
     if arr is None or arr.size == 0:
         return
@@ -231,48 +253,34 @@ def flatten_scene(scene: Dict[str, Any], device="cuda", validate: bool = True, k
         counts.append(count)
     ob.n_segments = len(kinds)
 
-    lights = scene["lights"]
-    lpos = _as_tensor(lights["pos"], f32, device, keep_graph).reshape(-1, 4)
-    lidx = _as_tensor(lights["color_idx"], i32, device).reshape(-1)
-    colors = _as_tensor(scene["colors"], f32, device, keep_graph).reshape(-1, 3)
-    albedo = _as_tensor(scene["materials"]["albedo"], f32, device, keep_graph).reshape(-1, 3)
-    if lpos.shape[0] != lidx.shape[0]:
+    src = _scene_leaves(scene)
+    for key, x in src.items():
+        leaf = _SCENE_LEAVES[key]
+        tensors[key] = _as_tensor(x, i32 if leaf.grad is None else f32, device, keep_graph).reshape(leaf.shape)
+    lpos, colors, albedo = tensors["lights.pos"], tensors["colors"], tensors["materials.albedo"]
+    if lpos.shape[0] != tensors["lights.color_idx"].shape[0]:
         raise ValueError("lights.pos and lights.color_idx disagree on the number of lights")
     if lpos.shape[0] > _lib.MAX_LIGHTS:
         raise ValueError(f"at most {_lib.MAX_LIGHTS} lights")
     if validate:
-        _check_w("lights.pos", _host_view(lights["pos"]), 1.0)
-        ci = _host_view(lights["color_idx"])
+        _check_w("lights.pos", _host_view(src["lights.pos"]), 1.0)
+        ci = _host_view(src["lights.color_idx"])
         if ci is not None and ci.size and (ci.min() < 0 or ci.max() >= colors.shape[0]):
             raise IndexError("lights.color_idx out of range for the colour table")
-    tensors.update({"lights.pos": lpos, "lights.color_idx": lidx, "colors": colors, "materials.albedo": albedo})
-    # inputs of the torch backend's shading model only (ignored by the numpy one, numpy/renderer.py:234-255)
-    if "attenuation" in lights:
-        att = _as_tensor(lights["attenuation"], f32, device, keep_graph).reshape(-1, 3)
-        if att.shape[0] != lpos.shape[0]:
-            raise ValueError("lights.attenuation must have one (kc, kl, kq) row per light")
-        tensors["lights.attenuation"] = att
-    if "ambient" in lights:
-        tensors["lights.ambient"] = _as_tensor(lights["ambient"], f32, device, keep_graph).reshape(3)
-    if "coeffs" in scene["materials"]:
-        cfs = _as_tensor(scene["materials"]["coeffs"], f32, device, keep_graph).reshape(-1, 3)
-        if cfs.shape[0] != albedo.shape[0]:
-            raise ValueError("materials.coeffs must have one row per material")
-        tensors["materials.coeffs"] = cfs
+    if "lights.attenuation" in tensors and tensors["lights.attenuation"].shape[0] != lpos.shape[0]:
+        raise ValueError("lights.attenuation must have one (kc, kl, kq) row per light")
+    if "materials.coeffs" in tensors and tensors["materials.coeffs"].shape[0] != albedo.shape[0]:
+        raise ValueError("materials.coeffs must have one row per material")
 
     _upload(tensors, device)
     for s, kind in enumerate(kinds):
         for name in _OBJ_FIELDS[kind] + ("material_idx",):
             setattr(ob.seg[s], name, tensors[f"{kind}.{name}"].data_ptr())
-    ls = _lib.SrhLights(n_lights=lpos.shape[0], n_colors=colors.shape[0], pos=tensors["lights.pos"].data_ptr(),
-                        color_idx=tensors["lights.color_idx"].data_ptr(), colors=tensors["colors"].data_ptr())
-    ms = _lib.SrhMaterials(n_materials=albedo.shape[0], albedo=tensors["materials.albedo"].data_ptr())
-    if "lights.attenuation" in tensors:
-        ls.attenuation = tensors["lights.attenuation"].data_ptr()
-    if "lights.ambient" in tensors:
-        ls.ambient = tensors["lights.ambient"].data_ptr()
-    if "materials.coeffs" in tensors:
-        ms.coeffs = tensors["materials.coeffs"].data_ptr()
+    ls = _lib.SrhLights(n_lights=lpos.shape[0], n_colors=colors.shape[0])
+    ms = _lib.SrhMaterials(n_materials=albedo.shape[0])
+    for key in src:
+        leaf = _SCENE_LEAVES[key]
+        setattr(ls if leaf.struct == "lights" else ms, leaf.path[-1], tensors[key].data_ptr())
 
     gamma = None
     if "tonemap" in scene:
@@ -290,6 +298,16 @@ def _shape_of(x):
     if isinstance(x, torch.Tensor):
         return tuple(x.shape)
     return np.asarray(x).shape
+
+
+def _scene_leaves(scene: Dict[str, Any]) -> Dict[str, Any]:
+    """The caller's own leaf objects outside scene['objects'] (``_SCENE_LEAVES``) that the scene has, by flat key."""
+    out: Dict[str, Any] = {}
+    for key, leaf in _SCENE_LEAVES.items():
+        grp = scene if len(leaf.path) == 1 else scene[leaf.path[0]]
+        if not leaf.torch_only or leaf.path[-1] in grp:
+            out[key] = grp[leaf.path[-1]]
+    return out
 
 
 def camera_struct(camera: Dict[str, Any], shading: str = "numpy") -> _lib.SrhCamera:
@@ -370,6 +388,29 @@ def _layout_key(buf: "SceneBuffers", width: int, height: int, what="frame"):
     return (what, tuple((ob.seg[s].type, ob.seg[s].count) for s in range(ob.n_segments)), int(width), int(height))
 
 
+class _Shade(NamedTuple):
+    """How a frame is shaded: the model (``'numpy'`` | ``'torch'``), the torch model's ``double_sided`` and
+    ``use_quartic``, whether the shadow-ray pass runs and whether the ``normal`` / ``pos`` outputs are written."""
+    shading: str = "numpy"
+    double_sided: bool = False
+    use_quartic: bool = False
+    shadow: bool = False
+    aux: bool = False
+
+
+def _rows(rows: Optional[Tuple[int, int]], height: int) -> Tuple[int, int]:
+    """The row slab ``rows`` as (r0, r1); None is the whole frame."""
+    return (0, height) if rows is None else (int(rows[0]), int(rows[1]))
+
+
+def _params(buf: SceneBuffers, rows: Tuple[int, int], mode: str, shade: _Shade, **fields) -> _lib.SrhParams:
+    """SrhParams of a call over the resolved ``rows``: the scene's tonemap, ``mode``, ``shade``'s options and the call's
+    own ``fields``."""
+    return _lib.SrhParams(row0=rows[0], row1=rows[1], mode=_lib.MODES[mode], tonemap_gamma=0 if buf.gamma is None else 1,
+                          gamma=1.0 if buf.gamma is None else buf.gamma, shading=_lib.SHADING[shade.shading],
+                          double_sided=int(bool(shade.double_sided)), use_quartic=int(bool(shade.use_quartic)), **fields)
+
+
 def render_buffers(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[int, int]] = None,
                    mode: str = "auto", out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
                    want_nearest: bool = True, events: Optional[_lib.EventPair] = None,
@@ -387,7 +428,7 @@ def render_buffers(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[
     dense (h,W,3) f32 outputs."""
     lib = _lib.load()
     width, height = frame_size(cam)
-    r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
+    r0, r1 = _rows(rows, height)
     h = r1 - r0
     if out is None:
         image = torch.empty((max(h, 0), width, 3), dtype=torch.float32, device=buf.device)
@@ -403,18 +444,20 @@ def render_buffers(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[
             if tuple(t.shape) != shape or t.dtype != dt or not inner or t.device != buf.device:
                 raise ValueError(f"out buffer mismatch: want {dt} {shape} with dense rows on {buf.device}, "
                                  f"got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
-    params = _lib.SrhParams(row0=r0, row1=r1, mode=_lib.MODES[mode],
-                            tonemap_gamma=0 if buf.gamma is None else 1,
-                            gamma=1.0 if buf.gamma is None else buf.gamma,
-                            shading=_lib.SHADING[shading], double_sided=int(bool(double_sided)),
-                            use_quartic=int(bool(use_quartic)), waves_per_tile=int(waves_per_tile),
-                            normal_out=aux[0].data_ptr() if aux and aux[0] is not None else None,
-                            pos_out=aux[1].data_ptr() if aux and aux[1] is not None else None,
-                            image_row_stride=image.stride(0) if h > 1 else 0,
-                            depth_row_stride=depth.stride(0) if h > 1 else 0,
-                            nearest_row_stride=nearest.stride(0) if (nearest is not None and h > 1) else 0,
-                            ev_start=events.start if events else None, ev_stop=events.stop if events else None,
-                            stages=int(stages))
+    params = _params(buf, (r0, r1), mode, _Shade(shading, double_sided, use_quartic))
+    # this call's own fields are assigned here, not forwarded through _params as keywords: that costs a microsecond of
+    # host time per frame
+    params.waves_per_tile = int(waves_per_tile)
+    params.stages = int(stages)
+    if aux:
+        params.normal_out = aux[0].data_ptr() if aux[0] is not None else None
+        params.pos_out = aux[1].data_ptr() if aux[1] is not None else None
+    if h > 1:
+        params.image_row_stride = image.stride(0)
+        params.depth_row_stride = depth.stride(0)
+        params.nearest_row_stride = nearest.stride(0) if nearest is not None else 0
+    if events:
+        params.ev_start, params.ev_stop = events.start, events.stop
     if workspace is None:
         workspace = buf.ensure_workspace(width, height)
     binned = mode in ("auto", "binned") and not cam.ortho
@@ -451,7 +494,7 @@ def bin_statistics(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[
     reference evaluates -- and ``tile_row_cost``, the per-tile-row sums ``dist.cost_weighted_slabs`` partitions."""
     lib = _lib.load()
     width, height = frame_size(cam)
-    r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
+    r0, r1 = _rows(rows, height)
     ws = buf.new_workspace(width, height)
     image = torch.empty((r1 - r0, width, 3), dtype=torch.float32, device=buf.device)
     depth = torch.empty((r1 - r0, width), dtype=torch.float32, device=buf.device)
@@ -480,24 +523,19 @@ def generate_rays(camera: Dict[str, Any], device="cuda", rows: Optional[Tuple[in
     lib = _lib.load()
     cam = camera_struct(camera)
     width, height = frame_size(cam)
-    r0, r1 = (0, height) if rows is None else rows
+    r0, r1 = _rows(rows, height)
     out = torch.empty((4, max(r1 - r0, 0) * width), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
         _lib.check(lib.srh_generate_rays(C.byref(cam), r0, r1, out.data_ptr(), _stream_ptr(device)))
     return out
 
 
-_TORCH_SHADING_KEYS = ("materials.coeffs", "lights.attenuation", "lights.ambient")
-
-
 def _float_keys(buf: SceneBuffers, shading: str = "numpy") -> List[str]:
     """Keys of buf.tensors that are differentiable inputs, in a fixed order (the torch shading model adds its own
     inputs where the scene has them)."""
     keys = [f"{kind}.{name}" for kind in buf.kinds for name in _OBJ_FIELDS[kind]]
-    keys += ["lights.pos", "colors", "materials.albedo"]
-    if shading == "torch":
-        keys += [k for k in _TORCH_SHADING_KEYS if k in buf.tensors]
-    return keys
+    return keys + [k for k, leaf in _SCENE_LEAVES.items()
+                   if leaf.grad and k in buf.tensors and (shading == "torch" or not leaf.torch_only)]
 
 
 def shadow_pass(buf: SceneBuffers, cam: _lib.SrhCamera, rows, image: torch.Tensor, depth: torch.Tensor,
@@ -509,12 +547,9 @@ def shadow_pass(buf: SceneBuffers, cam: _lib.SrhCamera, rows, image: torch.Tenso
     screen space; ``all_pairs=True`` runs the reference's O(pixels x lights x primitives) loop instead (same result)."""
     lib = _lib.load()
     width, height = frame_size(cam)
-    r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
+    r0, r1 = _rows(rows, height)
     vis = torch.empty((r1 - r0, width), dtype=torch.int64, device=buf.device)
-    params = _lib.SrhParams(row0=r0, row1=r1, mode=_lib.MODES["exact" if all_pairs else "auto"],
-                            tonemap_gamma=0 if buf.gamma is None else 1,
-                            gamma=1.0 if buf.gamma is None else buf.gamma, shading=_lib.SHADING["torch"],
-                            double_sided=int(bool(double_sided)), use_quartic=int(bool(use_quartic)))
+    params = _params(buf, (r0, r1), "exact" if all_pairs else "auto", _Shade("torch", double_sided, use_quartic))
     if all_pairs:
         workspace = buf.ensure_workspace(width, height)
     else:
@@ -526,58 +561,73 @@ def shadow_pass(buf: SceneBuffers, cam: _lib.SrhCamera, rows, image: torch.Tenso
     return vis
 
 
+def _frame(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Shade, waves_per_tile: int = 0,
+           workspace: Optional[torch.Tensor] = None):
+    """render_buffers with what ``shade`` asks for around it: image, depth, nearest, the (normal, pos) buffers with
+    ``shade.aux`` (else None) and the shadow pass's visibility with ``shade.shadow`` (else None)."""
+    aux = _aux_buffers(cam, rows, buf.device) if shade.aux else None
+    image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode, shading=shade.shading,
+                                           double_sided=shade.double_sided, use_quartic=shade.use_quartic, aux=aux,
+                                           waves_per_tile=waves_per_tile, workspace=workspace)
+    vis = shadow_pass(buf, cam, rows, image, depth, nearest, shade.double_sided, shade.use_quartic) if shade.shadow else None
+    return image, depth, nearest, aux, vis
+
+
 class _RenderFunction(torch.autograd.Function):
     """render_buffers with the analytic backward of libsrh (srh_render_bwd).  Gradient semantics are those of
     autograd through the reference's torch backend (SURVEY.md section 8, row a-B): selection and masks are piecewise
-    constant; a disc's radius and a triangle's vertices 1, 2 receive zero gradient.  With shade[4] (torch shading only)
-    the outputs are image, depth, nearest, normal, pos, and upstream gradients of normal / pos go to
+    constant; a disc's radius and a triangle's vertices 1, 2 receive zero gradient.  With ``shade.aux`` (torch shading
+    only) the outputs are image, depth, nearest, normal, pos, and upstream gradients of normal / pos go to
     srh_render_bwd_aux."""
 
     @staticmethod
-    def forward(ctx, buf, cam, rows, mode, shade, *inputs):
-        # shade = (shading, double_sided, use_quartic, shadow, aux)
-        aux = None
-        if shade[4]:
-            aux = _aux_buffers(cam, rows, buf.device)
+    def forward(ctx, buf, cam, rows, mode, shade: _Shade, *inputs):
+        if shade.aux:
             ctx.set_materialize_grads(False)            # an unused normal / pos must arrive as None, not as zeros
-        image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode, shading=shade[0],
-                                               double_sided=shade[1], use_quartic=shade[2], aux=aux)
-        vis = shadow_pass(buf, cam, rows, image, depth, nearest, shade[1], shade[2]) if shade[3] else None
+        image, depth, nearest, aux, vis = _frame(buf, cam, rows, mode, shade)
         ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade = buf, cam, rows, mode, shade
-        ctx.has_vis = vis is not None
-        if vis is not None:
-            ctx.save_for_backward(depth, nearest, vis)
-        else:
-            ctx.save_for_backward(depth, nearest)
+        ctx.save_for_backward(depth, nearest, vis)
         ctx.mark_non_differentiable(nearest)
-        if aux is not None:
-            return image, depth, nearest, aux[0], aux[1]
-        return image, depth, nearest
+        return (image, depth, nearest) + (aux or ())
 
     @staticmethod
     def backward(ctx, g_image, g_depth, _g_nearest, g_normal=None, g_pos=None):
-        if ctx.has_vis:
-            depth, nearest, vis = ctx.saved_tensors
-        else:
-            (depth, nearest), vis = ctx.saved_tensors, None
-        keys = _float_keys(ctx.buf, ctx.shade[0])
+        depth, nearest, vis = ctx.saved_tensors
+        keys = _float_keys(ctx.buf, ctx.shade.shading)
         grads = _render_backward(ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade, depth, nearest, vis, g_image, g_depth,
                                  ctx.needs_input_grad[5:], g_normal, g_pos)
         return (None, None, None, None, None) + tuple(grads.get(k) for k in keys)
 
 
-def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade, depth: torch.Tensor,
+def _forward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Shade, inputs: Sequence[torch.Tensor],
+             differentiable: bool, waves_per_tile: int = 0):
+    """One frame for ``render`` and ``ResidentScene.render``: through ``_RenderFunction`` when ``differentiable`` (the
+    shadow pass, if any, then runs inside it), else straight from ``_frame``.  Returns image, depth, nearest and a dict
+    of the extra outputs: ``normal`` and ``pos`` with ``shade.aux``, and outside autograd ``light_visibility`` with
+    ``shade.shadow``."""
+    if differentiable:
+        out = _RenderFunction.apply(buf, cam, rows, mode, shade, *inputs)
+        return out[0], out[1], out[2], ({"normal": out[3], "pos": out[4]} if shade.aux else {})
+    image, depth, nearest, aux, vis = _frame(buf, cam, rows, mode, shade, waves_per_tile)
+    extra = {"normal": aux[0], "pos": aux[1]} if aux else {}
+    if vis is not None:
+        extra["light_visibility"] = vis
+    return image, depth, nearest, extra
+
+
+def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Shade, depth: torch.Tensor,
                      nearest: torch.Tensor, vis: Optional[torch.Tensor], g_image: Optional[torch.Tensor],
                      g_depth: Optional[torch.Tensor], need: Sequence[bool], g_normal: Optional[torch.Tensor] = None,
-                     g_pos: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                     g_pos: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """srh_render_bwd: gradients of the inputs named by ``_float_keys`` (those with ``need``) for the upstream gradients
     of image and depth, from the winners the forward pass saved.  Everything is enqueued on the current stream.
     With an upstream gradient of the torch shading's ``normal`` or ``pos`` output the call is srh_render_bwd_aux
-    instead; there a missing ``g_image`` is passed as NULL (the geometry-only kernel) rather than as zeros."""
+    instead; there a missing ``g_image`` is passed as NULL (the geometry-only kernel) rather than as zeros.
+    ``workspace`` defaults to the buffers' own scratch (``ensure_workspace``)."""
     lib = _lib.load()
     width, height = frame_size(cam)
-    r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
-    keys = _float_keys(buf, shade[0])
+    r0, r1 = _rows(rows, height)
+    keys = _float_keys(buf, shade.shading)
     grads: Dict[str, torch.Tensor] = {}
     sg = _lib.SrhGrads()
     for key, want in zip(keys, need):
@@ -585,37 +635,20 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
             continue
         g = torch.zeros_like(buf.tensors[key])
         grads[key] = g
-        if key == "lights.pos":
-            sg.lights_pos = g.data_ptr()
-        elif key == "colors":
-            sg.colors = g.data_ptr()
-        elif key == "materials.albedo":
-            sg.albedo = g.data_ptr()
-        elif key == "materials.coeffs":
-            sg.coeffs = g.data_ptr()
-        elif key == "lights.attenuation":
-            sg.attenuation = g.data_ptr()
-        elif key == "lights.ambient":
-            sg.ambient = g.data_ptr()
-        else:
+        if key in _SCENE_LEAVES:
+            setattr(sg, _SCENE_LEAVES[key].grad, g.data_ptr())
+        elif key != "disk.radius":            # identically zero (numpy/renderer.py:88: the radius only feeds a mask)
             kind, name = key.split(".")
-            s = buf.kinds.index(kind)
-            if name == "radius" and kind == "disk":
-                continue                      # identically zero (numpy/renderer.py:88: the radius only feeds a mask)
-            getattr(sg, name)[s] = g.data_ptr()
+            getattr(sg, name)[buf.kinds.index(kind)] = g.data_ptr()
     aux = g_normal is not None or g_pos is not None
     g_image = g_image.to(torch.float32).contiguous() if g_image is not None else \
         (None if aux else torch.zeros((r1 - r0, width, 3), dtype=torch.float32, device=buf.device))
     g_depth = g_depth.to(torch.float32).contiguous() if g_depth is not None else None
     g_normal = g_normal.to(torch.float32).contiguous() if g_normal is not None else None
     g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
-    params = _lib.SrhParams(row0=r0, row1=r1, mode=_lib.MODES[mode],
-                            tonemap_gamma=0 if buf.gamma is None else 1,
-                            gamma=1.0 if buf.gamma is None else buf.gamma,
-                            shading=_lib.SHADING[shade[0]], double_sided=int(bool(shade[1])),
-                            use_quartic=int(bool(shade[2])),
-                            visibility=vis.data_ptr() if vis is not None else None)
-    workspace = buf.ensure_workspace(width, height)
+    params = _params(buf, (r0, r1), mode, shade, visibility=vis.data_ptr() if vis is not None else None)
+    if workspace is None:
+        workspace = buf.ensure_workspace(width, height)
     def ptr(t):
         return t.data_ptr() if t is not None else None
 
@@ -632,12 +665,6 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
                                     nearest.data_ptr(), depth.data_ptr(), C.byref(sg), _stream_ptr(buf.device))
     _lib.check(rc)
     return grads
-
-
-_OVERRIDE_FIELDS = {"lights.pos": ("lights", "pos"), "lights.color_idx": ("lights", "color_idx"),
-                    "colors": ("lights", "colors"), "lights.attenuation": ("lights", "attenuation"),
-                    "lights.ambient": ("lights", "ambient"), "materials.albedo": ("materials", "albedo"),
-                    "materials.coeffs": ("materials", "coeffs")}
 
 
 class ViewScenes:
@@ -666,10 +693,10 @@ class ViewScenes:
                 if tuple(t.shape) != tuple(base.shape):
                     raise ValueError(f"view {v}: {key} has shape {tuple(t.shape)}, the scene's leaf {tuple(base.shape)}")
                 self.keep.append(t)
-                if key in _OVERRIDE_FIELDS:
-                    which, field = _OVERRIDE_FIELDS[key]
-                    setattr((self.lights if which == "lights" else self.materials)[v], field, t.data_ptr())
-                    self.mask |= _lib.VIEWS_LIGHTS if which == "lights" else _lib.VIEWS_MATERIALS
+                leaf = _SCENE_LEAVES.get(key)
+                if leaf is not None:
+                    setattr(getattr(self, leaf.struct)[v], leaf.path[-1], t.data_ptr())
+                    self.mask |= _lib.VIEWS_LIGHTS if leaf.struct == "lights" else _lib.VIEWS_MATERIALS
                 else:
                     kind, field = key.split(".")
                     setattr(self.objects[v].seg[buf.kinds.index(kind)], field, t.data_ptr())
@@ -687,24 +714,21 @@ def render_views_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], imag
                          nearests: Optional[torch.Tensor] = None, rows: Optional[Tuple[int, int]] = None,
                          workspace: Optional[torch.Tensor] = None, image_row_stride: int = 0,
                          depth_row_stride: int = 0, view_row0: Optional[Sequence[int]] = None,
-                         scenes: Optional[ViewScenes] = None, **shading_kw) -> torch.Tensor:
+                         scenes: Optional[ViewScenes] = None, mode: str = "auto", first_view: int = 0,
+                         **shading_kw) -> torch.Tensor:
     """Low-level form of ``render_views``: resident scene buffers, camera structs, caller-provided stacked outputs
     (view v starts v * rows * row_stride elements after view 0) and an optional row slab; with ``view_row0`` view v
     renders rows [view_row0[v], view_row0[v] + rows[1] - rows[0]) instead; ``scenes`` gives every view its own
-    geometry / lights / materials (``ViewScenes``).  One library call, every pipeline kernel launched once for the
-    whole batch.  Returns the workspace (pass it back in to reuse it)."""
+    geometry / lights / materials (``ViewScenes``), camera i drawing view ``first_view + i`` of it.  ``mode`` is
+    'auto' or 'binned'.  One library call, every pipeline kernel launched once for the whole batch.  Returns the
+    workspace (pass it back in to reuse it)."""
     lib = _lib.load()
     width, height = frame_size(cams[0])
-    r0, r1 = (0, height) if rows is None else (int(rows[0]), int(rows[1]))
     n = len(cams)
-    shading = shading_kw.get("shading", "numpy")
-    params = _lib.SrhParams(row0=r0, row1=r1, mode=_lib.MODES["auto"],
-                            tonemap_gamma=0 if buf.gamma is None else 1,
-                            gamma=1.0 if buf.gamma is None else buf.gamma,
-                            shading=_lib.SHADING[shading], double_sided=int(bool(shading_kw.get("double_sided", False))),
-                            use_quartic=int(bool(shading_kw.get("use_quartic", False))),
-                            waves_per_tile=int(shading_kw.get("waves_per_tile", 0)),
-                            image_row_stride=int(image_row_stride), depth_row_stride=int(depth_row_stride))
+    shade = _Shade(shading_kw.get("shading", "numpy"), shading_kw.get("double_sided", False),
+                   shading_kw.get("use_quartic", False))
+    params = _params(buf, _rows(rows, height), mode, shade, waves_per_tile=int(shading_kw.get("waves_per_tile", 0)),
+                     image_row_stride=int(image_row_stride), depth_row_stride=int(depth_row_stride))
     row0_arr = None
     if view_row0 is not None:
         if len(view_row0) != n:
@@ -724,15 +748,15 @@ def render_views_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], imag
         _ws_note(workspace, None)
     ob, ls, ms = C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials)
     if scenes is not None:
-        if scenes.n != n:
-            raise ValueError(f"{scenes.n} per-view scenes for {n} cameras")
+        if first_view < 0 or first_view + n > scenes.n:
+            raise ValueError(f"{scenes.n} per-view scenes for {n} cameras from view {first_view}")
         params.per_view = scenes.mask
         if scenes.mask & _lib.VIEWS_OBJECTS:
-            ob = scenes.objects
+            ob = C.byref(scenes.objects[first_view])
         if scenes.mask & _lib.VIEWS_LIGHTS:
-            ls = scenes.lights
+            ls = C.byref(scenes.lights[first_view])
         if scenes.mask & _lib.VIEWS_MATERIALS:
-            ms = scenes.materials
+            ms = C.byref(scenes.materials[first_view])
     with torch.cuda.device(buf.device):
         _lib.check(lib.srh_render_views(n, arr, ob, ls, ms,
                                         C.byref(params), workspace.data_ptr(), workspace.numel(), images.data_ptr(),
@@ -798,46 +822,15 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
                                                double_sided=bool(shading_kw.get("double_sided", False)),
                                                use_quartic=bool(shading_kw.get("use_quartic", False)))
 
-    if every is not None and not (mode in ("auto", "binned") and int(batch) > 0):
-        # per-view scenes outside the batched call: one frame per view from that view's buffers
-        for v in range(n):
-            render_buffers(scene_of(v), cams[v], mode=mode, out=(image[v], depth[v], nearest[v] if want_nearest else None),
-                           **shading_kw)
-        shadows(0, n)
-        return out
     if mode in ("auto", "binned") and int(batch) > 0:
-        lib = _lib.load()
-        shading = shading_kw.get("shading", "numpy")
-        params = _lib.SrhParams(row0=0, row1=height, mode=_lib.MODES[mode],
-                                tonemap_gamma=0 if buf.gamma is None else 1,
-                                gamma=1.0 if buf.gamma is None else buf.gamma,
-                                shading=_lib.SHADING[shading], double_sided=int(bool(shading_kw.get("double_sided", False))),
-                                use_quartic=int(bool(shading_kw.get("use_quartic", False))),
-                                waves_per_tile=int(shading_kw.get("waves_per_tile", 0)))
         step = max(1, min(int(batch), n))
-        nbytes = lib.srh_workspace_bytes_views(C.byref(buf.objects), width, height, step)
-        if nbytes == 0:
-            raise _lib.SrhError(-2, lib.srh_last_error().decode())
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            for i in range(0, n, step):
-                m = min(step, n - i)
-                arr = (_lib.SrhCamera * m)(*cams[i:i + m])
-                ob, ls, ms = C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials)
-                params.per_view = 0
-                if every is not None:                       # element i of each per-view array is this batch's view 0
-                    params.per_view = every.mask
-                    if every.mask & _lib.VIEWS_OBJECTS:
-                        ob = C.byref(every.objects[i])
-                    if every.mask & _lib.VIEWS_LIGHTS:
-                        ls = C.byref(every.lights[i])
-                    if every.mask & _lib.VIEWS_MATERIALS:
-                        ms = C.byref(every.materials[i])
-                _lib.check(lib.srh_render_views(m, arr, ob, ls, ms,
-                                                C.byref(params), workspace.data_ptr(), workspace.numel(),
-                                                image[i].data_ptr(), depth[i].data_ptr(),
-                                                nearest[i].data_ptr() if want_nearest else None, _stream_ptr(device)))
-                shadows(i, m)
+        workspace = None                                    # sized by the first (largest) batch, reused by the others
+        for i in range(0, n, step):
+            m = min(step, n - i)
+            workspace = render_views_buffers(buf, cams[i:i + m], image[i:i + m], depth[i:i + m],
+                                             nearest[i:i + m] if want_nearest else None, workspace=workspace,
+                                             scenes=every, mode=mode, first_view=i, **shading_kw)
+            shadows(i, m)
         return out
     n_streams = max(1, min(int(streams), n))
     pool = [torch.cuda.Stream(device) for _ in range(n_streams)]
@@ -845,14 +838,14 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
     current = torch.cuda.current_stream(device)
     for st in pool:
         st.wait_stream(current)                 # uploads and allocations above happen-before the views
-    for i, cam in enumerate(cams):
-        k = i % n_streams
+    for v, cam in enumerate(cams):
+        k = v % n_streams
         with torch.cuda.stream(pool[k]):
-            render_buffers(buf, cam, mode=mode, out=(image[i], depth[i], nearest[i] if want_nearest else None),
+            render_buffers(scene_of(v), cam, mode=mode, out=(image[v], depth[v], nearest[v] if want_nearest else None),
                            workspace=scratch[k], **shading_kw)
     for st in pool:
         current.wait_stream(st)
-    for t in (image, depth, nearest, *scratch, *buf.tensors.values()):
+    for t in (image, depth, nearest, *scratch, *buf.tensors.values(), *(every.keep if every is not None else ())):
         if t is not None:
             t.record_stream(current)
     shadows(0, n)
@@ -866,13 +859,7 @@ def _source_leaves(scene: Dict[str, Any]) -> Dict[str, Any]:
         for name in _OBJ_FIELDS.get(kind, ()):
             if name in grp:
                 out[f"{kind}.{name}"] = grp[name]
-    out["lights.pos"] = scene["lights"]["pos"]
-    out["colors"] = scene["colors"]
-    out["materials.albedo"] = scene["materials"]["albedo"]
-    for key, (grp, name) in {"lights.attenuation": ("lights", "attenuation"), "lights.ambient": ("lights", "ambient"),
-                             "materials.coeffs": ("materials", "coeffs")}.items():
-        if name in scene[grp]:
-            out[key] = scene[grp][name]
+    out.update(_scene_leaves(scene))
     return out
 
 
@@ -908,7 +895,7 @@ class ResidentScene:
         if self.cam.ortho and shading != "torch":
             raise ValueError("orthographic projection exists only in the torch backend's semantics: shading='torch'")
         self.aux = bool(aux)
-        self.shade = (shading, bool(double_sided), bool(use_quartic), False, self.aux)
+        self.shade = _Shade(shading, bool(double_sided), bool(use_quartic), False, self.aux)
         self.inputs = [self.buf.tensors[k] for k in _float_keys(self.buf, shading)]
         self.differentiable = any(t.requires_grad for t in self.inputs)
         # "In place" has to be true for every leaf that is being optimised: a float64, CPU or non-contiguous leaf is
@@ -933,18 +920,8 @@ class ResidentScene:
         self.cam = camera_struct(camera, self.shading)
 
     def render(self, rows: Optional[Tuple[int, int]] = None) -> "RenderResult":
-        extra = {}
-        if self.differentiable and torch.is_grad_enabled():
-            out = _RenderFunction.apply(self.buf, self.cam, rows, self.mode, self.shade, *self.inputs)
-            image, depth, nearest = out[:3]
-            if self.aux:
-                extra = {"normal": out[3], "pos": out[4]}
-        else:
-            aux = _aux_buffers(self.cam, rows, self.device) if self.aux else None
-            image, depth, nearest = render_buffers(self.buf, self.cam, rows=rows, mode=self.mode, shading=self.shading,
-                                                   double_sided=self.shade[1], use_quartic=self.shade[2], aux=aux)
-            if aux is not None:
-                extra = {"normal": aux[0], "pos": aux[1]}
+        image, depth, nearest, extra = _forward(self.buf, self.cam, rows, self.mode, self.shade, self.inputs,
+                                                self.differentiable and torch.is_grad_enabled())
         return RenderResult(self._camera, self.device, image=image, depth=depth, nearest=nearest, **extra)
 
     def capture_step(self, loss_fn, warmup: int = 3) -> "CapturedStep":
@@ -962,12 +939,13 @@ class CapturedStep:
     with ``ResidentScene(aux=True)``), torch's own backward of the loss down to those outputs, and the library's
     backward from there to the leaves, called directly.  (Letting
     the autograd engine run the renderer's autograd.Function inside a capture ends in a segmentation fault in
-    hipStreamEndCapture on ROCm 7.2 -- tools/diag_capture.py; each of the pieces used here captures fine.)  The
+    hipStreamEndCapture on ROCm 7.2 -- profiles/r03_capture_diag.txt; each of the pieces used here captures fine.)  The
     leaves' ``.grad`` tensors are static: every replay overwrites them (they do not accumulate), ``loss`` and
     ``result`` are static tensors too.
     What a replay reads is device memory only -- the leaves (an optimiser's in-place step is seen by the next replay)
     and whatever tensors ``loss_fn`` closes over (update a target with ``copy_``) -- while the camera and everything
-    else on the host was frozen at capture time."""
+    else on the host was frozen at capture time.  The step holds one frame's scratch of its own (``workspace``), so
+    eager ``rs.render()`` calls between replays, at any frame size, leave the replays alone."""
 
     def __init__(self, rs: ResidentScene, loss_fn, warmup: int = 3):
         if not rs.differentiable:
@@ -978,14 +956,18 @@ class CapturedStep:
         # hand-made .grad has to be put on the leaves themselves)
         self.keys = [k for k in keys if k in rs.leaves]
         self.leaves = [rs.leaves[k] for k in self.keys]
+        self.workspace = rs.buf.new_workspace(*frame_size(rs.cam))
         current = torch.cuda.current_stream(rs.device)
         side = torch.cuda.Stream(rs.device)
         side.wait_stream(current)
         with torch.cuda.stream(side):
-            for _ in range(max(1, int(warmup))):        # module load, allocator, the scratch's bin counters
+            for _ in range(max(1, int(warmup))):        # module load, allocator
                 for t in self.leaves:
                     t.grad = None
                 loss_fn(rs.render()).backward()
+            # one frame in the step's own scratch clears its bin counters and leaves them clean: the graph then holds no
+            # clearing launch
+            _frame(rs.buf, rs.cam, None, rs.mode, rs.shade, workspace=self.workspace)
         current.wait_stream(side)
         torch.cuda.synchronize(rs.device)
         for t in self.leaves:
@@ -994,9 +976,7 @@ class CapturedStep:
         need = [k in rs.leaves for k in keys]
         with torch.cuda.graph(self.graph):
             with torch.no_grad():
-                aux = _aux_buffers(rs.cam, None, rs.device) if rs.aux else None
-                image, depth, nearest = render_buffers(rs.buf, rs.cam, mode=rs.mode, shading=rs.shading,
-                                                       double_sided=rs.shade[1], use_quartic=rs.shade[2], aux=aux)
+                image, depth, nearest, aux, _ = _frame(rs.buf, rs.cam, None, rs.mode, rs.shade, workspace=self.workspace)
             outs = [image.requires_grad_(), depth.requires_grad_()]
             extra = {}
             if aux is not None:
@@ -1006,7 +986,7 @@ class CapturedStep:
             self.loss = loss_fn(self.result)
             g = list(torch.autograd.grad(self.loss, outs, allow_unused=True)) + [None, None]
             got = _render_backward(rs.buf, rs.cam, None, rs.mode, rs.shade, depth, nearest, None, g[0], g[1], need,
-                                   g[2], g[3])
+                                   g[2], g[3], workspace=self.workspace)
         # the static gradient tensors every replay writes, in the order of self.leaves and in the leaves' own shapes
         self.grads = [(got[k] if k in got else torch.zeros_like(rs.buf.tensors[k])).view(leaf.shape)
                       for k, leaf in zip(self.keys, self.leaves)]
@@ -1023,7 +1003,8 @@ class CapturedStep:
 def _aux_buffers(cam: _lib.SrhCamera, rows, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
     """The (rows, W, 3) float32 ``normal`` and ``pos`` outputs of a torch-shading frame (or slab)."""
     width, height = frame_size(cam)
-    h = height if rows is None else int(rows[1]) - int(rows[0])
+    r0, r1 = _rows(rows, height)
+    h = r1 - r0
     return (torch.empty((h, width, 3), dtype=torch.float32, device=device),
             torch.empty((h, width, 3), dtype=torch.float32, device=device))
 
@@ -1109,43 +1090,17 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
     norm_depth = bool(params.get("norm_depth_image_only", False))
     if norm_depth and shading != "torch":
         raise ValueError("norm_depth_image_only exists only in the torch backend's semantics: shading='torch'")
+    if cam.ortho and shading != "torch":
+        raise ValueError("orthographic projection exists only in the torch backend's semantics: shading='torch'")
     inputs = [buf.tensors[k] for k in _float_keys(buf, shading)]
-    if cam.ortho:
-        if shading != "torch":
-            raise ValueError("orthographic projection exists only in the torch backend's semantics: shading='torch'")
-    if shading == "torch":
-        # the torch backend's semantics
-        shade = ("torch", bool(params.get("double_sided", False)), bool(params.get("use_quartic", False)), shadow)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
-            # differentiable call; norm_depth_image_only returns no normal / pos (torch/renderer.py:245-260)
-            out = _RenderFunction.apply(buf, cam, rows, mode, shade + (not norm_depth,), *inputs)
-            image, depth, nearest = out[:3]
-            if norm_depth:
-                return RenderResult(scene["camera"], device, image=_norm_depth_image(depth, cam.far_clip), depth=depth,
-                                    nearest=nearest.to(torch.int64))
-            return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64),
-                                normal=out[3], pos=out[4])
-        width, height = frame_size(cam)
-        r0, r1 = (0, height) if rows is None else rows
-        normal = torch.empty((r1 - r0, width, 3), dtype=torch.float32, device=device)
-        pos = torch.empty((r1 - r0, width, 3), dtype=torch.float32, device=device)
-        image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode, shading="torch",
-                                               double_sided=params.get("double_sided", False),
-                                               use_quartic=params.get("use_quartic", False), aux=(normal, pos),
-                                               waves_per_tile=params.get("waves_per_tile", 0))
-        if norm_depth:          # torch/renderer.py:245-260 returns before the fragment stage: no normal / pos, no shadows
-            return RenderResult(scene["camera"], device, image=_norm_depth_image(depth, cam.far_clip), depth=depth,
-                                nearest=nearest.to(torch.int64))
-        extra = {}
-        if shadow:
-            extra["light_visibility"] = shadow_pass(buf, cam, rows, image, depth, nearest, shade[1], shade[2])
-        return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64),
-                            normal=normal, pos=pos, **extra)
-    if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
-        # differentiable call: image and depth carry a grad_fn backed by the analytic HIP backward
-        image, depth, nearest = _RenderFunction.apply(buf, cam, rows, mode, ("numpy", False, False, False, False),
-                                                      *inputs)
-    else:
-        image, depth, nearest = render_buffers(buf, cam, rows=rows, mode=mode,
-                                               waves_per_tile=params.get("waves_per_tile", 0))
-    return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64))
+    differentiable = torch.is_grad_enabled() and any(t.requires_grad for t in inputs)
+    tch = shading == "torch"                    # the torch backend's semantics
+    # norm_depth_image_only returns before the fragment stage (torch/renderer.py:245-260): no normal / pos, and outside
+    # autograd no shadow pass
+    shade = _Shade(shading, tch and bool(params.get("double_sided", False)), tch and bool(params.get("use_quartic", False)),
+                   shadow and (differentiable or not norm_depth), tch and not norm_depth)
+    image, depth, nearest, extra = _forward(buf, cam, rows, mode, shade, inputs, differentiable,
+                                            params.get("waves_per_tile", 0))
+    if norm_depth:
+        image = _norm_depth_image(depth, cam.far_clip)
+    return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64), **extra)

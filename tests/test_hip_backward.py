@@ -362,7 +362,9 @@ def test_resident_scene_refuses_leaves_it_would_have_to_copy(how):
 
 def test_captured_step_equals_the_eager_iteration():
     """ResidentScene.capture_step: render + loss + backward as one hipGraph.  Loss and gradients of a replay equal the
-    eager iteration's, and a replay after an in-place update of the leaves (an optimiser step) follows it."""
+    eager iteration's, and a replay after an in-place update of the leaves (an optimiser step) follows it -- also when
+    an eager frame at another size ran in between (the step has scratch of its own): smaller, which would leave its
+    lists over the bin counters of a shared scratch, and larger, which makes ensure_workspace replace the scene's."""
     import torch
     from surf_renderer_amd import ResidentScene, synthetic
     scene = synthetic.bunny_mesh_scene(160, 128)
@@ -386,6 +388,11 @@ def test_captured_step_equals_the_eager_iteration():
     step = rs.capture_step(loss_fn)
     for it in range(3):
         want = eager()
+        if it < 2:                                       # an eager frame at another size, right before the replay
+            rs.set_camera(dict(scene["camera"], viewport=[0, 0, 96, 80] if it == 0 else [0, 0, 320, 256]))
+            with torch.no_grad():
+                rs.render()
+            rs.set_camera(scene["camera"])
         face.grad = None                                 # as optimiser.zero_grad(set_to_none=True) leaves them
         normal.grad = None
         got_loss = step.replay().clone()
