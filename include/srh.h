@@ -242,6 +242,35 @@ int srh_render_bwd_aux(const SrhCamera* camera, const SrhObjects* objects, const
                        const int32_t* nearest, const float* depth,
                        const SrhGrads* grads, void* stream);
 
+/* Camera gradients (device pointers to 4 floats each; NULL = not wanted).  srh_render_bwd_camera OVERWRITES them (it
+ * does not add); w is written as 0. */
+typedef struct SrhCameraGrads {
+  float* eye;
+  float* at;
+  float* up;
+} SrhCameraGrads;
+
+/* srh_render_bwd_aux plus the gradients of the camera's eye, at and up (SRH_SHADING_TORCH only; SRH_SHADING_NUMPY is
+ * refused with SRH_E_TYPE).  Defined as autograd through the reference's ray generation (torch/utils.py:402-427,
+ * 439-478, its in-place division read as d = v / |v|) on top of the winners' hit distance, hit point, normal and view
+ * direction; misses contribute nothing; fovy and focal_length have no gradient.  Every hit pixel's contribution is
+ * reduced in fp64 over its workgroup and stored (no atomics) to `camera_scratch`, srh_camera_grad_scratch_bytes(W,
+ * row1 - row0) bytes of caller-provided device memory (8-byte aligned; its previous contents do not matter: workgroups
+ * without a hit store zeros); a one-workgroup kernel then adds the partial sums in a fixed order and applies the chain
+ * rule of the look-at basis, so the three gradients are identical from run to run.  One launch more than
+ * srh_render_bwd_aux.  A row slab sums over its own rows.  With all three camera pointers NULL the call is
+ * srh_render_bwd_aux (the scratch is not looked at).  Added without an ABI version change: no existing struct or
+ * signature changed. */
+size_t srh_camera_grad_scratch_bytes(int32_t width, int32_t rows);
+int srh_render_bwd_camera(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                          const SrhMaterials* materials, const SrhParams* params,
+                          void* workspace, size_t workspace_bytes,
+                          const float* grad_image, const float* grad_depth,
+                          const float* grad_normal, const float* grad_pos,
+                          const int32_t* nearest, const float* depth,
+                          const SrhGrads* grads, const SrhCameraGrads* camera_grads,
+                          void* camera_scratch, size_t camera_scratch_size, void* stream);
+
 /* Many views in one call: the batch axis of the reference's real callers, which render one view per
  * render() call in a Python loop (diffrend/torch/GAN/gan.py:325-378, torch/batch_render.py:36-53).  `cameras` is an
  * array of n_views cameras with one viewport size; objects / lights / materials are one scene for all views or, per

@@ -69,6 +69,10 @@ class SrhGrads(C.Structure):
                 ("coeffs", C.c_void_p), ("attenuation", C.c_void_p), ("ambient", C.c_void_p)]
 
 
+class SrhCameraGrads(C.Structure):
+    _fields_ = [("eye", C.c_void_p), ("at", C.c_void_p), ("up", C.c_void_p)]
+
+
 class SrhSplatParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32),
                 ("pos_cols", C.c_int32), ("use_quartic", C.c_int32), ("shade", C.c_int32), ("reserved", C.c_int32),
@@ -88,7 +92,8 @@ class SrhSplatGrads(C.Structure):
 
 
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
-           "srh_render_bwd", "srh_render_bwd_aux", "srh_workspace_bytes_views", "srh_render_views", "srh_shadow_shade",
+           "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
+           "srh_workspace_bytes_views", "srh_render_views", "srh_shadow_shade",
            "srh_shadow_workspace_bytes", "srh_bin_counters",
            "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
            "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd")
@@ -146,6 +151,14 @@ def load(build_if_missing: bool = True) -> C.CDLL:
                                        C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(SrhGrads), C.c_void_p]
+    lib.srh_camera_grad_scratch_bytes.restype = C.c_size_t
+    lib.srh_camera_grad_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.srh_render_bwd_camera.restype = C.c_int
+    lib.srh_render_bwd_camera.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
+                                          C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(SrhGrads), C.POINTER(SrhCameraGrads), C.c_void_p, C.c_size_t,
+                                          C.c_void_p]
     lib.srh_workspace_bytes_views.restype = C.c_size_t
     lib.srh_workspace_bytes_views.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32, C.c_int32]
     lib.srh_render_views.restype = C.c_int

@@ -1311,12 +1311,22 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
   return e == hipSuccess ? SRH_OK : hip_fail(e, "shadow launch");
 }
 
-// srh_render_bwd (grad_normal = grad_pos = NULL) and srh_render_bwd_aux; the callers have checked which upstream
-// gradients may be NULL
+// workgroups of a backward launch over width x rows pixels (64 x 4 pixels each), and the bytes of their camera partials
+static size_t camera_groups(int32_t width, int32_t rows) {
+  return (size_t)((width + 63) / 64) * (size_t)((rows + 3) / 4);
+}
+static size_t camera_scratch_bytes(int32_t width, int32_t rows) {
+  return camera_groups(width, rows) * kCamSums * sizeof(double);
+}
+
+// srh_render_bwd (grad_normal = grad_pos = NULL), srh_render_bwd_aux and srh_render_bwd_camera (cam_part != NULL: the
+// camera variant of the torch kernel, then k_camera_finish); the callers have checked which upstream gradients may be
+// NULL, and the camera scratch
 static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
                       const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
                       const float* grad_image, const float* grad_depth, const float* grad_normal, const float* grad_pos,
-                      const int32_t* nearest, const float* depth, const SrhGrads* grads, void* stream) {
+                      const int32_t* nearest, const float* depth, const SrhGrads* grads, void* stream,
+                      const SrhCameraGrads* camera_grads = nullptr, double* cam_part = nullptr) {
   FrameDev F;
   WsLayout L;
   int rc = setup_frame(camera, objects, lights, materials, params, workspace, workspace_bytes, &F, &L);
@@ -1346,6 +1356,12 @@ static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const 
   const uint64_t* vis = (const uint64_t*)params->visibility;
   const bool aux = grad_normal || grad_pos;
   if (!tch) hipLaunchKernelGGL(k_render_bwd, grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth);
+  else if (cam_part && grad_image)
+    hipLaunchKernelGGL((k_render_bwd_tch<true, true, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest,
+                       depth, vis, grad_normal, grad_pos, cam_part);
+  else if (cam_part)
+    hipLaunchKernelGGL((k_render_bwd_tch<true, false, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest,
+                       depth, vis, grad_normal, grad_pos, cam_part);
   else if (!aux && grad_image)
     hipLaunchKernelGGL((k_render_bwd_tch<false, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
                        vis, nullptr, nullptr);
@@ -1356,6 +1372,15 @@ static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const 
     hipLaunchKernelGGL((k_render_bwd_tch<true, false>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
                        vis, grad_normal, grad_pos);
   if (params->ev_stop) (void)hipEventRecord((hipEvent_t)params->ev_stop, st);
+  if (cam_part) {
+    CamFinish P;
+    for (int k = 0; k < 3; ++k) { P.eye[k] = camera->eye[k]; P.at[k] = camera->at[k]; P.up[k] = camera->up[k]; }
+    P.focal = F.focal;
+    P.ortho = F.ortho;
+    P.ngroups = (int32_t)(grid.x * grid.y);
+    P.g_eye = camera_grads->eye; P.g_at = camera_grads->at; P.g_up = camera_grads->up;
+    hipLaunchKernelGGL(k_camera_finish, dim3(1), dim3(1024), 0, st, P, cam_part);
+  }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SRH_OK : hip_fail(e, "backward launch");
 }
@@ -1383,6 +1408,36 @@ int srh_render_bwd_aux(const SrhCamera* camera, const SrhObjects* objects, const
   }
   return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
                     grad_normal, grad_pos, nearest, depth, grads, stream);
+}
+
+size_t srh_camera_grad_scratch_bytes(int32_t width, int32_t rows) {
+  if (width < 1 || rows < 1) { fail(SRH_E_RANGE, "camera gradient scratch for %d x %d pixels", width, rows); return 0; }
+  return camera_scratch_bytes(width, rows);
+}
+
+int srh_render_bwd_camera(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
+                          const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                          const float* grad_image, const float* grad_depth, const float* grad_normal,
+                          const float* grad_pos, const int32_t* nearest, const float* depth, const SrhGrads* grads,
+                          const SrhCameraGrads* camera_grads, void* camera_scratch, size_t camera_scratch_size,
+                          void* stream) {
+  if (!grad_image && !grad_depth && !grad_normal && !grad_pos)
+    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_normal and grad_pos are all NULL");
+  if (!params || !camera) return fail(SRH_E_NULL, "camera / params is NULL");
+  if (params->shading != SRH_SHADING_TORCH)
+    return fail(SRH_E_TYPE, "camera gradients exist only under SRH_SHADING_TORCH");
+  if (!camera_grads) return fail(SRH_E_NULL, "camera_grads is NULL");
+  if (!camera_grads->eye && !camera_grads->at && !camera_grads->up)         // nothing wanted: srh_render_bwd_aux
+    return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
+                      grad_normal, grad_pos, nearest, depth, grads, stream);
+  const int32_t width = camera->viewport[2] - camera->viewport[0], rows = params->row1 - params->row0;
+  if (width < 1 || rows < 1) return fail(SRH_E_RANGE, "empty frame %d x %d", width, rows);
+  const size_t need = camera_scratch_bytes(width, rows);
+  if (!camera_scratch || camera_scratch_size < need || ((uintptr_t)camera_scratch % sizeof(double)) != 0)
+    return fail(SRH_E_WORKSPACE, "camera scratch: need %zu bytes, 8-byte aligned (got %zu at %p)", need,
+                camera_scratch_size, camera_scratch);
+  return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
+                    grad_normal, grad_pos, nearest, depth, grads, stream, camera_grads, (double*)camera_scratch);
 }
 
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,

@@ -363,16 +363,30 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
 //           grad_normal / grad_pos are dense (rows,W,3) like the forward's normal_out / pos_out; either may be NULL.
 //   kImage  grad_image is read and the shading differentiated.  Without it both light loops and every light /
 //           material / colour accumulation drop out: a geometry-only backward for losses on normal / pos / depth.
-// <false, true> is srh_render_bwd's kernel (the two trailing arguments are unused there).
+//   kCam    camera gradients (srh_render_bwd_camera): every hit pixel also forms the gradients of its ray origin and ray
+//           direction, maps them to the camera basis (end of the kernel) and the workgroup stores its twelve fp64 partial sums
+//           to cam_part[workgroup][12] with plain stores; k_camera_finish adds the workgroups up in a fixed order.  A
+//           workgroup that leaves at the top stores zeros, so the scratch needs no clearing launch and never holds a
+//           stale partial.  Without kCam the trailing argument is unused and the code is what it was without it.
+// <false, true> is srh_render_bwd's kernel (the trailing arguments are unused there).
 constexpr int kBwdTchWaves = 3;
-template <bool kAux, bool kImage>
+constexpr int kCamSums = 12;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+template <bool kAux, bool kImage, bool kCam = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
                                                          const float* __restrict__ grad_depth,
                                                          const int32_t* __restrict__ nearest,
                                                          const float* __restrict__ depth,
                                                          const uint64_t* __restrict__ visibility,
                                                          const float* __restrict__ grad_normal,
-                                                         const float* __restrict__ grad_pos) {
+                                                         const float* __restrict__ grad_pos,
+                                                         double* __restrict__ cam_part = nullptr) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
   const int lane = threadIdx.x;
@@ -383,7 +397,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
   // a workgroup (4 rows x 64 pixels) without a single hit pixel contributes nothing: it leaves together, before the
   // reductions below (whose barriers every thread of a workgroup that stays still reaches) -- a mesh that covers a fifth
   // of the frame then runs a fifth of the workgroups through the fp64 chain rule
-  if (!__syncthreads_or(hit ? 1 : 0)) return;
+  if (!__syncthreads_or(hit ? 1 : 0)) {
+    if (kCam && threadIdx.y == 0 && lane < kCamSums)       // its slot of the camera partials: zeros, never a stale frame's
+      cam_part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCamSums + lane] = 0.0;
+    return;
+  }
 
   float g_out[3] = {0, 0, 0}, g_dep = 0.0f;               // upstream gradients are fp32
   int win = 0;
@@ -642,13 +660,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
   }
   // ---- view direction and geometry: every lane takes part (run reduction below); lanes without a hit carry zeros ------
   double gA[3] = {0, 0, 0}, gB[3] = {0, 0, 0}, g_r = 0.0;
+  // kCam: d/d eye through the view direction, d/d ray origin and d/d ray direction (zeros at pixels without a hit)
+  double g_eye[3] = {0, 0, 0}, g_org[3] = {0, 0, 0}, g_d[3] = {0, 0, 0};
   if (kImage && hit) {
     // c^ . n^ and c^ = u / sqrt(|u|^2 + eps), u = o - p
 #pragma unroll
     for (int k = 0; k < 3; ++k) { g_cdir[k] += g_cdotn * n[k]; g_n[k] += g_cdotn * cdir[k]; }
     const double projc = (cdir[0] * g_cdir[0] + cdir[1] * g_cdir[1]) + cdir[2] * g_cdir[2];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) g_p[k] -= (g_cdir[k] - cdir[k] * projc) * sc_inv;
+    for (int k = 0; k < 3; ++k) {
+      const double g_u = (g_cdir[k] - cdir[k] * projc) * sc_inv;
+      g_p[k] -= g_u;
+      if (kCam) g_eye[k] = g_u;                            // u = eye - p: the eye itself, not the ray origin
+    }
   }
   if (hit && type == SRH_PRIM_SPHERE) {
     const double proj = (n[0] * g_n[0] + n[1] * g_n[1]) + n[2] * g_n[2];
@@ -676,6 +700,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
       g_r = -2.0 * (double)seg_ptr([](const SegDev& S) { return S.radius; })[li] * g_cc;
 #pragma unroll
       for (int k = 0; k < 3; ++k) gA[k] -= 2.0 * oc[k] * g_cc + 2.0 * d[k] * g_b;  // oc = origin - c
+      if (kCam) {
+        // the origin enters through oc as the centre does, with the other sign; the direction through b = 2 oc.d and
+        // a = d.d (t = (-b -/+ root) / 2a: d t / d a = -t / a - 4 cq d t / d disc)
+        const double g_a = -g_t * t / a - 4.0 * cq * g_disc;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          g_org[k] = 2.0 * oc[k] * g_cc + 2.0 * d[k] * g_b;
+          g_d[k] = 2.0 * oc[k] * g_b + 2.0 * d[k] * g_a;
+        }
+      }
+    }
+    if (kCam) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { g_org[k] += g_p[k]; g_d[k] += t * g_p[k]; }     // p = origin + t d
     }
   } else if (hit) {
     // planar: t = k/den, k = n^.(q - origin), den = n^.d
@@ -689,6 +727,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
     for (int k = 0; k < 3; ++k) {
       gA[k] = g_k * n[k];
       g_nh[k] = g_n[k] + g_k * ((double)qp[k] - org[k]) + g_den * d[k];
+      if (kCam) { g_org[k] = g_p[k] - g_k * n[k]; g_d[k] = t * g_p[k] + g_den * n[k]; }   // p = origin + t d, k, den
     }
     // n^ = nin / sqrt(|nin|^2 + 3e-10) over xyz
     const float* np_ = seg_ptr([](const SegDev& S) { return S.normal; }) + 4 * (size_t)li;
@@ -698,7 +737,120 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
 #pragma unroll
     for (int k = 0; k < 3; ++k) gB[k] = (g_nh[k] - n[k] * proj) * ninv;
   }
+  if (kCam) {
+    // Camera sums of this pixel: [0..2] d/d eye, [3..5] d/d bx, [6..8] d/d by, [9..11] the sum that gives
+    // d/d bz.  Perspective: d = v / |v| with v = bx X + by Y - bz f and |v| = sqrt(X^2 + Y^2 + f^2) (orthonormal basis),
+    // g_v = (g_d - d (d . g_d)) / |v|; the sums are g_org, X g_v, Y g_v, g_v.  Orthographic: origin = eye + bx X + by Y,
+    // d = -bz; the sums are g_org, X g_org, Y g_org, g_d.
+    const int pc = live ? c : 0, pr = live ? r : F.row0;
+    const double xs = (F.W > 1 && pc == F.W - 1) ? 1.0 : (pc * F.step_x + -1.0);
+    const double ys = (F.H > 1 && pr == F.H - 1) ? -1.0 : (pr * F.step_y + 1.0);
+    const double X = xs * F.half_w, Y = ys * F.half_h;
+    double cs[kCamSums];
+    if (F.ortho) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { cs[k] = g_org[k] + g_eye[k]; cs[3 + k] = X * g_org[k]; cs[6 + k] = Y * g_org[k]; cs[9 + k] = g_d[k]; }
+    } else {
+      const double vinv = 1.0 / sqrt((X * X + Y * Y) + F.focal * F.focal);
+      const double dg = (d[0] * g_d[0] + d[1] * g_d[1]) + d[2] * g_d[2];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double g_v = (g_d[k] - d[k] * dg) * vinv;
+        cs[k] = g_org[k] + g_eye[k]; cs[3 + k] = X * g_v; cs[6 + k] = Y * g_v; cs[9 + k] = g_v;
+      }
+    }
+    // wave sum, then the four waves through LDS in a fixed order, then ONE plain store per sum and workgroup: no atomics,
+    // so the frame's result does not depend on the order in which workgroups finish
+    __shared__ double cam_lds[4][kCamSums];
+#pragma unroll
+    for (int k = 0; k < kCamSums; ++k) {
+      const double sum = wave_sum(cs[k]);
+      if (lane == 0) cam_lds[threadIdx.y][k] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.y == 0 && lane < kCamSums)
+      cam_part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCamSums + lane] =
+          (cam_lds[0][lane] + cam_lds[1][lane]) + (cam_lds[2][lane] + cam_lds[3][lane]);
+  }
   scatter_primitive_grads(G, hit ? win : -1, lane, s, type, li, gA, gB, g_r);
+}
+
+// The frame's camera gradients from the workgroups' partial sums (one workgroup).  Thread (j, k) adds sum k of workgroups
+// j, j + kCamFinishRows, ... in that order, the rows are added in order through LDS, and thread 0 applies the chain rule
+// of the look-at basis in fp64 -- every addition has a fixed place, so two runs give the same bits.
+//     z = unit(eye - at), u^ = unit(up), x = unit(cross(u^, z)), y = cross(z, x)          (torch/utils.py:402-427, exact
+//     unit vectors as camera_to_frame builds them; the reference's +1e-10 inside its norms is 1e-10 relative)
+// persp: g_x = S1, g_y = S2, g_z = -f S3;  ortho: g_x = S1, g_y = S2, g_z = -S3;  g_eye = S0 + chain, g_at = -chain.
+struct CamFinish {
+  double eye[3], at[3], up[3], focal;
+  int32_t ortho, ngroups;
+  float* g_eye;
+  float* g_at;
+  float* g_up;
+};
+constexpr int kCamFinishRows = 85;                        // 85 x 12 = 1020 threads
+
+__device__ __forceinline__ void cross3(const double a[3], const double b[3], double o[3]) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// g_v for u = v / |v| given g_u:  (g_u - u (u . g_u)) / |v|
+__device__ __forceinline__ void unit_bwd(const double u[3], double len, const double g_u[3], double g_v[3]) {
+  const double pr = dot3(u, g_u);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) g_v[k] = (g_u[k] - u[k] * pr) / len;
+}
+
+__global__ __launch_bounds__(1024) void k_camera_finish(CamFinish P, const double* __restrict__ cam_part) {
+  __shared__ double part[kCamFinishRows][kCamSums];
+  __shared__ double S[kCamSums];
+  const int tid = threadIdx.x;
+  if (tid < kCamFinishRows * kCamSums) {
+    const int j = tid / kCamSums, k = tid % kCamSums;
+    double acc = 0.0;
+    for (int g = j; g < P.ngroups; g += kCamFinishRows) acc += cam_part[(size_t)g * kCamSums + k];
+    part[j][k] = acc;
+  }
+  __syncthreads();
+  if (tid < kCamSums) {
+    double acc = 0.0;
+    for (int j = 0; j < kCamFinishRows; ++j) acc += part[j][tid];
+    S[tid] = acc;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double w[3], z[3], uh[3], cx[3], x[3];
+  for (int k = 0; k < 3; ++k) w[k] = P.eye[k] - P.at[k];
+  const double wl = sqrt(dot3(w, w)), ul = sqrt(dot3(P.up, P.up));
+  for (int k = 0; k < 3; ++k) { z[k] = w[k] / wl; uh[k] = P.up[k] / ul; }
+  cross3(uh, z, cx);
+  const double cl = sqrt(dot3(cx, cx));
+  for (int k = 0; k < 3; ++k) x[k] = cx[k] / cl;
+  double g_x[3], g_y[3], g_z[3];
+  for (int k = 0; k < 3; ++k) { g_x[k] = S[3 + k]; g_y[k] = S[6 + k]; g_z[k] = -(P.ortho ? 1.0 : P.focal) * S[9 + k]; }
+  // y = cross(z, x)
+  double t0[3], t1[3];
+  cross3(x, g_y, t0);
+  cross3(g_y, z, t1);
+  for (int k = 0; k < 3; ++k) { g_z[k] += t0[k]; g_x[k] += t1[k]; }
+  // x = cx / |cx|, cx = cross(u^, z)
+  double g_cx[3], g_uh[3], g_up[3], g_w[3];
+  unit_bwd(x, cl, g_x, g_cx);
+  cross3(z, g_cx, g_uh);
+  cross3(g_cx, uh, t0);
+  for (int k = 0; k < 3; ++k) g_z[k] += t0[k];
+  unit_bwd(uh, ul, g_uh, g_up);
+  unit_bwd(z, wl, g_z, g_w);
+  for (int k = 0; k < 3; ++k) {
+    if (P.g_eye) P.g_eye[k] = (float)(S[k] + g_w[k]);
+    if (P.g_at) P.g_at[k] = (float)(-g_w[k]);
+    if (P.g_up) P.g_up[k] = (float)g_up[k];
+  }
+  if (P.g_eye) P.g_eye[3] = 0.0f;
+  if (P.g_at) P.g_at[3] = 0.0f;
+  if (P.g_up) P.g_up[3] = 0.0f;
 }
 
 }  // namespace srh

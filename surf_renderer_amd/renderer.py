@@ -124,6 +124,7 @@ class SceneBuffers:
     workspace_frame: Tuple[int, int] = (0, 0)
     total: int = 0
     shadow_workspace: Optional[torch.Tensor] = None   # scratch of the accelerated shadow pass (light views)
+    camera_scratch: Optional[torch.Tensor] = None     # workgroup partial sums of the camera gradients (srh_render_bwd_camera)
 
     def ensure_workspace(self, width: int, height: int) -> torch.Tensor:
         """Device scratch for libsrh (primitive records + tile bins) at ``width x height``."""
@@ -147,6 +148,17 @@ class SceneBuffers:
         if self.shadow_workspace is None or self.shadow_workspace.numel() < need:
             self.shadow_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.shadow_workspace
+
+    def ensure_camera_scratch(self, width: int, rows: int) -> torch.Tensor:
+        """Scratch of srh_render_bwd_camera for a backward over ``width x rows`` pixels.  Its contents never matter: every
+        workgroup of a backward launch overwrites its own slot."""
+        lib = _lib.load()
+        need = lib.srh_camera_grad_scratch_bytes(width, rows)
+        if need == 0:
+            raise _lib.SrhError(-2, lib.srh_last_error().decode())
+        if self.camera_scratch is None or self.camera_scratch.numel() * 8 < need:
+            self.camera_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        return self.camera_scratch
 
     def new_workspace(self, width: int, height: int) -> torch.Tensor:
         """An additional scratch buffer (one per frame in flight when frames are pipelined over several streams)."""
@@ -358,6 +370,20 @@ def camera_struct(camera: Dict[str, Any], shading: str = "numpy") -> _lib.SrhCam
     elif proj not in ("persp", "perspective"):
         raise ValueError(f"camera.proj_type {proj!r}: expected 'perspective' or 'ortho'")
     return cam
+
+
+_CAMERA_LEAVES = ("eye", "at", "up")
+
+
+def camera_leaves(camera: Dict[str, Any], shading: str) -> Dict[str, torch.Tensor]:
+    """The camera's differentiable leaves: those of ``eye``, ``at`` and ``up`` that are tensors with ``requires_grad``,
+    under ``shading='torch'``.  The numpy backend's semantics keep detaching the camera (a different, non-orthonormal
+    basis, and no autograd in the reference); ``fovy`` and ``focal_length`` never get a gradient (the reference passes
+    them through numpy)."""
+    if shading != "torch":
+        return {}
+    return {k: camera[k] for k in _CAMERA_LEAVES
+            if isinstance(camera.get(k), torch.Tensor) and camera[k].requires_grad}
 
 
 def frame_size(cam: _lib.SrhCamera) -> Tuple[int, int]:
@@ -578,14 +604,18 @@ class _RenderFunction(torch.autograd.Function):
     autograd through the reference's torch backend (SURVEY.md section 8, row a-B): selection and masks are piecewise
     constant; a disc's radius and a triangle's vertices 1, 2 receive zero gradient.  With ``shade.aux`` (torch shading
     only) the outputs are image, depth, nearest, normal, pos, and upstream gradients of normal / pos go to
-    srh_render_bwd_aux."""
+    srh_render_bwd_aux.  ``cam_names`` names the camera leaves (``camera_leaves``) that follow the scene's inputs at the
+    end of ``inputs``: the forward reads their values through ``cam`` as always, the backward is srh_render_bwd_camera
+    and returns their gradients in each leaf's own shape, dtype and device (w = 0; a 3-vector ``up`` gets 3 values)."""
 
     @staticmethod
-    def forward(ctx, buf, cam, rows, mode, shade: _Shade, *inputs):
+    def forward(ctx, buf, cam, rows, mode, shade: _Shade, cam_names, *inputs):
         if shade.aux:
             ctx.set_materialize_grads(False)            # an unused normal / pos must arrive as None, not as zeros
         image, depth, nearest, aux, vis = _frame(buf, cam, rows, mode, shade)
         ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade = buf, cam, rows, mode, shade
+        ctx.cam_names = tuple(cam_names)
+        ctx.cam_like = [(t.shape, t.dtype, t.device) for t in inputs[len(inputs) - len(ctx.cam_names):]]
         ctx.save_for_backward(depth, nearest, vis)
         ctx.mark_non_differentiable(nearest)
         return (image, depth, nearest) + (aux or ())
@@ -594,19 +624,26 @@ class _RenderFunction(torch.autograd.Function):
     def backward(ctx, g_image, g_depth, _g_nearest, g_normal=None, g_pos=None):
         depth, nearest, vis = ctx.saved_tensors
         keys = _float_keys(ctx.buf, ctx.shade.shading)
+        need = ctx.needs_input_grad[6:]
+        cam_need = tuple(k for k, want in zip(ctx.cam_names, need[len(keys):]) if want)
         grads = _render_backward(ctx.buf, ctx.cam, ctx.rows, ctx.mode, ctx.shade, depth, nearest, vis, g_image, g_depth,
-                                 ctx.needs_input_grad[5:], g_normal, g_pos)
-        return (None, None, None, None, None) + tuple(grads.get(k) for k in keys)
+                                 need[:len(keys)], g_normal, g_pos, camera=cam_need)
+        cam_grads = []
+        for k, (shape, dtype, device) in zip(ctx.cam_names, ctx.cam_like):
+            g = grads.get("camera." + k)
+            cam_grads.append(None if g is None else g[:int(np.prod(shape))].to(device=device, dtype=dtype).reshape(shape))
+        return (None, None, None, None, None, None) + tuple(grads.get(k) for k in keys) + tuple(cam_grads)
 
 
 def _forward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Shade, inputs: Sequence[torch.Tensor],
-             differentiable: bool, waves_per_tile: int = 0):
+             differentiable: bool, waves_per_tile: int = 0, cam_leaves: Optional[Dict[str, torch.Tensor]] = None):
     """One frame for ``render`` and ``ResidentScene.render``: through ``_RenderFunction`` when ``differentiable`` (the
     shadow pass, if any, then runs inside it), else straight from ``_frame``.  Returns image, depth, nearest and a dict
     of the extra outputs: ``normal`` and ``pos`` with ``shade.aux``, and outside autograd ``light_visibility`` with
-    ``shade.shadow``."""
+    ``shade.shadow``.  ``cam_leaves`` (``camera_leaves``) become inputs of the function beside the scene's."""
     if differentiable:
-        out = _RenderFunction.apply(buf, cam, rows, mode, shade, *inputs)
+        cam_leaves = cam_leaves or {}
+        out = _RenderFunction.apply(buf, cam, rows, mode, shade, tuple(cam_leaves), *inputs, *cam_leaves.values())
         return out[0], out[1], out[2], ({"normal": out[3], "pos": out[4]} if shade.aux else {})
     image, depth, nearest, aux, vis = _frame(buf, cam, rows, mode, shade, waves_per_tile)
     extra = {"normal": aux[0], "pos": aux[1]} if aux else {}
@@ -618,12 +655,15 @@ def _forward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Sh
 def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, shade: _Shade, depth: torch.Tensor,
                      nearest: torch.Tensor, vis: Optional[torch.Tensor], g_image: Optional[torch.Tensor],
                      g_depth: Optional[torch.Tensor], need: Sequence[bool], g_normal: Optional[torch.Tensor] = None,
-                     g_pos: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                     g_pos: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                     camera: Sequence[str] = ()) -> Dict[str, torch.Tensor]:
     """srh_render_bwd: gradients of the inputs named by ``_float_keys`` (those with ``need``) for the upstream gradients
     of image and depth, from the winners the forward pass saved.  Everything is enqueued on the current stream.
     With an upstream gradient of the torch shading's ``normal`` or ``pos`` output the call is srh_render_bwd_aux
     instead; there a missing ``g_image`` is passed as NULL (the geometry-only kernel) rather than as zeros.
-    ``workspace`` defaults to the buffers' own scratch (``ensure_workspace``)."""
+    ``workspace`` defaults to the buffers' own scratch (``ensure_workspace``).  ``camera`` names the camera leaves
+    (of 'eye', 'at', 'up') whose gradients are wanted too: the call is then srh_render_bwd_camera, and they come back as
+    (4,) float32 device tensors under 'camera.eye' / 'camera.at' / 'camera.up'."""
     lib = _lib.load()
     width, height = frame_size(cam)
     r0, r1 = _rows(rows, height)
@@ -641,8 +681,10 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
             kind, name = key.split(".")
             getattr(sg, name)[buf.kinds.index(kind)] = g.data_ptr()
     aux = g_normal is not None or g_pos is not None
+    if camera and shade.shading != "torch":
+        raise ValueError("camera gradients exist only in the torch backend's semantics: shading='torch'")
     g_image = g_image.to(torch.float32).contiguous() if g_image is not None else \
-        (None if aux else torch.zeros((r1 - r0, width, 3), dtype=torch.float32, device=buf.device))
+        (None if aux or (camera and g_depth is not None) else torch.zeros((r1 - r0, width, 3), dtype=torch.float32, device=buf.device))
     g_depth = g_depth.to(torch.float32).contiguous() if g_depth is not None else None
     g_normal = g_normal.to(torch.float32).contiguous() if g_normal is not None else None
     g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
@@ -653,7 +695,18 @@ def _render_backward(buf: SceneBuffers, cam: _lib.SrhCamera, rows, mode: str, sh
         return t.data_ptr() if t is not None else None
 
     with torch.cuda.device(buf.device):
-        if aux:
+        if camera:
+            cg = _lib.SrhCameraGrads()
+            for k in camera:
+                grads["camera." + k] = torch.empty(4, dtype=torch.float32, device=buf.device)
+                setattr(cg, k, grads["camera." + k].data_ptr())
+            scratch = buf.ensure_camera_scratch(width, r1 - r0)
+            rc = lib.srh_render_bwd_camera(C.byref(cam), C.byref(buf.objects), C.byref(buf.lights),
+                                           C.byref(buf.materials), C.byref(params), workspace.data_ptr(),
+                                           workspace.numel(), ptr(g_image), ptr(g_depth), ptr(g_normal), ptr(g_pos),
+                                           nearest.data_ptr(), depth.data_ptr(), C.byref(sg), C.byref(cg),
+                                           scratch.data_ptr(), scratch.numel() * 8, _stream_ptr(buf.device))
+        elif aux:
             rc = lib.srh_render_bwd_aux(C.byref(cam), C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials),
                                         C.byref(params), workspace.data_ptr(), workspace.numel(), ptr(g_image),
                                         ptr(g_depth), ptr(g_normal), ptr(g_pos), nearest.data_ptr(), depth.data_ptr(),
@@ -879,6 +932,13 @@ class ResidentScene:
     ``aux=True`` (``shading='torch'`` only) adds the torch backend's ``normal`` and ``pos`` outputs to ``render()``,
     differentiable like ``image`` and ``depth``, and lets a ``capture_step`` loss use them.  It is off by default:
     writing them costs 24 bytes per pixel and frame.
+
+    Camera: with ``shading='torch'``, ``eye`` / ``at`` / ``up`` of the camera dict that are tensors with
+    ``requires_grad`` get their ``.grad`` too (``camera_leaves``).  While one of them requires grad, ``render()`` rebuilds
+    the camera struct from the tensors' current values on every call, so an optimiser's in-place step is seen: that
+    reads three small tensors on the host per call (a device tensor costs a synchronising copy each).  Otherwise the
+    camera is read once, here and in ``set_camera``.  ``capture_step`` keeps freezing the camera at capture time and
+    produces no camera gradient; ``fovy`` / ``focal_length`` have none.
     """
 
     def __init__(self, scene: Dict[str, Any], device="cuda", shading: str = "numpy", mode: str = "auto",
@@ -897,7 +957,8 @@ class ResidentScene:
         self.aux = bool(aux)
         self.shade = _Shade(shading, bool(double_sided), bool(use_quartic), False, self.aux)
         self.inputs = [self.buf.tensors[k] for k in _float_keys(self.buf, shading)]
-        self.differentiable = any(t.requires_grad for t in self.inputs)
+        self.cam_leaves = camera_leaves(self._camera, shading)
+        self.differentiable = any(t.requires_grad for t in self.inputs) or bool(self.cam_leaves)
         # "In place" has to be true for every leaf that is being optimised: a float64, CPU or non-contiguous leaf is
         # COPIED once by flatten_scene (the copy stays attached to autograd, so its gradients still reach the leaf and
         # the optimiser keeps stepping it) -- and every later render() would draw the first iteration's values.
@@ -918,10 +979,15 @@ class ResidentScene:
     def set_camera(self, camera: Dict[str, Any]) -> None:
         self._camera = camera
         self.cam = camera_struct(camera, self.shading)
+        self.cam_leaves = camera_leaves(camera, self.shading)
+        self.differentiable = any(t.requires_grad for t in self.inputs) or bool(self.cam_leaves)
 
     def render(self, rows: Optional[Tuple[int, int]] = None) -> "RenderResult":
+        if self.cam_leaves:
+            self.cam = camera_struct(self._camera, self.shading)       # the leaves' current values
         image, depth, nearest, extra = _forward(self.buf, self.cam, rows, self.mode, self.shade, self.inputs,
-                                                self.differentiable and torch.is_grad_enabled())
+                                                self.differentiable and torch.is_grad_enabled(),
+                                                cam_leaves=self.cam_leaves)
         return RenderResult(self._camera, self.device, image=image, depth=depth, nearest=nearest, **extra)
 
     def capture_step(self, loss_fn, warmup: int = 3) -> "CapturedStep":
@@ -948,8 +1014,9 @@ class CapturedStep:
     eager ``rs.render()`` calls between replays, at any frame size, leave the replays alone."""
 
     def __init__(self, rs: ResidentScene, loss_fn, warmup: int = 3):
-        if not rs.differentiable:
-            raise ValueError("capture_step needs at least one leaf that requires grad")
+        if not any(t.requires_grad for t in rs.inputs):
+            raise ValueError("capture_step needs at least one scene leaf that requires grad (the camera is frozen at "
+                             "capture time and gets no gradient from a captured step)")
         self.rs = rs
         keys = _float_keys(rs.buf, rs.shading)
         # the CALLER's leaves (rs.inputs are reshaped views of them: autograd reaches the leaves through the views, a
@@ -960,11 +1027,13 @@ class CapturedStep:
         current = torch.cuda.current_stream(rs.device)
         side = torch.cuda.Stream(rs.device)
         side.wait_stream(current)
+        cam_leaves, rs.cam_leaves = rs.cam_leaves, {}   # the camera is frozen: its leaves take no part, warm-up included
         with torch.cuda.stream(side):
             for _ in range(max(1, int(warmup))):        # module load, allocator
                 for t in self.leaves:
                     t.grad = None
                 loss_fn(rs.render()).backward()
+            rs.cam_leaves = cam_leaves
             # one frame in the step's own scratch clears its bin counters and leaves them clean: the graph then holds no
             # clearing launch
             _frame(rs.buf, rs.cam, None, rs.mode, rs.shade, workspace=self.workspace)
@@ -1070,6 +1139,11 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
     ``camera.proj_type = 'ortho'``; ``norm_depth_image_only=True`` returns the normalised depth as ``image``).  The
     torch backend's remaining kwargs are accepted where they change no output of the reference (``tiled``,
     ``tile_size``, ``backface_culling`` -- see ``_TORCH_ONLY_KWARGS``); ``vis_stat=True`` raises as it does there.
+
+    Camera gradients (``shading='torch'``): ``camera['eye'|'at'|'up']`` given as tensors with ``requires_grad`` receive
+    ``.grad`` like the scene's leaves (in their own shape, dtype and device; w gets 0), also when nothing else requires
+    grad -- autograd through the reference's ray generation, misses contributing nothing.  ``fovy`` and ``focal_length``
+    get no gradient, and ``shading='numpy'`` keeps detaching the camera (see ``camera_leaves``).
     """
     unknown = set(params) - _TORCH_ONLY_KWARGS - {"device", "mode", "rows", "validate", "shading", "double_sided",
                                                   "use_quartic", "waves_per_tile"}
@@ -1093,14 +1167,15 @@ def render(scene: Dict[str, Any], **params) -> RenderResult:
     if cam.ortho and shading != "torch":
         raise ValueError("orthographic projection exists only in the torch backend's semantics: shading='torch'")
     inputs = [buf.tensors[k] for k in _float_keys(buf, shading)]
-    differentiable = torch.is_grad_enabled() and any(t.requires_grad for t in inputs)
+    cam_leaves = camera_leaves(scene["camera"], shading) if torch.is_grad_enabled() else {}
+    differentiable = torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or bool(cam_leaves))
     tch = shading == "torch"                    # the torch backend's semantics
     # norm_depth_image_only returns before the fragment stage (torch/renderer.py:245-260): no normal / pos, and outside
     # autograd no shadow pass
     shade = _Shade(shading, tch and bool(params.get("double_sided", False)), tch and bool(params.get("use_quartic", False)),
                    shadow and (differentiable or not norm_depth), tch and not norm_depth)
     image, depth, nearest, extra = _forward(buf, cam, rows, mode, shade, inputs, differentiable,
-                                            params.get("waves_per_tile", 0))
+                                            params.get("waves_per_tile", 0), cam_leaves)
     if norm_depth:
         image = _norm_depth_image(depth, cam.far_clip)
     return RenderResult(scene["camera"], device, image=image, depth=depth, nearest=nearest.to(torch.int64), **extra)

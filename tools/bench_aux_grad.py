@@ -38,7 +38,7 @@ def main():
         buf = renderer.flatten_scene(mesh, "cuda:0", validate=False, keep_graph=True)
         cam = renderer.camera_struct(mesh["camera"], "torch")
         inputs = [buf.tensors[k] for k in renderer._float_keys(buf, "torch")]
-        image = renderer._RenderFunction.apply(buf, cam, None, "auto", renderer._Shade("torch"), *inputs)[0]
+        image = renderer._RenderFunction.apply(buf, cam, None, "auto", renderer._Shade("torch"), (), *inputs)[0]
         image.sum().backward()
 
     def image():
