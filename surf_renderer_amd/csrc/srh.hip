@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256) void k_shadow_shade(FrameDev F, float* __restr
 
   vis = 0ull;
   for (int l = 0; l < F.nlights; ++l) {
-    const float* lp = F.lpos + 4 * l;
+    const auto lp = as_constant(F.lpos) + 4 * l;            // (hipcc takes this load through the scalar cache anyway: no store precedes it here)
     const double v[3] = {(double)lp[0] - p[0], (double)lp[1] - p[1], (double)lp[2] - p[2]};
     const double dist = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     const double dir[3] = {v[0] / dist, v[1] / dist, v[2] / dist};

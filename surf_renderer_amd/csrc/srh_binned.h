@@ -1264,7 +1264,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
         if (besti == 0x7fffffff) besti = 0;   // nothing hit: np.argmin of an all-inf column
         float rgb[3], aux[6];
         const ShadeHint hint = fr.hint();
-        shade_pixel_t<TCH, BATCH>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint);
+        shade_pixel_t<TCH, BATCH, true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint);
         const size_t row = (size_t)(r - F.row0);
         float* px = image + row * F.img_stride + 3 * (size_t)c;
         out_store(px, rgb[0]); out_store(px + 1, rgb[1]); out_store(px + 2, rgb[2]);

@@ -282,6 +282,27 @@ __device__ __forceinline__ void store_aux(const FrameDev& F, size_t row, int c, 
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// A pointer in its constant-address-space form: loads through it from a wave-uniform address are scalar loads (one
+// request per wave into SGPRs, through the scalar cache) instead of 64 lanes fetching the same word over the vector
+// memory path, and they no longer queue behind the wave's vector loads and output stores (vmcnt retires in order).
+// The contract, as for FrameDev::self:
+//   - the memory was written by an EARLIER launch on the same stream (or by the host before it): a launch starts with
+//     an invalidated scalar cache, so it sees that data;
+//   - the RUNNING kernel never writes it -- hipcc treats the loads as invariant, and the scalar cache is not coherent
+//     with the kernel's own vector stores.
+// So: frame inputs (lights, colours, attenuation, ambient) and what k_prep left for the render kernels (lights64) --
+// never in k_prep itself, which writes lights64, and never the bin counters, which the render kernel zeroes at its end.
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* as_constant(const T* p) {
+  return (const __attribute__((address_space(4))) T*)p;
+}
+// as_constant(p) where ON, p itself otherwise
+template <bool ON, class T>
+__device__ __forceinline__ auto as_constant_if(const T* p) {
+  if constexpr (ON) return as_constant(p);
+  else return p;
+}
+
 // 1/sqrt(x) for x > 0 without the IEEE sqrt + divide expansions: v_rsq_f64 seed (about 26 bits) and one Newton step
 // (about 50 bits).  Only the fragment stage uses it; its result is rounded to fp32 on output.
 __device__ __forceinline__ double rsqrt_newton(double x) {
@@ -352,7 +373,11 @@ struct ShadeHint {
   double n[3];        // its unit normal (planar types; unused for spheres)
 };
 
-template <bool TCH, int BATCH = -1>
+// UNIFORM: the light data goes through as_constant.  Set by the binned render kernels, whose finish rounds otherwise
+// fetch it with vector loads (their output stores keep hipcc from proving the data unchanged).  The per-pixel kernels
+// (exact, fast, ortho, shadow) have no store in front of the fragment stage: hipcc already uses scalar loads there, and
+// the address-space form only added spilled scalars to k_render_fast, so they keep the plain pointers.
+template <bool TCH, int BATCH = -1, bool UNIFORM = false>
 __device__ __forceinline__ void shade_pixel_t(const FrameDev& F, const double d[3], double z, int win,
                                               float rgb[3], float aux[6] = nullptr, const ShadeHint* hint = nullptr,
                                               const double* origin = nullptr, uint64_t vis = ~0ull) {
@@ -422,16 +447,21 @@ __device__ __forceinline__ void shade_pixel_t(const FrameDev& F, const double d[
     const double cdir[3] = {cv[0] * cinv, cv[1] * cinv, cv[2] * cinv};
     const double cdotn = (cdir[0] * n[0] + cdir[1] * n[1]) + cdir[2] * n[2];
     const double sgn = F.double_sided ? ((cdotn > 0.0) ? 1.0 : ((cdotn < 0.0) ? -1.0 : 0.0)) : 1.0;
+    // the lights, their colours, attenuation and the ambient term are the same for every lane: scalar loads
+    const auto latt = as_constant_if<UNIFORM>(F.latt);
+    const auto lcidx = as_constant_if<UNIFORM>(F.lcidx);
+    const auto colors = as_constant_if<UNIFORM>(F.colors);
+    const auto ambient = as_constant_if<UNIFORM>(F.ambient);
     for (int l = 0; l < F.nlights; ++l) {
-      const float* lp = F.lpos + 4 * l;
+      const auto lp = as_constant_if<UNIFORM>(F.lpos) + 4 * l;
       const double v[3] = {(double)lp[0] - p[0], (double)lp[1] - p[1], (double)lp[2] - p[2]};
       const double len2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
       // |l| and 1 / |l| from one reciprocal square root (equal to ~1e-15, immaterial after the fp32 store)
       const double inv = (len2 > 0.0) ? rsqrt_newton(len2) : 1.0;
       const double dist = (len2 > 0.0) ? len2 * inv : 0.0;
       const double lh[3] = {v[0] * inv, v[1] * inv, v[2] * inv};
-      const double kc = F.latt ? (double)F.latt[3 * l] : 1.0, kl = F.latt ? (double)F.latt[3 * l + 1] : 0.0,
-                   kq = F.latt ? (double)F.latt[3 * l + 2] : 0.0;
+      const double kc = F.latt ? (double)latt[3 * l] : 1.0, kl = F.latt ? (double)latt[3 * l + 1] : 0.0,
+                   kq = F.latt ? (double)latt[3 * l + 2] : 0.0;
       const double dp = F.use_quartic ? (len2 * len2) : len2;
       const double den = (kc + dist * kl) + dp * kq;
       const double afac = (fabs(den) > 0.0) ? rcp_newton(den) : 1.0;
@@ -444,16 +474,16 @@ __device__ __forceinline__ void shade_pixel_t(const FrameDev& F, const double d[
       const double spec = (cf[1] != 0.0) ? cf[1] * spec_pow_f32(rdotc, cf[2]) : 0.0;
       // light visibility (shadow rays, :116-118) multiplies light colour x albedo, not the ambient term
       const double w = (cf[0] * ndotl + spec) * (double)((vis >> l) & 1ull);
-      const int ci = clampi(F.lcidx[l], 0, F.ncolors - 1);
+      const int ci = clampi(lcidx[l], 0, F.ncolors - 1);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch)      // the ambient term is added once per light, as the reference does (:116-121)
-        im[ch] += w * ((double)F.colors[3 * ci + ch] * alb[ch]) + (F.ambient ? (double)F.ambient[ch] : 0.0) * alb[ch];
+        im[ch] += w * ((double)colors[3 * ci + ch] * alb[ch]) + (F.ambient ? (double)ambient[ch] : 0.0) * alb[ch];
     }
   } else {
     // sum_l (n . l^_l) colour_l, times the albedo once at the end (the reference multiplies inside the sum: equal to
     // ~1e-16, immaterial after the fp32 store); lights come as doubles from the per-frame copy
     for (int l = 0; l < F.nlights; ++l) {
-      const double* L = F.lights64 + 6 * l;
+      const auto L = as_constant_if<UNIFORM>(F.lights64) + 6 * l;   // one scalar load per light, not 64 lanes' worth
       const double v[3] = {L[0] - p[0], L[1] - p[1], L[2] - p[2]};
       const double len2 = __builtin_fma(v[2], v[2], __builtin_fma(v[1], v[1], v[0] * v[0]));
       // |l| <= 0 -> 1 (Q7): the light sits exactly on the fragment and contributes n . 0 = 0.  Clamping |l|^2 at the
