@@ -51,6 +51,15 @@ def _unit(v: torch.Tensor) -> torch.Tensor:
     return v / torch.where(n > 0, n, torch.ones_like(n))
 
 
+def _norm(v: torch.Tensor) -> torch.Tensor:
+    """|v| over the last axis (kept), with a zero gradient -- not sqrt's 0 * inf = NaN -- where v = 0: a pixel that hits
+    nothing is given t = 0 below, so a light placed exactly at the eye coincides with its 'fragment', and the NaN would
+    reach the light's gradient through the masked-out pixel."""
+    sq = torch.sum(v * v, dim=-1, keepdim=True)
+    pos = sq > 0
+    return torch.where(pos, torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))), torch.zeros_like(sq))
+
+
 def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None):
     """Differentiable image (H,W,3) and depth (H,W).  ``ref`` = {'nearest', 'depth'} of the same scene (which
     primitive wins each pixel, and -- through depth being finite -- whether the pixel is hit at all); computed with
@@ -113,7 +122,7 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional
     lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])]
     alb = leaves["materials.albedo"][mat]
     l = lpos[None, :, :] - p[:, None, :]
-    ln = torch.sqrt(torch.sum(l * l, dim=-1, keepdim=True))
+    ln = _norm(l)
     l = l / torch.where(ln > 0, ln, torch.ones_like(ln))
     s = torch.sum(nrm[:, None, :] * l, dim=-1)                               # (N,L)
     im = torch.sum(s[:, :, None] * lcol[None, :, :] * alb[:, None, :], dim=1)
@@ -226,7 +235,7 @@ def render_tch(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Opti
     alb = leaves["materials.albedo"][mat]
     cf = leaves["materials.coeffs"][mat]
     ldir = lpos[None, :, :] - p[:, None, :]                                  # (N,L,3)
-    lnorm = torch.sqrt(torch.sum(ldir * ldir, dim=-1, keepdim=True))
+    lnorm = _norm(ldir)
     ldir = ldir / torch.where(lnorm > 0, lnorm, torch.ones_like(lnorm))
     powv = 4 if use_quartic else 2
     den = att[None, :, 0:1] + lnorm * att[None, :, 1:2] + (lnorm ** powv) * att[None, :, 2:3]

@@ -632,10 +632,25 @@ int camera_to_frame(const SrhCamera* cam, FrameDev* F, bool orthonormal = false)
   for (int i = 0; i < 3; ++i) { z[i] /= zl; y[i] = cam->up_is_unit ? cam->up[i] : cam->up[i] / ul; }
   double x[3] = {y[1] * z[2] - y[2] * z[1], y[2] * z[0] - y[0] * z[2], y[0] * z[1] - y[1] * z[0]};
   if (orthonormal) {
-    // torch backend (torch/utils.py:402-427): x = unit(cross(unit(up), z)), y = cross(z, x)
-    const double xl = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    if (!(xl > 0)) return fail(SRH_E_CAMERA, "degenerate camera: up is parallel to the view direction");
-    for (int i = 0; i < 3; ++i) x[i] /= xl;
+    // torch backend (torch/utils.py:402-427): z = unit(eye - at), x = unit(cross(unit(up), z)), y = cross(z, x), where
+    // unit is that backend's normalize (:135-139): v / sqrt(sum(v_i^2 + 1e-10)).  The eps leaves x and y 1.5e-10 short of
+    // unit length: nothing an fp32 output shows, but a reflected ray that grazes the edge of a specular lobe
+    // (rdotc = 3e-8) moves by 2 % of itself, and the gradient of rdotc ** 0.5 with it
+    // (tests/test_hip_pow_paths.py::test_specular_lobe_backward).
+    if (!(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] > 0))
+      return fail(SRH_E_CAMERA, "degenerate camera: up is parallel to the view direction");
+    auto unit_eps = [](double* v) {
+      const double l = sqrt(((v[0] * v[0] + 1e-10) + (v[1] * v[1] + 1e-10)) + (v[2] * v[2] + 1e-10));
+      for (int i = 0; i < 3; ++i) v[i] /= l;
+    };
+    double u[3];
+    for (int i = 0; i < 3; ++i) { z[i] = cam->eye[i] - cam->at[i]; u[i] = cam->up[i]; }
+    unit_eps(z);
+    unit_eps(u);
+    x[0] = u[1] * z[2] - u[2] * z[1];
+    x[1] = u[2] * z[0] - u[0] * z[2];
+    x[2] = u[0] * z[1] - u[1] * z[0];
+    unit_eps(x);
     y[0] = z[1] * x[2] - z[2] * x[1];
     y[1] = z[2] * x[0] - z[0] * x[2];
     y[2] = z[0] * x[1] - z[1] * x[0];

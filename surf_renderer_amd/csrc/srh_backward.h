@@ -500,7 +500,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
   auto light_terms = [&](int l, LightTerms& T) {
     const float* lp = F.lpos + 4 * l;
     // the difference is formed in fp64 (light and fragment may be far from the origin and close to each other)
-    const float v[3] = {(float)((double)lp[0] - p[0]), (float)((double)lp[1] - p[1]), (float)((double)lp[2] - p[2])};
+    const double vd[3] = {(double)lp[0] - p[0], (double)lp[1] - p[1], (double)lp[2] - p[2]};
+    const float v[3] = {(float)vd[0], (float)vd[1], (float)vd[2]};
     T.dist = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     T.nz = T.dist > 0.0f;
     const float inv = T.nz ? 1.0f / T.dist : 1.0f;
@@ -514,7 +515,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
     T.ldn = (T.lh[0] * nf[0] + T.lh[1] * nf[1]) + T.lh[2] * nf[2];
     T.cl = (cdf[0] * T.lh[0] + cdf[1] * T.lh[1]) + cdf[2] * T.lh[2];
     T.nd = sgnf * (T.afac * T.ldn);
-    T.rd = sgnf * (2.0f * T.ldn * cdotnf - T.cl);
+    // The lobe's base is the exception: r.c = 2 (l^.n)(c^.n) - c^.l^ cancels to 0 at the lobe's edge, where rdotc ** (n - 1)
+    // of an exponent below 1 is unbounded, and comes within 1e-6 of 1 at the highlight's centre, where an exponent of
+    // 1000 multiplies every error of the base by 1000.  In fp32 it carries ~1e-7 ABSOLUTE either way; formed in fp64, as
+    // the forward pass forms it, and rounded once, it is good to 6e-8 RELATIVE at 3e-8 as well.
+    const double len2 = (vd[0] * vd[0] + vd[1] * vd[1]) + vd[2] * vd[2];
+    const double invd = (len2 > 0.0) ? rsqrt_newton(len2) : 1.0;
+    const double ldn = ((vd[0] * n[0] + vd[1] * n[1]) + vd[2] * n[2]) * invd;
+    const double cl = ((vd[0] * cdir[0] + vd[1] * cdir[1]) + vd[2] * cdir[2]) * invd;
+    T.rd = (float)(sgn * (2.0 * ldn * cdotn - cl));
   };
   // the forward pass evaluates the lobe in fp32 too (spec_pow_f32)
   auto spec_pow = [&](float rdotc) { return (rdotc == 0.0f && cf[2] == 0.0f) ? 1.0f : powf(rdotc, cf[2]); };
