@@ -1,12 +1,11 @@
-// libsrh.so -- MI355X (gfx950) render(scene) backend: kernels + the C ABI declared in include/srh.h.
+// libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
+// kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
+// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
 //                 centre, ...) in fp64, plus the fp32 reject records of the FAST mode
-//   k_render_*    one 256-thread workgroup per 64x4-pixel tile; every wave owns 64 consecutive pixels
-//                 of one image row, so depth / nearest / RGB stores are full-wave coalesced rows
-// The primitive stream is wave-uniform (every lane walks the same record), so records arrive through
-// the scalar cache into SGPRs; no LDS staging is needed for uniform reads.
+//   k_render_*    the frame's pixels, in the mode the caller asked for
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -14,11 +13,14 @@
 #include <string.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "srh.h"
 #include "srh_device.h"
 #include "srh_reject.h"
 #include "srh_binned.h"
+#include "srh_prep.h"
+#include "srh_allpairs.h"
 #include "srh_backward.h"
 #include "srh_shadow.h"
 #include "srh_splat.h"
@@ -42,509 +44,97 @@ int hip_fail(hipError_t e, const char* what) {
   return (int)e;
 }
 
+// what every entry point returns after its launches
+int launch_status(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SRH_OK : hip_fail(e, what);
+}
+
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // ------------------------------------------------------------------------------------------------
-// k_prep: per-frame primitive records
+// launch shapes and typed launches
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void prep_record64(const SegDev& S, int type, int i, const double o[3], bool tch, double* R);
-
-// Can no pixel of rows [row0, row1) see anything of the ball (centre x relative to the eye, radius rho)?  The ball's
-// points have a in a0 +- rho |m_a| and g in g0 +- rho |m_g| (Cauchy-Schwarz) and lie on image row g / a; rays exist
-// only through integer rows, hence the half-row slack.  A ball that reaches the eye plane (a <= 0) is kept.
-__device__ inline bool ball_misses_slab(const FrameDev& F, const double x[3], double rho) {
-  const double a0 = dot3(F.slab_ma, x), g0 = dot3(F.slab_mg, x);
-  const double a_lo = a0 - rho * F.slab_na, a_hi = a0 + rho * F.slab_na;
-  const double g_lo = g0 - rho * F.slab_ng, g_hi = g0 + rho * F.slab_ng;
-  // fp64 side: a0 and g0 carry 2^-52 of their absolute terms.  The cull is used only while a_lo keeps 1e-6 of them
-  // (relative error of a below 2^-32, of the rows below 1e-6 of a row: inside the half-row slack); a ball that far off
-  // axis, or that cancelled (centre ~1e20 away, radius to match), is simply kept
-  if (!(a_lo > 1.0e-6 * (abs_dot3(F.slab_ma, x) + rho * F.slab_na)) || !isfinite(a_hi + g_lo + g_hi)) return false;
-  const double r_lo = g_lo / (g_lo >= 0.0 ? a_hi : a_lo), r_hi = g_hi / (g_hi >= 0.0 ? a_lo : a_hi);
-  return r_hi < (double)F.row0 - 0.5 || r_lo > (double)F.row1 - 0.5;
+// The per-pixel kernels' launch: one 64 x 4-thread workgroup per 64 * P x 4 pixels (P columns per lane: k_render_fast).
+// The camera-gradient scratch holds one set of partial sums per workgroup of this grid.
+struct PixelGrid {
+  dim3 block, grid;
+  size_t groups() const { return (size_t)grid.x * grid.y; }
+};
+PixelGrid pixel_grid(int32_t width, int32_t rows, int P = 1) {
+  return {dim3(64, 4), dim3((width + 64 * P - 1) / (64 * P), (rows + 3) / 4)};
 }
+PixelGrid pixel_grid(const FrameDev& F, int P = 1) { return pixel_grid(F.W, F.row1 - F.row0, P); }
 
-// multi-GPU row slabs: most primitives project outside a rank's rows; they are recognised from their bounding ball
-// before any of the per-frame records is computed, and are simply not binned (no list refers to their records)
-__device__ inline bool primitive_misses_slab(const FrameDev& F, const SegDev& S, int i) {
-  double x[3], rho;
-  // numpy semantics, near <= 0: a sphere whose line a ray MISSES yields the valid distance 0 (Q2) -- on every pixel
-  // of the image, wherever the sphere projects; it can never be culled
-  if (S.type == SRH_PRIM_SPHERE && !(F.near_clip > 0.0)) return false;
-  if (S.type == SRH_PRIM_DISK || S.type == SRH_PRIM_SPHERE) {
-    const float* c = S.pos + 4 * (size_t)i;
-    for (int k = 0; k < 3; ++k) x[k] = (double)c[k] - F.o[k];
-    rho = fabs((double)S.radius[i]);
-  } else if (S.type == SRH_PRIM_TRIANGLE) {
-    const float* f = S.face + 12 * (size_t)i;
-    double cen[3];
-    for (int k = 0; k < 3; ++k) cen[k] = ((double)f[k] + (double)f[4 + k] + (double)f[8 + k]) / 3.0;
-    rho = 0.0;
-    for (int v = 0; v < 3; ++v) {
-      const double w[3] = {(double)f[4 * v] - cen[0], (double)f[4 * v + 1] - cen[1], (double)f[4 * v + 2] - cen[2]};
-      rho = fmax(rho, sqrt(dot3(w, w)));
-    }
-    rho *= 1.0000001;
-    for (int k = 0; k < 3; ++k) x[k] = cen[k] - F.o[k];
-  } else {
-    return false;
-  }
-  return ball_misses_slab(F, x, rho);
-}
-
-// TYPE = the batch's primitive type (the host launches the matching instantiation): the fp64 record and the reject
-// record are built in REGISTERS, stored once, and the tile box and the bin placement work from the register copies --
-// a thread never waits for its own stores to come back (measured: the kernel was 76 % s_waitcnt).
-template <int TYPE>
-__device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec64, float* rec32) {
-  const SegDev& S = F.seg[s];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= S.count) return;
-  // which set of frame-wide list lengths this frame counts into (srh_device.h: kLargeNext); stable for the whole binning
-  const uint32_t set = F.tilerange ? (F.counters[kLargeNext] & 1u) : 0u;
-  if (s == 0 && i == 0) {
-    if (F.tilerange) F.counters[kLargeNow] = set;          // ... and the render kernel reads the same one
-    // per-frame fp64 copy of the lights for the fragment stage: position, colour looked up through color_idx
-    double* L = const_cast<double*>(F.lights64);
-    for (int l = 0; l < F.nlights; ++l) {
-      const int ci = clampi(F.lcidx[l], 0, F.ncolors - 1);
-      for (int k = 0; k < 3; ++k) {
-        L[6 * l + k] = (double)F.lpos[4 * l + k];
-        L[6 * l + 3 + k] = (double)F.colors[3 * ci + k];
-      }
-    }
-  }
-  if (F.tilerange && F.slab_cull && primitive_misses_slab(F, S, i)) {
-    uint16_t* tr = F.tilerange + 4 * (size_t)(S.first + i);
-    tr[0] = 1; tr[1] = 0; tr[2] = 0; tr[3] = 0;                   // not binned
-    return;
-  }
-  constexpr int N64 = kRec64Stride[TYPE], N32 = kRec32Stride[TYPE];
-  double R[N64];
-  prep_record64(S, TYPE, i, F.o, F.shading != 0, R);
-  // screen-space reject record of the FAST / binned modes, from the fp64 record
-  float Q[N32];
-  const PixelBasis B = pixel_basis(F);
-  const bool near_pos = F.near_clip > 0.0;
-  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q);
-  else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q);
-  else if (TYPE == SRH_PRIM_TRIANGLE) triangle_reject_record(R, F.o, B, F.W, F.H, near_pos, Q);
-  else plane_reject_record(R, B, F.W, F.H, Q);
-  {
-    double2* r2 = reinterpret_cast<double2*>(rec64 + (size_t)i * N64);      // records are 16-byte aligned (strides 4, 8, 24)
-#pragma unroll
-    for (int k = 0; k < N64 / 2; ++k) r2[k] = make_double2(R[2 * k], R[2 * k + 1]);
-    float4* q4 = reinterpret_cast<float4*>(rec32 + (size_t)i * N32);
-#pragma unroll
-    for (int k = 0; k < N32 / 4; ++k) q4[k] = make_float4(Q[4 * k], Q[4 * k + 1], Q[4 * k + 2], Q[4 * k + 3]);
-  }
-  if (F.tilerange) {
-    // light views: a primitive that comes within near_ball of the eye can block a shadow ray from BEHIND the light
-    // (the reference accepts hits up to 0.1 beyond it); its screen-space shape says nothing about that, so every
-    // query tests it
-    bool near_eye = false;
-    if (F.near_ball > 0.0) {
-      // distance from the light to the nearest point the primitive can have, as a difference of two lengths -- which
-      // cancels for a primitive as large as it is far (centre 1e20 away, radius 1e20): 2^-46 of the lengths' sum,
-      // 64x their rounding, comes off
-      double dmin = 0.0, mag = 0.0;
-      if (TYPE == SRH_PRIM_DISK) {
-        const double oc[3] = {F.o[0] - R[4], F.o[1] - R[5], F.o[2] - R[6]};
-        const double dc = sqrt(dot3(oc, oc)), rr = sqrt(fabs(R[7]));
-        dmin = dc - rr; mag = dc + rr;
-      }
-      else if (TYPE == SRH_PRIM_SPHERE) {
-        // (the radius itself: |oc|^2 - (|oc|^2 - r^2) gives r^2 back only to 2^-52 |oc|^2)
-        const double dc = sqrt(dot3(R, R)), rr = fabs((double)S.radius[i]);
-        dmin = dc - rr; mag = dc + rr;
-      }
-      else if (TYPE == SRH_PRIM_TRIANGLE) {
-        double far2 = 0.0, near2 = 1.0e300;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          const double w[3] = {R[4 + 3 * v] - F.o[0], R[5 + 3 * v] - F.o[1], R[6 + 3 * v] - F.o[2]};
-          near2 = fmin(near2, dot3(w, w));
-          const double e[3] = {R[13 + 3 * v], R[14 + 3 * v], R[15 + 3 * v]};
-          far2 = fmax(far2, dot3(e, e));
-        }
-        dmin = sqrt(near2) - sqrt(far2);                        // every point is within one edge length of a vertex
-        mag = sqrt(near2) + sqrt(far2);
-      }
-      dmin -= 1.4210854715202004e-14 * mag;
-      near_eye = !(dmin > F.near_ball);                         // NaN -> large
-      // what the shadow pass skips candidates by: no point of the primitive is closer to the light than this (rounded
-      // DOWN to fp32; 0 = unknown: planes, non-finite geometry)
-      const float nd = (TYPE != SRH_PRIM_PLANE && dmin > 0.0 && dmin < 1.0e30) ? (float)dmin * 0.999999f : 0.0f;
-      F.neardist[S.first + i] = nd;
-    }
-    const TileBox box = bin_primitive(F, s, TYPE, Q, S.first + i, set, near_eye);
-    if (box.tx0 <= box.tx1) bin_place(F, s, TYPE, S.first, Q, S.first + i, box.tx0, box.ty0, box.tx1, box.ty1, set);
+// f(std::integral_constant<int, T>) for the primitive type T = `type` (validated by check_objects)
+template <class Fn>
+void with_prim_type(int type, Fn f) {
+  switch (type) {
+    case SRH_PRIM_DISK: f(std::integral_constant<int, SRH_PRIM_DISK>{}); break;
+    case SRH_PRIM_PLANE: f(std::integral_constant<int, SRH_PRIM_PLANE>{}); break;
+    case SRH_PRIM_SPHERE: f(std::integral_constant<int, SRH_PRIM_SPHERE>{}); break;
+    default: f(std::integral_constant<int, SRH_PRIM_TRIANGLE>{}); break;
   }
 }
 
-// Four waves per SIMD (at most 128 VGPRs), asked for explicitly: left alone hipcc takes what it likes -- 150 registers for
-// the disc instantiation once the fp64 trust terms of srh_reject.h went in, three waves per SIMD -- and the prep waves of
-// the frames in flight then hold their slots longer beside the render waves: config 5 went from 0.078 to 0.093 ms per
-// frame on that alone.  At 128 the compiler needs no spills.
-constexpr int kPrepWaves = 4;
-template <int TYPE>
-__global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrepWaves))) void k_prep(FrameDev F, int s, double* rec64, float* rec32) {
-  // the frame's constants into the workspace, where the render kernel reads them (FrameDev::self; srh_binned.h)
-  if (F.self && s == 0 && blockIdx.x == 0) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&F);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(F.self);
-    for (unsigned i = threadIdx.x; i < sizeof(FrameDev) / 4; i += kBinBlock) dst[i] = src[i];
-  }
-  prep_body<TYPE>(F, s, rec64, rec32);
-}
-
-template <int TYPE>
-__global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrepWaves))) void k_prep_views(const FrameDev* __restrict__ Fs, int s) {
-  const FrameDev& F = Fs[blockIdx.y];
-  prep_body<TYPE>(F, s, const_cast<double*>(F.seg[s].rec64), const_cast<float*>(F.seg[s].rec32));
-}
-
-// host side: the instantiation for the batch's type
-static void launch_prep(const FrameDev& F, int s, hipStream_t st) {
+// k_prep of batch s: the instantiation for the batch's type
+void launch_prep(const FrameDev& F, int s, hipStream_t st) {
   const SegDev& S = F.seg[s];
   const dim3 grid((S.count + kBinBlock - 1) / kBinBlock), block(kBinBlock);
-  double* r64 = (double*)S.rec64;
-  float* r32 = (float*)S.rec32;
-  switch (S.type) {
-    case SRH_PRIM_DISK: hipLaunchKernelGGL(k_prep<SRH_PRIM_DISK>, grid, block, 0, st, F, s, r64, r32); break;
-    case SRH_PRIM_PLANE: hipLaunchKernelGGL(k_prep<SRH_PRIM_PLANE>, grid, block, 0, st, F, s, r64, r32); break;
-    case SRH_PRIM_SPHERE: hipLaunchKernelGGL(k_prep<SRH_PRIM_SPHERE>, grid, block, 0, st, F, s, r64, r32); break;
-    default: hipLaunchKernelGGL(k_prep<SRH_PRIM_TRIANGLE>, grid, block, 0, st, F, s, r64, r32); break;
-  }
+  with_prim_type(S.type, [&](auto type) {
+    hipLaunchKernelGGL(k_prep<decltype(type)::value>, grid, block, 0, st, F, s, (double*)S.rec64, (float*)S.rec32);
+  });
 }
-static void launch_prep_views(const FrameDev& F0, const FrameDev* Fs, int s, int V, hipStream_t st) {
+void launch_prep_views(const FrameDev& F0, const FrameDev* Fs, int s, int V, hipStream_t st) {
   const dim3 grid((F0.seg[s].count + kBinBlock - 1) / kBinBlock, V), block(kBinBlock);
-  switch (F0.seg[s].type) {
-    case SRH_PRIM_DISK: hipLaunchKernelGGL(k_prep_views<SRH_PRIM_DISK>, grid, block, 0, st, Fs, s); break;
-    case SRH_PRIM_PLANE: hipLaunchKernelGGL(k_prep_views<SRH_PRIM_PLANE>, grid, block, 0, st, Fs, s); break;
-    case SRH_PRIM_SPHERE: hipLaunchKernelGGL(k_prep_views<SRH_PRIM_SPHERE>, grid, block, 0, st, Fs, s); break;
-    default: hipLaunchKernelGGL(k_prep_views<SRH_PRIM_TRIANGLE>, grid, block, 0, st, Fs, s); break;
-  }
+  with_prim_type(F0.seg[s].type, [&](auto type) {
+    hipLaunchKernelGGL(k_prep_views<decltype(type)::value>, grid, block, 0, st, Fs, s);
+  });
 }
 
-__device__ __forceinline__ void prep_record64(const SegDev& S, int type, int i, const double o[3], bool tch, double* R) {
-  double nh[3] = {0, 0, 0};
-  if (type != SRH_PRIM_SPHERE) {
-    // ops.normalize: divide by the 4-D length, by 1 if that is zero (numpy/ops.py:18-26)
-    const float* q = S.normal + 4 * (size_t)i;
-    const double v[4] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3]};
-    double len = sqrt(((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3]);
-    // the torch backend normalises xyz only, with an eps inside the sum (torch/utils.py:131-135, :289)
-    if (tch) len = sqrt(((v[0] * v[0] + 1e-10) + (v[1] * v[1] + 1e-10)) + (v[2] * v[2] + 1e-10));
-    if (!(fabs(len) > 0.0)) len = 1.0;
-    nh[0] = v[0] / len; nh[1] = v[1] / len; nh[2] = v[2] / len;
-  }
-  if (type == SRH_PRIM_SPHERE) {
-    const float* c = S.pos + 4 * (size_t)i;
-    const double r = (double)S.radius[i];
-    const double oc[3] = {o[0] - (double)c[0], o[1] - (double)c[1], o[2] - (double)c[2]};
-    R[0] = oc[0]; R[1] = oc[1]; R[2] = oc[2];
-    R[3] = ((oc[0] * oc[0] + oc[1] * oc[1]) + oc[2] * oc[2]) - r * r;     // numpy/renderer.py:22
-    return;
-  }
-  // point on the plane: pos, or vertex 0 of the triangle (numpy/renderer.py:107)
-  const float* pp = (type == SRH_PRIM_TRIANGLE) ? S.face + 12 * (size_t)i : S.pos + 4 * (size_t)i;
-  const double p[3] = {(double)pp[0], (double)pp[1], (double)pp[2]};
-  // dist - n^.eye (numpy/renderer.py:62,69)
-  const double dist = (p[0] * nh[0] + p[1] * nh[1]) + p[2] * nh[2];
-  const double neye = (nh[0] * o[0] + nh[1] * o[1]) + nh[2] * o[2];
-  R[0] = nh[0]; R[1] = nh[1]; R[2] = nh[2];
-  R[3] = dist - neye;
-  if (type == SRH_PRIM_DISK) {
-    const double r = (double)S.radius[i];
-    R[4] = p[0]; R[5] = p[1]; R[6] = p[2];
-    R[7] = r * r;
-  } else if (type == SRH_PRIM_TRIANGLE) {
-    const float* f = S.face + 12 * (size_t)i;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      const int w = (v + 1) % 3;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        R[4 + 3 * v + k] = (double)f[4 * v + k];
-        R[13 + 3 * v + k] = (double)f[4 * w + k] - (double)f[4 * v + k];
-      }
-    }
-    R[22] = 0.0; R[23] = 0.0;
-  }
-}
+// The two families of the binned render kernel, as launch_binned takes them
+struct BinnedMem {
+  template <bool TCH, int WPT, int BATCH>
+  static constexpr auto kernel = &k_render_binned_mem<TCH, WPT, BATCH>;
+};
+struct BinnedViews {
+  template <bool TCH, int WPT, int BATCH>
+  static constexpr auto kernel = &k_render_binned_views<TCH, WPT, BATCH>;
+};
 
-// ------------------------------------------------------------------------------------------------
-// k_rays: generate_rays as an output (reference returns 'ray_dir' (4,N))
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rays(FrameDev F, float* ray_dir) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
-  if (c >= F.W || r >= F.row1) return;
-  double d[3];
-  pixel_ray(F, c, r, d);
-  const size_t n = (size_t)(F.row1 - F.row0) * F.W;
-  const size_t p = (size_t)(r - F.row0) * F.W + c;
-  ray_dir[p] = (float)d[0];
-  ray_dir[n + p] = (float)d[1];
-  ray_dir[2 * n + p] = (float)d[2];
-  ray_dir[3 * n + p] = 0.0f;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_render_exact: every (pixel, primitive) pair through the fp64 intersection
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void store_pixel(const FrameDev& F, int c, int r, const float rgb[3], double z, int win,
-                                            float* __restrict__ image, float* __restrict__ depth,
-                                            int32_t* __restrict__ nearest, const float* aux = nullptr) {
-  const size_t row = (size_t)(r - F.row0);
-  float* px = image + row * F.img_stride + 3 * (size_t)c;
-  px[0] = rgb[0];
-  px[1] = rgb[1];
-  px[2] = rgb[2];
-  depth[row * F.depth_stride + c] = background_depth(F, z);
-  if (nearest) nearest[row * F.near_stride + c] = win;
-  if (aux) store_aux(F, row, c, aux);
-}
-
-__global__ __launch_bounds__(256) void k_render_exact(FrameDev F, float* __restrict__ image,
-                                                       float* __restrict__ depth, int32_t* __restrict__ nearest) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
-  const bool live = (c < F.W) && (r < F.row1);
-  double d[3];
-  pixel_ray(F, live ? c : F.W - 1, live ? r : F.row1 - 1, d);
-
-  double best = __builtin_inf();
-  int besti = 0;
-  for (int s = 0; s < F.nseg; ++s) {
-    const SegDev& S = F.seg[s];
-    const int stride = kRec64Stride[S.type];
-    for (int i = 0; i < S.count; ++i) {
-      const double t = hit_any64(S.type, S.rec64 + (size_t)i * stride, F.o, d, F.shading != 0);
-      resolve(F, t, S.first + i, best, besti);
-    }
-  }
-  float rgb[3], aux[6];
-  const bool want_aux = F.normal_out || F.pos_out;
-  shade_pixel(F, d, best, besti, rgb, want_aux ? aux : nullptr);
-  if (live) store_pixel(F, c, r, rgb, best, besti, image, depth, nearest, want_aux ? aux : nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_render_ortho: orthographic projection of the torch backend (torch/utils.py:461-468): every ray has the direction
-// -z of the camera basis and its own origin eye + x X + y Y.  All pairs in fp64 (the screen-space reject records are
-// derived for a pinhole); the reference's own ortho branch only works for images below one 4096-pixel tile.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_render_ortho(FrameDev F, float* __restrict__ image,
-                                                       float* __restrict__ depth, int32_t* __restrict__ nearest) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
-  const bool live = (c < F.W) && (r < F.row1);
-  const int cc = live ? c : F.W - 1, rr = live ? r : F.row1 - 1;
-  const double xs = (F.W > 1 && cc == F.W - 1) ? 1.0 : (cc * F.step_x + -1.0);
-  const double ys = (F.H > 1 && rr == F.H - 1) ? -1.0 : (rr * F.step_y + 1.0);
-  const double X = xs * F.half_w, Y = ys * F.half_h;
-  double q[3], org[3], d[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    q[i] = F.bx[i] * X + F.by[i] * Y;
-    org[i] = F.o[i] + q[i];
-    d[i] = -F.bz[i];
-  }
-  double best = __builtin_inf();
-  int besti = 0;
-  for (int s = 0; s < F.nseg; ++s) {
-    const SegDev& S = F.seg[s];
-    const int stride = kRec64Stride[S.type];
-    for (int i = 0; i < S.count; ++i)
-      resolve(F, hit_any64_from(S.type, S.rec64 + (size_t)i * stride, F.o, q, d), S.first + i, best, besti);
-  }
-  float rgb[3], aux[6];
-  const bool want_aux = F.normal_out || F.pos_out;
-  shade_pixel_t<true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, nullptr, org);
-  if (live) store_pixel(F, c, r, rgb, best, besti, image, depth, nearest, want_aux ? aux : nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_shadow_shade: the torch backend's `shadow=True` (torch/renderer.py:291-314) as a second pass over a rendered
-// frame.  Per hit pixel and light a ray from the fragment towards the light, started 0.1 along it, against EVERY
-// primitive in fp64 (arbitrary origins and directions: no screen-space structure to exploit, and the reference is
-// all-pairs too); the light counts as visible unless a primitive other than the fragment's own is hit before the
-// light.  Then the pixel is shaded again with the visibility bits and the image is overwritten.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_shadow_shade(FrameDev F, float* __restrict__ image,
-                                                       const float* __restrict__ depth,
-                                                       const int32_t* __restrict__ nearest,
-                                                       uint64_t* __restrict__ visibility) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
-  if (c >= F.W || r >= F.row1) return;
-  const size_t row = (size_t)(r - F.row0);
-  const bool hit = (double)depth[row * F.depth_stride + c] <= F.far_clip;
-  uint64_t vis = ~0ull;
-  if (!hit) {                                               // background: nothing to shade, every bit set
-    if (visibility) visibility[row * (size_t)F.W + c] = vis;
-    return;
-  }
-  const int win = nearest[row * F.near_stride + c];
-  const int s = segment_of(F, win);
-  const SegDev& S = F.seg[s];
-  const double* R = S.rec64 + (size_t)(win - S.first) * kRec64Stride[S.type];
-  // the primary ray and its hit, exactly as the forward pass computed them
-  double d[3], q0[3] = {0, 0, 0}, org[3];
-  double t;
-  if (F.ortho) {
-    const double xs = (F.W > 1 && c == F.W - 1) ? 1.0 : (c * F.step_x + -1.0);
-    const double ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
-    const double X = xs * F.half_w, Y = ys * F.half_h;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { q0[i] = F.bx[i] * X + F.by[i] * Y; d[i] = -F.bz[i]; }
-    t = hit_any64_from(S.type, R, F.o, q0, d);
-  } else {
-    pixel_ray(F, c, r, d);
-    t = hit_any64(S.type, R, F.o, d, true);
-  }
-  double p[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { org[i] = F.o[i] + q0[i]; p[i] = org[i] + t * d[i]; }
-
-  vis = 0ull;
-  for (int l = 0; l < F.nlights; ++l) {
-    const auto lp = as_constant(F.lpos) + 4 * l;            // (hipcc takes this load through the scalar cache anyway: no store precedes it here)
-    const double v[3] = {(double)lp[0] - p[0], (double)lp[1] - p[1], (double)lp[2] - p[2]};
-    const double dist = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    const double dir[3] = {v[0] / dist, v[1] / dist, v[2] / dist};
-    const double q[3] = {(p[0] + 0.1 * dir[0]) - F.o[0], (p[1] + 0.1 * dir[1]) - F.o[1], (p[2] + 0.1 * dir[2]) - F.o[2]};
-    double tmin = __builtin_inf();
-    int blocker = -1;
-    for (int sg = 0; sg < F.nseg; ++sg) {
-      const SegDev& B = F.seg[sg];
-      const int stride = kRec64Stride[B.type];
-      for (int i = 0; i < B.count; ++i) {
-        const double ts = hit_any64_from(B.type, B.rec64 + (size_t)i * stride, F.o, q, dir);
-        if (ts > 0.0 && ts < dist && ts < tmin) { tmin = ts; blocker = B.first + i; }   // lowest index wins ties
-      }
-    }
-    if (blocker < 0 || blocker == win) vis |= 1ull << l;
-  }
-  float rgb[3];
-  shade_pixel_t<true>(F, d, t, win, rgb, nullptr, nullptr, org, vis);
-  float* px = image + row * F.img_stride + 3 * (size_t)c;
-  px[0] = rgb[0]; px[1] = rgb[1]; px[2] = rgb[2];
-  if (visibility) visibility[row * (size_t)F.W + c] = vis;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_render_fast<P>: fp32 screen-space reject per pair, fp64 confirmation of the survivors.
-// A wave owns 64*P consecutive pixels of one row: lane l holds columns c0 + l + 64*j, j < P.  Reject
-// records are wave-uniform reads (scalar loads); the survivor branch is entered by a wave only when one
-// of its 64*P pixels passes the reject test, which for small primitives is a fraction of a percent of
-// the primitives, so the loop is bound by ~3 VALU operations per pair.
-// ------------------------------------------------------------------------------------------------
-template <int P>
-__device__ __forceinline__ void confirm(const FrameDev& F, const SegDev& S, int i, int r, int cbase,
-                                        const float (&q)[P], bool ge_zero, double (&best)[P], int (&besti)[P]) {
-  const double* R = S.rec64 + (size_t)i * kRec64Stride[S.type];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const bool cand = ge_zero ? (q[j] >= 0.0f) : (q[j] <= 0.0f);
-    const int c = cbase + 64 * j;
-    if (cand && c < F.W) {
-      double d[3];
-      pixel_ray(F, c, r, d);
-      resolve(F, hit_any64(S.type, R, F.o, d, F.shading != 0), S.first + i, best[j], besti[j]);
-    }
-  }
-}
-
-template <int P>
-__global__ __launch_bounds__(256) void k_render_fast(FrameDev F, float* __restrict__ image,
-                                                      float* __restrict__ depth, int32_t* __restrict__ nearest) {
-  const int cbase = blockIdx.x * (64 * P) + threadIdx.x;
-  const int r_raw = F.row0 + blockIdx.y * 4 + threadIdx.y;
-  const bool row_live = r_raw < F.row1;
-  const int r = row_live ? r_raw : F.row1 - 1;
-  const float rf = (float)r;
-  float cf[P];
-  double best[P];
-  int besti[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    cf[j] = (float)(cbase + 64 * j);
-    best[j] = __builtin_inf();
-    besti[j] = 0;
-  }
-
-  for (int s = 0; s < F.nseg; ++s) {
-    const SegDev& S = F.seg[s];
-    if (S.type == SRH_PRIM_DISK || S.type == SRH_PRIM_SPHERE) {
-      for (int i = 0; i < S.count; ++i) {
-        const float* Q = S.rec32 + (size_t)i * kRec32Stride[SRH_PRIM_DISK];
-        const float dr = rf - Q[1];
-        float q[P];
-        float m = __builtin_inff();
-        {
-          const float e = Q[3] * dr;
-          const float g = __builtin_fmaf(Q[4] * dr, dr, -1.0f);
-#pragma unroll
-          for (int j = 0; j < P; ++j) {
-            const float dc = cf[j] - Q[0];
-            q[j] = __builtin_fmaf(dc, __builtin_fmaf(Q[2], dc, e), g);
-            m = fminf(m, q[j]);
-          }
-        }
-        if (m <= 0.0f) confirm<P>(F, S, i, r, cbase, q, false, best, besti);
-      }
-    } else if (S.type == SRH_PRIM_TRIANGLE) {
-      for (int i = 0; i < S.count; ++i) {
-        const float* Q = S.rec32 + (size_t)i * kRec32Stride[SRH_PRIM_TRIANGLE];
-        const float r0 = __builtin_fmaf(Q[1], rf, Q[2]);
-        const float r1 = __builtin_fmaf(Q[5], rf, Q[6]);
-        const float r2 = __builtin_fmaf(Q[9], rf, Q[10]);
-        float q[P];
-        float m = -__builtin_inff();
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const float e0 = __builtin_fmaf(Q[0], cf[j], r0);
-          const float e1 = __builtin_fmaf(Q[4], cf[j], r1);
-          const float e2 = __builtin_fmaf(Q[8], cf[j], r2);
-          q[j] = fminf(fminf(e0, e1), e2);
-          m = fmaxf(m, q[j]);
-        }
-        if (m >= 0.0f) confirm<P>(F, S, i, r, cbase, q, true, best, besti);
-      }
-    } else {
-      float q[P];
-#pragma unroll
-      for (int j = 0; j < P; ++j) q[j] = 0.0f;
-      for (int i = 0; i < S.count; ++i) confirm<P>(F, S, i, r, cbase, q, false, best, besti);
-    }
-  }
-
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const int c = cbase + 64 * j;
-    if (c < F.W) {      // wave-divergent only in the last column block
-      double d[3];
-      pixel_ray(F, c, r, d);
-      float rgb[3], aux[6];
-      const bool want_aux = F.normal_out || F.pos_out;
-      shade_pixel(F, d, best[j], besti[j], rgb, want_aux ? aux : nullptr);
-      if (row_live) store_pixel(F, c, r_raw, rgb, best[j], besti[j], image, depth, nearest, want_aux ? aux : nullptr);
-    }
-  }
+// The binned render kernel of frame F (of grid_y views shaped like F) with the kernel's own arguments `args`.
+// One wave per tile while that still gives every SIMD several waves, four waves per tile for small frames / slabs:
+// SrhParams.waves_per_tile (1 or 4) decides, else the caller's `auto_split`.
+template <class Family, class... Args>
+void launch_binned(const FrameDev& F, int waves_per_tile, bool auto_split, unsigned grid_y, hipStream_t st, Args... args) {
+  const bool split = (waves_per_tile == 1 || waves_per_tile == 4) ? waves_per_tile == 4 : auto_split;
+  // whole regions of tiles, a multiple of 8 of them (see binned_grid)
+  const dim3 grid(binned_grid(F) * 4, grid_y), block(split ? 256 : 64);
+  // one object batch of a known type: the instantiation without per-batch generality and without the other types' code
+  const int batch = F.nseg == 1 ? F.seg[0].type : -1;
+  auto typed = [&](auto b) {
+    auto launch = [&](auto tch, auto wpt) {
+      hipLaunchKernelGGL((Family::template kernel<decltype(tch)::value, decltype(wpt)::value, decltype(b)::value>), grid,
+                         block, 0, st, args...);
+    };
+    using One = std::integral_constant<int, 1>;
+    using Four = std::integral_constant<int, 4>;
+    if (F.shading) { if (split) launch(std::true_type{}, Four{}); else launch(std::true_type{}, One{}); }
+    else { if (split) launch(std::false_type{}, Four{}); else launch(std::false_type{}, One{}); }
+  };
+  if (batch < 0) typed(std::integral_constant<int, -1>{});
+  else with_prim_type(batch, typed);
 }
 
 template <int P>
 void launch_fast(const FrameDev& F, hipStream_t st, float* image, float* depth, int32_t* nearest) {
-  const dim3 block(64, 4), grid((F.W + 64 * P - 1) / (64 * P), (F.row1 - F.row0 + 3) / 4);
-  hipLaunchKernelGGL(k_render_fast<P>, grid, block, 0, st, F, image, depth, nearest);
+  const PixelGrid pg = pixel_grid(F, P);
+  hipLaunchKernelGGL(k_render_fast<P>, pg.grid, pg.block, 0, st, F, image, depth, nearest);
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// workspace layout, camera set-up and argument validation
 // ------------------------------------------------------------------------------------------------
 struct WsLayout {
   size_t off64[SRH_MAX_SEGMENTS];
@@ -685,6 +275,16 @@ int check_rows(const FrameDev& F, int row0, int row1) {
   return SRH_OK;
 }
 
+// what a shaded frame needs of its (non-NULL) lights and materials
+int check_lights_materials(const SrhLights* lights, const SrhMaterials* materials) {
+  if (lights->n_lights < 0 || lights->n_lights > SRH_MAX_LIGHTS)
+    return fail(SRH_E_RANGE, "n_lights = %d, expected 0..%d", lights->n_lights, SRH_MAX_LIGHTS);
+  if (lights->n_lights > 0 && (!lights->pos || !lights->color_idx || !lights->colors || lights->n_colors < 1))
+    return fail(SRH_E_NULL, "lights arrays missing");
+  if (materials->n_materials < 1 || !materials->albedo) return fail(SRH_E_NULL, "materials.albedo missing");
+  return SRH_OK;
+}
+
 // Validation and per-frame constants shared by the forward and the backward entry points.
 int setup_frame(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
                 const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
@@ -699,11 +299,7 @@ int setup_frame(const SrhCamera* camera, const SrhObjects* objects, const SrhLig
   if ((rc = check_objects(objects))) return rc;
   if (!lights || !materials) return fail(SRH_E_NULL, "lights / materials is NULL");
   if ((rc = check_rows(F, params->row0, params->row1))) return rc;
-  if (lights->n_lights < 0 || lights->n_lights > SRH_MAX_LIGHTS)
-    return fail(SRH_E_RANGE, "n_lights = %d, expected 0..%d", lights->n_lights, SRH_MAX_LIGHTS);
-  if (lights->n_lights > 0 && (!lights->pos || !lights->color_idx || !lights->colors || lights->n_colors < 1))
-    return fail(SRH_E_NULL, "lights arrays missing");
-  if (materials->n_materials < 1 || !materials->albedo) return fail(SRH_E_NULL, "materials.albedo missing");
+  if ((rc = check_lights_materials(lights, materials))) return rc;
   if (params->mode < SRH_MODE_AUTO || params->mode > SRH_MODE_BINNED) return fail(SRH_E_TYPE, "unknown mode %d", params->mode);
   const WsLayout L = layout_for(objects, F.W, F.H);
   *Lp = L;
@@ -756,15 +352,42 @@ int setup_frame(const SrhCamera* camera, const SrhObjects* objects, const SrhLig
   return SRH_OK;
 }
 
-}  // namespace
+// Tile-binning fields of a frame whose primitive records live in `workspace` (layout L).
+void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
+  F.tiles_x = L.tiles_x;
+  F.tiles_y = (F.row1 - F.row0 + kTile - 1) / kTile;
+  F.ntiles = F.tiles_x * F.tiles_y;
+  F.ntiles_pad = (F.ntiles + 3) / 4 * 4;
+  F.nbins = F.nseg * F.ntiles_pad;
+  F.bin_cap = (int32_t)std::min<size_t>(L.entries_words / (size_t)F.nbins, 1u << 20);
+  char* ws = (char*)workspace;
+  F.tilerange = (uint16_t*)(ws + L.tilerange);
+  F.neardist = (float*)(ws + L.neardist);
+  F.counters = (uint32_t*)(ws + L.counters);
+  F.large = (uint32_t*)(ws + L.large);
+  F.entries = (uint32_t*)(ws + L.entries);
+  F.slab_cull = 0;
+  if (F.row0 > 0 || F.row1 < F.H) {
+    // rows of [D0 Dc Dr]^-1 via the adjugate (cross products)
+    const PixelBasis B = pixel_basis(F);
+    const double* p0 = B.D0; const double* pc = B.Dc; const double* pr = B.Dr;
+    const double cx[3] = {pc[1] * pr[2] - pc[2] * pr[1], pc[2] * pr[0] - pc[0] * pr[2], pc[0] * pr[1] - pc[1] * pr[0]};
+    const double cg[3] = {p0[1] * pc[2] - p0[2] * pc[1], p0[2] * pc[0] - p0[0] * pc[2], p0[0] * pc[1] - p0[1] * pc[0]};
+    const double det = p0[0] * cx[0] + p0[1] * cx[1] + p0[2] * cx[2];
+    if (std::isfinite(det) && std::fabs(det) > 0.0) {
+      for (int k = 0; k < 3; ++k) { F.slab_ma[k] = cx[k] / det; F.slab_mg[k] = cg[k] / det; }
+      F.slab_na = std::sqrt(F.slab_ma[0] * F.slab_ma[0] + F.slab_ma[1] * F.slab_ma[1] + F.slab_ma[2] * F.slab_ma[2]) * 1.000001;
+      F.slab_ng = std::sqrt(F.slab_mg[0] * F.slab_mg[0] + F.slab_mg[1] * F.slab_mg[1] + F.slab_mg[2] * F.slab_mg[2]) * 1.000001;
+      F.slab_cull = std::isfinite(F.slab_na) && std::isfinite(F.slab_ng) ? 1 : 0;
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // the splat renderer (srh_splat.h)
 // ------------------------------------------------------------------------------------------------
-namespace {
 
 constexpr int kSplatMaxSamples = 8;
-
 // argument checks (no HIP call) and the device view of a splat launch
 int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLights* lights, const SrhMaterials* mats,
                 SplatDev* S) {
@@ -784,13 +407,8 @@ int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLigh
       in->eye_view_stride < 0 || in->lights_pos_view_stride < 0)
     return fail(SRH_E_RANGE, "negative view stride");
   if (!lights || !mats) return fail(SRH_E_NULL, "lights / materials is NULL");
-  if (p->shade) {
-    if (lights->n_lights < 0 || lights->n_lights > SRH_MAX_LIGHTS)
-      return fail(SRH_E_RANGE, "n_lights = %d, expected 0..%d", lights->n_lights, SRH_MAX_LIGHTS);
-    if (lights->n_lights > 0 && (!lights->pos || !lights->color_idx || !lights->colors || lights->n_colors < 1))
-      return fail(SRH_E_NULL, "lights arrays missing");
-    if (mats->n_materials < 1 || !mats->albedo) return fail(SRH_E_NULL, "materials.albedo missing");
-  }
+  if (p->shade)
+    if (int rc = check_lights_materials(lights, mats)) return rc;
   const double up2 = p->up[0] * p->up[0] + p->up[1] * p->up[1] + p->up[2] * p->up[2];
   if (!(up2 > 0.0)) return fail(SRH_E_CAMERA, "camera.up is zero");
   memset(S, 0, sizeof(*S));
@@ -823,74 +441,6 @@ size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N
 
 }  // namespace
 
-extern "C" {
-
-size_t srh_splat_workspace_bytes(const SrhSplatParams* params, const SrhSplatInputs* inputs) {
-  SrhLights L;
-  SrhMaterials M;
-  memset(&L, 0, sizeof(L));
-  memset(&M, 0, sizeof(M));
-  SrhSplatParams p;
-  if (!params) { fail(SRH_E_NULL, "params is NULL"); return 0; }
-  p = *params;
-  p.shade = 0;                                           // the size does not depend on the lights
-  SplatDev S;
-  if (splat_setup(&p, inputs, &L, &M, &S)) return 0;
-  return splat_ws_bytes(S);
-}
-
-int srh_splat_fwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
-                  const SrhMaterials* materials, float* image, float* depth, float* pos, float* normal, void* stream) {
-  SplatDev S;
-  int rc = splat_setup(params, inputs, lights, materials, &S);
-  if (rc) return rc;
-  if (!depth || !pos || !normal || (S.shade && !image)) return fail(SRH_E_NULL, "an output buffer is NULL");
-  const dim3 grid((S.N + 255) / 256, S.B);
-  hipLaunchKernelGGL(k_splat_fwd, grid, dim3(256), 0, (hipStream_t)stream, S, image, depth, pos, normal);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "k_splat_fwd launch");
-}
-
-int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
-                  const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
-                  const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
-                  const SrhSplatGrads* grads, void* stream) {
-  SplatDev S;
-  int rc = splat_setup(params, inputs, lights, materials, &S);
-  if (rc) return rc;
-  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
-  if (!grad_image && !grad_depth && !grad_pos && !grad_normal)
-    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_pos and grad_normal are all NULL");
-  if (!S.shade && (grad_image || grads->light_vis || grads->lights_pos || grads->colors || grads->attenuation ||
-                   grads->ambient || grads->albedo || grads->coeffs))
-    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
-  if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
-  if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
-  const size_t need = splat_ws_bytes(S);
-  const bool gather = S.estimate && grads->pos;
-  if (gather && (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double))))
-    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
-                workspace);
-  SplatGradsDev G;
-  G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
-  G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
-  G.coeffs = grads->coeffs;
-  if (S.estimate && !gather) {
-    G.pos = nullptr;
-    if (!G.vis && !G.lpos && !G.colors && !G.latt && !G.amb && !G.albedo && !G.coeffs) return SRH_OK;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((S.N + 255) / 256, S.B);
-  // without z gradients the stencil slots are not wanted: k_splat_bwd then needs no workspace
-  double* ws = gather ? (double*)workspace : nullptr;
-  hipLaunchKernelGGL(k_splat_bwd, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws);
-  if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "splat backward launch");
-}
-
-}  // extern "C"
-
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -902,8 +452,8 @@ const char* srh_last_error(void) { return g_err; }
 
 size_t srh_workspace_bytes(const SrhObjects* objects, int32_t width, int32_t height) {
   if (check_objects(objects) != SRH_OK) return 0;
-  if (width < 1 || height < 1 || (int64_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile) > 65535LL * 65535LL ||
-      (width + kTile - 1) / kTile > 65535 || (height + kTile - 1) / kTile > 65535) {
+  const int64_t tiles_x = ((int64_t)width + kTile - 1) / kTile, tiles_y = ((int64_t)height + kTile - 1) / kTile;
+  if (width < 1 || height < 1 || tiles_x * tiles_y > 65535LL * 65535LL || tiles_x > 65535 || tiles_y > 65535) {
     fail(SRH_E_RANGE, "frame size %d x %d out of range", width, height);
     return 0;
   }
@@ -920,41 +470,9 @@ int srh_generate_rays(const SrhCamera* camera, int32_t row0, int32_t row1, float
   if (!ray_dir) return fail(SRH_E_NULL, "ray_dir is NULL");
   F.row0 = row0;
   F.row1 = row1;
-  const dim3 block(64, 4), grid((F.W + 63) / 64, (row1 - row0 + 3) / 4);
-  hipLaunchKernelGGL(k_rays, grid, block, 0, (hipStream_t)stream, F, ray_dir);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "k_rays launch");
-}
-
-// Tile-binning fields of a frame whose primitive records live in `workspace` (layout L).
-static void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
-    F.tiles_x = L.tiles_x;
-  F.tiles_y = (F.row1 - F.row0 + kTile - 1) / kTile;
-  F.ntiles = F.tiles_x * F.tiles_y;
-  F.ntiles_pad = (F.ntiles + 3) / 4 * 4;
-  F.nbins = F.nseg * F.ntiles_pad;
-  F.bin_cap = (int32_t)std::min<size_t>(L.entries_words / (size_t)F.nbins, 1u << 20);
-  char* ws = (char*)workspace;
-  F.tilerange = (uint16_t*)(ws + L.tilerange);
-  F.neardist = (float*)(ws + L.neardist);
-  F.counters = (uint32_t*)(ws + L.counters);
-  F.large = (uint32_t*)(ws + L.large);
-  F.entries = (uint32_t*)(ws + L.entries);
-  F.slab_cull = 0;
-  if (F.row0 > 0 || F.row1 < F.H) {
-    // rows of [D0 Dc Dr]^-1 via the adjugate (cross products)
-    const PixelBasis B = pixel_basis(F);
-    const double* p0 = B.D0; const double* pc = B.Dc; const double* pr = B.Dr;
-    const double cx[3] = {pc[1] * pr[2] - pc[2] * pr[1], pc[2] * pr[0] - pc[0] * pr[2], pc[0] * pr[1] - pc[1] * pr[0]};
-    const double cg[3] = {p0[1] * pc[2] - p0[2] * pc[1], p0[2] * pc[0] - p0[0] * pc[2], p0[0] * pc[1] - p0[1] * pc[0]};
-    const double det = p0[0] * cx[0] + p0[1] * cx[1] + p0[2] * cx[2];
-    if (std::isfinite(det) && std::fabs(det) > 0.0) {
-      for (int k = 0; k < 3; ++k) { F.slab_ma[k] = cx[k] / det; F.slab_mg[k] = cg[k] / det; }
-      F.slab_na = std::sqrt(F.slab_ma[0] * F.slab_ma[0] + F.slab_ma[1] * F.slab_ma[1] + F.slab_ma[2] * F.slab_ma[2]) * 1.000001;
-      F.slab_ng = std::sqrt(F.slab_mg[0] * F.slab_mg[0] + F.slab_mg[1] * F.slab_mg[1] + F.slab_mg[2] * F.slab_mg[2]) * 1.000001;
-      F.slab_cull = std::isfinite(F.slab_na) && std::isfinite(F.slab_ng) ? 1 : 0;
-    }
-  }
+  const PixelGrid pg = pixel_grid(F);
+  hipLaunchKernelGGL(k_rays, pg.grid, pg.block, 0, (hipStream_t)stream, F, ray_dir);
+  return launch_status("k_rays launch");
 }
 
 int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
@@ -995,37 +513,16 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
     launch_prep(F, s, st);
   }
   if (params->ev_start) (void)hipEventRecord((hipEvent_t)params->ev_start, st);
-  if (!run_render) {
-  } else if (mode == SRH_MODE_BINNED) {
-    const unsigned groups = binned_grid(F);   // whole regions of tiles, a multiple of 8 of them (see binned_grid)
-    // one wave per tile while that still gives every SIMD several waves; four waves per tile for small frames / slabs
-    const bool split = (params->waves_per_tile == 1 || params->waves_per_tile == 4) ? params->waves_per_tile == 4
-                                                                                   : binned_waves_per_tile(F) == 4;
-    const dim3 g4(groups * 4), b4(256), g1(groups * 4), b1(64);
-    // one object batch of a known type: the instantiation without per-batch generality and without the other types' code
-    const int batch = F.nseg == 1 ? F.seg[0].type : -1;
+  if (mode == SRH_MODE_BINNED) {                 // the one mode that can come without its render stage
     // the render kernel reads the frame's constants from the workspace: k_prep of batch 0 put them there, unless this
     // call renders from bins an earlier call made
-    if (!run_binning) hipLaunchKernelGGL(k_put_frame, dim3(1), dim3(64), 0, st, F);
-    const FrameConstPtr Fc = (FrameConstPtr)F.self;
-#define SRH_LAUNCH_BINNED(TCH_, WPT_, G_, B_)                                                                          \
-    switch (batch) {                                                                                                   \
-      case SRH_PRIM_DISK: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_DISK>), G_, B_, 0, st, Fc, image, depth, nearest); break;       \
-      case SRH_PRIM_PLANE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_PLANE>), G_, B_, 0, st, Fc, image, depth, nearest); break;     \
-      case SRH_PRIM_SPHERE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_SPHERE>), G_, B_, 0, st, Fc, image, depth, nearest); break;   \
-      case SRH_PRIM_TRIANGLE: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, SRH_PRIM_TRIANGLE>), G_, B_, 0, st, Fc, image, depth, nearest); break; \
-      default: hipLaunchKernelGGL((k_render_binned_mem<TCH_, WPT_, -1>), G_, B_, 0, st, Fc, image, depth, nearest); break;  \
-    }
-    if (F.shading) {
-      if (split) { SRH_LAUNCH_BINNED(true, 4, g4, b4) } else { SRH_LAUNCH_BINNED(true, 1, g1, b1) }
-    } else {
-      if (split) { SRH_LAUNCH_BINNED(false, 4, g4, b4) } else { SRH_LAUNCH_BINNED(false, 1, g1, b1) }
-    }
-#undef SRH_LAUNCH_BINNED
+    if (run_render && !run_binning) hipLaunchKernelGGL(k_put_frame, dim3(1), dim3(64), 0, st, F);
+    if (run_render)
+      launch_binned<BinnedMem>(F, params->waves_per_tile, binned_waves_per_tile(F) == 4, 1, st, (FrameConstPtr)F.self,
+                               image, depth, nearest);
   } else if (mode == SRH_MODE_EXACT) {
-    const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
-    if (F.ortho) hipLaunchKernelGGL(k_render_ortho, grid, block, 0, st, F, image, depth, nearest);
-    else hipLaunchKernelGGL(k_render_exact, grid, block, 0, st, F, image, depth, nearest);
+    const PixelGrid pg = pixel_grid(F);
+    hipLaunchKernelGGL(F.ortho ? k_render_ortho : k_render_exact, pg.grid, pg.block, 0, st, F, image, depth, nearest);
   } else if (F.W >= 2048) {
     launch_fast<8>(F, st, image, depth, nearest);
   } else if (F.W >= 512) {
@@ -1034,8 +531,7 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
     launch_fast<1>(F, st, image, depth, nearest);
   }
   if (params->ev_stop) (void)hipEventRecord((hipEvent_t)params->ev_stop, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "render launch");
+  return launch_status("render launch");
 }
 
 // ---- many views of one scene per call ---------------------------------------------------------------------------
@@ -1108,37 +604,47 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
       if (lights[v].n_lights != lights[0].n_lights)
         return fail(SRH_E_RANGE, "view %d has %d lights, view 0 has %d", v, lights[v].n_lights, lights[0].n_lights);
   const size_t head = views_header_bytes(n_views);
+  char* ws = (char*)workspace;
   if (workspace_bytes < head + (size_t)n_views * one)
     return fail(SRH_E_RANGE, "workspace holds %zu bytes, %d views need %zu", workspace_bytes, n_views,
                 head + (size_t)n_views * one);
   hipStream_t st = (hipStream_t)stream;
+  // view v's frame: its own rows (same count for every view) of a viewport like view 0's, records in its own workspace
+  // slice, the projection of view 0
+  auto build_view = [&](int v, FrameDev* F, WsLayout* L) {
+    const int w = cameras[v].viewport[2] - cameras[v].viewport[0], h = cameras[v].viewport[3] - cameras[v].viewport[1];
+    if (w != W || h != H) return fail(SRH_E_RANGE, "view %d is %d x %d, view 0 is %d x %d", v, w, h, W, H);
+    SrhParams pv = *params;
+    if (params->view_row0) {
+      pv.row0 = params->view_row0[v];
+      pv.row1 = pv.row0 + (params->row1 - params->row0);
+    }
+    const int rc = setup_frame(&cameras[v], objects_of(v), lights_of(v), materials_of(v), &pv, ws + head + (size_t)v * one, one, F, L);
+    if (rc) return rc;
+    const char* const kind[2] = {"perspective", "orthographic"};
+    if (F->ortho != (cameras[0].ortho ? 1 : 0))
+      return fail(SRH_E_CAMERA, "view %d is %s, view 0 %s: one projection per call", v, kind[F->ortho], kind[!F->ortho]);
+    return (int)SRH_OK;
+  };
   if (cameras[0].ortho) {
     // Orthographic views (torch semantics): each view is the all-pairs fp64 frame of k_render_ortho -- its frame
     // constants travel as kernel arguments, so this branch needs no staging, no ring and no lock.
     if (params->shading != SRH_SHADING_TORCH)
       return fail(SRH_E_CAMERA, "orthographic projection exists only under SRH_SHADING_TORCH");
-    char* wso = (char*)workspace;
     const size_t rows = (size_t)(params->row1 - params->row0);
     for (int v = 0; v < n_views; ++v) {
-      if (!cameras[v].ortho) return fail(SRH_E_CAMERA, "view %d is perspective, view 0 orthographic: one projection per call", v);
-      const int w = cameras[v].viewport[2] - cameras[v].viewport[0], h = cameras[v].viewport[3] - cameras[v].viewport[1];
-      if (w != W || h != H) return fail(SRH_E_RANGE, "view %d is %d x %d, view 0 is %d x %d", v, w, h, W, H);
       FrameDev F;
       WsLayout Lo;
-      SrhParams pv = *params;
-      if (params->view_row0) { pv.row0 = params->view_row0[v]; pv.row1 = pv.row0 + (params->row1 - params->row0); }
-      int rc = setup_frame(&cameras[v], objects_of(v), lights_of(v), materials_of(v), &pv, wso + head + (size_t)v * one, one, &F, &Lo);
-      if (rc) return rc;
+      if (int rc = build_view(v, &F, &Lo)) return rc;
       for (int s = 0; s < F.nseg; ++s) {
         launch_prep(F, s, st);
       }
-      const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
-      hipLaunchKernelGGL(k_render_ortho, grid, block, 0, st, F, images + (size_t)v * rows * F.img_stride,
+      const PixelGrid pg = pixel_grid(F);
+      hipLaunchKernelGGL(k_render_ortho, pg.grid, pg.block, 0, st, F, images + (size_t)v * rows * F.img_stride,
                          depths + (size_t)v * rows * F.depth_stride,
                          nearests ? nearests + (size_t)v * rows * F.near_stride : nullptr);
     }
-    hipError_t eo = hipGetLastError();
-    return eo == hipSuccess ? SRH_OK : hip_fail(eo, "ortho views launch");
+    return launch_status("ortho views launch");
   }
   int dev = 0;
   if (int rc = device_of(st, &dev)) return rc;
@@ -1169,21 +675,10 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     if (es != hipSuccess) return hip_fail(es, "hipEventSynchronize(slot)");
   }
   FrameDev* stage = ring.stage[slot];
-  char* ws = (char*)workspace;
   WsLayout L;
   for (int v = 0; v < n_views; ++v) {
-    const int w = cameras[v].viewport[2] - cameras[v].viewport[0], h = cameras[v].viewport[3] - cameras[v].viewport[1];
-    if (w != W || h != H) return fail(SRH_E_RANGE, "view %d is %d x %d, view 0 is %d x %d", v, w, h, W, H);
-    FrameDev& F = stage[v];
-    SrhParams pv = *params;
-    if (params->view_row0) {                        // this view's own rows, same count for every view
-      pv.row0 = params->view_row0[v];
-      pv.row1 = pv.row0 + (params->row1 - params->row0);
-    }
-    int rc = setup_frame(&cameras[v], objects_of(v), lights_of(v), materials_of(v), &pv, ws + head + (size_t)v * one, one, &F, &L);
-    if (rc) return rc;
-    if (F.ortho) return fail(SRH_E_CAMERA, "view %d is orthographic, view 0 perspective: one projection per call", v);
-    setup_binning(F, L, ws + head + (size_t)v * one);
+    if (int rc = build_view(v, &stage[v], &L)) return rc;
+    setup_binning(stage[v], L, ws + head + (size_t)v * one);
   }
   const FrameDev* Fs = (const FrameDev*)ws;
   hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * sizeof(FrameDev), hipMemcpyHostToDevice, st);
@@ -1199,28 +694,9 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     hipLaunchKernelGGL(k_views_zero, dim3((unsigned)((ncount + 255) / 256), V), dim3(256), 0, st, Fs);
   for (int s = 0; s < F0.nseg; ++s)
     launch_prep_views(F0, Fs, s, V, st);
-  const unsigned groups = binned_grid(F0);
   // all views share the GPU, so the batch as a whole decides the launch shape
-  const bool split = (params->waves_per_tile == 1 || params->waves_per_tile == 4)
-                         ? params->waves_per_tile == 4 : (size_t)F0.ntiles * V < (size_t)kSplitTiles;
-  {
-    const dim3 g4(groups * 4, V), b4(256), g1(groups * 4, V), b1(64);
-    const int batch = F0.nseg == 1 ? F0.seg[0].type : -1;        // as in srh_render_fwd: the typed instantiation
-#define SRH_LAUNCH_VIEWS(TCH_, WPT_, G_, B_)                                                                            \
-    switch (batch) {                                                                                                   \
-      case SRH_PRIM_DISK: hipLaunchKernelGGL((k_render_binned_views<TCH_, WPT_, SRH_PRIM_DISK>), G_, B_, 0, st, base, images, depths, nearests); break;       \
-      case SRH_PRIM_PLANE: hipLaunchKernelGGL((k_render_binned_views<TCH_, WPT_, SRH_PRIM_PLANE>), G_, B_, 0, st, base, images, depths, nearests); break;     \
-      case SRH_PRIM_SPHERE: hipLaunchKernelGGL((k_render_binned_views<TCH_, WPT_, SRH_PRIM_SPHERE>), G_, B_, 0, st, base, images, depths, nearests); break;   \
-      case SRH_PRIM_TRIANGLE: hipLaunchKernelGGL((k_render_binned_views<TCH_, WPT_, SRH_PRIM_TRIANGLE>), G_, B_, 0, st, base, images, depths, nearests); break; \
-      default: hipLaunchKernelGGL((k_render_binned_views<TCH_, WPT_, -1>), G_, B_, 0, st, base, images, depths, nearests); break;  \
-    }
-    if (F0.shading) {
-      if (split) { SRH_LAUNCH_VIEWS(true, 4, g4, b4) } else { SRH_LAUNCH_VIEWS(true, 1, g1, b1) }
-    } else {
-      if (split) { SRH_LAUNCH_VIEWS(false, 4, g4, b4) } else { SRH_LAUNCH_VIEWS(false, 1, g1, b1) }
-    }
-#undef SRH_LAUNCH_VIEWS
-  }
+  launch_binned<BinnedViews>(F0, params->waves_per_tile, (size_t)F0.ntiles * V < (size_t)kSplitTiles, V, st, base, images,
+                             depths, nearests);
   // the slot is consumed only now: a call that failed validation above leaves the ring as it was
   const hipError_t er = hipEventRecord(ring.done[slot], st);
   ring.next++;
@@ -1229,8 +705,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     (void)hipStreamSynchronize(st);
     return hip_fail(er, "hipEventRecord(slot)");
   }
-  e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "views launch");
+  return launch_status("views launch");
 }
 
 namespace {
@@ -1277,14 +752,13 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
   for (int s = 0; s < F.nseg; ++s) {
     launch_prep(F, s, st);
   }
-  const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
+  const PixelGrid pg = pixel_grid(F);
   const ShadowLayout SL = shadow_layout_for(objects, F.W, F.H, F.nlights);
   const bool accelerated = params->mode != SRH_MODE_EXACT && F.nlights > 0 && workspace_bytes >= SL.total;
   if (!accelerated) {
     // all pairs (mode = SRH_MODE_EXACT asks for it; a workspace sized by srh_workspace_bytes has no room for the views)
-    hipLaunchKernelGGL(k_shadow_shade, grid, block, 0, st, F, image, depth, nearest, visibility);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SRH_OK : hip_fail(e, "shadow launch");
+    hipLaunchKernelGGL(k_shadow_shade, pg.grid, pg.block, 0, st, F, image, depth, nearest, visibility);
+    return launch_status("shadow launch");
   }
   char* ws = (char*)workspace;
   FrameDev* frames = (FrameDev*)(ws + SL.frames);
@@ -1321,15 +795,12 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
   hipLaunchKernelGGL(k_views_zero, dim3((unsigned)((ncount + 255) / 256), V), dim3(256), 0, st, frames);
   for (int s = 0; s < T.nseg; ++s)
     launch_prep_views(T, frames, s, V, st);
-  hipLaunchKernelGGL(k_shadow_shade_binned, grid, block, 0, st, F, frames, image, depth, nearest, visibility);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "shadow launch");
+  hipLaunchKernelGGL(k_shadow_shade_binned, pg.grid, pg.block, 0, st, F, frames, image, depth, nearest, visibility);
+  return launch_status("shadow launch");
 }
 
 // workgroups of a backward launch over width x rows pixels (64 x 4 pixels each), and the bytes of their camera partials
-static size_t camera_groups(int32_t width, int32_t rows) {
-  return (size_t)((width + 63) / 64) * (size_t)((rows + 3) / 4);
-}
+static size_t camera_groups(int32_t width, int32_t rows) { return pixel_grid(width, rows).groups(); }
 static size_t camera_scratch_bytes(int32_t width, int32_t rows) {
   return camera_groups(width, rows) * kCamSums * sizeof(double);
 }
@@ -1366,38 +837,33 @@ static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const 
   for (int s = 0; s < F.nseg; ++s) {
     launch_prep(F, s, st);
   }
-  const dim3 block(64, 4), grid((F.W + 63) / 64, (F.row1 - F.row0 + 3) / 4);
+  const PixelGrid pg = pixel_grid(F);
   if (params->ev_start) (void)hipEventRecord((hipEvent_t)params->ev_start, st);
   const uint64_t* vis = (const uint64_t*)params->visibility;
   const bool aux = grad_normal || grad_pos;
-  if (!tch) hipLaunchKernelGGL(k_render_bwd, grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth);
-  else if (cam_part && grad_image)
-    hipLaunchKernelGGL((k_render_bwd_tch<true, true, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest,
-                       depth, vis, grad_normal, grad_pos, cam_part);
-  else if (cam_part)
-    hipLaunchKernelGGL((k_render_bwd_tch<true, false, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest,
-                       depth, vis, grad_normal, grad_pos, cam_part);
-  else if (!aux && grad_image)
-    hipLaunchKernelGGL((k_render_bwd_tch<false, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
-                       vis, nullptr, nullptr);
-  else if (grad_image)
-    hipLaunchKernelGGL((k_render_bwd_tch<true, true>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
-                       vis, grad_normal, grad_pos);
-  else          // geometry only; a depth-only call runs it too, with both aux pointers NULL
-    hipLaunchKernelGGL((k_render_bwd_tch<true, false>), grid, block, 0, st, F, G, grad_image, grad_depth, nearest, depth,
-                       vis, grad_normal, grad_pos);
+  if (!tch) {
+    hipLaunchKernelGGL(k_render_bwd, pg.grid, pg.block, 0, st, F, G, grad_image, grad_depth, nearest, depth);
+  } else {
+    // <kAux, kImage, kCam>: the camera variants carry the aux gradients; without an image gradient the geometry-only
+    // kernel runs (a depth-only call too, with both aux pointers NULL)
+    const auto kernel = cam_part      ? (grad_image ? k_render_bwd_tch<true, true, true> : k_render_bwd_tch<true, false, true>)
+                        : !grad_image ? k_render_bwd_tch<true, false>
+                        : aux         ? k_render_bwd_tch<true, true>
+                                      : k_render_bwd_tch<false, true>;
+    hipLaunchKernelGGL(kernel, pg.grid, pg.block, 0, st, F, G, grad_image, grad_depth, nearest, depth, vis, grad_normal,
+                       grad_pos, cam_part);
+  }
   if (params->ev_stop) (void)hipEventRecord((hipEvent_t)params->ev_stop, st);
   if (cam_part) {
     CamFinish P;
     for (int k = 0; k < 3; ++k) { P.eye[k] = camera->eye[k]; P.at[k] = camera->at[k]; P.up[k] = camera->up[k]; }
     P.focal = F.focal;
     P.ortho = F.ortho;
-    P.ngroups = (int32_t)(grid.x * grid.y);
+    P.ngroups = (int32_t)camera_groups(F.W, F.row1 - F.row0);
     P.g_eye = camera_grads->eye; P.g_at = camera_grads->at; P.g_up = camera_grads->up;
     hipLaunchKernelGGL(k_camera_finish, dim3(1), dim3(1024), 0, st, P, cam_part);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SRH_OK : hip_fail(e, "backward launch");
+  return launch_status("backward launch");
 }
 
 int srh_render_bwd(const SrhCamera* camera, const SrhObjects* objects, const SrhLights* lights,
@@ -1492,5 +958,70 @@ int srh_event_elapsed_ms(void* start, void* stop, float* ms) {
   e = hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop);
   return e == hipSuccess ? SRH_OK : hip_fail(e, "hipEventElapsedTime");
 }
+
+
+// ---- the splat renderer ----------------------------------------------------------------------------------------
+size_t srh_splat_workspace_bytes(const SrhSplatParams* params, const SrhSplatInputs* inputs) {
+  SrhLights L;
+  SrhMaterials M;
+  memset(&L, 0, sizeof(L));
+  memset(&M, 0, sizeof(M));
+  SrhSplatParams p;
+  if (!params) { fail(SRH_E_NULL, "params is NULL"); return 0; }
+  p = *params;
+  p.shade = 0;                                           // the size does not depend on the lights
+  SplatDev S;
+  if (splat_setup(&p, inputs, &L, &M, &S)) return 0;
+  return splat_ws_bytes(S);
+}
+
+int srh_splat_fwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, float* image, float* depth, float* pos, float* normal, void* stream) {
+  SplatDev S;
+  int rc = splat_setup(params, inputs, lights, materials, &S);
+  if (rc) return rc;
+  if (!depth || !pos || !normal || (S.shade && !image)) return fail(SRH_E_NULL, "an output buffer is NULL");
+  const dim3 grid((S.N + 255) / 256, S.B);
+  hipLaunchKernelGGL(k_splat_fwd, grid, dim3(256), 0, (hipStream_t)stream, S, image, depth, pos, normal);
+  return launch_status("k_splat_fwd launch");
+}
+
+int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
+                  const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
+                  const SrhSplatGrads* grads, void* stream) {
+  SplatDev S;
+  int rc = splat_setup(params, inputs, lights, materials, &S);
+  if (rc) return rc;
+  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
+  if (!grad_image && !grad_depth && !grad_pos && !grad_normal)
+    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_pos and grad_normal are all NULL");
+  if (!S.shade && (grad_image || grads->light_vis || grads->lights_pos || grads->colors || grads->attenuation ||
+                   grads->ambient || grads->albedo || grads->coeffs))
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
+  if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
+  if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
+  const size_t need = splat_ws_bytes(S);
+  const bool gather = S.estimate && grads->pos;
+  if (gather && (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double))))
+    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
+                workspace);
+  SplatGradsDev G;
+  G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
+  G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
+  G.coeffs = grads->coeffs;
+  if (S.estimate && !gather) {
+    G.pos = nullptr;
+    if (!G.vis && !G.lpos && !G.colors && !G.latt && !G.amb && !G.albedo && !G.coeffs) return SRH_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((S.N + 255) / 256, S.B);
+  // without z gradients the stencil slots are not wanted: k_splat_bwd then needs no workspace
+  double* ws = gather ? (double*)workspace : nullptr;
+  hipLaunchKernelGGL(k_splat_bwd, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws);
+  if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
+  return launch_status("splat backward launch");
+}
+
 
 }  // extern "C"

@@ -437,25 +437,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
 
   // the pixel's ray: from the eye (perspective), or from its own origin eye + q0 on the image plane with the one
   // direction -z of the camera basis (orthographic, torch/utils.py:461-468); org is what the reference calls ray_orig
-  double d[3] = {0, 0, -1}, q0[3] = {0, 0, 0};
-  if (F.ortho) {
-    const int pc = live ? c : 0, pr = live ? r : F.row0;
-    const double xs = (F.W > 1 && pc == F.W - 1) ? 1.0 : (pc * F.step_x + -1.0);
-    const double ys = (F.H > 1 && pr == F.H - 1) ? -1.0 : (pr * F.step_y + 1.0);
-    const double X = xs * F.half_w, Y = ys * F.half_h;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { q0[i] = F.bx[i] * X + F.by[i] * Y; d[i] = -F.bz[i]; }
-  } else {
-    pixel_ray(F, live ? c : 0, live ? r : F.row0, d);
-  }
-  const double org[3] = {F.o[0] + q0[0], F.o[1] + q0[1], F.o[2] + q0[2]};
+  const int pc = live ? c : 0, pr = live ? r : F.row0;
+  double d[3], q0[3], org[3];
+  const double* R = rec_base + (size_t)li * kRec64Stride[type];
+  const double t = primary_hit(F, pc, pr, type, R, d, q0, org, hit);
 
   // ---- forward quantities of this pixel ---------------------------------------------------------------------
-  double t = 0.0, n[3] = {0, 0, 0}, p[3] = {0, 0, 0};
+  double n[3] = {0, 0, 0}, p[3] = {0, 0, 0};
   double sph_inv = 0.0;                                    // sphere: 1 / sqrt(|p - c|^2 + 3e-10)
-  const double* R = rec_base + (size_t)li * kRec64Stride[type];
   if (hit) {
-    t = F.ortho ? hit_any64_from(type, R, F.o, q0, d) : hit_any64(type, R, F.o, d, true);
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = org[k] + t * d[k];
     if (type == SRH_PRIM_SPHERE) {
@@ -751,10 +741,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
     // d/d bz.  Perspective: d = v / |v| with v = bx X + by Y - bz f and |v| = sqrt(X^2 + Y^2 + f^2) (orthonormal basis),
     // g_v = (g_d - d (d . g_d)) / |v|; the sums are g_org, X g_v, Y g_v, g_v.  Orthographic: origin = eye + bx X + by Y,
     // d = -bz; the sums are g_org, X g_org, Y g_org, g_d.
-    const int pc = live ? c : 0, pr = live ? r : F.row0;
-    const double xs = (F.W > 1 && pc == F.W - 1) ? 1.0 : (pc * F.step_x + -1.0);
-    const double ys = (F.H > 1 && pr == F.H - 1) ? -1.0 : (pr * F.step_y + 1.0);
-    const double X = xs * F.half_w, Y = ys * F.half_h;
+    double X, Y;
+    pixel_plane_xy(F, pc, pr, X, Y);
     double cs[kCamSums];
     if (F.ortho) {
 #pragma unroll

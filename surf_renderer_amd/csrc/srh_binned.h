@@ -1,6 +1,6 @@
 // BINNED mode kernels (gfx950): screen-space tile binning + one WAVE per 16x16-pixel tile.
 //
-//   k_prep (srh.hip)   builds a primitive's records, finds its box of tiles (or appends it to its batch's `large`
+//   k_prep (srh_prep.h) builds a primitive's records, finds its box of tiles (or appends it to its batch's `large`
 //                      list) and PLACES it: for every tile of the box the reject shape really reaches, an atomicAdd on
 //                      the bin's counter claims a slot of the bin's fixed-capacity list and the index goes there
 //                      (bin_place).  One pass over the primitives, no count / scan / fill.  A bin that is full sends

@@ -100,13 +100,22 @@ __device__ __forceinline__ double dot3(const double* a, const double* b) {
   return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
 }
 
+// Image-plane coordinates of pixel (column c, row r) of the full W x H grid: np.linspace(-1, 1, W)[c] and
+// np.linspace(1, -1, H)[r] -- start + i*step, last sample forced to stop -- times half the plane's width / height.
+// The one copy of the reference's end-point rule (srh_binned.h has a wave-uniform variant that needs no last-column test).
+__device__ __forceinline__ void pixel_plane_xy(const FrameDev& F, int c, int r, double& X, double& Y) {
+  const double xs = (F.W > 1 && c == F.W - 1) ? 1.0 : (c * F.step_x + -1.0);
+  const double ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
+  X = xs * F.half_w;
+  Y = ys * F.half_h;
+}
+
 // numpy/renderer.py:145-169 for pixel (column c, row r) of the full W x H grid.
 // Returns |D|, the length of the un-normalised direction.
 __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, double d[3]) {
-  // np.linspace(-1, 1, W)[c], np.linspace(1, -1, H)[r]: start + i*step, last sample forced to stop
-  const double xs = (F.W > 1 && c == F.W - 1) ? 1.0 : (c * F.step_x + -1.0);
-  const double ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
-  const double X = xs * F.half_w, Y = ys * F.half_h, Z = -F.focal;
+  double X, Y;
+  pixel_plane_xy(F, c, r, X, Y);
+  const double Z = -F.focal;
   double v[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
@@ -138,9 +147,9 @@ __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, dou
 // |D|^2 of the un-normalised direction of pixel (c, r): the part of pixel_ray the fp32 sweep needs (its 1 / |D| comes
 // from one v_rsq_f32 of this, no fp64 square root or division)
 __device__ __forceinline__ double pixel_len2(const FrameDev& F, int c, int r) {
-  const double xs = (F.W > 1 && c == F.W - 1) ? 1.0 : (c * F.step_x + -1.0);
-  const double ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
-  const double X = xs * F.half_w, Y = ys * F.half_h, Z = -F.focal;
+  double X, Y;
+  pixel_plane_xy(F, c, r, X, Y);
+  const double Z = -F.focal;
   double v[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
@@ -251,6 +260,35 @@ __device__ __forceinline__ double hit_any64_from(int type, const double* R, cons
     inside = inside && (((cx * R[0] + cy * R[1]) + cz * R[2]) >= 0.0);
   }
   return inside ? t : __builtin_inf();
+}
+
+// Orthographic ray of pixel (c, r) (torch/utils.py:461-468): it starts at eye + q0 on the image plane and every ray has
+// the direction -z of the camera basis.
+__device__ __forceinline__ void ortho_ray(const FrameDev& F, int c, int r, double q0[3], double d[3]) {
+  double X, Y;
+  pixel_plane_xy(F, c, r, X, Y);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    q0[i] = F.bx[i] * X + F.by[i] * Y;
+    d[i] = -F.bz[i];
+  }
+}
+
+// The primary ray of pixel (c, r) under the torch backend and its hit with the primitive of record R, exactly as the
+// forward pass computed them: direction d, origin org = eye + q0 (q0 = 0 for a pinhole ray), returns the ray distance.
+// `hit` = false (a pixel that shows no primitive) builds the ray only and returns 0.
+__device__ __forceinline__ double primary_hit(const FrameDev& F, int c, int r, int type, const double* R, double d[3],
+                                              double q0[3], double org[3], bool hit = true) {
+  if (F.ortho) {
+    ortho_ray(F, c, r, q0, d);
+  } else {
+    q0[0] = q0[1] = q0[2] = 0.0;
+    pixel_ray(F, c, r, d);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) org[i] = F.o[i] + q0[i];
+  if (!hit) return 0.0;
+  return F.ortho ? hit_any64_from(type, R, F.o, q0, d) : hit_any64(type, R, F.o, d, true);
 }
 
 // numpy/renderer.py:219-223: a hit is valid iff near <= t <= far; the running minimum only moves on

@@ -1,7 +1,7 @@
 // Shadow pass of the torch backend's `shadow=True` (torch/renderer.py:291-314), accelerated (gfx950).
 //
 // Per hit pixel and light the reference casts a ray from the fragment towards the light, started 0.1 along it, against
-// EVERY primitive (O(pixels x lights x primitives); k_shadow_shade in srh.hip is that all-pairs pass in fp64 and
+// EVERY primitive (O(pixels x lights x primitives); k_shadow_shade below is that all-pairs pass in fp64 and
 // stays as the checker and the fallback).  All shadow rays of one light pass through the light, so seen FROM the
 // light they are the rays of a pinhole camera, and the primitives a ray can meet are those whose image in that camera
 // covers the ray's image point.  That is the problem the primary pass already solves with tile bins:
@@ -205,10 +205,14 @@ __device__ __forceinline__ bool light_image_point(const FrameDev& LF, const doub
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_shadow_shade_binned(FrameDev F, const FrameDev* __restrict__ LFs,
-                                                              float* __restrict__ image, const float* __restrict__ depth,
-                                                              const int32_t* __restrict__ nearest,
-                                                              uint64_t* __restrict__ visibility) {
+// What the two shadow kernels share: per hit pixel the primary ray and its hit, exactly as the forward pass computed
+// them, then per light the shadow ray from the fragment towards the light, started 0.1 along it -- `lit(l, win, dist,
+// dir, q)` says whether light l (at distance dist in direction dir; q = the ray's origin relative to the eye) reaches the
+// pixel's primitive `win` -- then the pixel is shaded again with the visibility bits and the image is overwritten.
+template <class Lit>
+__device__ __forceinline__ void shadow_shade_body(const FrameDev& F, float* __restrict__ image,
+                                                  const float* __restrict__ depth, const int32_t* __restrict__ nearest,
+                                                  uint64_t* __restrict__ visibility, Lit lit) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
   if (c >= F.W || r >= F.row1) return;
@@ -220,26 +224,11 @@ __global__ __launch_bounds__(256) void k_shadow_shade_binned(FrameDev F, const F
     return;
   }
   const int win = nearest[row * F.near_stride + c];
-  const int sw = segment_of(F, win);
-  const SegDev& SW = F.seg[sw];
-  const double* RW = SW.rec64 + (size_t)(win - SW.first) * kRec64Stride[SW.type];
-  // the primary ray and its hit, exactly as the forward pass computed them
-  double d[3], q0[3] = {0, 0, 0}, org[3];
-  double t;
-  if (F.ortho) {
-    const double xs = (F.W > 1 && c == F.W - 1) ? 1.0 : (c * F.step_x + -1.0);
-    const double ys = (F.H > 1 && r == F.H - 1) ? -1.0 : (r * F.step_y + 1.0);
-    const double X = xs * F.half_w, Y = ys * F.half_h;
+  const SegDev& S = F.seg[segment_of(F, win)];
+  double d[3], q0[3], org[3], p[3];
+  const double t = primary_hit(F, c, r, S.type, S.rec64 + (size_t)(win - S.first) * kRec64Stride[S.type], d, q0, org);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) { q0[i] = F.bx[i] * X + F.by[i] * Y; d[i] = -F.bz[i]; }
-    t = hit_any64_from(SW.type, RW, F.o, q0, d);
-  } else {
-    pixel_ray(F, c, r, d);
-    t = hit_any64(SW.type, RW, F.o, d, true);
-  }
-  double p[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { org[i] = F.o[i] + q0[i]; p[i] = org[i] + t * d[i]; }
+  for (int i = 0; i < 3; ++i) p[i] = org[i] + t * d[i];
 
   vis = 0ull;
   for (int l = 0; l < F.nlights; ++l) {
@@ -248,6 +237,48 @@ __global__ __launch_bounds__(256) void k_shadow_shade_binned(FrameDev F, const F
     const double dist = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     const double dir[3] = {v[0] / dist, v[1] / dist, v[2] / dist};
     const double q[3] = {(p[0] + 0.1 * dir[0]) - F.o[0], (p[1] + 0.1 * dir[1]) - F.o[1], (p[2] + 0.1 * dir[2]) - F.o[2]};
+    if (lit(l, win, dist, dir, q)) vis |= 1ull << l;
+  }
+  float rgb[3];
+  shade_pixel_t<true>(F, d, t, win, rgb, nullptr, nullptr, org, vis);
+  float* px = image + row * F.img_stride + 3 * (size_t)c;
+  px[0] = rgb[0]; px[1] = rgb[1]; px[2] = rgb[2];
+  if (visibility) visibility[row * (size_t)F.W + c] = vis;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_shadow_shade: the torch backend's `shadow=True` (torch/renderer.py:291-314) as a second pass over a rendered
+// frame.  Per hit pixel and light the shadow ray against EVERY primitive in fp64 (arbitrary origins and directions: no
+// screen-space structure to exploit, and the reference is all-pairs too); the light counts as visible unless a
+// primitive other than the fragment's own is hit before the light.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_shadow_shade(FrameDev F, float* __restrict__ image,
+                                                       const float* __restrict__ depth,
+                                                       const int32_t* __restrict__ nearest,
+                                                       uint64_t* __restrict__ visibility) {
+  shadow_shade_body(F, image, depth, nearest, visibility,
+                    [&](int l, int win, double dist, const double (&dir)[3], const double (&q)[3]) {
+    double tmin = __builtin_inf();
+    int blocker = -1;
+    for (int sg = 0; sg < F.nseg; ++sg) {
+      const SegDev& B = F.seg[sg];
+      const int stride = kRec64Stride[B.type];
+      for (int i = 0; i < B.count; ++i) {
+        const double ts = hit_any64_from(B.type, B.rec64 + (size_t)i * stride, F.o, q, dir);
+        if (ts > 0.0 && ts < dist && ts < tmin) { tmin = ts; blocker = B.first + i; }   // lowest index wins ties
+      }
+    }
+    return blocker < 0 || blocker == win;
+  });
+}
+
+__global__ __launch_bounds__(256) void k_shadow_shade_binned(FrameDev F, const FrameDev* __restrict__ LFs,
+                                                              float* __restrict__ image, const float* __restrict__ depth,
+                                                              const int32_t* __restrict__ nearest,
+                                                              uint64_t* __restrict__ visibility) {
+  shadow_shade_body(F, image, depth, nearest, visibility,
+                    [&](int l, int win, double dist, const double (&dir)[3], const double (&q)[3]) {
+    const int sw = segment_of(F, win);
     auto hit = [&](int sg, int g) {
       const SegDev& B = F.seg[sg];
       return hit_any64_from(B.type, B.rec64 + (size_t)(g - B.first) * kRec64Stride[B.type], F.o, q, dir);
@@ -320,13 +351,8 @@ __global__ __launch_bounds__(256) void k_shadow_shade_binned(FrameDev F, const F
         }
       }
     }
-    if (!blocked) vis |= 1ull << l;
-  }
-  float rgb[3];
-  shade_pixel_t<true>(F, d, t, win, rgb, nullptr, nullptr, org, vis);
-  float* px = image + row * F.img_stride + 3 * (size_t)c;
-  px[0] = rgb[0]; px[1] = rgb[1]; px[2] = rgb[2];
-  if (visibility) visibility[row * (size_t)F.W + c] = vis;
+    return !blocked;
+  });
 }
 
 }  // namespace srh
