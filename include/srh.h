@@ -11,14 +11,14 @@
  * Conventions
  *   - Every device buffer is allocated and freed by the caller.  The library keeps no device memory
  *     and no state between calls; all work is enqueued on the stream that is passed in and no entry
- *     point synchronises.  One documented exception, srh_render_views: its per-view frame descriptors
- *     go through pinned staging buffers and a ring of four batches in constant memory that the library
+ *     point synchronises.  One documented exception, srh_render_views and srh_render_views_bwd: their per-view
+ *     descriptors go through pinned staging buffers and a ring of four batches in constant memory that the library
  *     owns PER DEVICE (created on first use of a device, kept until the process ends, one mutex per
  *     device; calls on different devices do not share anything).  A call waits on the host only if the
  *     slot it reuses is still in flight, four calls back; it must be made with the stream's device
  *     current, and it cannot be stream-captured (srh_render_fwd can).
  *   - Thread safety: every entry point may be called from any thread; srh_last_error() is per thread.
- *     Concurrent srh_render_views calls on one device serialise on that device's mutex.
+ *     Concurrent srh_render_views / srh_render_views_bwd calls on one device serialise on that device's mutex.
  *   - Arrays use the reference's layouts (docs/scene_description.md, numpy/renderer.py:299-358):
  *     homogeneous 4-vectors, points w = 1, directions / normals w = 0, row-major, float32 on the
  *     device; index arrays are int32.
@@ -285,6 +285,33 @@ size_t srh_workspace_bytes_views(const SrhObjects* objects, int32_t width, int32
 int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
                      const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
                      float* images, float* depths, int32_t* nearests, void* stream);
+
+/* The backward of a batch of views in one call: srh_render_bwd for every view of an srh_render_views batch, with
+ * the view as a grid dimension of ONE backward launch (and of the record launches in front of it).  cameras, objects,
+ * lights, materials and params are exactly what srh_render_views takes, with the same checks (per_view, row0 / row1,
+ * view_row0, the row strides, one viewport size and one projection per call, 1..256 views); params->mode is ignored (a
+ * backward bins nothing, so the forward may have run in any mode or one frame at a time), normal_out / pos_out and the
+ * event hooks are refused.  Orthographic views (SRH_SHADING_TORCH) take the same kernel.
+ *   grad_images, grad_depths   upstream gradients, stacked like the forward's outputs; grad_images is required (a
+ *                              caller with a depth-only loss passes zeros), grad_depths may be NULL
+ *   nearests, depths           the forward's stacked outputs
+ *   params->visibility         SRH_SHADING_TORCH: the stacked (n_views,rows,W) uint64 bits of the views' shadow passes,
+ *                              or NULL
+ *   grads                      HOST array of n_views structs: where view v's gradients are ADDED.  A leaf all views share
+ *                              has the same pointer in every struct (the fp32 atomics then sum over the views); a leaf a
+ *                              view overrides points into that view's own buffer; NULL = not wanted.  The caller
+ *                              zero-fills the buffers, as for srh_render_bwd.
+ * The gradients equal srh_render_bwd per view, shared leaves summed.  No camera gradients and no normal / pos
+ * gradients: those stay single-frame calls.  The workspace holds srh_workspace_bytes_views(...) bytes; only the
+ * header and the views' primitive records are written -- bin counters and lists are not touched, so a workspace whose
+ * counters were clean before the call (SrhParams.counters_clean) is clean after it.  The descriptors go through the
+ * same per-device staging ring as srh_render_views, with the same consequences: the stream's device must be current
+ * and the call cannot be stream-captured.  Added without an ABI version change: no existing struct or signature
+ * changed. */
+int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                         const float* grad_images, const float* grad_depths, const int32_t* nearests,
+                         const float* depths, const SrhGrads* grads, void* stream);
 
 /* The torch backend's `shadow=True` (diffrend/torch/renderer.py:291-314) as a second pass over a frame rendered by
  * srh_render_fwd with the same camera / scene / params (SRH_SHADING_TORCH): per hit pixel and light a shadow ray from

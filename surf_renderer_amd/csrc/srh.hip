@@ -536,7 +536,8 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
 
 // ---- many views of one scene per call ---------------------------------------------------------------------------
 namespace {
-size_t views_header_bytes(int n_views) { return align_up((size_t)n_views * sizeof(FrameDev)); }
+// head of a views workspace: the views' FrameDev array and, for srh_render_views_bwd, their GradsDev array behind it
+size_t views_header_bytes(int n_views) { return align_up((size_t)n_views * (sizeof(FrameDev) + sizeof(GradsDev))); }
 // Frame descriptors of the batches in flight, PER DEVICE: a ring of kViewRing slots, each a pinned host staging area, a
 // range of that device's constant-memory array g_view_frames (read by the render kernel) and an event that says "the
 // batch that used this slot has finished".  The other kernels read the copy at the head of the caller's workspace.
@@ -557,6 +558,131 @@ int device_of(hipStream_t st, int* dev) {
   const hipError_t e = hipGetDevice(dev);
   return e == hipSuccess ? SRH_OK : hip_fail(e, "hipGetDevice");
 }
+
+// What srh_render_views and srh_render_views_bwd check about the stream before they stage descriptors: the device's
+// ring, the device being current, and no capture in progress.
+int views_ring(hipStream_t st, const char* who, const char* instead, ViewRing** ring) {
+  int dev = 0;
+  if (int rc = device_of(st, &dev)) return rc;
+  if (dev < 0 || dev >= kMaxDevices) return fail(SRH_E_RANGE, "device %d: %s supports devices 0..%d", dev, who, kMaxDevices - 1);
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess || cur != dev)
+    return fail(SRH_E_RANGE, "%s: the stream belongs to device %d but device %d is current", who, dev, cur);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return fail(SRH_E_TYPE, "%s cannot be stream-captured (it waits on an event and stages through library-owned pinned "
+                            "memory); capture %s calls instead", who, instead);
+  *ring = &g_rings[dev];
+  return SRH_OK;
+}
+
+// Claim the ring's next slot (ring.mu held): its previous batch must have finished -- a host wait only when kViewRing
+// batches are behind.  A slot stages kMaxViewsPerCall FrameDev and as many GradsDev.
+int claim_slot(ViewRing& ring, unsigned* slot_out) {
+  const unsigned slot = ring.next % kViewRing;
+  if (!ring.stage[slot]) {
+    // staging first, then the event: a slot is usable only when it has both
+    FrameDev* mem = nullptr;
+    const hipError_t em = hipHostMalloc((void**)&mem, (size_t)kMaxViewsPerCall * (sizeof(FrameDev) + sizeof(GradsDev)),
+                                        hipHostMallocDefault);
+    if (em != hipSuccess) return hip_fail(em, "hipHostMalloc(frames)");
+    hipEvent_t ev = nullptr;
+    const hipError_t ee = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (ee != hipSuccess) { (void)hipHostFree(mem); return hip_fail(ee, "hipEventCreate"); }
+    ring.stage[slot] = mem;
+    ring.done[slot] = ev;
+  } else {
+    const hipError_t es = hipEventSynchronize(ring.done[slot]);
+    if (es != hipSuccess) return hip_fail(es, "hipEventSynchronize(slot)");
+  }
+  *slot_out = slot;
+  return SRH_OK;
+}
+
+// The slot is consumed only after its launches: a call that failed validation leaves the ring as it was.
+int release_slot(ViewRing& ring, unsigned slot, hipStream_t st) {
+  const hipError_t er = hipEventRecord(ring.done[slot], st);
+  ring.next++;
+  if (er != hipSuccess) {
+    // without the event nothing says when the staging may be reused: wait here, once, rather than race later
+    (void)hipStreamSynchronize(st);
+    return hip_fail(er, "hipEventRecord(slot)");
+  }
+  return SRH_OK;
+}
+
+// The arguments srh_render_views and srh_render_views_bwd share, and the checks both make of them before any HIP call.
+struct ViewsCall {
+  int32_t n_views;
+  const SrhCamera* cameras;
+  const SrhObjects* objects;
+  const SrhLights* lights;
+  const SrhMaterials* materials;
+  const SrhParams* params;
+  char* ws;
+  size_t workspace_bytes;
+  int W = 0, H = 0;
+  size_t one = 0, head = 0;          // bytes of one view's workspace slice and of the header in front of the slices
+
+  // view v's scene: the shared structs, or element v of the arrays SrhParams.per_view names
+  const SrhObjects* objects_of(int v) const { return (params->per_view & SRH_VIEWS_OBJECTS) ? objects + v : objects; }
+  const SrhLights* lights_of(int v) const { return (params->per_view & SRH_VIEWS_LIGHTS) ? lights + v : lights; }
+  const SrhMaterials* materials_of(int v) const { return (params->per_view & SRH_VIEWS_MATERIALS) ? materials + v : materials; }
+  char* slice(int v) const { return ws + head + (size_t)v * one; }
+
+  // cameras, params and ws are not NULL
+  int check(const char* who) {
+    if (n_views < 1 || n_views > kMaxViewsPerCall)
+      return fail(SRH_E_RANGE, "n_views = %d, expected 1..%d per call", n_views, kMaxViewsPerCall);
+    if (params->normal_out || params->pos_out || params->ev_start || params->ev_stop)
+      return fail(SRH_E_TYPE, "%s: normal / pos outputs and event hooks are per-frame features", who);
+    W = cameras[0].viewport[2] - cameras[0].viewport[0];
+    H = cameras[0].viewport[3] - cameras[0].viewport[1];
+    one = srh_workspace_bytes(objects, W, H);
+    if (!one) return SRH_E_RANGE;               // srh_workspace_bytes left the message
+    if (params->per_view & ~(SRH_VIEWS_OBJECTS | SRH_VIEWS_LIGHTS | SRH_VIEWS_MATERIALS))
+      return fail(SRH_E_TYPE, "unknown per_view mask %d", params->per_view);
+    if (!lights || !materials) return fail(SRH_E_NULL, "lights / materials is NULL");
+    if (params->per_view & SRH_VIEWS_OBJECTS)
+      for (int v = 1; v < n_views; ++v) {     // one workspace layout, one kernel instantiation and one grid for the whole batch
+        if (objects[v].n_segments != objects[0].n_segments)
+          return fail(SRH_E_RANGE, "view %d has %d object batches, view 0 has %d", v, objects[v].n_segments, objects[0].n_segments);
+        for (int s = 0; s < objects[0].n_segments; ++s)
+          if (objects[v].seg[s].type != objects[0].seg[s].type || objects[v].seg[s].count != objects[0].seg[s].count)
+            return fail(SRH_E_RANGE, "view %d, batch %d: type %d x %d, view 0 has type %d x %d", v, s, objects[v].seg[s].type,
+                        objects[v].seg[s].count, objects[0].seg[s].type, objects[0].seg[s].count);
+      }
+    if (params->per_view & SRH_VIEWS_LIGHTS)
+      for (int v = 1; v < n_views; ++v)
+        if (lights[v].n_lights != lights[0].n_lights)
+          return fail(SRH_E_RANGE, "view %d has %d lights, view 0 has %d", v, lights[v].n_lights, lights[0].n_lights);
+    head = views_header_bytes(n_views);
+    if (workspace_bytes < head + (size_t)n_views * one)
+      return fail(SRH_E_RANGE, "workspace holds %zu bytes, %d views need %zu", workspace_bytes, n_views,
+                  head + (size_t)n_views * one);
+    if (cameras[0].ortho && params->shading != SRH_SHADING_TORCH)
+      return fail(SRH_E_CAMERA, "orthographic projection exists only under SRH_SHADING_TORCH");
+    return SRH_OK;
+  }
+
+  // view v's frame: its own rows (same count for every view) of a viewport like view 0's, records in its own workspace
+  // slice, the projection of view 0
+  int build_view(int v, FrameDev* F, WsLayout* L) const {
+    const int w = cameras[v].viewport[2] - cameras[v].viewport[0], h = cameras[v].viewport[3] - cameras[v].viewport[1];
+    if (w != W || h != H) return fail(SRH_E_RANGE, "view %d is %d x %d, view 0 is %d x %d", v, w, h, W, H);
+    SrhParams pv = *params;
+    if (params->view_row0) {
+      pv.row0 = params->view_row0[v];
+      pv.row1 = pv.row0 + (params->row1 - params->row0);
+    }
+    const int rc = setup_frame(&cameras[v], objects_of(v), lights_of(v), materials_of(v), &pv, slice(v), one, F, L);
+    if (rc) return rc;
+    const char* const kind[2] = {"perspective", "orthographic"};
+    if (F->ortho != (cameras[0].ortho ? 1 : 0))
+      return fail(SRH_E_CAMERA, "view %d is %s, view 0 %s: one projection per call", v, kind[F->ortho], kind[!F->ortho]);
+    return SRH_OK;
+  }
+};
 }  // namespace
 
 size_t srh_workspace_bytes_views(const SrhObjects* objects, int32_t width, int32_t height, int32_t n_views) {
@@ -574,68 +700,20 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
                      float* images, float* depths, int32_t* nearests, void* stream) {
   if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
   if (!images || !depths) return fail(SRH_E_NULL, "images / depths is NULL");
-  if (n_views < 1 || n_views > kMaxViewsPerCall)
-    return fail(SRH_E_RANGE, "n_views = %d, expected 1..%d per call", n_views, kMaxViewsPerCall);
   if (params->mode != SRH_MODE_AUTO && params->mode != SRH_MODE_BINNED)
     return fail(SRH_E_TYPE, "srh_render_views renders in the binned mode only");
-  if (params->normal_out || params->pos_out || params->ev_start || params->ev_stop)
-    return fail(SRH_E_TYPE, "srh_render_views: normal / pos outputs and event hooks are per-frame features");
-  const int W = cameras[0].viewport[2] - cameras[0].viewport[0], H = cameras[0].viewport[3] - cameras[0].viewport[1];
-  const size_t one = srh_workspace_bytes(objects, W, H);
-  if (!one) return SRH_E_RANGE;               // srh_workspace_bytes left the message
-  if (params->per_view & ~(SRH_VIEWS_OBJECTS | SRH_VIEWS_LIGHTS | SRH_VIEWS_MATERIALS))
-    return fail(SRH_E_TYPE, "unknown per_view mask %d", params->per_view);
-  if (!lights || !materials) return fail(SRH_E_NULL, "lights / materials is NULL");
-  // view v's scene: the shared structs, or element v of the arrays SrhParams.per_view names
-  auto objects_of = [&](int v) { return (params->per_view & SRH_VIEWS_OBJECTS) ? objects + v : objects; };
-  auto lights_of = [&](int v) { return (params->per_view & SRH_VIEWS_LIGHTS) ? lights + v : lights; };
-  auto materials_of = [&](int v) { return (params->per_view & SRH_VIEWS_MATERIALS) ? materials + v : materials; };
-  if (params->per_view & SRH_VIEWS_OBJECTS)
-    for (int v = 1; v < n_views; ++v) {     // one workspace layout, one kernel instantiation and one grid for the whole batch
-      if (objects[v].n_segments != objects[0].n_segments)
-        return fail(SRH_E_RANGE, "view %d has %d object batches, view 0 has %d", v, objects[v].n_segments, objects[0].n_segments);
-      for (int s = 0; s < objects[0].n_segments; ++s)
-        if (objects[v].seg[s].type != objects[0].seg[s].type || objects[v].seg[s].count != objects[0].seg[s].count)
-          return fail(SRH_E_RANGE, "view %d, batch %d: type %d x %d, view 0 has type %d x %d", v, s, objects[v].seg[s].type,
-                      objects[v].seg[s].count, objects[0].seg[s].type, objects[0].seg[s].count);
-    }
-  if (params->per_view & SRH_VIEWS_LIGHTS)
-    for (int v = 1; v < n_views; ++v)
-      if (lights[v].n_lights != lights[0].n_lights)
-        return fail(SRH_E_RANGE, "view %d has %d lights, view 0 has %d", v, lights[v].n_lights, lights[0].n_lights);
-  const size_t head = views_header_bytes(n_views);
+  ViewsCall call{n_views, cameras, objects, lights, materials, params, (char*)workspace, workspace_bytes};
+  if (int rc = call.check("srh_render_views")) return rc;
   char* ws = (char*)workspace;
-  if (workspace_bytes < head + (size_t)n_views * one)
-    return fail(SRH_E_RANGE, "workspace holds %zu bytes, %d views need %zu", workspace_bytes, n_views,
-                head + (size_t)n_views * one);
   hipStream_t st = (hipStream_t)stream;
-  // view v's frame: its own rows (same count for every view) of a viewport like view 0's, records in its own workspace
-  // slice, the projection of view 0
-  auto build_view = [&](int v, FrameDev* F, WsLayout* L) {
-    const int w = cameras[v].viewport[2] - cameras[v].viewport[0], h = cameras[v].viewport[3] - cameras[v].viewport[1];
-    if (w != W || h != H) return fail(SRH_E_RANGE, "view %d is %d x %d, view 0 is %d x %d", v, w, h, W, H);
-    SrhParams pv = *params;
-    if (params->view_row0) {
-      pv.row0 = params->view_row0[v];
-      pv.row1 = pv.row0 + (params->row1 - params->row0);
-    }
-    const int rc = setup_frame(&cameras[v], objects_of(v), lights_of(v), materials_of(v), &pv, ws + head + (size_t)v * one, one, F, L);
-    if (rc) return rc;
-    const char* const kind[2] = {"perspective", "orthographic"};
-    if (F->ortho != (cameras[0].ortho ? 1 : 0))
-      return fail(SRH_E_CAMERA, "view %d is %s, view 0 %s: one projection per call", v, kind[F->ortho], kind[!F->ortho]);
-    return (int)SRH_OK;
-  };
   if (cameras[0].ortho) {
     // Orthographic views (torch semantics): each view is the all-pairs fp64 frame of k_render_ortho -- its frame
     // constants travel as kernel arguments, so this branch needs no staging, no ring and no lock.
-    if (params->shading != SRH_SHADING_TORCH)
-      return fail(SRH_E_CAMERA, "orthographic projection exists only under SRH_SHADING_TORCH");
     const size_t rows = (size_t)(params->row1 - params->row0);
     for (int v = 0; v < n_views; ++v) {
       FrameDev F;
       WsLayout Lo;
-      if (int rc = build_view(v, &F, &Lo)) return rc;
+      if (int rc = call.build_view(v, &F, &Lo)) return rc;
       for (int s = 0; s < F.nseg; ++s) {
         launch_prep(F, s, st);
       }
@@ -646,39 +724,17 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     }
     return launch_status("ortho views launch");
   }
-  int dev = 0;
-  if (int rc = device_of(st, &dev)) return rc;
-  if (dev < 0 || dev >= kMaxDevices) return fail(SRH_E_RANGE, "device %d: srh_render_views supports devices 0..%d", dev, kMaxDevices - 1);
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess || cur != dev)
-    return fail(SRH_E_RANGE, "srh_render_views: the stream belongs to device %d but device %d is current", dev, cur);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return fail(SRH_E_TYPE, "srh_render_views cannot be stream-captured (it waits on an event and stages through "
-                            "library-owned pinned memory); capture srh_render_fwd calls instead");
-  ViewRing& ring = g_rings[dev];
+  ViewRing* ringp = nullptr;
+  if (int rc = views_ring(st, "srh_render_views", "srh_render_fwd", &ringp)) return rc;
+  ViewRing& ring = *ringp;
   std::lock_guard<std::mutex> lock(ring.mu);
-  // claim the next ring slot; its previous batch must have finished (host wait only when kViewRing batches are behind)
-  const unsigned slot = ring.next % kViewRing;
-  if (!ring.stage[slot]) {
-    // staging first, then the event: a slot is usable only when it has both
-    FrameDev* mem = nullptr;
-    const hipError_t em = hipHostMalloc((void**)&mem, (size_t)kMaxViewsPerCall * sizeof(FrameDev), hipHostMallocDefault);
-    if (em != hipSuccess) return hip_fail(em, "hipHostMalloc(frames)");
-    hipEvent_t ev = nullptr;
-    const hipError_t ee = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (ee != hipSuccess) { (void)hipHostFree(mem); return hip_fail(ee, "hipEventCreate"); }
-    ring.stage[slot] = mem;
-    ring.done[slot] = ev;
-  } else {
-    const hipError_t es = hipEventSynchronize(ring.done[slot]);
-    if (es != hipSuccess) return hip_fail(es, "hipEventSynchronize(slot)");
-  }
+  unsigned slot = 0;
+  if (int rc = claim_slot(ring, &slot)) return rc;
   FrameDev* stage = ring.stage[slot];
   WsLayout L;
   for (int v = 0; v < n_views; ++v) {
-    if (int rc = build_view(v, &stage[v], &L)) return rc;
-    setup_binning(stage[v], L, ws + head + (size_t)v * one);
+    if (int rc = call.build_view(v, &stage[v], &L)) return rc;
+    setup_binning(stage[v], L, call.slice(v));
   }
   const FrameDev* Fs = (const FrameDev*)ws;
   hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * sizeof(FrameDev), hipMemcpyHostToDevice, st);
@@ -697,14 +753,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
   // all views share the GPU, so the batch as a whole decides the launch shape
   launch_binned<BinnedViews>(F0, params->waves_per_tile, (size_t)F0.ntiles * V < (size_t)kSplitTiles, V, st, base, images,
                              depths, nearests);
-  // the slot is consumed only now: a call that failed validation above leaves the ring as it was
-  const hipError_t er = hipEventRecord(ring.done[slot], st);
-  ring.next++;
-  if (er != hipSuccess) {
-    // without the event nothing says when the staging may be reused: wait here, once, rather than race later
-    (void)hipStreamSynchronize(st);
-    return hip_fail(er, "hipEventRecord(slot)");
-  }
+  if (int rc = release_slot(ring, slot, st)) return rc;
   return launch_status("views launch");
 }
 
@@ -805,6 +854,21 @@ static size_t camera_scratch_bytes(int32_t width, int32_t rows) {
   return camera_groups(width, rows) * kCamSums * sizeof(double);
 }
 
+// where a backward adds its gradients, as the kernels take it (the torch shading's extra inputs only under `tch`)
+static GradsDev grads_dev(const SrhGrads& g, bool tch) {
+  GradsDev G;
+  for (int s = 0; s < SRH_MAX_SEGMENTS; ++s) {
+    G.pos[s] = g.pos[s]; G.normal[s] = g.normal[s]; G.radius[s] = g.radius[s]; G.face[s] = g.face[s];
+  }
+  G.lights_pos = g.lights_pos;
+  G.colors = g.colors;
+  G.albedo = g.albedo;
+  G.coeffs = tch ? g.coeffs : nullptr;
+  G.attenuation = tch ? g.attenuation : nullptr;
+  G.ambient = tch ? g.ambient : nullptr;
+  return G;
+}
+
 // srh_render_bwd (grad_normal = grad_pos = NULL), srh_render_bwd_aux and srh_render_bwd_camera (cam_part != NULL: the
 // camera variant of the torch kernel, then k_camera_finish); the callers have checked which upstream gradients may be
 // NULL, and the camera scratch
@@ -821,17 +885,8 @@ static int render_bwd(const SrhCamera* camera, const SrhObjects* objects, const 
     return fail(SRH_E_NULL, "nearest / depth / grads is NULL");
   if (F.ortho && params->shading != SRH_SHADING_TORCH)
     return fail(SRH_E_CAMERA, "orthographic projection exists only under SRH_SHADING_TORCH");
-  GradsDev G;
-  for (int s = 0; s < SRH_MAX_SEGMENTS; ++s) {
-    G.pos[s] = grads->pos[s]; G.normal[s] = grads->normal[s]; G.radius[s] = grads->radius[s]; G.face[s] = grads->face[s];
-  }
-  G.lights_pos = grads->lights_pos;
-  G.colors = grads->colors;
-  G.albedo = grads->albedo;
   const bool tch = params->shading == SRH_SHADING_TORCH;
-  G.coeffs = tch ? grads->coeffs : nullptr;
-  G.attenuation = tch ? grads->attenuation : nullptr;
-  G.ambient = tch ? grads->ambient : nullptr;
+  const GradsDev G = grads_dev(*grads, tch);
   hipStream_t st = (hipStream_t)stream;
   // the workspace may have served other frames since the forward pass: rebuild the fp64 records (no binning)
   for (int s = 0; s < F.nseg; ++s) {
@@ -919,6 +974,53 @@ int srh_render_bwd_camera(const SrhCamera* camera, const SrhObjects* objects, co
                 camera_scratch_size, camera_scratch);
   return render_bwd(camera, objects, lights, materials, params, workspace, workspace_bytes, grad_image, grad_depth,
                     grad_normal, grad_pos, nearest, depth, grads, stream, camera_grads, (double*)camera_scratch);
+}
+
+int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                         const float* grad_images, const float* grad_depths, const int32_t* nearests, const float* depths,
+                         const SrhGrads* grads, void* stream) {
+  if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
+  if (!grad_images || !nearests || !depths || !grads) return fail(SRH_E_NULL, "grad_images / nearests / depths / grads is NULL");
+  ViewsCall call{n_views, cameras, objects, lights, materials, params, (char*)workspace, workspace_bytes};
+  if (int rc = call.check("srh_render_views_bwd")) return rc;
+  const bool tch = params->shading == SRH_SHADING_TORCH;
+  hipStream_t st = (hipStream_t)stream;
+  ViewRing* ringp = nullptr;
+  if (int rc = views_ring(st, "srh_render_views_bwd", "srh_render_bwd", &ringp)) return rc;
+  ViewRing& ring = *ringp;
+  std::lock_guard<std::mutex> lock(ring.mu);
+  unsigned slot = 0;
+  if (int rc = claim_slot(ring, &slot)) return rc;
+  // the views' frames and, straight behind them, their gradient destinations: one copy to the head of the workspace
+  FrameDev* stage = ring.stage[slot];
+  GradsDev* gstage = (GradsDev*)(stage + n_views);
+  SrhParams pv = *params;
+  pv.mode = SRH_MODE_AUTO;                     // a backward bins nothing: whatever the forward ran in is accepted
+  call.params = &pv;
+  WsLayout L;
+  for (int v = 0; v < n_views; ++v) {
+    // records only (no setup_binning): k_prep_views then leaves the bin counters, the lists and F.self alone
+    if (int rc = call.build_view(v, &stage[v], &L)) return rc;
+    gstage[v] = grads_dev(grads[v], tch);
+  }
+  char* ws = (char*)workspace;
+  const hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * (sizeof(FrameDev) + sizeof(GradsDev)),
+                                      hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frames, grads)");
+  const FrameDev* Fs = (const FrameDev*)ws;
+  const GradsDev* Gs = (const GradsDev*)(Fs + n_views);
+  const FrameDev& F0 = stage[0];
+  const unsigned V = (unsigned)n_views;
+  for (int s = 0; s < F0.nseg; ++s)
+    launch_prep_views(F0, Fs, s, V, st);
+  const PixelGrid pg = pixel_grid(F0);
+  const dim3 grid(pg.grid.x, pg.grid.y, V);
+  const uint64_t* vis = tch ? (const uint64_t*)params->visibility : nullptr;
+  hipLaunchKernelGGL(tch ? k_render_bwd_tch_views : k_render_bwd_views, grid, pg.block, 0, st, Fs, Gs, grad_images,
+                     grad_depths, nearests, depths, vis);
+  if (int rc = release_slot(ring, slot, st)) return rc;
+  return launch_status("views backward launch");
 }
 
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,

@@ -132,10 +132,11 @@ __device__ __forceinline__ void scatter_primitive_grads(const GradsDev& G, int k
   if (dstR && v[6] != 0.0f) atomicAdd(dstR, v[6]);
 }
 
-__global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
-                                                     const float* __restrict__ grad_depth,
-                                                     const int32_t* __restrict__ nearest,
-                                                     const float* __restrict__ depth) {
+// The body of k_render_bwd and k_render_bwd_views: one frame F with its gradient destinations G.
+__device__ __forceinline__ void render_bwd_body(const FrameDev& F, const GradsDev& G, const float* grad_image,
+                                                const float* grad_depth,
+                                                const int32_t* nearest,
+                                                const float* depth) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
   const int lane = threadIdx.x;
@@ -161,20 +162,22 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
 #pragma unroll
   for (int i = 1; i < SRH_MAX_SEGMENTS; ++i)
     if (i < F.nseg && win >= F.seg[i].first) s = i;
+  // type, local index and record are selected here; the other per-batch pointers where they are used (seg_ptr), as in
+  // render_bwd_tch_body.  (Eight fields selected in one chain: behind a reference to F hipcc turns the chain into
+  // reads at per-lane addresses inside F, which for a by-value kernel argument means a copy of F.seg in scratch.)
   int type = F.seg[0].type, first = F.seg[0].first;
   const double* rec_base = F.seg[0].rec64;
-  const float* pos_base = F.seg[0].pos;
-  const float* nrm_base = F.seg[0].normal;
-  const float* rad_base = F.seg[0].radius;
-  const float* face_base = F.seg[0].face;
-  const int32_t* mat_base = F.seg[0].mat;
 #pragma unroll
   for (int i = 1; i < SRH_MAX_SEGMENTS; ++i)
-    if (s == i) {
-      type = F.seg[i].type; first = F.seg[i].first; rec_base = F.seg[i].rec64; pos_base = F.seg[i].pos;
-      nrm_base = F.seg[i].normal; rad_base = F.seg[i].radius; face_base = F.seg[i].face; mat_base = F.seg[i].mat;
-    }
+    if (s == i) { type = F.seg[i].type; first = F.seg[i].first; rec_base = F.seg[i].rec64; }
   const int li = win - first;
+  auto seg_ptr = [&](auto field) {
+    auto ptr = field(F.seg[0]);
+#pragma unroll
+    for (int i = 1; i < SRH_MAX_SEGMENTS; ++i)
+      if (s == i) ptr = field(F.seg[i]);
+    return ptr;
+  };
 
   double d[3] = {0, 0, -1};
   pixel_ray(F, live ? c : 0, live ? r : F.row0, d);
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = F.o[k] + t * d[k];
     if (type == SRH_PRIM_SPHERE) {
-      const float* cp = pos_base + 4 * (size_t)li;
+      const float* cp = seg_ptr([](const SegDev& S) { return S.pos; }) + 4 * (size_t)li;
 #pragma unroll
       for (int k = 0; k < 3; ++k) sph_v[k] = p[k] - (double)cp[k];
       const double len2 = (sph_v[0] * sph_v[0] + sph_v[1] * sph_v[1]) + sph_v[2] * sph_v[2];
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
       n[0] = R[0]; n[1] = R[1]; n[2] = R[2];
     }
   }
-  const int m = hit ? clampi(mat_base[li], 0, F.nmat - 1) : 0;
+  const int m = hit ? clampi(seg_ptr([](const SegDev& S) { return S.mat; })[li], 0, F.nmat - 1) : 0;
   double alb[3] = {0, 0, 0};
   if (hit) { alb[0] = F.albedo[3 * m]; alb[1] = F.albedo[3 * m + 1]; alb[2] = F.albedo[3 * m + 2]; }
 
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
         const double g_disc = sgn * g_t * inv2a / (2.0 * root);
         g_b += 2.0 * b * g_disc;
         const double g_cc = -4.0 * a * g_disc;
-        g_r = -2.0 * (double)rad_base[li] * g_cc;
+        g_r = -2.0 * (double)seg_ptr([](const SegDev& S) { return S.radius; })[li] * g_cc;
 #pragma unroll
         for (int k = 0; k < 3; ++k) gA[k] -= 2.0 * R[k] * g_cc + 2.0 * d[k] * g_b;   // oc = o - c
       }
@@ -328,7 +331,8 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
     const double g_t = ((g_p[0] * d[0] + g_p[1] * d[1]) + g_p[2] * d[2]) + g_dep;
     const double den = dot3(R, d);
     const double g_k = g_t / den, g_den = -g_t * t / den;
-    const float* qp = (type == SRH_PRIM_TRIANGLE) ? face_base + 12 * (size_t)li : pos_base + 4 * (size_t)li;
+    const float* qp = (type == SRH_PRIM_TRIANGLE) ? seg_ptr([](const SegDev& S) { return S.face; }) + 12 * (size_t)li
+                                                  : seg_ptr([](const SegDev& S) { return S.pos; }) + 4 * (size_t)li;
     double g_nh[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -336,7 +340,7 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
       g_nh[k] = g_n[k] + g_k * ((double)qp[k] - F.o[k]) + g_den * d[k];
     }
     // n^ = nin/|nin| (4-D norm with w = 0; a zero normal stays zero and gets the gradient divided by 1)
-    const float* np_ = nrm_base + 4 * (size_t)li;
+    const float* np_ = seg_ptr([](const SegDev& S) { return S.normal; }) + 4 * (size_t)li;
     const double nin2 = (((double)np_[0] * np_[0] + (double)np_[1] * np_[1]) + (double)np_[2] * np_[2]) + (double)np_[3] * np_[3];
     const double ninv = (nin2 > 0.0) ? 1.0 / sqrt(nin2) : 1.0;
     const double proj = (nin2 > 0.0) ? (n[0] * g_nh[0] + n[1] * g_nh[1]) + n[2] * g_nh[2] : 0.0;
@@ -344,6 +348,34 @@ __global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, cons
     for (int k = 0; k < 3; ++k) gB[k] = (g_nh[k] - n[k] * proj) * ninv;
   }
   scatter_primitive_grads(G, hit ? win : -1, lane, s, type, li, gA, gB, g_r);
+}
+
+__global__ __launch_bounds__(256) void k_render_bwd(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
+                                                     const float* __restrict__ grad_depth,
+                                                     const int32_t* __restrict__ nearest,
+                                                     const float* __restrict__ depth) {
+  render_bwd_body(F, G, grad_image, grad_depth, nearest, depth);
+}
+
+// A batch of views per launch (srh_render_views_bwd): grid (pixel_grid.x, pixel_grid.y, n_views), view v = blockIdx.z
+// works on Fs[v] and adds into Gs[v]; the stacked per-view arrays are offset as srh_render_views offsets its outputs.
+// Fs and Gs were written by a copy in front of the launch and nothing in the kernel writes them: they are read in
+// their constant-address-space form (as_constant), so a view's descriptors arrive by scalar loads where they are used,
+// as a by-value kernel argument's fields do, and never occupy vector registers.
+__global__ __launch_bounds__(256) void k_render_bwd_views(const FrameDev* __restrict__ Fs, const GradsDev* __restrict__ Gs,
+                                                           const float* __restrict__ grad_images,
+                                                           const float* __restrict__ grad_depths,
+                                                           const int32_t* __restrict__ nearests,
+                                                           const float* __restrict__ depths,
+                                                           const uint64_t* __restrict__ visibility) {
+  const size_t v = blockIdx.z;
+  const FrameDev& F = *(const FrameDev*)(as_constant(Fs) + v);
+  const GradsDev& G = *(const GradsDev*)(as_constant(Gs) + v);
+  const size_t rows = (size_t)(F.row1 - F.row0);
+  (void)visibility;                                       // the numpy backend has no shadow rays
+  render_bwd_body(F, G, grad_images + v * rows * F.img_stride,
+                  grad_depths ? grad_depths + v * rows * F.depth_stride : nullptr,
+                  nearests + v * rows * F.near_stride, depths + v * rows * F.depth_stride);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -378,15 +410,16 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-template <bool kAux, bool kImage, bool kCam = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
-                                                         const float* __restrict__ grad_depth,
-                                                         const int32_t* __restrict__ nearest,
-                                                         const float* __restrict__ depth,
-                                                         const uint64_t* __restrict__ visibility,
-                                                         const float* __restrict__ grad_normal,
-                                                         const float* __restrict__ grad_pos,
-                                                         double* __restrict__ cam_part = nullptr) {
+// The body of k_render_bwd_tch and k_render_bwd_tch_views: one frame F with its gradient destinations G.
+template <bool kAux, bool kImage, bool kCam>
+__device__ __forceinline__ void render_bwd_tch_body(const FrameDev& F, const GradsDev& G, const float* grad_image,
+                                                    const float* grad_depth,
+                                                    const int32_t* nearest,
+                                                    const float* depth,
+                                                    const uint64_t* visibility,
+                                                    const float* grad_normal,
+                                                    const float* grad_pos,
+                                                    double* cam_part) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   const int r = F.row0 + blockIdx.y * 4 + threadIdx.y;
   const int lane = threadIdx.x;
@@ -770,6 +803,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
           (cam_lds[0][lane] + cam_lds[1][lane]) + (cam_lds[2][lane] + cam_lds[3][lane]);
   }
   scatter_primitive_grads(G, hit ? win : -1, lane, s, type, li, gA, gB, g_r);
+}
+
+template <bool kAux, bool kImage, bool kCam = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch(FrameDev F, GradsDev G, const float* __restrict__ grad_image,
+                                                         const float* __restrict__ grad_depth,
+                                                         const int32_t* __restrict__ nearest,
+                                                         const float* __restrict__ depth,
+                                                         const uint64_t* __restrict__ visibility,
+                                                         const float* __restrict__ grad_normal,
+                                                         const float* __restrict__ grad_pos,
+                                                         double* __restrict__ cam_part = nullptr) {
+  render_bwd_tch_body<kAux, kImage, kCam>(F, G, grad_image, grad_depth, nearest, depth, visibility, grad_normal, grad_pos,
+                                          cam_part);
+}
+
+// k_render_bwd_views for the torch backend's semantics: the <false, true> body (image plus optional depth gradient, no
+// aux outputs, no camera) with the view as grid dimension z.  `visibility` is the stacked (n_views, rows, W) bit field
+// of the views' shadow passes, or NULL.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch_views(
+    const FrameDev* __restrict__ Fs, const GradsDev* __restrict__ Gs, const float* __restrict__ grad_images,
+    const float* __restrict__ grad_depths, const int32_t* __restrict__ nearests, const float* __restrict__ depths,
+    const uint64_t* __restrict__ visibility) {
+  const size_t v = blockIdx.z;
+  const FrameDev& F = *(const FrameDev*)(as_constant(Fs) + v);
+  const GradsDev& G = *(const GradsDev*)(as_constant(Gs) + v);
+  const size_t rows = (size_t)(F.row1 - F.row0);
+  render_bwd_tch_body<false, true, false>(F, G, grad_images + v * rows * F.img_stride,
+                                          grad_depths ? grad_depths + v * rows * F.depth_stride : nullptr,
+                                          nearests + v * rows * F.near_stride, depths + v * rows * F.depth_stride,
+                                          visibility ? visibility + v * rows * (size_t)F.W : nullptr, nullptr, nullptr,
+                                          nullptr);
 }
 
 // The frame's camera gradients from the workgroups' partial sums (one workgroup).  Thread (j, k) adds sum k of workgroups

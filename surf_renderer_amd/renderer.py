@@ -731,6 +731,7 @@ class ViewScenes:
     def __init__(self, buf: SceneBuffers, overrides: Sequence[Dict[str, Any]]):
         n = len(overrides)
         self.n, self.mask, self.keep = n, 0, []
+        self.keys: List[Dict[str, torch.Tensor]] = [{} for _ in range(n)]      # per view: leaf key -> the tensor it reads
         self.objects = (_lib.SrhObjects * n)(*[_lib.SrhObjects.from_buffer_copy(buf.objects) for _ in range(n)])
         self.lights = (_lib.SrhLights * n)(*[_lib.SrhLights.from_buffer_copy(buf.lights) for _ in range(n)])
         self.materials = (_lib.SrhMaterials * n)(*[_lib.SrhMaterials.from_buffer_copy(buf.materials) for _ in range(n)])
@@ -746,6 +747,7 @@ class ViewScenes:
                 if tuple(t.shape) != tuple(base.shape):
                     raise ValueError(f"view {v}: {key} has shape {tuple(t.shape)}, the scene's leaf {tuple(base.shape)}")
                 self.keep.append(t)
+                self.keys[v][key] = t
                 leaf = _SCENE_LEAVES.get(key)
                 if leaf is not None:
                     setattr(getattr(self, leaf.struct)[v], leaf.path[-1], t.data_ptr())
@@ -820,46 +822,76 @@ def render_views_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], imag
     return workspace
 
 
-def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], device="cuda", mode: str = "auto",
-                 streams: int = 4, want_nearest: bool = True, batch: int = 256,
-                 overrides: Optional[Sequence[Dict[str, Any]]] = None, **shading_kw) -> Dict[str, torch.Tensor]:
-    """Many views per call: the batch axis of the reference's real callers (one ``render()`` per view in a
-    Python loop, diffrend/torch/GAN/gan.py:325-378, torch/batch_render.py:36-53).  The scene is uploaded once;
-    ``overrides[v]`` replaces leaves of it for view v (``{"disk.pos": ..., "disk.normal": ..., "lights.pos": ...}``: what
-    the GAN's loop assigns per batch element -- see ``ViewScenes``), so a batch may hold a different splat set and light
-    per view.  In the default binned mode the views go to the library ``batch`` at a time (``srh_render_views``): every
-    kernel of the frame pipeline is launched once per batch with the view as a grid dimension, so small views neither
-    pay three launches each nor leave the GPU idle.  Other modes, or ``batch=0``, issue one call per view round-robin
-    over ``streams`` HIP streams.  All cameras must share one viewport size.  ``shadow=True`` (with ``shading='torch'``)
-    runs the shadow-ray pass on every view after its batch (torch/batch_render.py:59,104-106 renders that way by
-    default); ``visibility`` (B,H,W) int64 is then returned too.  Returns stacked tensors ``image`` (B,H,W,3), ``depth``
-    (B,H,W) and ``nearest`` (B,H,W) int32; ``shading`` / ``double_sided`` / ``use_quartic`` as in ``render``.
-    Forward only."""
-    unknown = set(shading_kw) - {"shading", "double_sided", "use_quartic", "waves_per_tile", "shadow"}
-    if unknown:
-        raise TypeError(f"render_views() got unexpected keyword arguments {sorted(unknown)}")
-    shadow = bool(shading_kw.pop("shadow", False))
-    if shadow and shading_kw.get("shading", "numpy") != "torch":
-        raise ValueError("shadow rays exist only in the torch backend's semantics: shading='torch'")
-    device = torch.device(device)
-    buf = flatten_scene(scene, device)
-    cams = [camera_struct(c, shading_kw.get("shading", "numpy")) for c in cameras]
-    if not cams:
-        raise ValueError("no cameras")
+def render_views_bwd_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], g_images: torch.Tensor,
+                             g_depths: Optional[torch.Tensor], nearests: torch.Tensor, depths: torch.Tensor, grads,
+                             workspace: Optional[torch.Tensor] = None, scenes: Optional[ViewScenes] = None,
+                             first_view: int = 0, visibility: Optional[torch.Tensor] = None,
+                             **shading_kw) -> torch.Tensor:
+    """Low-level form of the backward of ``render_views`` (srh_render_views_bwd): the views of ``cams`` in one call, from
+    stacked contiguous upstream gradients ``g_images`` (n,H,W,3) and ``g_depths`` (n,H,W) or None, the forward's stacked
+    ``nearests`` / ``depths`` and, for a ``shadow=True`` forward, its stacked ``visibility``.  ``grads`` is a ctypes
+    array of n ``_lib.SrhGrads``: where each view's gradients are ADDED (the same pointer in every struct for a leaf the
+    views share; zero-filled by the caller).  ``scenes`` / ``first_view`` as in ``render_views_buffers``.  The bin
+    counters of ``workspace`` are not touched: what is noted about them stays true.  Returns the workspace."""
+    lib = _lib.load()
     width, height = frame_size(cams[0])
-    if any(frame_size(c) != (width, height) for c in cams):
-        raise ValueError("all cameras of a batch must have the same viewport size")
     n = len(cams)
-    if overrides is not None and len(overrides) != n:
-        raise ValueError(f"{len(overrides)} overrides for {n} cameras")
-    want_nearest = want_nearest or shadow                   # the shadow pass starts from the winners
+    shade = _Shade(shading_kw.get("shading", "numpy"), shading_kw.get("double_sided", False),
+                   shading_kw.get("use_quartic", False))
+    params = _params(buf, (0, height), "auto", shade, visibility=visibility.data_ptr() if visibility is not None else None)
+    nbytes = lib.srh_workspace_bytes_views(C.byref(buf.objects), width, height, n)
+    if nbytes == 0:
+        raise _lib.SrhError(-2, lib.srh_last_error().decode())
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=buf.device)
+    state = _ws_state(workspace)
+    if state is not None and state[1] != _layout_key(buf, width, height, ("views", n)):
+        _ws_note(workspace, None)                           # another batch size's layout: its counters may lie under records
+    arr = (_lib.SrhCamera * n)(*cams)
+    ob, ls, ms = C.byref(buf.objects), C.byref(buf.lights), C.byref(buf.materials)
+    if scenes is not None:
+        if first_view < 0 or first_view + n > scenes.n:
+            raise ValueError(f"{scenes.n} per-view scenes for {n} cameras from view {first_view}")
+        params.per_view = scenes.mask
+        if scenes.mask & _lib.VIEWS_OBJECTS:
+            ob = C.byref(scenes.objects[first_view])
+        if scenes.mask & _lib.VIEWS_LIGHTS:
+            ls = C.byref(scenes.lights[first_view])
+        if scenes.mask & _lib.VIEWS_MATERIALS:
+            ms = C.byref(scenes.materials[first_view])
+    with torch.cuda.device(buf.device):
+        _lib.check(lib.srh_render_views_bwd(n, arr, ob, ls, ms, C.byref(params), workspace.data_ptr(), workspace.numel(),
+                                            g_images.data_ptr(), g_depths.data_ptr() if g_depths is not None else None,
+                                            nearests.data_ptr(), depths.data_ptr(), grads, _stream_ptr(buf.device)))
+    return workspace
+
+
+class _ViewsCall(NamedTuple):
+    """What one ``render_views`` call renders: the resident scene, the camera structs, the per-view scenes (or None) and
+    the call's options."""
+    buf: SceneBuffers
+    cams: List[_lib.SrhCamera]
+    every: Optional[ViewScenes]
+    mode: str
+    streams: int
+    want_nearest: bool
+    batch: int
+    shadow: bool
+    shading_kw: Dict[str, Any]
+
+
+def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[torch.Tensor]]:
+    """The forward of ``render_views``: the result dict and the workspace of the batched path (None round-robin)."""
+    buf, cams, every, mode, shading_kw = call.buf, call.cams, call.every, call.mode, call.shading_kw
+    device, want_nearest, shadow = buf.device, call.want_nearest, call.shadow
+    width, height = frame_size(cams[0])
+    n = len(cams)
     image = torch.empty((n, height, width, 3), dtype=torch.float32, device=device)
     depth = torch.empty((n, height, width), dtype=torch.float32, device=device)
     nearest = torch.empty((n, height, width), dtype=torch.int32, device=device) if want_nearest else None
     out = {"image": image, "depth": depth}
     if want_nearest:
         out["nearest"] = nearest
-    every = ViewScenes(buf, overrides) if overrides is not None else None
 
     def scene_of(v: int) -> SceneBuffers:
         return every.view(buf, v) if every is not None else buf
@@ -875,8 +907,8 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
                                                double_sided=bool(shading_kw.get("double_sided", False)),
                                                use_quartic=bool(shading_kw.get("use_quartic", False)))
 
-    if mode in ("auto", "binned") and int(batch) > 0:
-        step = max(1, min(int(batch), n))
+    if mode in ("auto", "binned") and int(call.batch) > 0:
+        step = max(1, min(int(call.batch), n))
         workspace = None                                    # sized by the first (largest) batch, reused by the others
         for i in range(0, n, step):
             m = min(step, n - i)
@@ -884,8 +916,8 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
                                              nearest[i:i + m] if want_nearest else None, workspace=workspace,
                                              scenes=every, mode=mode, first_view=i, **shading_kw)
             shadows(i, m)
-        return out
-    n_streams = max(1, min(int(streams), n))
+        return out, workspace
+    n_streams = max(1, min(int(call.streams), n))
     pool = [torch.cuda.Stream(device) for _ in range(n_streams)]
     scratch = [buf.new_workspace(width, height) for _ in range(n_streams)]
     current = torch.cuda.current_stream(device)
@@ -902,6 +934,144 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
         if t is not None:
             t.record_stream(current)
     shadows(0, n)
+    return out, None
+
+
+class _RenderViewsFunction(torch.autograd.Function):
+    """``render_views`` with the batched analytic backward of libsrh (srh_render_views_bwd): one library call, and one
+    backward launch, per chunk of views.  ``inputs`` are the scene's shared leaves (``_float_keys``) followed by the
+    override tensors named by ``slots`` = ((view, key), ...).  Gradient semantics are ``_RenderFunction``'s per view; a
+    shared leaf gets the sum over the views that read it, an override tensor the gradient of its own view."""
+
+    @staticmethod
+    def forward(ctx, call: _ViewsCall, slots, *inputs):
+        out, workspace = _views_forward(call)
+        ctx.call, ctx.slots, ctx.workspace = call, tuple(slots), workspace
+        ctx.like = [(t.shape, t.dtype, t.device) for t in inputs[len(inputs) - len(ctx.slots):]]
+        vis = out.get("visibility")
+        ctx.save_for_backward(out["depth"], out["nearest"], vis)
+        ctx.mark_non_differentiable(out["nearest"])
+        if vis is None:
+            return out["image"], out["depth"], out["nearest"]
+        ctx.mark_non_differentiable(vis)
+        return out["image"], out["depth"], out["nearest"], vis
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, _g_nearest, _g_vis=None):
+        depth, nearest, vis = ctx.saved_tensors
+        call, slots = ctx.call, ctx.slots
+        buf, cams, every = call.buf, call.cams, call.every
+        shading = call.shading_kw.get("shading", "numpy")
+        keys = _float_keys(buf, shading)
+        need = ctx.needs_input_grad[2:]
+        n = len(cams)
+        g_image = g_image.to(torch.float32).contiguous() if g_image is not None else torch.zeros(
+            tuple(depth.shape) + (3,), dtype=torch.float32, device=buf.device)
+        g_depth = g_depth.to(torch.float32).contiguous() if g_depth is not None else None
+        # one buffer per wanted shared leaf; one stacked buffer per overridden key, a row for every view whose override
+        # wants a gradient
+        shared = {k: torch.zeros_like(buf.tensors[k]) for k, want in zip(keys, need) if want}
+        rows: Dict[str, Dict[int, int]] = {}
+        for (v, key), want in zip(slots, need[len(keys):]):
+            if want:
+                rows.setdefault(key, {})[v] = len(rows.get(key, ()))
+        stacked = {k: torch.zeros((len(r),) + tuple(buf.tensors[k].shape), dtype=torch.float32, device=buf.device)
+                   for k, r in rows.items()}
+        sg = (_lib.SrhGrads * n)()
+        for v in range(n):
+            own = every.keys[v] if every is not None else {}
+            for key in keys:
+                if key in own:                              # view v reads its own tensor: the shared leaf gets nothing from it
+                    row = rows.get(key, {}).get(v)
+                    g = stacked[key][row] if row is not None else None
+                else:
+                    g = shared.get(key)
+                if g is None or key == "disk.radius":       # identically zero (numpy/renderer.py:88: the radius only feeds a mask)
+                    continue
+                if key in _SCENE_LEAVES:
+                    setattr(sg[v], _SCENE_LEAVES[key].grad, g.data_ptr())
+                else:
+                    kind, name = key.split(".")
+                    getattr(sg[v], name)[buf.kinds.index(kind)] = g.data_ptr()
+        step = min(int(call.batch) if int(call.batch) > 0 else 256, 256, n)
+        workspace = ctx.workspace
+        kw = {k: call.shading_kw[k] for k in ("shading", "double_sided", "use_quartic") if k in call.shading_kw}
+        for i in range(0, n, step):
+            m = min(step, n - i)
+            chunk = (_lib.SrhGrads * m).from_buffer(sg, i * C.sizeof(_lib.SrhGrads))
+            workspace = render_views_bwd_buffers(buf, cams[i:i + m], g_image[i:i + m],
+                                                 g_depth[i:i + m] if g_depth is not None else None, nearest[i:i + m],
+                                                 depth[i:i + m], chunk, workspace=workspace, scenes=every, first_view=i,
+                                                 visibility=vis[i:i + m] if vis is not None else None, **kw)
+        own_grads = []
+        for (v, key), (shape, dtype, device) in zip(slots, ctx.like):
+            row = rows.get(key, {}).get(v)
+            own_grads.append(None if row is None else stacked[key][row].to(device=device, dtype=dtype).reshape(shape))
+        return (None, None) + tuple(shared.get(k) for k in keys) + tuple(own_grads)
+
+
+def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], device="cuda", mode: str = "auto",
+                 streams: int = 4, want_nearest: bool = True, batch: int = 256,
+                 overrides: Optional[Sequence[Dict[str, Any]]] = None, **shading_kw) -> Dict[str, torch.Tensor]:
+    """Many views per call: the batch axis of the reference's real callers (one ``render()`` per view in a
+    Python loop, diffrend/torch/GAN/gan.py:325-378, torch/batch_render.py:36-53).  The scene is uploaded once;
+    ``overrides[v]`` replaces leaves of it for view v (``{"disk.pos": ..., "disk.normal": ..., "lights.pos": ...}``: what
+    the GAN's loop assigns per batch element -- see ``ViewScenes``), so a batch may hold a different splat set and light
+    per view.  In the default binned mode the views go to the library ``batch`` at a time (``srh_render_views``): every
+    kernel of the frame pipeline is launched once per batch with the view as a grid dimension, so small views neither
+    pay three launches each nor leave the GPU idle.  Other modes, or ``batch=0``, issue one call per view round-robin
+    over ``streams`` HIP streams.  All cameras must share one viewport size.  ``shadow=True`` (with ``shading='torch'``)
+    runs the shadow-ray pass on every view after its batch (torch/batch_render.py:59,104-106 renders that way by
+    default); ``visibility`` (B,H,W) int64 is then returned too.  Returns stacked tensors ``image`` (B,H,W,3), ``depth``
+    (B,H,W) and ``nearest`` (B,H,W) int32; ``shading`` / ``double_sided`` / ``use_quartic`` as in ``render``.
+
+    Differentiable: with grad enabled, and a float leaf of ``scene`` or a tensor in ``overrides`` that requires grad,
+    ``image`` and ``depth`` carry the analytic HIP backward (``srh_render_views_bwd``: one library call and one backward
+    launch per chunk of ``batch`` views, at most 256, however the forward ran).  Gradient semantics are ``render``'s for
+    every view: a shared leaf of ``scene`` receives the sum over the views that read it, an override tensor -- a leaf or
+    not, e.g. a slice of a generator's output -- the gradient of its own view (zeros, not None, for a view that hits
+    nothing; a tensor given to several views the sum), ``disk.radius`` zeros.  ``nearest`` is then always returned.
+    Otherwise, and under ``torch.no_grad()``, nothing of autograd is touched.  Not covered by a batch: gradients of
+    the cameras (camera tensors are detached; use ``render`` per view), the ``normal`` / ``pos`` outputs, and
+    ``ResidentScene`` / ``capture_step`` -- the call cannot be stream-captured, like its forward."""
+    unknown = set(shading_kw) - {"shading", "double_sided", "use_quartic", "waves_per_tile", "shadow"}
+    if unknown:
+        raise TypeError(f"render_views() got unexpected keyword arguments {sorted(unknown)}")
+    shadow = bool(shading_kw.pop("shadow", False))
+    shading = shading_kw.get("shading", "numpy")
+    if shadow and shading != "torch":
+        raise ValueError("shadow rays exist only in the torch backend's semantics: shading='torch'")
+    device = torch.device(device)
+
+    def wants_grad(x) -> bool:
+        return isinstance(x, torch.Tensor) and x.requires_grad and x.is_floating_point()
+
+    differentiable = torch.is_grad_enabled() and (
+        any(wants_grad(x) for x in _source_leaves(scene).values()) or
+        any(wants_grad(x) for ov in (overrides or ()) for x in (ov or {}).values()))
+    buf = flatten_scene(scene, device, keep_graph=differentiable)
+    cams = [camera_struct(c, shading) for c in cameras]
+    if not cams:
+        raise ValueError("no cameras")
+    width, height = frame_size(cams[0])
+    if any(frame_size(c) != (width, height) for c in cams):
+        raise ValueError("all cameras of a batch must have the same viewport size")
+    n = len(cams)
+    if overrides is not None and len(overrides) != n:
+        raise ValueError(f"{len(overrides)} overrides for {n} cameras")
+    every = ViewScenes(buf, overrides) if overrides is not None else None
+    # the shadow pass and the backward start from the winners
+    call = _ViewsCall(buf, cams, every, mode, streams, want_nearest or shadow or differentiable, batch, shadow, shading_kw)
+    if not differentiable:
+        return _views_forward(call)[0]
+    keys = _float_keys(buf, shading)
+    slots = [(v, key) for v, ov in enumerate(overrides or ()) for key, x in (ov or {}).items()
+             if key in keys and isinstance(x, torch.Tensor) and x.is_floating_point()]
+    res = _RenderViewsFunction.apply(call, tuple(slots), *[buf.tensors[k] for k in keys],
+                                     *[overrides[v][key] for v, key in slots])
+    out = {"image": res[0], "depth": res[1], "nearest": res[2]}
+    if shadow:
+        out["visibility"] = res[3]
     return out
 
 
