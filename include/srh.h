@@ -286,6 +286,19 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
                      const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
                      float* images, float* depths, int32_t* nearests, void* stream);
 
+/* srh_render_views with the torch backend's extra outputs for every view (SRH_SHADING_TORCH): `normals` and `poses` are
+ * caller-owned, stacked and dense, (n_views,rows,W,3) float32 -- view v starts v * rows * W * 3 elements after view 0,
+ * whatever the image row stride -- and are WRITTEN at every pixel of the rows rendered: the hit's unit normal (before
+ * the double_sided flip) and the hit point, 0 where nothing is hit, equal to srh_render_fwd with SrhParams.normal_out /
+ * pos_out per view.  Either may be NULL; with both NULL the call is srh_render_views.  With one of them set,
+ * SRH_SHADING_NUMPY is refused with SRH_E_TYPE (that backend has no such outputs).  params->normal_out / pos_out stay
+ * refused: they name one frame's buffers.  Perspective batches and orthographic ones (one frame per view) alike.
+ * Everything else -- workspace, staging ring, checks -- is srh_render_views'.  Added without an ABI version change: no
+ * existing struct or signature changed. */
+int srh_render_views_aux(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                         float* images, float* depths, int32_t* nearests, float* normals, float* poses, void* stream);
+
 /* The backward of a batch of views in one call: srh_render_bwd for every view of an srh_render_views batch, with
  * the view as a grid dimension of ONE backward launch (and of the record launches in front of it).  cameras, objects,
  * lights, materials and params are exactly what srh_render_views takes, with the same checks (per_view, row0 / row1,
@@ -302,7 +315,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
  *                              view overrides points into that view's own buffer; NULL = not wanted.  The caller
  *                              zero-fills the buffers, as for srh_render_bwd.
  * The gradients equal srh_render_bwd per view, shared leaves summed.  No camera gradients and no normal / pos
- * gradients: those stay single-frame calls.  The workspace holds srh_workspace_bytes_views(...) bytes; only the
+ * gradients here: srh_render_views_bwd_camera below has both.  The workspace holds srh_workspace_bytes_views(...) bytes; only the
  * header and the views' primitive records are written -- bin counters and lists are not touched, so a workspace whose
  * counters were clean before the call (SrhParams.counters_clean) is clean after it.  The descriptors go through the
  * same per-device staging ring as srh_render_views, with the same consequences: the stream's device must be current
@@ -312,6 +325,46 @@ int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObj
                          const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
                          const float* grad_images, const float* grad_depths, const int32_t* nearests,
                          const float* depths, const SrhGrads* grads, void* stream);
+
+/* srh_render_views_bwd with the upstream gradients of the normal / pos outputs and with camera gradients for every view
+ * (SRH_SHADING_TORCH only; SRH_SHADING_NUMPY is refused with SRH_E_TYPE): srh_render_bwd_camera for every view of a
+ * batch, in the record launches, ONE backward launch and, when a view wants a camera gradient, ONE finish launch (one
+ * workgroup per view).  cameras .. workspace_bytes, nearests, depths and params->visibility are srh_render_views_bwd's.
+ *   grad_images, grad_depths   stacked like the forward's outputs (params' row strides)
+ *   grad_normals, grad_poses   stacked dense (n_views,rows,W,3), like srh_render_views_aux's outputs
+ *                              Any of the four may be NULL, but not all.  Without grad_images the geometry-only kernel
+ *                              runs: light, colour and material gradients stay untouched, as in srh_render_bwd_aux.
+ *                              At pixels that hit nothing all four are ignored.
+ *   grads                      HOST array of n_views SrhGrads: ADDED into with fp32 atomics, exactly as in
+ *                              srh_render_views_bwd (shared leaves share pointers; the caller zero-fills)
+ *   camera_grads               HOST array of n_views SrhCameraGrads (device pointers to 4 floats each), or NULL when no
+ *                              view wants any.  OVERWRITTEN, not added to: view v's eye / at / up gradients, w = 0;
+ *                              a NULL member is not wanted, a view with three NULL members is skipped by the finish.
+ *                              A view that hits nothing gets zeros.  When at least one member of one view is set, the
+ *                              whole batch runs the camera variant of the kernel.
+ *   camera_scratch             caller-owned device memory, srh_camera_grad_scratch_bytes_views(W, row1 - row0, n_views)
+ *                              bytes, 8-byte aligned: a 256-byte aligned head that receives the views' finish
+ *                              descriptors (written by a copy on the stream) and one srh_camera_grad_scratch_bytes
+ *                              slice of fp64 workgroup partial sums per view.  Its previous contents do not matter
+ *                              (workgroups without a hit store zeros).  Size and alignment are checked
+ *                              (SRH_E_WORKSPACE, the needed size in the message) only when a camera gradient is wanted;
+ *                              otherwise it is not looked at and may be NULL.  It must stay untouched until the call's
+ *                              work on the stream has finished.
+ * srh_camera_grad_scratch_bytes_views returns 0 and sets srh_last_error for width < 1, rows < 1 or n_views outside
+ * 1..256.  The camera gradients use no atomics and fixed-order fp64 sums (k_camera_finish's, per view): identical from
+ * run to run, and equal to srh_render_bwd_camera per view.  The workspace is srh_workspace_bytes_views(...) bytes and is
+ * written as srh_render_views_bwd writes it (header and records, never the bin counters).  Staging ring, current device
+ * and "cannot be stream-captured" as for srh_render_views_bwd.  Added without an ABI version change: no existing struct
+ * or signature changed. */
+size_t srh_camera_grad_scratch_bytes_views(int32_t width, int32_t rows, int32_t n_views);
+int srh_render_views_bwd_camera(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects,
+                                const SrhLights* lights, const SrhMaterials* materials, const SrhParams* params,
+                                void* workspace, size_t workspace_bytes,
+                                const float* grad_images, const float* grad_depths,
+                                const float* grad_normals, const float* grad_poses,
+                                const int32_t* nearests, const float* depths,
+                                const SrhGrads* grads, const SrhCameraGrads* camera_grads,
+                                void* camera_scratch, size_t camera_scratch_size, void* stream);
 
 /* The torch backend's `shadow=True` (diffrend/torch/renderer.py:291-314) as a second pass over a frame rendered by
  * srh_render_fwd with the same camera / scene / params (SRH_SHADING_TORCH): per hit pixel and light a shadow ray from

@@ -93,7 +93,8 @@ class SrhSplatGrads(C.Structure):
 
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
            "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
-           "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_shadow_shade",
+           "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_render_views_aux",
+           "srh_camera_grad_scratch_bytes_views", "srh_render_views_bwd_camera", "srh_shadow_shade",
            "srh_shadow_workspace_bytes", "srh_bin_counters",
            "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
            "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd")
@@ -169,6 +170,16 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib.srh_render_views_bwd.argtypes = [C.c_int32, C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
                                          C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrhGrads), C.c_void_p]
+    lib.srh_render_views_aux.restype = C.c_int
+    lib.srh_render_views_aux.argtypes = lib.srh_render_views.argtypes[:11] + [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.srh_camera_grad_scratch_bytes_views.restype = C.c_size_t
+    lib.srh_camera_grad_scratch_bytes_views.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.srh_render_views_bwd_camera.restype = C.c_int
+    lib.srh_render_views_bwd_camera.argtypes = [C.c_int32, C.POINTER(SrhCamera), C.POINTER(SrhObjects),
+                                                C.POINTER(SrhLights), C.POINTER(SrhMaterials), C.POINTER(SrhParams),
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(SrhGrads), C.POINTER(SrhCameraGrads),
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
     lib.srh_shadow_workspace_bytes.restype = C.c_size_t
     lib.srh_shadow_workspace_bytes.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32, C.c_int32]
     lib.srh_shadow_shade.restype = C.c_int

@@ -577,14 +577,17 @@ int views_ring(hipStream_t st, const char* who, const char* instead, ViewRing** 
 }
 
 // Claim the ring's next slot (ring.mu held): its previous batch must have finished -- a host wait only when kViewRing
-// batches are behind.  A slot stages kMaxViewsPerCall FrameDev and as many GradsDev.
+// batches are behind.  A slot stages kMaxViewsPerCall FrameDev, behind them as many GradsDev (packed behind the FrameDev
+// of the call's own n_views: one copy takes both), and behind room for kMaxViewsPerCall of each as many CamFinish.
+constexpr size_t kStageFinish = (size_t)kMaxViewsPerCall * (sizeof(FrameDev) + sizeof(GradsDev));
+constexpr size_t kStageBytes = kStageFinish + (size_t)kMaxViewsPerCall * sizeof(CamFinish);
+static_assert(kStageFinish % alignof(CamFinish) == 0, "the CamFinish staging is aligned");
 int claim_slot(ViewRing& ring, unsigned* slot_out) {
   const unsigned slot = ring.next % kViewRing;
   if (!ring.stage[slot]) {
     // staging first, then the event: a slot is usable only when it has both
     FrameDev* mem = nullptr;
-    const hipError_t em = hipHostMalloc((void**)&mem, (size_t)kMaxViewsPerCall * (sizeof(FrameDev) + sizeof(GradsDev)),
-                                        hipHostMallocDefault);
+    const hipError_t em = hipHostMalloc((void**)&mem, kStageBytes, hipHostMallocDefault);
     if (em != hipSuccess) return hip_fail(em, "hipHostMalloc(frames)");
     hipEvent_t ev = nullptr;
     const hipError_t ee = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -695,15 +698,25 @@ size_t srh_workspace_bytes_views(const SrhObjects* objects, int32_t width, int32
   return views_header_bytes(n_views) + (size_t)n_views * one;
 }
 
-int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
-                     const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
-                     float* images, float* depths, int32_t* nearests, void* stream) {
+// srh_render_views (normals = poses = NULL) and srh_render_views_aux: view v's normal / pos outputs are its slice of the
+// stacked dense arrays, set in its frame descriptor as SrhParams.normal_out / pos_out set a single frame's
+static int render_views(const char* who, int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects,
+                        const SrhLights* lights, const SrhMaterials* materials, const SrhParams* params, void* workspace,
+                        size_t workspace_bytes, float* images, float* depths, int32_t* nearests, float* normals,
+                        float* poses, void* stream) {
   if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
   if (!images || !depths) return fail(SRH_E_NULL, "images / depths is NULL");
+  if ((normals || poses) && params->shading != SRH_SHADING_TORCH)
+    return fail(SRH_E_TYPE, "%s: normal / pos outputs exist only under SRH_SHADING_TORCH: normals / poses must be NULL", who);
   if (params->mode != SRH_MODE_AUTO && params->mode != SRH_MODE_BINNED)
-    return fail(SRH_E_TYPE, "srh_render_views renders in the binned mode only");
+    return fail(SRH_E_TYPE, "%s renders in the binned mode only", who);
   ViewsCall call{n_views, cameras, objects, lights, materials, params, (char*)workspace, workspace_bytes};
-  if (int rc = call.check("srh_render_views")) return rc;
+  if (int rc = call.check(who)) return rc;
+  auto set_aux = [&](int v, FrameDev& F) {
+    const size_t off = (size_t)v * (size_t)(F.row1 - F.row0) * (size_t)F.W * 3;
+    F.normal_out = normals ? normals + off : nullptr;
+    F.pos_out = poses ? poses + off : nullptr;
+  };
   char* ws = (char*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (cameras[0].ortho) {
@@ -714,6 +727,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
       FrameDev F;
       WsLayout Lo;
       if (int rc = call.build_view(v, &F, &Lo)) return rc;
+      set_aux(v, F);
       for (int s = 0; s < F.nseg; ++s) {
         launch_prep(F, s, st);
       }
@@ -725,7 +739,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
     return launch_status("ortho views launch");
   }
   ViewRing* ringp = nullptr;
-  if (int rc = views_ring(st, "srh_render_views", "srh_render_fwd", &ringp)) return rc;
+  if (int rc = views_ring(st, who, "srh_render_fwd", &ringp)) return rc;
   ViewRing& ring = *ringp;
   std::lock_guard<std::mutex> lock(ring.mu);
   unsigned slot = 0;
@@ -734,6 +748,7 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
   WsLayout L;
   for (int v = 0; v < n_views; ++v) {
     if (int rc = call.build_view(v, &stage[v], &L)) return rc;
+    set_aux(v, stage[v]);
     setup_binning(stage[v], L, call.slice(v));
   }
   const FrameDev* Fs = (const FrameDev*)ws;
@@ -755,6 +770,20 @@ int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects
                              depths, nearests);
   if (int rc = release_slot(ring, slot, st)) return rc;
   return launch_status("views launch");
+}
+
+int srh_render_views(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                     const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                     float* images, float* depths, int32_t* nearests, void* stream) {
+  return render_views("srh_render_views", n_views, cameras, objects, lights, materials, params, workspace,
+                      workspace_bytes, images, depths, nearests, nullptr, nullptr, stream);
+}
+
+int srh_render_views_aux(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                         float* images, float* depths, int32_t* nearests, float* normals, float* poses, void* stream) {
+  return render_views("srh_render_views_aux", n_views, cameras, objects, lights, materials, params, workspace,
+                      workspace_bytes, images, depths, nearests, normals, poses, stream);
 }
 
 namespace {
@@ -976,18 +1005,33 @@ int srh_render_bwd_camera(const SrhCamera* camera, const SrhObjects* objects, co
                     grad_normal, grad_pos, nearest, depth, grads, stream, camera_grads, (double*)camera_scratch);
 }
 
-int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
-                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
-                         const float* grad_images, const float* grad_depths, const int32_t* nearests, const float* depths,
-                         const SrhGrads* grads, void* stream) {
-  if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
-  if (!grad_images || !nearests || !depths || !grads) return fail(SRH_E_NULL, "grad_images / nearests / depths / grads is NULL");
+// head of a batch's camera scratch: the views' CamFinish array, in front of their slices of partial sums
+static size_t camera_head_bytes(int n_views) { return align_up((size_t)n_views * sizeof(CamFinish)); }
+
+size_t srh_camera_grad_scratch_bytes_views(int32_t width, int32_t rows, int32_t n_views) {
+  if (width < 1 || rows < 1) { fail(SRH_E_RANGE, "camera gradient scratch for %d x %d pixels", width, rows); return 0; }
+  if (n_views < 1 || n_views > kMaxViewsPerCall) {
+    fail(SRH_E_RANGE, "n_views = %d, expected 1..%d per call", n_views, kMaxViewsPerCall);
+    return 0;
+  }
+  return camera_head_bytes(n_views) + (size_t)n_views * camera_scratch_bytes(width, rows);
+}
+
+// srh_render_views_bwd (grad_normals = grad_poses = NULL, no camera) and srh_render_views_bwd_camera (camera_scratch !=
+// NULL: the camera variant of the torch kernel for the whole batch, then k_camera_finish_views); the callers have checked
+// the NULLs, which upstream gradients may be missing, and the camera scratch
+static int render_views_bwd(const char* who, int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects,
+                            const SrhLights* lights, const SrhMaterials* materials, const SrhParams* params,
+                            void* workspace, size_t workspace_bytes, const float* grad_images, const float* grad_depths,
+                            const float* grad_normals, const float* grad_poses, const int32_t* nearests,
+                            const float* depths, const SrhGrads* grads, const SrhCameraGrads* camera_grads,
+                            void* camera_scratch, void* stream) {
   ViewsCall call{n_views, cameras, objects, lights, materials, params, (char*)workspace, workspace_bytes};
-  if (int rc = call.check("srh_render_views_bwd")) return rc;
+  if (int rc = call.check(who)) return rc;
   const bool tch = params->shading == SRH_SHADING_TORCH;
   hipStream_t st = (hipStream_t)stream;
   ViewRing* ringp = nullptr;
-  if (int rc = views_ring(st, "srh_render_views_bwd", "srh_render_bwd", &ringp)) return rc;
+  if (int rc = views_ring(st, who, "srh_render_bwd", &ringp)) return rc;
   ViewRing& ring = *ringp;
   std::lock_guard<std::mutex> lock(ring.mu);
   unsigned slot = 0;
@@ -995,6 +1039,7 @@ int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObj
   // the views' frames and, straight behind them, their gradient destinations: one copy to the head of the workspace
   FrameDev* stage = ring.stage[slot];
   GradsDev* gstage = (GradsDev*)(stage + n_views);
+  CamFinish* cstage = (CamFinish*)((char*)stage + kStageFinish);
   SrhParams pv = *params;
   pv.mode = SRH_MODE_AUTO;                     // a backward bins nothing: whatever the forward ran in is accepted
   call.params = &pv;
@@ -1005,22 +1050,92 @@ int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObj
     gstage[v] = grads_dev(grads[v], tch);
   }
   char* ws = (char*)workspace;
-  const hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * (sizeof(FrameDev) + sizeof(GradsDev)),
-                                      hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * (sizeof(FrameDev) + sizeof(GradsDev)),
+                                hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frames, grads)");
   const FrameDev* Fs = (const FrameDev*)ws;
   const GradsDev* Gs = (const GradsDev*)(Fs + n_views);
   const FrameDev& F0 = stage[0];
   const unsigned V = (unsigned)n_views;
+  const PixelGrid pg = pixel_grid(F0);
+  double* cam_part = nullptr;
+  if (camera_scratch) {
+    // the finish descriptors travel in the head of the camera scratch, the partial sums of view v in slice v behind it
+    for (int v = 0; v < n_views; ++v) {
+      CamFinish& P = cstage[v];
+      for (int k = 0; k < 3; ++k) { P.eye[k] = cameras[v].eye[k]; P.at[k] = cameras[v].at[k]; P.up[k] = cameras[v].up[k]; }
+      P.focal = stage[v].focal;
+      P.ortho = stage[v].ortho;
+      P.ngroups = (int32_t)pg.groups();
+      P.g_eye = camera_grads[v].eye; P.g_at = camera_grads[v].at; P.g_up = camera_grads[v].up;
+    }
+    e = hipMemcpyAsync(camera_scratch, cstage, (size_t)n_views * sizeof(CamFinish), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(camera finish)");
+    cam_part = (double*)((char*)camera_scratch + camera_head_bytes(n_views));
+  }
   for (int s = 0; s < F0.nseg; ++s)
     launch_prep_views(F0, Fs, s, V, st);
-  const PixelGrid pg = pixel_grid(F0);
   const dim3 grid(pg.grid.x, pg.grid.y, V);
-  const uint64_t* vis = tch ? (const uint64_t*)params->visibility : nullptr;
-  hipLaunchKernelGGL(tch ? k_render_bwd_tch_views : k_render_bwd_views, grid, pg.block, 0, st, Fs, Gs, grad_images,
-                     grad_depths, nearests, depths, vis);
+  if (!tch) {
+    hipLaunchKernelGGL(k_render_bwd_views, grid, pg.block, 0, st, Fs, Gs, grad_images, grad_depths, nearests, depths,
+                       (const uint64_t*)nullptr);
+  } else {
+    // <kAux, kImage, kCam>, chosen as render_bwd chooses the single frame's
+    const bool aux = grad_normals || grad_poses;
+    const auto kernel = cam_part      ? (grad_images ? k_render_bwd_tch_views<true, true, true> : k_render_bwd_tch_views<true, false, true>)
+                        : !grad_images ? k_render_bwd_tch_views<true, false, false>
+                        : aux          ? k_render_bwd_tch_views<true, true, false>
+                                       : k_render_bwd_tch_views<false, true, false>;
+    hipLaunchKernelGGL(kernel, grid, pg.block, 0, st, Fs, Gs, grad_images, grad_depths, nearests, depths,
+                       (const uint64_t*)params->visibility, grad_normals, grad_poses, cam_part);
+  }
+  if (cam_part)
+    hipLaunchKernelGGL(k_camera_finish_views, dim3(V), dim3(1024), 0, st, (const CamFinish*)camera_scratch,
+                       (const double*)cam_part);
   if (int rc = release_slot(ring, slot, st)) return rc;
   return launch_status("views backward launch");
+}
+
+int srh_render_views_bwd(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects, const SrhLights* lights,
+                         const SrhMaterials* materials, const SrhParams* params, void* workspace, size_t workspace_bytes,
+                         const float* grad_images, const float* grad_depths, const int32_t* nearests, const float* depths,
+                         const SrhGrads* grads, void* stream) {
+  if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
+  if (!grad_images || !nearests || !depths || !grads) return fail(SRH_E_NULL, "grad_images / nearests / depths / grads is NULL");
+  return render_views_bwd("srh_render_views_bwd", n_views, cameras, objects, lights, materials, params, workspace,
+                          workspace_bytes, grad_images, grad_depths, nullptr, nullptr, nearests, depths, grads, nullptr,
+                          nullptr, stream);
+}
+
+int srh_render_views_bwd_camera(int32_t n_views, const SrhCamera* cameras, const SrhObjects* objects,
+                                const SrhLights* lights, const SrhMaterials* materials, const SrhParams* params,
+                                void* workspace, size_t workspace_bytes, const float* grad_images,
+                                const float* grad_depths, const float* grad_normals, const float* grad_poses,
+                                const int32_t* nearests, const float* depths, const SrhGrads* grads,
+                                const SrhCameraGrads* camera_grads, void* camera_scratch, size_t camera_scratch_size,
+                                void* stream) {
+  if (!cameras || !params || !workspace) return fail(SRH_E_NULL, "cameras / params / workspace is NULL");
+  if (!nearests || !depths || !grads) return fail(SRH_E_NULL, "nearests / depths / grads is NULL");
+  if (!grad_images && !grad_depths && !grad_normals && !grad_poses)
+    return fail(SRH_E_NULL, "grad_images, grad_depths, grad_normals and grad_poses are all NULL");
+  if (n_views < 1 || n_views > kMaxViewsPerCall)
+    return fail(SRH_E_RANGE, "n_views = %d, expected 1..%d per call", n_views, kMaxViewsPerCall);
+  if (params->shading != SRH_SHADING_TORCH)
+    return fail(SRH_E_TYPE, "srh_render_views_bwd_camera: camera, normal and pos gradients exist only under SRH_SHADING_TORCH");
+  bool want = false;
+  for (int v = 0; camera_grads && v < n_views; ++v)
+    want = want || camera_grads[v].eye || camera_grads[v].at || camera_grads[v].up;
+  if (want) {
+    const int32_t width = cameras[0].viewport[2] - cameras[0].viewport[0], rows = params->row1 - params->row0;
+    if (width < 1 || rows < 1) return fail(SRH_E_RANGE, "empty frame %d x %d", width, rows);
+    const size_t need = camera_head_bytes(n_views) + (size_t)n_views * camera_scratch_bytes(width, rows);
+    if (!camera_scratch || camera_scratch_size < need || ((uintptr_t)camera_scratch % sizeof(double)) != 0)
+      return fail(SRH_E_WORKSPACE, "camera scratch: %d views need %zu bytes, 8-byte aligned (got %zu at %p)", n_views,
+                  need, camera_scratch_size, camera_scratch);
+  }
+  return render_views_bwd("srh_render_views_bwd_camera", n_views, cameras, objects, lights, materials, params, workspace,
+                          workspace_bytes, grad_images, grad_depths, grad_normals, grad_poses, nearests, depths, grads,
+                          want ? camera_grads : nullptr, want ? camera_scratch : nullptr, stream);
 }
 
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,

@@ -818,22 +818,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
                                           cam_part);
 }
 
-// k_render_bwd_views for the torch backend's semantics: the <false, true> body (image plus optional depth gradient, no
-// aux outputs, no camera) with the view as grid dimension z.  `visibility` is the stacked (n_views, rows, W) bit field
-// of the views' shadow passes, or NULL.
+// k_render_bwd_views for the torch backend's semantics: the body's variants with the view as grid dimension z.
+// <false, true, false> (image plus optional depth gradient, no aux outputs, no camera) is srh_render_views_bwd's kernel;
+// the kAux variants are srh_render_views_bwd_camera's.  `visibility` is the stacked (n_views, rows, W) bit field of the
+// views' shadow passes, or NULL; `grad_normals` / `grad_poses` are the stacked dense (n_views, rows, W, 3) upstream
+// gradients of the aux outputs, either NULL, offset per view like the image gradient; view v's camera partials start
+// v * groups * kCamSums doubles into `cam_part` (groups = workgroups of one view: gridDim.x * gridDim.y).
+template <bool kAux, bool kImage, bool kCam>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWaves))) void k_render_bwd_tch_views(
     const FrameDev* __restrict__ Fs, const GradsDev* __restrict__ Gs, const float* __restrict__ grad_images,
     const float* __restrict__ grad_depths, const int32_t* __restrict__ nearests, const float* __restrict__ depths,
-    const uint64_t* __restrict__ visibility) {
+    const uint64_t* __restrict__ visibility, const float* __restrict__ grad_normals,
+    const float* __restrict__ grad_poses, double* __restrict__ cam_part) {
   const size_t v = blockIdx.z;
   const FrameDev& F = *(const FrameDev*)(as_constant(Fs) + v);
   const GradsDev& G = *(const GradsDev*)(as_constant(Gs) + v);
   const size_t rows = (size_t)(F.row1 - F.row0);
-  render_bwd_tch_body<false, true, false>(F, G, grad_images + v * rows * F.img_stride,
+  const size_t aux_off = kAux ? v * rows * (size_t)F.W * 3 : 0;
+  render_bwd_tch_body<kAux, kImage, kCam>(F, G, kImage ? grad_images + v * rows * F.img_stride : nullptr,
                                           grad_depths ? grad_depths + v * rows * F.depth_stride : nullptr,
                                           nearests + v * rows * F.near_stride, depths + v * rows * F.depth_stride,
-                                          visibility ? visibility + v * rows * (size_t)F.W : nullptr, nullptr, nullptr,
-                                          nullptr);
+                                          visibility ? visibility + v * rows * (size_t)F.W : nullptr,
+                                          (kAux && grad_normals) ? grad_normals + aux_off : nullptr,
+                                          (kAux && grad_poses) ? grad_poses + aux_off : nullptr,
+                                          kCam ? cam_part + v * ((size_t)gridDim.x * gridDim.y) * kCamSums : nullptr);
 }
 
 // The frame's camera gradients from the workgroups' partial sums (one workgroup).  Thread (j, k) adds sum k of workgroups
@@ -864,7 +872,11 @@ __device__ __forceinline__ void unit_bwd(const double u[3], double len, const do
   for (int k = 0; k < 3; ++k) g_v[k] = (g_u[k] - u[k] * pr) / len;
 }
 
-__global__ __launch_bounds__(1024) void k_camera_finish(CamFinish P, const double* __restrict__ cam_part) {
+// The body of k_camera_finish and k_camera_finish_views: one frame's finish P over its workgroups' partial sums.
+// (A template over the kernel it serves: each instantiation has LDS arrays of its own, so each kernel's LDS layout is
+// that of a kernel that declares them itself.)
+template <bool kViews>
+__device__ __forceinline__ void camera_finish_body(const CamFinish& P, const double* __restrict__ cam_part) {
   __shared__ double part[kCamFinishRows][kCamSums];
   __shared__ double S[kCamSums];
   const int tid = threadIdx.x;
@@ -912,6 +924,22 @@ __global__ __launch_bounds__(1024) void k_camera_finish(CamFinish P, const doubl
   if (P.g_eye) P.g_eye[3] = 0.0f;
   if (P.g_at) P.g_at[3] = 0.0f;
   if (P.g_up) P.g_up[3] = 0.0f;
+}
+
+__global__ __launch_bounds__(1024) void k_camera_finish(CamFinish P, const double* __restrict__ cam_part) {
+  camera_finish_body<false>(P, cam_part);
+}
+
+// A batch of views per launch (srh_render_views_bwd_camera): one workgroup per view, view v = blockIdx.x finishes Ps[v]
+// over its own slice of the partial sums, which starts v * ngroups * kCamSums doubles into `cam_part` (every view of a
+// batch has the same ngroups).  Ps was written by a copy in front of the launch and is read as k_render_bwd_tch_views
+// reads Fs.  A view that wants no camera gradient (three NULL destinations) leaves as a whole before the first barrier.
+__global__ __launch_bounds__(1024) void k_camera_finish_views(const CamFinish* __restrict__ Ps,
+                                                              const double* __restrict__ cam_part) {
+  const size_t v = blockIdx.x;
+  const CamFinish& P = *(const CamFinish*)(as_constant(Ps) + v);
+  if (!P.g_eye && !P.g_at && !P.g_up) return;
+  camera_finish_body<true>(P, cam_part + v * (size_t)P.ngroups * kCamSums);
 }
 
 }  // namespace srh

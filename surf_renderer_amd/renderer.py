@@ -125,6 +125,7 @@ class SceneBuffers:
     total: int = 0
     shadow_workspace: Optional[torch.Tensor] = None   # scratch of the accelerated shadow pass (light views)
     camera_scratch: Optional[torch.Tensor] = None     # workgroup partial sums of the camera gradients (srh_render_bwd_camera)
+    camera_scratch_views: Optional[torch.Tensor] = None   # the same for a batch of views (srh_render_views_bwd_camera)
 
     def ensure_workspace(self, width: int, height: int) -> torch.Tensor:
         """Device scratch for libsrh (primitive records + tile bins) at ``width x height``."""
@@ -159,6 +160,17 @@ class SceneBuffers:
         if self.camera_scratch is None or self.camera_scratch.numel() * 8 < need:
             self.camera_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
         return self.camera_scratch
+
+    def ensure_camera_scratch_views(self, width: int, rows: int, n_views: int) -> torch.Tensor:
+        """Scratch of srh_render_views_bwd_camera for a backward over ``n_views`` views of ``width x rows`` pixels: the
+        views' finish descriptors and a slice of partial sums per view.  Its contents never matter either."""
+        lib = _lib.load()
+        need = lib.srh_camera_grad_scratch_bytes_views(width, rows, n_views)
+        if need == 0:
+            raise _lib.SrhError(-2, lib.srh_last_error().decode())
+        if self.camera_scratch_views is None or self.camera_scratch_views.numel() * 8 < need:
+            self.camera_scratch_views = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        return self.camera_scratch_views
 
     def new_workspace(self, width: int, height: int) -> torch.Tensor:
         """An additional scratch buffer (one per frame in flight when frames are pipelined over several streams)."""
@@ -770,13 +782,15 @@ def render_views_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], imag
                          workspace: Optional[torch.Tensor] = None, image_row_stride: int = 0,
                          depth_row_stride: int = 0, view_row0: Optional[Sequence[int]] = None,
                          scenes: Optional[ViewScenes] = None, mode: str = "auto", first_view: int = 0,
+                         aux: Optional[Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]] = None,
                          **shading_kw) -> torch.Tensor:
     """Low-level form of ``render_views``: resident scene buffers, camera structs, caller-provided stacked outputs
     (view v starts v * rows * row_stride elements after view 0) and an optional row slab; with ``view_row0`` view v
     renders rows [view_row0[v], view_row0[v] + rows[1] - rows[0]) instead; ``scenes`` gives every view its own
     geometry / lights / materials (``ViewScenes``), camera i drawing view ``first_view + i`` of it.  ``mode`` is
-    'auto' or 'binned'.  One library call, every pipeline kernel launched once for the whole batch.  Returns the
-    workspace (pass it back in to reuse it)."""
+    'auto' or 'binned'.  ``aux=(normals, poses)`` are optional stacked dense (n,rows,W,3) float32 outputs of the torch
+    shading (srh_render_views_aux).  One library call, every pipeline kernel launched once for the whole batch.  Returns
+    the workspace (pass it back in to reuse it)."""
     lib = _lib.load()
     width, height = frame_size(cams[0])
     n = len(cams)
@@ -812,27 +826,45 @@ def render_views_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], imag
             ls = C.byref(scenes.lights[first_view])
         if scenes.mask & _lib.VIEWS_MATERIALS:
             ms = C.byref(scenes.materials[first_view])
+    if aux is not None:
+        for t in aux:
+            if t is not None and (tuple(t.shape) != (n, params.row1 - params.row0, width, 3) or t.dtype != torch.float32
+                                  or not t.is_contiguous() or t.device != buf.device):
+                raise ValueError(f"aux buffer mismatch: want contiguous float32 {(n, params.row1 - params.row0, width, 3)} "
+                                 f"on {buf.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
     with torch.cuda.device(buf.device):
-        _lib.check(lib.srh_render_views(n, arr, ob, ls, ms,
-                                        C.byref(params), workspace.data_ptr(), workspace.numel(), images.data_ptr(),
-                                        depths.data_ptr(), nearests.data_ptr() if nearests is not None else None,
-                                        _stream_ptr(buf.device)))
+        args = (n, arr, ob, ls, ms, C.byref(params), workspace.data_ptr(), workspace.numel(), images.data_ptr(),
+                depths.data_ptr(), nearests.data_ptr() if nearests is not None else None)
+        if aux is None:
+            _lib.check(lib.srh_render_views(*args, _stream_ptr(buf.device)))
+        else:
+            _lib.check(lib.srh_render_views_aux(*args, aux[0].data_ptr() if aux[0] is not None else None,
+                                                aux[1].data_ptr() if aux[1] is not None else None,
+                                                _stream_ptr(buf.device)))
     if binned:
         _ws_note(workspace, ("clean", key))
     return workspace
 
 
-def render_views_bwd_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], g_images: torch.Tensor,
+def render_views_bwd_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], g_images: Optional[torch.Tensor],
                              g_depths: Optional[torch.Tensor], nearests: torch.Tensor, depths: torch.Tensor, grads,
                              workspace: Optional[torch.Tensor] = None, scenes: Optional[ViewScenes] = None,
                              first_view: int = 0, visibility: Optional[torch.Tensor] = None,
+                             g_normals: Optional[torch.Tensor] = None, g_poses: Optional[torch.Tensor] = None,
+                             camera_grads=None, camera_scratch: Optional[torch.Tensor] = None,
                              **shading_kw) -> torch.Tensor:
     """Low-level form of the backward of ``render_views`` (srh_render_views_bwd): the views of ``cams`` in one call, from
     stacked contiguous upstream gradients ``g_images`` (n,H,W,3) and ``g_depths`` (n,H,W) or None, the forward's stacked
     ``nearests`` / ``depths`` and, for a ``shadow=True`` forward, its stacked ``visibility``.  ``grads`` is a ctypes
     array of n ``_lib.SrhGrads``: where each view's gradients are ADDED (the same pointer in every struct for a leaf the
     views share; zero-filled by the caller).  ``scenes`` / ``first_view`` as in ``render_views_buffers``.  The bin
-    counters of ``workspace`` are not touched: what is noted about them stays true.  Returns the workspace."""
+    counters of ``workspace`` are not touched: what is noted about them stays true.  Returns the workspace.
+
+    With ``g_normals`` / ``g_poses`` (stacked contiguous (n,H,W,3) upstream gradients of the torch shading's ``normal`` /
+    ``pos`` outputs), ``camera_grads`` (a ctypes array of n ``_lib.SrhCameraGrads``: where each view's eye / at / up
+    gradients are WRITTEN, 4 floats each) or ``camera_scratch`` the call is srh_render_views_bwd_camera instead; there
+    ``g_images`` may be None (the geometry-only kernel) as long as one upstream gradient is given, and ``camera_scratch``
+    defaults to the buffers' own (``ensure_camera_scratch_views``) when ``camera_grads`` is given."""
     lib = _lib.load()
     width, height = frame_size(cams[0])
     n = len(cams)
@@ -859,10 +891,22 @@ def render_views_bwd_buffers(buf: SceneBuffers, cams: Sequence[_lib.SrhCamera], 
             ls = C.byref(scenes.lights[first_view])
         if scenes.mask & _lib.VIEWS_MATERIALS:
             ms = C.byref(scenes.materials[first_view])
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
     with torch.cuda.device(buf.device):
-        _lib.check(lib.srh_render_views_bwd(n, arr, ob, ls, ms, C.byref(params), workspace.data_ptr(), workspace.numel(),
-                                            g_images.data_ptr(), g_depths.data_ptr() if g_depths is not None else None,
-                                            nearests.data_ptr(), depths.data_ptr(), grads, _stream_ptr(buf.device)))
+        if g_normals is None and g_poses is None and camera_grads is None and camera_scratch is None:
+            _lib.check(lib.srh_render_views_bwd(n, arr, ob, ls, ms, C.byref(params), workspace.data_ptr(),
+                                                workspace.numel(), g_images.data_ptr(), ptr(g_depths),
+                                                nearests.data_ptr(), depths.data_ptr(), grads, _stream_ptr(buf.device)))
+        else:
+            if camera_grads is not None and camera_scratch is None:
+                camera_scratch = buf.ensure_camera_scratch_views(width, height, n)
+            _lib.check(lib.srh_render_views_bwd_camera(
+                n, arr, ob, ls, ms, C.byref(params), workspace.data_ptr(), workspace.numel(), ptr(g_images), ptr(g_depths),
+                ptr(g_normals), ptr(g_poses), nearests.data_ptr(), depths.data_ptr(), grads, camera_grads,
+                ptr(camera_scratch), camera_scratch.numel() * camera_scratch.element_size() if camera_scratch is not None else 0,
+                _stream_ptr(buf.device)))
     return workspace
 
 
@@ -878,6 +922,7 @@ class _ViewsCall(NamedTuple):
     batch: int
     shadow: bool
     shading_kw: Dict[str, Any]
+    aux: bool = False
 
 
 def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[torch.Tensor]]:
@@ -892,6 +937,10 @@ def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[
     out = {"image": image, "depth": depth}
     if want_nearest:
         out["nearest"] = nearest
+    normal = pos = None
+    if call.aux:
+        normal = out["normal"] = torch.empty((n, height, width, 3), dtype=torch.float32, device=device)
+        pos = out["pos"] = torch.empty((n, height, width, 3), dtype=torch.float32, device=device)
 
     def scene_of(v: int) -> SceneBuffers:
         return every.view(buf, v) if every is not None else buf
@@ -914,7 +963,8 @@ def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[
             m = min(step, n - i)
             workspace = render_views_buffers(buf, cams[i:i + m], image[i:i + m], depth[i:i + m],
                                              nearest[i:i + m] if want_nearest else None, workspace=workspace,
-                                             scenes=every, mode=mode, first_view=i, **shading_kw)
+                                             scenes=every, mode=mode, first_view=i,
+                                             aux=(normal[i:i + m], pos[i:i + m]) if call.aux else None, **shading_kw)
             shadows(i, m)
         return out, workspace
     n_streams = max(1, min(int(call.streams), n))
@@ -927,10 +977,10 @@ def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[
         k = v % n_streams
         with torch.cuda.stream(pool[k]):
             render_buffers(scene_of(v), cam, mode=mode, out=(image[v], depth[v], nearest[v] if want_nearest else None),
-                           workspace=scratch[k], **shading_kw)
+                           workspace=scratch[k], aux=(normal[v], pos[v]) if call.aux else None, **shading_kw)
     for st in pool:
         current.wait_stream(st)
-    for t in (image, depth, nearest, *scratch, *buf.tensors.values(), *(every.keep if every is not None else ())):
+    for t in (image, depth, nearest, normal, pos, *scratch, *buf.tensors.values(), *(every.keep if every is not None else ())):
         if t is not None:
             t.record_stream(current)
     shadows(0, n)
@@ -938,36 +988,54 @@ def _views_forward(call: _ViewsCall) -> Tuple[Dict[str, torch.Tensor], Optional[
 
 
 class _RenderViewsFunction(torch.autograd.Function):
-    """``render_views`` with the batched analytic backward of libsrh (srh_render_views_bwd): one library call, and one
-    backward launch, per chunk of views.  ``inputs`` are the scene's shared leaves (``_float_keys``) followed by the
-    override tensors named by ``slots`` = ((view, key), ...).  Gradient semantics are ``_RenderFunction``'s per view; a
-    shared leaf gets the sum over the views that read it, an override tensor the gradient of its own view."""
+    """``render_views`` with the batched analytic backward of libsrh: one library call, and one backward launch, per
+    chunk of views.  ``inputs`` are the scene's shared leaves (``_float_keys``), then the override tensors named by
+    ``slots`` = ((view, key), ...), then the camera leaves named by ``cam_slots`` = ((view, 'eye' | 'at' | 'up'), ...).
+    Gradient semantics are ``_RenderFunction``'s per view; a shared leaf gets the sum over the views that read it, an
+    override tensor and a camera leaf the gradient of its own view (the camera's in the leaf's own shape, dtype and
+    device, w = 0).  The outputs are image, depth, nearest, then ``visibility`` with ``call.shadow``, then ``normal`` and
+    ``pos`` with ``call.aux``.  The backward is srh_render_views_bwd; with an upstream gradient of normal / pos, or a
+    camera leaf that needs its gradient, it is srh_render_views_bwd_camera."""
 
     @staticmethod
-    def forward(ctx, call: _ViewsCall, slots, *inputs):
+    def forward(ctx, call: _ViewsCall, slots, cam_slots, *inputs):
+        if call.aux:
+            ctx.set_materialize_grads(False)            # an unused normal / pos must arrive as None, not as zeros
         out, workspace = _views_forward(call)
-        ctx.call, ctx.slots, ctx.workspace = call, tuple(slots), workspace
-        ctx.like = [(t.shape, t.dtype, t.device) for t in inputs[len(inputs) - len(ctx.slots):]]
+        ctx.call, ctx.slots, ctx.cam_slots, ctx.workspace = call, tuple(slots), tuple(cam_slots), workspace
+        n_cam = len(ctx.cam_slots)
+        ctx.like = [(t.shape, t.dtype, t.device) for t in inputs[len(inputs) - n_cam - len(ctx.slots):len(inputs) - n_cam]]
+        ctx.cam_like = [(t.shape, t.dtype, t.device) for t in inputs[len(inputs) - n_cam:]]
         vis = out.get("visibility")
         ctx.save_for_backward(out["depth"], out["nearest"], vis)
         ctx.mark_non_differentiable(out["nearest"])
-        if vis is None:
-            return out["image"], out["depth"], out["nearest"]
-        ctx.mark_non_differentiable(vis)
-        return out["image"], out["depth"], out["nearest"], vis
+        res = (out["image"], out["depth"], out["nearest"])
+        if vis is not None:
+            ctx.mark_non_differentiable(vis)
+            res += (vis,)
+        if call.aux:
+            res += (out["normal"], out["pos"])
+        return res
 
     @staticmethod
-    def backward(ctx, g_image, g_depth, _g_nearest, _g_vis=None):
+    def backward(ctx, g_image, g_depth, _g_nearest, *g_rest):
         depth, nearest, vis = ctx.saved_tensors
-        call, slots = ctx.call, ctx.slots
+        call, slots, cam_slots = ctx.call, ctx.slots, ctx.cam_slots
         buf, cams, every = call.buf, call.cams, call.every
         shading = call.shading_kw.get("shading", "numpy")
         keys = _float_keys(buf, shading)
-        need = ctx.needs_input_grad[2:]
+        need = ctx.needs_input_grad[3:]
         n = len(cams)
-        g_image = g_image.to(torch.float32).contiguous() if g_image is not None else torch.zeros(
-            tuple(depth.shape) + (3,), dtype=torch.float32, device=buf.device)
-        g_depth = g_depth.to(torch.float32).contiguous() if g_depth is not None else None
+        g_normal, g_pos = g_rest[-2:] if call.aux else (None, None)
+        cam_rows = {slot: i for i, (slot, want) in enumerate(zip(cam_slots, need[len(keys) + len(slots):])) if want}
+        extended = g_normal is not None or g_pos is not None or bool(cam_rows)      # srh_render_views_bwd_camera
+
+        def dense(g):
+            return g.to(torch.float32).contiguous() if g is not None else None
+
+        if g_image is None and not (extended and (g_depth is not None or g_normal is not None or g_pos is not None)):
+            g_image = torch.zeros(tuple(depth.shape) + (3,), dtype=torch.float32, device=buf.device)
+        g_image, g_depth, g_normal, g_pos = dense(g_image), dense(g_depth), dense(g_normal), dense(g_pos)
         # one buffer per wanted shared leaf; one stacked buffer per overridden key, a row for every view whose override
         # wants a gradient
         shared = {k: torch.zeros_like(buf.tensors[k]) for k, want in zip(keys, need) if want}
@@ -993,26 +1061,49 @@ class _RenderViewsFunction(torch.autograd.Function):
                 else:
                     kind, name = key.split(".")
                     getattr(sg[v], name)[buf.kinds.index(kind)] = g.data_ptr()
+        # the wanted camera gradients: a row of four floats each, written (not added to) by the finish kernel
+        cg = cam_out = None
+        if cam_rows:
+            cam_out = torch.zeros((len(cam_rows), 4), dtype=torch.float32, device=buf.device)
+            cg = (_lib.SrhCameraGrads * n)()
+            for (v, k), i in cam_rows.items():
+                setattr(cg[v], k, cam_out[i].data_ptr())
         step = min(int(call.batch) if int(call.batch) > 0 else 256, 256, n)
         workspace = ctx.workspace
         kw = {k: call.shading_kw[k] for k in ("shading", "double_sided", "use_quartic") if k in call.shading_kw}
         for i in range(0, n, step):
             m = min(step, n - i)
             chunk = (_lib.SrhGrads * m).from_buffer(sg, i * C.sizeof(_lib.SrhGrads))
-            workspace = render_views_bwd_buffers(buf, cams[i:i + m], g_image[i:i + m],
+            more = {}
+            if extended:
+                more = dict(g_normals=g_normal[i:i + m] if g_normal is not None else None,
+                            g_poses=g_pos[i:i + m] if g_pos is not None else None,
+                            camera_grads=(_lib.SrhCameraGrads * m).from_buffer(cg, i * C.sizeof(_lib.SrhCameraGrads))
+                            if cg is not None else None)
+            workspace = render_views_bwd_buffers(buf, cams[i:i + m], g_image[i:i + m] if g_image is not None else None,
                                                  g_depth[i:i + m] if g_depth is not None else None, nearest[i:i + m],
                                                  depth[i:i + m], chunk, workspace=workspace, scenes=every, first_view=i,
-                                                 visibility=vis[i:i + m] if vis is not None else None, **kw)
+                                                 visibility=vis[i:i + m] if vis is not None else None, **more, **kw)
         own_grads = []
         for (v, key), (shape, dtype, device) in zip(slots, ctx.like):
             row = rows.get(key, {}).get(v)
             own_grads.append(None if row is None else stacked[key][row].to(device=device, dtype=dtype).reshape(shape))
-        return (None, None) + tuple(shared.get(k) for k in keys) + tuple(own_grads)
+        cam_grads = []
+        on_host = cam_out.cpu() if cam_out is not None and any(d.type == "cpu" for _, _, d in ctx.cam_like) else None
+        for slot, (shape, dtype, device) in zip(cam_slots, ctx.cam_like):
+            i = cam_rows.get(slot)
+            if i is None:
+                cam_grads.append(None)
+                continue
+            src = on_host if (on_host is not None and device.type == "cpu") else cam_out
+            cam_grads.append(src[i][:int(np.prod(shape))].to(device=device, dtype=dtype).reshape(shape))
+        return (None, None, None) + tuple(shared.get(k) for k in keys) + tuple(own_grads) + tuple(cam_grads)
 
 
 def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], device="cuda", mode: str = "auto",
                  streams: int = 4, want_nearest: bool = True, batch: int = 256,
-                 overrides: Optional[Sequence[Dict[str, Any]]] = None, **shading_kw) -> Dict[str, torch.Tensor]:
+                 overrides: Optional[Sequence[Dict[str, Any]]] = None, aux: bool = False,
+                 **shading_kw) -> Dict[str, torch.Tensor]:
     """Many views per call: the batch axis of the reference's real callers (one ``render()`` per view in a
     Python loop, diffrend/torch/GAN/gan.py:325-378, torch/batch_render.py:36-53).  The scene is uploaded once;
     ``overrides[v]`` replaces leaves of it for view v (``{"disk.pos": ..., "disk.normal": ..., "lights.pos": ...}``: what
@@ -1024,15 +1115,28 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
     runs the shadow-ray pass on every view after its batch (torch/batch_render.py:59,104-106 renders that way by
     default); ``visibility`` (B,H,W) int64 is then returned too.  Returns stacked tensors ``image`` (B,H,W,3), ``depth``
     (B,H,W) and ``nearest`` (B,H,W) int32; ``shading`` / ``double_sided`` / ``use_quartic`` as in ``render``.
+    ``aux=True`` (``shading='torch'`` only, else ValueError) adds the torch backend's ``normal`` and ``pos`` outputs,
+    (B,H,W,3) float32 each, on the batched path (``srh_render_views_aux``) and round-robin alike: the hit's unit normal
+    and the hit point, 0 where nothing is hit, equal to ``render``'s per view.  It is off by default: writing them costs
+    24 bytes per pixel and view.
 
-    Differentiable: with grad enabled, and a float leaf of ``scene`` or a tensor in ``overrides`` that requires grad,
-    ``image`` and ``depth`` carry the analytic HIP backward (``srh_render_views_bwd``: one library call and one backward
-    launch per chunk of ``batch`` views, at most 256, however the forward ran).  Gradient semantics are ``render``'s for
-    every view: a shared leaf of ``scene`` receives the sum over the views that read it, an override tensor -- a leaf or
-    not, e.g. a slice of a generator's output -- the gradient of its own view (zeros, not None, for a view that hits
-    nothing; a tensor given to several views the sum), ``disk.radius`` zeros.  ``nearest`` is then always returned.
-    Otherwise, and under ``torch.no_grad()``, nothing of autograd is touched.  Not covered by a batch: gradients of
-    the cameras (camera tensors are detached; use ``render`` per view), the ``normal`` / ``pos`` outputs, and
+    Differentiable: with grad enabled, and a float leaf of ``scene``, a tensor in ``overrides`` or -- under
+    ``shading='torch'`` -- a camera's ``eye`` / ``at`` / ``up`` tensor that requires grad, ``image`` and ``depth`` (and
+    ``normal`` and ``pos`` with ``aux=True``) carry the analytic HIP backward: one library call and one backward launch
+    per chunk of ``batch`` views, at most 256, however the forward ran (``srh_render_views_bwd``; with an upstream
+    gradient of ``normal`` / ``pos`` or a camera leaf, ``srh_render_views_bwd_camera``, which adds one finish launch per
+    chunk for the cameras).  Gradient semantics are ``render``'s for every view: a shared leaf of ``scene`` receives the
+    sum over the views that read it, an override tensor -- a leaf or not, e.g. a slice of a generator's output -- the
+    gradient of its own view (zeros, not None, for a view that hits nothing; a tensor given to several views the sum),
+    ``disk.radius`` zeros.  Upstream gradients at pixels that hit nothing are ignored, those of ``normal`` and ``pos``
+    too.  ``nearest`` is then always returned.
+    Cameras: ``cameras[v]['eye' | 'at' | 'up']`` given as tensors that require grad receive their gradient in their own
+    shape, dtype and device (w gets 0, a 3-vector ``up`` 3 values; zeros for a view that hits nothing), also when
+    nothing else requires grad; every (view, key) pair is an input of its own, so a tensor several views share -- one
+    ``up``, or rows of one (B,4) pose tensor -- gets the sum through autograd.  The camera gradients use no atomics and
+    are identical from run to run.  ``shading='numpy'`` keeps detaching the cameras; ``fovy`` / ``focal_length`` get
+    nothing.
+    Otherwise, and under ``torch.no_grad()``, nothing of autograd is touched.  Not covered by a batch:
     ``ResidentScene`` / ``capture_step`` -- the call cannot be stream-captured, like its forward."""
     unknown = set(shading_kw) - {"shading", "double_sided", "use_quartic", "waves_per_tile", "shadow"}
     if unknown:
@@ -1041,13 +1145,16 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
     shading = shading_kw.get("shading", "numpy")
     if shadow and shading != "torch":
         raise ValueError("shadow rays exist only in the torch backend's semantics: shading='torch'")
+    if aux and shading != "torch":
+        raise ValueError("normal / pos outputs exist only in the torch backend's semantics: shading='torch'")
     device = torch.device(device)
+    cam_slots = [(v, k) for v, cam in enumerate(cameras) for k in camera_leaves(cam, shading)] if torch.is_grad_enabled() else []
 
     def wants_grad(x) -> bool:
         return isinstance(x, torch.Tensor) and x.requires_grad and x.is_floating_point()
 
     differentiable = torch.is_grad_enabled() and (
-        any(wants_grad(x) for x in _source_leaves(scene).values()) or
+        bool(cam_slots) or any(wants_grad(x) for x in _source_leaves(scene).values()) or
         any(wants_grad(x) for ov in (overrides or ()) for x in (ov or {}).values()))
     buf = flatten_scene(scene, device, keep_graph=differentiable)
     cams = [camera_struct(c, shading) for c in cameras]
@@ -1061,17 +1168,20 @@ def render_views(scene: Dict[str, Any], cameras: Sequence[Dict[str, Any]], devic
         raise ValueError(f"{len(overrides)} overrides for {n} cameras")
     every = ViewScenes(buf, overrides) if overrides is not None else None
     # the shadow pass and the backward start from the winners
-    call = _ViewsCall(buf, cams, every, mode, streams, want_nearest or shadow or differentiable, batch, shadow, shading_kw)
+    call = _ViewsCall(buf, cams, every, mode, streams, want_nearest or shadow or differentiable, batch, shadow, shading_kw,
+                      bool(aux))
     if not differentiable:
         return _views_forward(call)[0]
     keys = _float_keys(buf, shading)
     slots = [(v, key) for v, ov in enumerate(overrides or ()) for key, x in (ov or {}).items()
              if key in keys and isinstance(x, torch.Tensor) and x.is_floating_point()]
-    res = _RenderViewsFunction.apply(call, tuple(slots), *[buf.tensors[k] for k in keys],
-                                     *[overrides[v][key] for v, key in slots])
+    res = _RenderViewsFunction.apply(call, tuple(slots), tuple(cam_slots), *[buf.tensors[k] for k in keys],
+                                     *[overrides[v][key] for v, key in slots], *[cameras[v][k] for v, k in cam_slots])
     out = {"image": res[0], "depth": res[1], "nearest": res[2]}
     if shadow:
         out["visibility"] = res[3]
+    if aux:
+        out["normal"], out["pos"] = res[-2], res[-1]
     return out
 
 

@@ -2,7 +2,11 @@
 """Whole frames through the batched entry point (srh_render_views): V frames per library call, S calls in flight on
 S streams.  Diagnostic: us per frame against the per-frame pipeline of bench.py.
 --backward times the GAN-shaped batch (64 views x 128^2, 4096 splats and one light per view as overrides that require
-grad) forward + backward instead: one render_views call against one render() + backward() per view, one JSON line each."""
+grad) forward + backward instead: one render_views call against one render() + backward() per view, one JSON line each.
+--camera times the same batch under shading='torch' with every view's eye and at requiring grad (nothing else does),
+forward + backward: one render_views call (srh_render_views_bwd_camera) against one render() + backward() per view
+(srh_render_bwd_camera), alternating the two forms round by round in this process; one JSON line per form with the
+median, and the run-to-run spread (min .. max over the rounds) of both."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,9 +19,11 @@ ap.add_argument("--calls", type=int, default=100)
 ap.add_argument("--prims", type=int, default=100_000)
 ap.add_argument("--size", type=int, default=2048)
 ap.add_argument("--backward", action="store_true", help="time forward + backward of the GAN-shaped batch only")
+ap.add_argument("--camera", action="store_true", help="time forward + backward with every view's eye and at requiring grad")
+ap.add_argument("--rounds", type=int, default=7, help="--camera: A/B rounds")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-if not args.backward:
+if not args.backward and not args.camera:
     W = H = args.size
     sc = synthetic.disk_cloud_scene(args.prims, W, H)
     buf = renderer.flatten_scene(sc, dev)
@@ -71,6 +77,46 @@ def element(v):
     return {**base, "camera": cams[v], "lights": dict(base["lights"], pos=lp[v]),
             "objects": {"disk": dict(base["objects"]["disk"], pos=pos[v], normal=nrm[v])}}
 
+
+if args.camera:
+    # pose refinement: eye and at of every view are leaves, the scene is fixed (per-view splats and light as above)
+    eyes = [torch.tensor(c["eye"], dtype=torch.float32, device=dev, requires_grad=True) for c in cams]
+    ats = [torch.tensor(np.asarray(c["at"], dtype=np.float32), device=dev, requires_grad=True) for c in cams]
+    tcams = [dict(c, eye=eyes[v], at=ats[v]) for v, c in enumerate(cams)]
+    g_img = torch.tensor(rng.uniform(-1, 1, (B, R, R, 3)).astype(np.float32), device=dev)
+
+    def clear():
+        for t in eyes + ats:
+            t.grad = None
+
+    def batched():
+        clear()
+        out = render_views(base, tcams, device=dev, shading="torch", overrides=ov)
+        (out["image"] * g_img).sum().backward()
+
+    def looped():
+        clear()
+        for v in range(B):
+            (render({**element(v), "camera": tcams[v]}, device=dev, shading="torch")["image"] * g_img[v]).sum().backward()
+
+    def grads():
+        return torch.stack([t.grad for t in eyes + ats]).clone()
+
+    batched(); want = grads()
+    looped(); got = grads()
+    agree = float((got - want).abs().max() / want.abs().max())
+    times = {"render_views": [], "render_per_view": []}
+    for _ in range(args.rounds):                              # A/B, alternating: both forms see the same machine state
+        times["render_views"].append(timed(batched, 5))
+        times["render_per_view"].append(timed(looped, 2))
+    for form, ts in times.items():
+        med = float(np.median(ts))
+        print(json.dumps({"workload": "gan_batch_camera_fwd_bwd", "form": form, "views": B, "size": R, "splats_per_view": M,
+                          "leaves": "eye, at of every view", "rounds": args.rounds, "ms_per_batch": round(1e3 * med, 3),
+                          "ms_min": round(1e3 * min(ts), 3), "ms_max": round(1e3 * max(ts), 3),
+                          "spread_ms": round(1e3 * (max(ts) - min(ts)), 3), "views_per_s": round(B / med, 1),
+                          "max_rel_grad_diff_between_forms": agree}))
+    sys.exit(0)
 
 if not args.backward:
     t_batch = timed(lambda: render_views(base, cams, device=dev, overrides=ov, want_nearest=False))
