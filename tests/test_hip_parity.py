@@ -15,6 +15,7 @@ import torch
 from conftest import GOLDEN_DIR, golden_cases
 from oracle import np_oracle
 from oracle.golden_io import load_case
+from shadow_scenes import _random_scene                  # the fuzzes' recipe, shared with the shadow-pass fuzz
 
 pytestmark = pytest.mark.gpu
 
@@ -347,43 +348,6 @@ def test_views_batch_of_row_slabs_into_interleaved_buffers():
         i1, d1, _ = renderer.render_buffers(buf, cams[v // 2], rows=(row0[v], row0[v] + hh))
         np.testing.assert_array_equal(img2[v].cpu().numpy(), i1.cpu().numpy())
         np.testing.assert_array_equal(dep2[v].cpu().numpy(), d1.cpu().numpy())
-
-
-def _random_scene(rng):
-    """A random mixed scene for the fuzz below: 1-4 primitive types, 1-3000 primitives each with log-uniform sizes from
-    sub-pixel to screen-filling, random camera (also inside the cloud), near in {0, 0.01, 0.1, 1}."""
-    f32 = lambda a: np.asarray(a, dtype=np.float32)          # noqa: E731
-    W, H = int(rng.choice([48, 64, 97, 128, 200])), int(rng.choice([48, 64, 80, 128, 160]))
-    eye = rng.normal(size=3)
-    eye = eye / np.linalg.norm(eye) * rng.choice([0.3, 1.0, 2.5, 4.0, 8.0])
-    cam = {"viewport": [0, 0, W, H], "fovy": float(np.deg2rad(rng.choice([20, 45, 70, 110]))),
-           "focal_length": float(rng.choice([0.5, 1.0, 3.0])), "eye": [*map(float, eye), 1.0],
-           "at": [*map(float, rng.normal(size=3) * 0.2), 1.0], "up": [*map(float, rng.normal(size=3)), 0.0],
-           "near": float(rng.choice([0.0, 0.01, 0.1, 1.0])), "far": float(rng.choice([5.0, 50.0, 1000.0]))}
-    objs = {}
-    for k in list(rng.permutation(["disk", "triangle", "sphere", "plane"]))[: rng.randint(1, 5)]:
-        n = int(rng.choice([1, 5, 60, 700, 3000])) if k != "plane" else int(rng.choice([1, 2, 3]))
-        pos = np.concatenate([rng.uniform(-1.5, 1.5, (n, 3)), np.ones((n, 1))], 1)
-        nrm = np.concatenate([rng.normal(size=(n, 3)), np.zeros((n, 1))], 1)
-        mat = rng.randint(0, 3, n)
-        if k == "disk":
-            objs[k] = {"pos": f32(pos), "normal": f32(nrm), "material_idx": mat,
-                       "radius": f32(np.exp(rng.uniform(np.log(0.003), np.log(1.5), n)))}
-        elif k == "sphere":
-            objs[k] = {"pos": f32(pos), "radius": f32(np.exp(rng.uniform(np.log(0.005), np.log(0.8), n))), "material_idx": mat}
-        elif k == "plane":
-            pos[:, :3] *= 2.0
-            objs[k] = {"pos": f32(pos), "normal": f32(nrm), "material_idx": mat}
-        else:
-            c = rng.uniform(-1.5, 1.5, (n, 1, 3))
-            v = c + rng.normal(size=(n, 3, 3)) * np.exp(rng.uniform(np.log(0.01), np.log(0.8), (n, 1, 1)))
-            fn = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]) * rng.choice([-1, 1], (n, 1))
-            objs[k] = {"face": f32(np.concatenate([v, np.ones((n, 3, 1))], 2)),
-                       "normal": f32(np.concatenate([fn, np.zeros((n, 1))], 1)), "material_idx": mat}
-    return {"camera": cam, "lights": {"pos": f32([[3, 4, 5, 1], [-4, 2, 3, 1]]), "color_idx": np.array([1, 2])},
-            "colors": f32([[0, 0, 0], [.8, .5, .4], [.3, .6, .9]]),
-            "materials": {"albedo": f32([[.5, .5, .5], [.9, .3, .2], [.2, .7, .4]])},
-            "objects": objs, "tonemap": {"type": "gamma", "gamma": 0.8}}
 
 
 @pytest.mark.gpu

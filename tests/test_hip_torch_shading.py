@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import np_oracle_tch
+from shadow_scenes import shadow_both_ways as _shadow_both_ways
 from test_oracle_tch import CASES, assert_tch_parity, load_shadow_case, load_tch_case
 
 pytestmark = pytest.mark.gpu
@@ -170,21 +171,6 @@ def test_norm_depth_image_is_differentiable_through_depth():
     res = render(scene, device="cuda:0", shading="torch", norm_depth_image_only=True)
     res["image"].sum().backward()
     assert pos.grad is not None and torch.isfinite(pos.grad).all() and pos.grad.abs().sum() > 0
-
-
-def _shadow_both_ways(scene, **kw):
-    """(binned, all-pairs) results of the shadow pass over the same primary frame."""
-    from surf_renderer_amd import renderer
-    buf = renderer.flatten_scene(scene, "cuda:0")
-    cam = renderer.camera_struct(scene["camera"], "torch")
-    out = []
-    for all_pairs in (False, True):
-        image, depth, nearest = renderer.render_buffers(buf, cam, shading="torch", **kw)
-        vis = renderer.shadow_pass(buf, cam, None, image, depth, nearest, kw.get("double_sided", False),
-                                   kw.get("use_quartic", False), all_pairs=all_pairs)
-        torch.cuda.synchronize()
-        out.append((image.clone(), vis.clone(), depth.clone()))
-    return out
 
 
 def _with_torch_inputs(scene):
