@@ -170,29 +170,87 @@ def _unit3_eps(v: torch.Tensor) -> torch.Tensor:
     return v / torch.sqrt(torch.sum(v * v + 1e-10, dim=-1, keepdim=True))
 
 
-def render_tch(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None,
-               double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None):
-    """Differentiable image (H,W,3), depth (H,W) and hit mask under the torch backend's semantics
-    (diffrend/torch/renderer.py:82-125,136-355; see oracle/np_oracle_tch.py for the forward restatement and its two
-    documented deviations).  Selection and every mask (per-light relu, double_sided sign, clip) are piecewise
-    constant, as under the reference's autograd."""
+OUTPUTS = ("image", "depth", "normal", "pos")
+CAMERA_KEYS = ("camera.eye", "camera.at", "camera.up")
+
+
+def make_camera_leaves(camera: Dict[str, Any], requires_grad: bool = True) -> Dict[str, torch.Tensor]:
+    """eye, at, up as fp64 leaves holding the float32 values the torch backend holds (np_oracle_tch.cam_vec)."""
     from . import np_oracle_tch
-    cam = scene["camera"]
-    if np_oracle_tch.is_ortho(cam):
+    return {"camera." + k: torch.tensor(np_oracle_tch.cam_vec(camera[k]), requires_grad=requires_grad)
+            for k in ("eye", "at", "up")}
+
+
+def rays_np(camera: Dict[str, Any]):
+    """(eye (3), origin (N,3), direction (N,3), H, W) as fp64 constants from np_oracle_tch's ray generators: the graph
+    is cut at the camera.  This is the default path, and its values are the numpy oracle's to the bit."""
+    from . import np_oracle_tch
+    if np_oracle_tch.is_ortho(camera):
         # torch/utils.py:461-468: every ray has its own origin on the image plane and the one direction at - eye
-        eye_np, orig_np, dvec, H, W = np_oracle_tch.generate_rays_ortho(cam)
+        eye_np, orig_np, dvec, H, W = np_oracle_tch.generate_rays_ortho(camera)
         orig = torch.tensor(np.ascontiguousarray(orig_np))                  # (N,3)
         d = torch.tensor(np.broadcast_to(dvec[None, :], orig_np.shape).copy())
     else:
-        eye_np, ray_np, H, W = np_oracle_tch.generate_rays(cam)
+        eye_np, ray_np, H, W = np_oracle_tch.generate_rays(camera)
         d = torch.tensor(ray_np.T.copy())                                   # (N,3), unit
         orig = torch.tensor(eye_np[:3])[None, :].expand(d.shape[0], 3)
+    return torch.tensor(eye_np[:3]), orig, d, H, W
+
+
+def rays(camera: Dict[str, Any], cam_leaves: Dict[str, torch.Tensor]):
+    """(eye (3), origin (N,3), direction (N,3), H, W), differentiable in the camera leaves: the CAMERA inside the
+    graph.  The rays are built with torch from ``eye`` / ``at`` / ``up`` by the reference's formulae
+    (torch/utils.py:402-427 lookat_rot_inv, :439-478 generate_rays, its in-place ``ray_dir /=`` read as d = v / |v|).
+    rays_np builds the same rays in numpy, which cuts the graph at the camera; this builder exists for that reason
+    alone, and tests/test_camera_grad_golden_cpu.py holds the two to 1e-12 of each other."""
+    from . import np_oracle_tch
+    vp = camera["viewport"]
+    W, H = vp[2] - vp[0], vp[3] - vp[1]
+    h = np.tan(camera["fovy"] / 2) * 2 * camera["focal_length"]
+    w = h * (float(W) / float(H))
+    xg, yg = np.meshgrid(np.linspace(-1, 1, W), np.linspace(1, -1, H))
+    x = torch.tensor(xg.ravel() * (w / 2))
+    y = torch.tensor(yg.ravel() * (h / 2))
+    eye = cam_leaves["camera.eye"][:3]
+    at = cam_leaves["camera.at"][:3]
+    up = cam_leaves["camera.up"][:3]
+    z = _unit3_eps(eye - at)
+    xb = _unit3_eps(torch.linalg.cross(_unit3_eps(up), z))
+    yb = torch.linalg.cross(z, xb)
+    if np_oracle_tch.is_ortho(camera):
+        orig = eye[None, :] + x[:, None] * xb[None, :] + y[:, None] * yb[None, :]
+        d = _unit3_eps(at - eye)[None, :].expand(orig.shape[0], 3)
+    else:
+        rot = torch.stack((xb, yb, z), dim=-1)
+        v = rot @ torch.stack((x, y, -torch.ones_like(x) * camera["focal_length"]), dim=0)
+        d = (v / torch.sqrt(torch.sum(v ** 2, dim=0))).T
+        orig = eye[None, :].expand(d.shape[0], 3)
+    return eye, orig, d, H, W
+
+
+def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]],
+                 double_sided: bool, use_quartic: bool, visibility: Optional[np.ndarray], outputs=OUTPUTS):
+    """The one fp64 autograd restatement of the torch backend (diffrend/torch/renderer.py:82-125,136-355; see
+    oracle/np_oracle_tch.py for the forward restatement and its two documented deviations) on the rays of rays_np or
+    rays: (image (H,W,3), depth (H,W), normal (H,W,3), pos (H,W,3), hit (H,W)).  The shading is built -- and image is
+    not None -- only if 'image' is among ``outputs``, so a geometry-only loss pays for no light.
+
+    Winners are taken as given (``ref`` = {'nearest', 'depth'}: np_oracle_tch's, a reference fixture's or a GPU
+    frame's); selection and every mask (per-light relu, double_sided sign, clip) are piecewise constant, as under the
+    reference's autograd, and light ``visibility`` is an optional (L,N) constant.  At a hit pixel with winner m:
+    normal = n^ = n / sqrt(|n|^2 + 3e-10) (sphere: p - c likewise), NOT flipped by double_sided, which flips only
+    inside the shading; pos = origin + t d (per-pixel origin for orthographic cameras).  Misses: normal and pos are 0,
+    depth is far + 1, and upstream gradients there are ignored (the reference differentiates object 0's intersection
+    there; the hip backend does not -- the one deliberate difference).  Misses contribute nothing, which is also how
+    the sphere case is defined where the reference itself yields NaN."""
+    from . import np_oracle_tch
+    cam = scene["camera"]
+    eye, orig, d, H, W = ray_set
     if ref is None:
         ref = np_oracle_tch.render(scene, double_sided=double_sided, use_quartic=use_quartic)
     nearest = np.asarray(ref["nearest"]).reshape(-1)
     hit_np = np.asarray(ref["depth"]).reshape(-1) <= cam["far"]
     npix = H * W
-    eye = torch.tensor(eye_np[:3])
 
     t = torch.zeros(npix, dtype=torch.float64)
     nrm = torch.zeros((npix, 3), dtype=torch.float64)
@@ -216,8 +274,7 @@ def render_tch(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Opti
                 t1 = (-b - root) / (2 * a)
                 t2 = (-b + root) / (2 * a)
                 ts = torch.where(t1 >= 0, t1, t2)                             # the smaller non-negative root
-                p = orig[sel] + ts[:, None] * ds
-                n = _unit3_eps(p - c)
+                n = _unit3_eps(orig[sel] + ts[:, None] * ds - c)
             else:
                 q = (leaves["triangle.face"][loc][:, 0, :3] if kind == "triangle" else leaves[f"{kind}.pos"][loc][:, :3])
                 n = _unit3_eps(leaves[f"{kind}.normal"][loc][:, :3])
@@ -228,52 +285,109 @@ def render_tch(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Opti
 
     hit = torch.as_tensor(hit_np)
     p = orig + t[:, None] * d
-    lpos = leaves["lights.pos"][:, :3]
-    lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])]
-    att = leaves["lights.attenuation"]
-    amb = leaves["lights.ambient"]
-    alb = leaves["materials.albedo"][mat]
-    cf = leaves["materials.coeffs"][mat]
-    ldir = lpos[None, :, :] - p[:, None, :]                                  # (N,L,3)
-    lnorm = _norm(ldir)
-    ldir = ldir / torch.where(lnorm > 0, lnorm, torch.ones_like(lnorm))
-    powv = 4 if use_quartic else 2
-    den = att[None, :, 0:1] + lnorm * att[None, :, 1:2] + (lnorm ** powv) * att[None, :, 2:3]
-    afac = 1.0 / torch.where(den.abs() > 0, den, torch.ones_like(den))
-    ldn = torch.sum(nrm[:, None, :] * ldir, dim=-1)                          # (N,L)
-    ndotl = afac[..., 0] * ldn
-    cdir = _unit3_eps(eye[None, :] - p)                                      # (N,3)
-    cdotn = torch.sum(cdir * nrm, dim=-1)
-    rdotc = 2.0 * ldn * cdotn[:, None] - torch.sum(cdir[:, None, :] * ldir, dim=-1)
-    if double_sided:
-        sgn = torch.sign(cdotn).detach()[:, None]
-        ndotl = sgn * ndotl
-        rdotc = sgn * rdotc
-    ndotl = torch.relu(ndotl)
-    rdotc = torch.relu(rdotc)
-    spec = cf[:, None, 1] * rdotc ** cf[:, None, 2]                          # torch.pow: 0 ** 0 = 1, masked gradients at 0
-    w = cf[:, None, 0] * ndotl + spec                                        # (N,L)
-    if visibility is not None:                                               # (L,N) constants: shadow rays
-        w = w * torch.as_tensor(np.asarray(visibility, dtype=np.float64).reshape(w.shape[1], -1).T)
-    col = w[:, :, None] * (lcol[None, :, :] * alb[:, None, :]) + amb[None, None, :] * alb[:, None, :]
-    im = torch.sum(col, dim=1)
-    im = torch.where(hit[:, None], im, torch.zeros_like(im))
-    im = torch.relu(im)
-    if "tonemap" in scene:
-        g = float(np.ravel(scene["tonemap"]["gamma"])[0])
-        im = torch.where(im > 0, im.clamp_min(1e-300) ** g, torch.zeros_like(im) if g > 0 else torch.ones_like(im))
+    im = None
+    if "image" in outputs:
+        lpos = leaves["lights.pos"][:, :3]
+        lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])]
+        att = leaves["lights.attenuation"]
+        amb = leaves["lights.ambient"]
+        alb = leaves["materials.albedo"][mat]
+        cf = leaves["materials.coeffs"][mat]
+        ldir = lpos[None, :, :] - p[:, None, :]                              # (N,L,3)
+        lnorm = _norm(ldir)                                                  # a light exactly at a fragment: gradient 0
+        ldir = ldir / torch.where(lnorm > 0, lnorm, torch.ones_like(lnorm))
+        powv = 4 if use_quartic else 2
+        den = att[None, :, 0:1] + lnorm * att[None, :, 1:2] + (lnorm ** powv) * att[None, :, 2:3]
+        afac = 1.0 / torch.where(den.abs() > 0, den, torch.ones_like(den))
+        ldn = torch.sum(nrm[:, None, :] * ldir, dim=-1)                      # (N,L)
+        ndotl = afac[..., 0] * ldn
+        cdir = _unit3_eps(eye[None, :] - p)                                  # (N,3): the eye, not the ray origin
+        cdotn = torch.sum(cdir * nrm, dim=-1)
+        rdotc = 2.0 * ldn * cdotn[:, None] - torch.sum(cdir[:, None, :] * ldir, dim=-1)
+        if double_sided:
+            sgn = torch.sign(cdotn).detach()[:, None]
+            ndotl = sgn * ndotl
+            rdotc = sgn * rdotc
+        ndotl = torch.relu(ndotl)
+        rdotc = torch.relu(rdotc)
+        spec = cf[:, None, 1] * rdotc ** cf[:, None, 2]                      # torch.pow: 0 ** 0 = 1, masked gradients at 0
+        w = cf[:, None, 0] * ndotl + spec                                    # (N,L)
+        if visibility is not None:                                           # (L,N) constants: shadow rays
+            w = w * torch.as_tensor(np.asarray(visibility, dtype=np.float64).reshape(w.shape[1], -1).T)
+        col = w[:, :, None] * (lcol[None, :, :] * alb[:, None, :]) + amb[None, None, :] * alb[:, None, :]
+        im = torch.sum(col, dim=1)
+        im = torch.where(hit[:, None], im, torch.zeros_like(im))
+        im = torch.relu(im)
+        if "tonemap" in scene:
+            g = float(np.ravel(scene["tonemap"]["gamma"])[0])
+            im = torch.where(im > 0, im.clamp_min(1e-300) ** g, torch.zeros_like(im) if g > 0 else torch.ones_like(im))
+        im = im.reshape(H, W, 3)
+    # after the shading: autograd runs later-created nodes first, so this placement fixes the order in which p collects
+    # its gradients (profiles/grad_oracle_unify_ab.txt)
     depth = torch.where(hit, t, torch.full_like(t, float(cam["far"]) + 1.0))
-    return im.reshape(H, W, 3), depth.reshape(H, W), hit.reshape(H, W)
+    pos = torch.where(hit[:, None], p, torch.zeros_like(p))
+    return im, depth.reshape(H, W), nrm.reshape(H, W, 3), pos.reshape(H, W, 3), hit.reshape(H, W)
 
 
-def gradients_tch(scene: Dict[str, Any], grad_image: np.ndarray, grad_depth: Optional[np.ndarray] = None,
-                  ref: Optional[Dict[str, np.ndarray]] = None, double_sided: bool = False,
-                  use_quartic: bool = False, visibility: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+def render_tch(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None,
+               double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None):
+    """Differentiable image (H,W,3), depth (H,W) and hit mask under the torch backend's semantics, on numpy rays."""
+    image, depth, _, _, hit = _render_core(rays_np(scene["camera"]), scene, leaves, ref, double_sided, use_quartic,
+                                           visibility)
+    return image, depth, hit
+
+
+def render_aux(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None,
+               double_sided: bool = False, use_quartic: bool = False):
+    """Differentiable normal (H,W,3), pos (H,W,3) and the hit mask (H,W), zeros at misses, on numpy rays: the torch
+    backend's extra outputs (diffrend/torch/renderer.py:185-189, 342-355), without the shading.  Pinned to the
+    reference by tests/test_aux_grad_golden_cpu.py (tests/golden/n1_*.npz, tools/gen_golden_aux_grad.py)."""
+    _, _, normal, pos, hit = _render_core(rays_np(scene["camera"]), scene, leaves, ref, double_sided, use_quartic, None,
+                                          outputs=("normal", "pos"))
+    return normal, pos, hit
+
+
+def render_camera(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], cam_leaves: Dict[str, torch.Tensor],
+                  ref: Dict[str, np.ndarray], double_sided: bool = False, use_quartic: bool = False,
+                  visibility: Optional[np.ndarray] = None):
+    """Differentiable image, depth, normal, pos and the hit mask on the rays of the camera leaves.  Pinned to the
+    reference by tests/test_camera_grad_golden_cpu.py (tests/golden/c1_*.npz, tools/gen_golden_camera_grad.py)."""
+    return _render_core(rays(scene["camera"], cam_leaves), scene, leaves, ref, double_sided, use_quartic, visibility)
+
+
+def loss_camera(scene, leaves, cam_leaves, ref, grad_image=None, grad_depth=None, grad_normal=None, grad_pos=None,
+                double_sided=False, use_quartic=False, visibility=None) -> torch.Tensor:
+    """sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p) of ONE graph; None terms are left out, and so is
+    the shading without g_i.  ``cam_leaves`` None: numpy rays, the camera outside the graph."""
+    grads = dict(zip(OUTPUTS, (grad_image, grad_depth, grad_normal, grad_pos)))
+    ray_set = rays_np(scene["camera"]) if cam_leaves is None else rays(scene["camera"], cam_leaves)
+    *outs, hit = _render_core(ray_set, scene, leaves, ref, double_sided, use_quartic, visibility,
+                              outputs=[k for k, g in grads.items() if g is not None])
+    loss = torch.zeros((), dtype=torch.float64)
+    for out, (name, g) in zip(outs, grads.items()):
+        if g is not None:
+            term = out * torch.as_tensor(np.asarray(g, dtype=np.float64))
+            if name != "image":
+                term = torch.where(hit if name == "depth" else hit[..., None], term, torch.zeros_like(term))
+            loss = loss + torch.sum(term)
+    return loss
+
+
+def gradients_tch(scene: Dict[str, Any], grad_image: Optional[np.ndarray] = None,
+                  grad_depth: Optional[np.ndarray] = None, grad_normal: Optional[np.ndarray] = None,
+                  grad_pos: Optional[np.ndarray] = None, *, ref: Optional[Dict[str, np.ndarray]] = None,
+                  double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None,
+                  camera: bool = False) -> Dict[str, np.ndarray]:
+    """d loss_camera / d leaf as fp64 ndarrays for every scene leaf and, with ``camera``, for 'camera.eye',
+    'camera.at', 'camera.up' (4 values each, w = 0 -- the reference slices [:3] before anything else)."""
     leaves = make_leaves_tch(scene)
-    image, depth, hit = render_tch(scene, leaves, ref, double_sided, use_quartic, visibility)
-    loss = torch.sum(image * torch.as_tensor(grad_image))
-    if grad_depth is not None:
-        gd = torch.as_tensor(grad_depth)
-        loss = loss + torch.sum(torch.where(hit, depth * gd, torch.zeros_like(gd)))
-    loss.backward()
-    return {k: (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape))) for k, v in leaves.items()}
+    cam_leaves = make_camera_leaves(scene["camera"]) if camera else None
+    loss = loss_camera(scene, leaves, cam_leaves, ref, grad_image, grad_depth, grad_normal, grad_pos, double_sided,
+                       use_quartic, visibility)
+    if loss.requires_grad:
+        loss.backward()
+    out = {}
+    for k, v in {**leaves, **(cam_leaves or {})}.items():
+        g = v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape))
+        out[k] = np.append(g, 0.0) if (k in CAMERA_KEYS and g.size == 3) else g
+    return out

@@ -1,30 +1,22 @@
-"""The normal / pos gradient helper (tests/aux_oracle.py) against the reference torch backend under autograd
-(tests/golden/n1_*.npz, tools/gen_golden_aux_grad.py): forward normal and pos at hit pixels, and every leaf gradient of
+"""The normal / pos side of the gradient oracle (oracle/torch_oracle.py: render_aux, gradients_tch with grad_normal /
+grad_pos) against the reference torch backend under autograd (tests/golden/n1_*.npz, tools/gen_golden_aux_grad.py): forward normal and pos at hit pixels, and every leaf gradient of
 loss = sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p).  The reference's sphere gradients are NaN (sqrt
 under a mask, torch/utils.py:238-279), so the sphere leaves are pinned by central differences instead."""
 import copy
-import json
-import os
 
 import numpy as np
 import pytest
 
-from aux_oracle import gradients_aux, render_aux
-from conftest import GOLDEN_DIR
+from grad_cases import load
 from oracle import np_oracle_tch, torch_oracle
-from oracle.golden_io import unpack_scene
+from oracle.torch_oracle import gradients_tch, render_aux
 
 CASES = ["n1_aux_grad_phong", "n1_aux_grad_phong_ds_quartic", "n1_aux_grad_ortho"]
 
 
-def _load(case):
-    npz = np.load(os.path.join(GOLDEN_DIR, case + ".npz"), allow_pickle=False)
-    return npz, unpack_scene(npz), json.loads(str(npz["kwargs"]))
-
-
 @pytest.mark.parametrize("case", CASES)
 def test_forward_normal_and_pos_match_the_reference(case):
-    npz, scene, kw = _load(case)
+    npz, scene, kw = load(case)
     ref = np_oracle_tch.render(scene, **kw)
     normal, pos, hit = render_aux(scene, torch_oracle.make_leaves_tch(scene, requires_grad=False), ref, **kw)
     same = (np.asarray(npz["ref/nearest"]) == ref["nearest"]) & hit.numpy()
@@ -37,8 +29,8 @@ def test_forward_normal_and_pos_match_the_reference(case):
 
 @pytest.mark.parametrize("case", CASES)
 def test_gradients_match_the_reference_torch_backend(case):
-    npz, scene, kw = _load(case)
-    grads = gradients_aux(scene, *(npz["grad_in/" + k].astype(np.float64) for k in ("image", "depth", "normal", "pos")),
+    npz, scene, kw = load(case)
+    grads = gradients_tch(scene, *(npz["grad_in/" + k].astype(np.float64) for k in ("image", "depth", "normal", "pos")),
                           **kw)
     checked = 0
     for key in npz.files:
@@ -63,10 +55,10 @@ def test_gradients_match_the_reference_torch_backend(case):
 
 @pytest.mark.parametrize("case", ["n1_aux_grad_phong", "n1_aux_grad_ortho"])
 def test_sphere_gradients_are_consistent_with_finite_differences(case):
-    npz, scene, kw = _load(case)
+    npz, scene, kw = load(case)
     ref = np_oracle_tch.render(scene, **kw)
     g_n, g_p = npz["grad_in/normal"].astype(np.float64), npz["grad_in/pos"].astype(np.float64)
-    grads = gradients_aux(scene, grad_normal=g_n, grad_pos=g_p, ref=ref, **kw)
+    grads = gradients_tch(scene, grad_normal=g_n, grad_pos=g_p, ref=ref, **kw)
 
     def loss(sc):
         normal, pos, hit = render_aux(sc, torch_oracle.make_leaves_tch(sc, requires_grad=False), ref, **kw)
@@ -87,8 +79,8 @@ def test_sphere_gradients_are_consistent_with_finite_differences(case):
 
 
 def test_geometry_only_loss_leaves_shading_inputs_untouched():
-    npz, scene, kw = _load("n1_aux_grad_phong")
-    grads = gradients_aux(scene, grad_normal=npz["grad_in/normal"].astype(np.float64),
+    npz, scene, kw = load("n1_aux_grad_phong")
+    grads = gradients_tch(scene, grad_normal=npz["grad_in/normal"].astype(np.float64),
                           grad_pos=npz["grad_in/pos"].astype(np.float64), **kw)
     for name in ("lights.pos", "lights.attenuation", "lights.ambient", "colors", "materials.albedo", "materials.coeffs"):
         assert np.all(grads[name] == 0), name
@@ -96,11 +88,11 @@ def test_geometry_only_loss_leaves_shading_inputs_untouched():
 
 
 def test_linearity_of_the_helper():
-    npz, scene, kw = _load("n1_aux_grad_ortho")
+    npz, scene, kw = load("n1_aux_grad_ortho")
     ref = np_oracle_tch.render(scene, **kw)
     g = {k: npz["grad_in/" + k].astype(np.float64) for k in ("image", "depth", "normal", "pos")}
-    both = gradients_aux(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=ref, **kw)
-    img = gradients_aux(scene, g["image"], g["depth"], ref=ref, **kw)
-    aux = gradients_aux(scene, grad_normal=g["normal"], grad_pos=g["pos"], ref=ref, **kw)
+    both = gradients_tch(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=ref, **kw)
+    img = gradients_tch(scene, g["image"], g["depth"], ref=ref, **kw)
+    aux = gradients_tch(scene, grad_normal=g["normal"], grad_pos=g["pos"], ref=ref, **kw)
     for k in both:
         np.testing.assert_allclose(both[k], img[k] + aux[k], rtol=1e-9, atol=1e-9 * max(np.abs(both[k]).max(), 1.0))

@@ -1,6 +1,7 @@
-"""The camera gradient helper (tests/camera_oracle.py) against the reference torch backend under autograd
-(tests/golden/c1_*.npz, tools/gen_golden_camera_grad.py -- the sphere-free fixture scene, camera eye / at / up as leaves
-beside all others), against the existing helpers it restates, and against central differences on the full scene with
+"""The gradient oracle with the camera in its graph (oracle/torch_oracle.py: rays, gradients_tch with camera=True)
+against the reference torch backend under autograd (tests/golden/c1_*.npz, tools/gen_golden_camera_grad.py -- the
+sphere-free fixture scene, camera eye / at / up as leaves beside all others), against the same oracle on its numpy rays
+(the camera outside the graph), and against central differences on the full scene with
 spheres (where the reference's own camera gradients are NaN).
 
 Distances seen when these tests were written (largest over the three fixtures):
@@ -14,52 +15,23 @@ Distances seen when these tests were written (largest over the three fixtures):
   translation identity residual                                          2e-14 against S ~ 10..40    (bound 1e-12 S)
 """
 import copy
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-import camera_oracle
-from aux_oracle import gradients_aux
-from conftest import GOLDEN_DIR
+from grad_cases import full_scene, grad_kwargs, load, random_upstream, upstream
 from oracle import np_oracle_tch, torch_oracle
-from oracle.golden_io import unpack_scene
+from oracle.torch_oracle import gradients_tch
 
 CASES = ["c1_camera_grad_phong", "c1_camera_grad_phong_ds_quartic", "c1_camera_grad_ortho"]
-OUTPUTS = ("image", "depth", "normal", "pos")
-
-
-def _load(case):
-    npz = np.load(os.path.join(GOLDEN_DIR, case + ".npz"), allow_pickle=False)
-    return npz, unpack_scene(npz), json.loads(str(npz["kwargs"]))
-
-
-def _ups(npz):
-    return {"grad_" + k: npz["grad_in/" + k].astype(np.float64) for k in OUTPUTS}
-
-
-def _full_scene(ortho=False):
-    """The g10 / n1 fixture scene WITH its spheres, as ndarray leaves (from the n1 fixtures)."""
-    name = "n1_aux_grad_ortho" if ortho else "n1_aux_grad_phong"
-    return unpack_scene(np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False))
-
-
-def _upstream(seed_a=7, seed_b=11, H=36, W=48):
-    rng = np.random.RandomState(seed_a)
-    g = {"grad_image": rng.uniform(-1, 1, size=(H, W, 3)), "grad_depth": rng.uniform(-1, 1, size=(H, W))}
-    rng = np.random.RandomState(seed_b)
-    g["grad_normal"] = rng.uniform(-1, 1, size=(H, W, 3))
-    g["grad_pos"] = rng.uniform(-1, 1, size=(H, W, 3))
-    return g
 
 
 @pytest.mark.parametrize("ortho", [False, True])
 def test_rays_equal_the_numpy_oracle(ortho):
-    cam = _full_scene(ortho)["camera"]
+    cam = full_scene(ortho)["camera"]
     assert np_oracle_tch.is_ortho(cam) == ortho
-    eye, orig, d, H, W = camera_oracle.rays(cam, camera_oracle.make_camera_leaves(cam, requires_grad=False))
+    eye, orig, d, H, W = torch_oracle.rays(cam, torch_oracle.make_camera_leaves(cam, requires_grad=False))
     if ortho:
         eye_np, orig_np, dvec, H2, W2 = np_oracle_tch.generate_rays_ortho(cam)
         np.testing.assert_allclose(orig.numpy(), orig_np, rtol=0, atol=1e-12)
@@ -74,11 +46,11 @@ def test_rays_equal_the_numpy_oracle(ortho):
 
 @pytest.mark.parametrize("case", CASES)
 def test_camera_gradients_match_the_reference(case):
-    npz, scene, kw = _load(case)
+    npz, scene, kw = load(case)
     ref = {"nearest": npz["ref/nearest"], "depth": npz["ref/depth"].astype(np.float64)}
     assert (ref["depth"] <= scene["camera"]["far"]).all()          # the fixture frames hit something at every pixel
-    got = camera_oracle.gradients_camera(scene, ref, **_ups(npz), **kw)
-    for key in camera_oracle.CAMERA_KEYS:
+    got = gradients_tch(scene, ref=ref, camera=True, **grad_kwargs(upstream(npz)), **kw)
+    for key in torch_oracle.CAMERA_KEYS:
         want64 = npz["grad64/" + key]
         dist = np.abs(got[key] - want64).max() / np.abs(want64).max()
         print(case, key, "against fp64 reference:", dist)
@@ -105,11 +77,13 @@ def test_camera_gradients_match_the_reference(case):
 @pytest.mark.parametrize("ortho", [False, True])
 @pytest.mark.parametrize("kw", [{}, {"double_sided": True, "use_quartic": True}])
 def test_scene_leaf_gradients_equal_the_existing_helper(ortho, kw):
-    scene = _full_scene(ortho)
+    """Once one copy of the oracle against another; since they became one core, its torch-ray path (camera leaves in the
+    graph) against its numpy-ray path, scene leaf by scene leaf."""
+    scene = full_scene(ortho)
     ref = np_oracle_tch.render(scene, **kw)
-    g = _upstream()
-    want = gradients_aux(scene, g["grad_image"], g["grad_depth"], g["grad_normal"], g["grad_pos"], ref=ref, **kw)
-    got = camera_oracle.gradients_camera(scene, ref, **g, **kw)
+    g = grad_kwargs(random_upstream())
+    want = gradients_tch(scene, g["grad_image"], g["grad_depth"], g["grad_normal"], g["grad_pos"], ref=ref, **kw)
+    got = gradients_tch(scene, ref=ref, camera=True, **g, **kw)
     for key, w in want.items():
         np.testing.assert_allclose(got[key], w, rtol=0, atol=1e-12 * max(np.abs(w).max(), 1.0), err_msg=key)
 
@@ -129,16 +103,16 @@ def test_full_scene_with_spheres(ortho):
     """Finite camera gradients where the reference's are NaN; equal to central differences of the helper's own loss
     with the winners frozen; and the translation identity: moving camera, geometry and lights together changes
     nothing."""
-    scene = _full_scene(ortho)
+    scene = full_scene(ortho)
     ref = np_oracle_tch.render(scene)
     hit = ref["depth"] <= scene["camera"]["far"]
     sphere_first = sum((g["face"] if k == "triangle" else g["pos"]).shape[0]
                        for k, g in list(scene["objects"].items())[:list(scene["objects"]).index("sphere")])
     n_sph = scene["objects"]["sphere"]["pos"].shape[0]
     assert ((ref["nearest"] >= sphere_first) & (ref["nearest"] < sphere_first + n_sph) & hit).sum() > 20
-    g = _upstream()
-    grads = camera_oracle.gradients_camera(scene, ref, **g)
-    for key in camera_oracle.CAMERA_KEYS:
+    g = grad_kwargs(random_upstream())
+    grads = gradients_tch(scene, ref=ref, camera=True, **g)
+    for key in torch_oracle.CAMERA_KEYS:
         assert np.all(np.isfinite(grads[key])) and np.abs(grads[key]).max() > 0.1, key
 
     leaves = torch_oracle.make_leaves_tch(scene, requires_grad=False)
@@ -146,11 +120,11 @@ def test_full_scene_with_spheres(ortho):
     def loss(cam_values):
         cl = {k: torch.tensor(v) for k, v in cam_values.items()}
         with torch.no_grad():
-            return float(camera_oracle.loss_camera(scene, leaves, cl, ref, **g))
+            return float(torch_oracle.loss_camera(scene, leaves, cl, ref, **g))
 
-    base = {k: v.detach().numpy().copy() for k, v in camera_oracle.make_camera_leaves(scene["camera"]).items()}
+    base = {k: v.detach().numpy().copy() for k, v in torch_oracle.make_camera_leaves(scene["camera"]).items()}
     eps, worst = 1e-6, 0.0
-    for key in camera_oracle.CAMERA_KEYS:
+    for key in torch_oracle.CAMERA_KEYS:
         for i in range(3):
             vals = []
             for sign in (+1, -1):
@@ -165,7 +139,7 @@ def test_full_scene_with_spheres(ortho):
 
     # image, depth and normal do not change when camera, geometry and lights move together; pos moves along, so a
     # loss on pos is left out of this identity
-    inv = camera_oracle.gradients_camera(scene, ref, **{k: v for k, v in g.items() if k != "grad_pos"})
+    inv = gradients_tch(scene, ref=ref, camera=True, **{k: v for k, v in g.items() if k != "grad_pos"})
     res, S = _translation_residual(scene, inv)
     print("translation residual", res, "S", S)
     assert np.all(np.abs(res) <= 1e-12 * S)

@@ -1,77 +1,39 @@
 """GPU: differentiable ``normal`` and ``pos`` outputs of render(scene, shading='torch') (srh_render_bwd_aux, the kAux /
-kImage variants of k_render_bwd_tch) against the fp64 helper tests/aux_oracle.py, which tests/test_aux_grad_golden_cpu.py
-ties to the reference torch backend's autograd (tests/golden/n1_*.npz).
+kImage variants of k_render_bwd_tch) against the fp64 oracle (oracle/torch_oracle.gradients_tch), which
+tests/test_aux_grad_golden_cpu.py ties to the reference torch backend's autograd (tests/golden/n1_*.npz).
 
 Stated tolerances: gradients per input array |got - want| <= 2e-4 * max|want| + 1e-6 (tests/test_hip_backward.py);
 forward normal 3e-4 and pos 2e-4 at hit pixels against the float32 reference (tests/test_hip_torch_shading.py)."""
 import copy
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from aux_oracle import gradients_aux
-from conftest import GOLDEN_DIR
+from grad_cases import (RUN_TO_RUN, TCH_KEYS, assert_grads_close, gpu_leaf_scene, grad_kwargs, leaf_grads, load,
+                        masked_loss, upstream, winners)
 from oracle import np_oracle_tch
-from oracle.golden_io import unpack_scene
-from test_hip_backward import _leaf_scene_tch
+from oracle.torch_oracle import OUTPUTS, gradients_tch
 
 pytestmark = pytest.mark.gpu
 
 CASES = ["n1_aux_grad_phong", "n1_aux_grad_phong_ds_quartic", "n1_aux_grad_ortho"]
-OUTPUTS = ("image", "depth", "normal", "pos")
-# two runs of the same backward differ by the order of their fp32 atomic additions (<= 2e-5 of the largest
-# entry); a leaked 1e30 or a changed gradient is many orders above that
-RUN_TO_RUN = 2e-5
-
-
-def _load(case):
-    npz = np.load(os.path.join(GOLDEN_DIR, case + ".npz"), allow_pickle=False)
-    return npz, unpack_scene(npz), json.loads(str(npz["kwargs"]))
-
-
-def _upstream(npz, *keys):
-    return {k: npz["grad_in/" + k].astype(np.float64) for k in keys}
 
 
 def _hip(scene, g, rows=None, mask=True, **kw):
-    """render() with GPU leaves and loss = sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p) over the
-    outputs named in g (mask=False: the three sums run over every pixel); returns ({leaf: grad ndarray}, result)."""
+    """render() with GPU leaves and masked_loss over the outputs named in g; returns ({leaf: grad ndarray}, result)."""
     from surf_renderer_amd import render
-    leaf_scene, leaves = _leaf_scene_tch(scene)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     res = render(leaf_scene, device="cuda:0", shading="torch", rows=rows, **kw)
-    hit = res["depth"].detach() <= float(scene["camera"]["far"])
-    loss = torch.zeros((), device="cuda:0")
-    for k, up in g.items():
-        term = res[k] * torch.as_tensor(up, dtype=torch.float32, device="cuda:0")
-        if k != "image" and mask:
-            term = torch.where(hit if k == "depth" else hit[..., None], term, torch.zeros_like(term))
-        loss = loss + term.sum()
-    loss.backward()
+    masked_loss(res, g, scene["camera"]["far"], mask).backward()
     torch.cuda.synchronize()
-    grads = {k: (t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape)))
-             for k, t in leaves.items()}
-    return grads, res
-
-
-def _winners(res):
-    """The GPU frame's own winners, for the helper to differentiate the same selection."""
-    return {"nearest": res["nearest"].cpu().numpy(), "depth": res["depth"].detach().cpu().numpy().astype(np.float64)}
-
-
-def _compare(got, want, tol=2e-4, tag=""):
-    for key, w in want.items():
-        assert np.all(np.isfinite(w)), (tag, key)
-        g = got[key].reshape(w.shape)
-        np.testing.assert_allclose(g, w, rtol=0, atol=tol * np.abs(w).max() + 1e-6, err_msg=f"{tag} {key}")
+    return leaf_grads(leaves), res
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_reference_fixtures_through_render(case):
-    npz, scene, kw = _load(case)
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load(case)
+    g = upstream(npz)
     got, res = _hip(scene, g, **kw)
     assert res["normal"].requires_grad and res["pos"].requires_grad
     # forward, at hit pixels won by the reference's primitive
@@ -80,8 +42,8 @@ def test_reference_fixtures_through_render(case):
     np.testing.assert_allclose(res["normal"].detach().cpu().numpy()[same], npz["ref/normal"][same], atol=3e-4)
     np.testing.assert_allclose(res["pos"].detach().cpu().numpy()[same], npz["ref/pos"][same], atol=2e-4)
     # every leaf against the fp64 helper, and against the reference's own gradients where those are finite
-    want = gradients_aux(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=_winners(res), **kw)
-    _compare(got, want, tag=case)
+    want = gradients_tch(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=winners(res), **kw)
+    assert_grads_close(got, want, 2e-4, case)
     for key in npz.files:
         if key.startswith("grad/") and not key.startswith("grad/sphere."):
             ref = npz[key].astype(np.float64)
@@ -93,32 +55,32 @@ def test_reference_fixtures_through_render(case):
 @pytest.mark.parametrize("which", ["normal", "pos"])
 def test_geometry_only_losses(case, which):
     """A loss on normal or pos alone runs the geometry-only kernel: no light / colour / material gradient."""
-    npz, scene, kw = _load(case)
-    g = _upstream(npz, which)
+    npz, scene, kw = load(case)
+    g = upstream(npz, which)
     got, res = _hip(scene, g, **kw)
-    _compare(got, gradients_aux(scene, **{"grad_" + which: g[which]}, ref=_winners(res), **kw), tag=which)
-    for key in ("lights.pos", "colors", "materials.albedo", "materials.coeffs", "lights.attenuation", "lights.ambient"):
+    assert_grads_close(got, gradients_tch(scene, **grad_kwargs(g), ref=winners(res), **kw), 2e-4, which)
+    for key in TCH_KEYS:
         assert np.all(got[key] == 0), key
 
 
 def test_gradients_are_linear_in_the_losses():
-    npz, scene, kw = _load("n1_aux_grad_phong_ds_quartic")
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load("n1_aux_grad_phong_ds_quartic")
+    g = upstream(npz)
     both, _ = _hip(scene, g, **kw)
     parts = [_hip(scene, {k: g[k] for k in keys}, **kw)[0] for keys in (("image", "depth"), ("normal",), ("pos",))]
-    _compare(both, {k: sum(p[k] for p in parts) for k in both}, tag="sum of parts")
+    assert_grads_close(both, {k: sum(p[k] for p in parts) for k in both}, 2e-4, "sum of parts")
 
 
 def test_huge_upstream_gradients_on_misses_change_nothing():
     """normal and pos are the constant 0 where nothing is hit: whatever arrives there from upstream is ignored."""
-    npz, scene, kw = _load("n1_aux_grad_phong")
+    npz, scene, kw = load("n1_aux_grad_phong")
     scene = copy.deepcopy(scene)
     del scene["objects"]["plane"]                      # the background plane: without it, part of the frame misses
-    g = _upstream(npz, *OUTPUTS)
+    g = upstream(npz)
     base, res = _hip(scene, g, **kw)
     miss = res["depth"].detach().cpu().numpy() > scene["camera"]["far"]
     assert 0.05 < miss.mean() < 0.95
-    _compare(base, gradients_aux(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=_winners(res), **kw))
+    assert_grads_close(base, gradients_tch(scene, g["image"], g["depth"], g["normal"], g["pos"], ref=winners(res), **kw), 2e-4)
     poisoned = dict(g)
     for k in ("depth", "normal", "pos"):
         poisoned[k] = np.where(miss if k == "depth" else miss[..., None], 1e30, g[k])
@@ -129,8 +91,8 @@ def test_huge_upstream_gradients_on_misses_change_nothing():
 
 
 def test_shadow_rays_do_not_change_geometry_gradients():
-    npz, scene, kw = _load("n1_aux_grad_phong")
-    g = _upstream(npz, "depth", "normal", "pos")
+    npz, scene, kw = load("n1_aux_grad_phong")
+    g = upstream(npz, "depth", "normal", "pos")
     lit, _ = _hip(scene, g, **kw)
     shadowed, res = _hip(scene, g, shadow=True, **kw)
     assert res["normal"].requires_grad and res["pos"].requires_grad
@@ -139,9 +101,9 @@ def test_shadow_rays_do_not_change_geometry_gradients():
 
 
 def test_row_slab_equals_the_rows_of_the_full_frame():
-    npz, scene, kw = _load("n1_aux_grad_ortho")
+    npz, scene, kw = load("n1_aux_grad_ortho")
     r0, r1 = 9, 25
-    g = _upstream(npz, *OUTPUTS)
+    g = upstream(npz)
     rows = np.arange(g["image"].shape[0])
     inside = (rows >= r0) & (rows < r1)
     full_g = {k: v * (inside[:, None, None] if v.ndim == 3 else inside[:, None]) for k, v in g.items()}
@@ -150,7 +112,7 @@ def test_row_slab_equals_the_rows_of_the_full_frame():
     assert sres["normal"].shape == (r1 - r0, g["image"].shape[1], 3)
     for k in ("normal", "pos"):
         assert torch.equal(sres[k].detach(), fres[k].detach()[r0:r1]), k
-    _compare(slab, full, tag="slab")
+    assert_grads_close(slab, full, 2e-4, "slab")
 
 
 def _fuzz_scene(rng, ortho):
@@ -216,8 +178,8 @@ def test_fuzz_against_the_helper():
         got, res = _hip(scene, g, **kw)
         ref = np_oracle_tch.render(scene, **kw)
         assert (res["nearest"].cpu().numpy() == ref["nearest"]).mean() > 0.999, it
-        want = gradients_aux(scene, *(g.get(k) for k in OUTPUTS), ref=_winners(res), **kw)
-        _compare(got, want, tol=5e-4, tag=f"scene {it} {kw} {keys} ortho={ortho}")
+        want = gradients_tch(scene, *(g.get(k) for k in OUTPUTS), ref=winners(res), **kw)
+        assert_grads_close(got, want, 5e-4, f"scene {it} {kw} {keys} ortho={ortho}")
 
 
 def test_captured_step_with_a_normal_loss_equals_the_eager_iteration():

@@ -10,41 +10,11 @@ import pytest
 import torch
 
 from conftest import GOLDEN_DIR
+from grad_cases import TCH_KEYS, assert_grads_close, gpu_leaf_scene, hip_gradients, leaf_grads, load, masked_loss
 from oracle import torch_oracle
 from oracle.golden_io import load_case, unpack_scene
 
 pytestmark = pytest.mark.gpu
-
-LEAF_PATHS = {"lights.pos": ("lights", "pos"), "colors": ("colors",), "materials.albedo": ("materials", "albedo")}
-
-
-def _hip_gradients(scene, g_img, g_dep):
-    """Scene with torch leaves on the GPU -> render() -> backward; returns ({key: grad ndarray}, forward dict)."""
-    from surf_renderer_amd import render
-    import copy
-    sc = copy.deepcopy(scene)
-    leaves = {}
-
-    def leaf(arr):
-        return torch.tensor(np.asarray(arr, dtype=np.float32), device="cuda:0", requires_grad=True)
-
-    for kind, grp in sc["objects"].items():
-        for name in torch_oracle.LEAF_KEYS[kind]:
-            grp[name] = leaves[f"{kind}.{name}"] = leaf(grp[name])
-    sc["lights"]["pos"] = leaves["lights.pos"] = leaf(sc["lights"]["pos"])
-    sc["colors"] = leaves["colors"] = leaf(sc["colors"])
-    sc["materials"]["albedo"] = leaves["materials.albedo"] = leaf(sc["materials"]["albedo"])
-    res = render(sc, device="cuda:0")
-    assert res["image"].requires_grad and res["depth"].requires_grad
-    hit = torch.isfinite(res["depth"].detach())
-    loss = torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device="cuda:0"))
-    if g_dep is not None:
-        gd = torch.as_tensor(g_dep, dtype=torch.float32, device="cuda:0")
-        loss = loss + torch.sum(torch.where(hit, res["depth"] * gd, torch.zeros_like(gd)))
-    loss.backward()
-    torch.cuda.synchronize()
-    fwd = {"nearest": res["nearest"].cpu().numpy(), "depth": res["depth"].detach().cpu().numpy().astype(np.float64)}
-    return {k: v.grad.cpu().numpy().astype(np.float64) for k, v in leaves.items()}, fwd
 
 
 def _check(scene, seed=0, with_depth=True):
@@ -53,11 +23,9 @@ def _check(scene, seed=0, with_depth=True):
     rng = np.random.RandomState(seed)
     g_img = rng.uniform(-1, 1, size=(h, w, 3)).astype(np.float32).astype(np.float64)
     g_dep = rng.uniform(-1, 1, size=(h, w)).astype(np.float32).astype(np.float64) if with_depth else None
-    got, fwd = _hip_gradients(scene, g_img, g_dep)
+    got, fwd = hip_gradients(scene, g_img, g_dep)
     want = torch_oracle.gradients(scene, g_img, g_dep, ref=fwd)
-    for key, w_arr in want.items():
-        scale = np.abs(w_arr).max()
-        np.testing.assert_allclose(got[key], w_arr, rtol=0, atol=2e-4 * scale + 1e-6, err_msg=key)
+    assert_grads_close(got, want, 2e-4)
     return got, want
 
 
@@ -78,7 +46,7 @@ def test_backward_matches_gradient_oracle(case):
 def test_backward_against_reference_autograd_fixture():
     npz = np.load(os.path.join(GOLDEN_DIR, "g9_torch_autograd.npz"), allow_pickle=False)
     scene = unpack_scene(npz)
-    got, _ = _hip_gradients(scene, npz["grad_in/image"].astype(np.float64), npz["grad_in/depth"].astype(np.float64))
+    got, _ = hip_gradients(scene, npz["grad_in/image"].astype(np.float64), npz["grad_in/depth"].astype(np.float64))
     for key in npz.files:
         if key.startswith("grad/"):
             name = key[5:]
@@ -127,8 +95,8 @@ def test_backward_plane_filling_a_large_frame():
              "tonemap": {"type": "gamma", "gamma": 0.8}}
     got, want = _check(scene, seed=5)
     assert np.abs(want["plane.pos"]).max() > 0 and np.abs(want["plane.normal"]).max() > 0
-    a, _ = _hip_gradients(scene, np.ones((1024, 2048, 3)), None)
-    b, _ = _hip_gradients(scene, np.ones((1024, 2048, 3)), None)
+    a, _ = hip_gradients(scene, np.ones((1024, 2048, 3)), None)
+    b, _ = hip_gradients(scene, np.ones((1024, 2048, 3)), None)
     for key in a:
         spread = np.abs(a[key] - b[key]).max()
         assert spread <= 2e-5 * max(np.abs(a[key]).max(), 1e-30), f"{key}: run-to-run spread {spread}"
@@ -151,11 +119,8 @@ def test_backward_disk_cloud_and_no_grad_inputs():
 def _torch_shading_scene(name):
     """Scenes with the torch backend's extra inputs: the reference-pinned gradient fixture (all four primitive
     types, specular materials, ambient, three attenuation laws), and a disc cloud lit from both sides."""
-    import json
     if name.startswith(("g10", "g11")):
-        npz = np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
-        from oracle.golden_io import unpack_scene
-        return unpack_scene(npz), json.loads(str(npz["kwargs"]))
+        return load(name)[1:]
     from surf_renderer_amd import synthetic
     from surf_renderer_amd.scene import scene_to_numpy
     sc = scene_to_numpy(synthetic.disk_cloud_scene(400, 64, 48, radius=0.12, seed=4), round_fp32=True)
@@ -166,27 +131,6 @@ def _torch_shading_scene(name):
     sc["lights"]["ambient"] = np.array([0.02, 0.01, 0.03])
     sc["materials"]["coeffs"] = np.array([[0.8, 0.2, 5.0]])
     return sc, {"double_sided": True}
-
-
-def _leaf_scene_tch(scene):
-    """Copy of the scene whose differentiable arrays (incl. coeffs / attenuation / ambient) are GPU leaves."""
-    import copy
-    sc = copy.deepcopy(scene)
-    leaves = {}
-
-    def leaf(arr):
-        return torch.tensor(np.asarray(arr, dtype=np.float32), device="cuda:0", requires_grad=True)
-
-    for kind, grp in sc["objects"].items():
-        for name in torch_oracle.LEAF_KEYS[kind]:
-            grp[name] = leaves[f"{kind}.{name}"] = leaf(grp[name])
-    sc["lights"]["pos"] = leaves["lights.pos"] = leaf(sc["lights"]["pos"])
-    sc["lights"]["attenuation"] = leaves["lights.attenuation"] = leaf(sc["lights"]["attenuation"])
-    sc["lights"]["ambient"] = leaves["lights.ambient"] = leaf(sc["lights"]["ambient"])
-    sc["colors"] = leaves["colors"] = leaf(sc["colors"])
-    sc["materials"]["albedo"] = leaves["materials.albedo"] = leaf(sc["materials"]["albedo"])
-    sc["materials"]["coeffs"] = leaves["materials.coeffs"] = leaf(sc["materials"]["coeffs"])
-    return sc, leaves
 
 
 @pytest.mark.parametrize("name", ["g10_torch_autograd_phong", "g10_torch_autograd_phong_ds_quartic", "cloud_ds",
@@ -203,26 +147,15 @@ def test_torch_shading_backward_matches_gradient_oracle(name):
     g_dep = rng.uniform(-1, 1, size=(H, W))
 
     from surf_renderer_amd import render
-    leaf_scene, leaves = _leaf_scene_tch(scene)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     res = render(leaf_scene, device="cuda:0", shading="torch", **kw)
     same = res["nearest"].cpu().numpy() == ref["nearest"]
     hit = ref["depth"] <= scene["camera"]["far"]
     assert (same | ~hit).mean() > 0.999
-    far = float(scene["camera"]["far"])
-    dep = res["depth"]
-    loss = torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device=dep.device)) + \
-        torch.sum(torch.where(dep <= far, dep * torch.as_tensor(g_dep, dtype=torch.float32, device=dep.device),
-                              torch.zeros_like(dep)))
-    loss.backward()
+    masked_loss(res, {"image": g_img, "depth": g_dep}, scene["camera"]["far"]).backward()
     want = torch_oracle.gradients_tch(scene, g_img, g_dep, ref=ref, **kw)
-    checked = 0
-    for key, t in leaves.items():
-        got = t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape))
-        w = want[key].reshape(got.shape)
-        scale = max(np.abs(w).max(), 1e-9)
-        np.testing.assert_allclose(got, w, atol=2e-4 * scale + 1e-6, err_msg=key)
-        checked += 1
-    assert checked >= 9
+    assert_grads_close(leaf_grads(leaves), want, 2e-4, name, keys=leaves)
+    assert len(leaves) >= 9
 
 
 def test_torch_shading_backward_with_shadows():
@@ -236,17 +169,14 @@ def test_torch_shading_backward_with_shadows():
     H, W = ref["depth"].shape
     rng = np.random.RandomState(9)
     g_img = rng.uniform(-1, 1, size=(H, W, 3))
-    leaf_scene, leaves = _leaf_scene_tch(scene)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     res = render(leaf_scene, device="cuda:0", shading="torch", shadow=True, **kw)
-    torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device="cuda:0")).backward()
+    masked_loss(res, {"image": g_img}).backward()
     want = torch_oracle.gradients_tch(scene, g_img, None, ref=ref, visibility=ref["visibility"], **kw)
     plain = torch_oracle.gradients_tch(scene, g_img, None, ref=ref, **kw)
     assert np.abs(want["materials.albedo"] - plain["materials.albedo"]).max() > 1e-3    # shadows matter here
-    for key, t in leaves.items():
-        got = t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape))
-        w = want[key].reshape(got.shape)
-        # a handful of grazing shadow rays may be decided differently: 0.5 % of the largest entry
-        np.testing.assert_allclose(got, w, atol=5e-3 * max(np.abs(w).max(), 1e-9) + 1e-6, err_msg=key)
+    # a handful of grazing shadow rays may be decided differently: 0.5 % of the largest entry
+    assert_grads_close(leaf_grads(leaves), want, 5e-3, "shadow", keys=leaves)
 
 
 def test_fuzz_backward_against_the_gradient_oracles():
@@ -257,16 +187,10 @@ def test_fuzz_backward_against_the_gradient_oracles():
     from oracle import np_oracle_tch
     from surf_renderer_amd import render
     from surf_renderer_amd.scene import scene_to_numpy
-    from test_hip_parity import _random_scene
+    from shadow_scenes import _random_scene
     # SRH_FUZZ_BWD_SEED / SRH_FUZZ_BWD_SCENES: one-off campaigns with other seeds (profiles/r02_fuzz_campaign.txt)
     rng = np.random.RandomState(int(os.environ.get("SRH_FUZZ_BWD_SEED", "41")))
     n_scenes = int(os.environ.get("SRH_FUZZ_BWD_SCENES", "40"))
-
-    def compare(tag, got, want, tol):
-        for key, w in want.items():
-            assert np.all(np.isfinite(w)), (tag, key)
-            g = got[key].reshape(w.shape)
-            np.testing.assert_allclose(g, w, rtol=0, atol=tol * max(np.abs(w).max(), 1e-9) + 1e-6, err_msg=f"{tag} {key}")
 
     done = 0
     while done < n_scenes:
@@ -279,8 +203,8 @@ def test_fuzz_backward_against_the_gradient_oracles():
         sc = scene_to_numpy(scene, round_fp32=True)
         g_img = rng.uniform(-1, 1, size=(H, W, 3)).astype(np.float32).astype(np.float64)
         g_dep = rng.uniform(-1, 1, size=(H, W)).astype(np.float32).astype(np.float64)
-        got, fwd = _hip_gradients(sc, g_img, g_dep)
-        compare(f"scene {done} numpy", got, torch_oracle.gradients(sc, g_img, g_dep, ref=fwd), 5e-4)
+        got, fwd = hip_gradients(sc, g_img, g_dep)
+        assert_grads_close(got, torch_oracle.gradients(sc, g_img, g_dep, ref=fwd), 5e-4, f"scene {done} numpy")
 
         sc["lights"]["attenuation"] = np.array([[1, 0, 0], [0.5, 0.1, 0.01]])
         sc["lights"]["ambient"] = np.array([0.01, 0.02, 0.01])
@@ -288,18 +212,12 @@ def test_fuzz_backward_against_the_gradient_oracles():
         kw = {"double_sided": bool(rng.randint(2)), "use_quartic": bool(rng.randint(2))}
         shadow = bool(rng.randint(2))
         ref = np_oracle_tch.render(sc, shadow=shadow, **kw)
-        leaf_scene, leaves = _leaf_scene_tch(sc)
+        leaf_scene, leaves = gpu_leaf_scene(sc, TCH_KEYS)
         res = render(leaf_scene, device="cuda:0", shading="torch", shadow=shadow, **kw)
         assert np.array_equal(res["nearest"].cpu().numpy(), ref["nearest"])
-        dep, far = res["depth"], float(sc["camera"]["far"])
-        loss = torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device=dep.device)) + \
-            torch.sum(torch.where(dep <= far, dep * torch.as_tensor(g_dep, dtype=torch.float32, device=dep.device),
-                                  torch.zeros_like(dep)))
-        loss.backward()
+        masked_loss(res, {"image": g_img, "depth": g_dep}, sc["camera"]["far"]).backward()
         want = torch_oracle.gradients_tch(sc, g_img, g_dep, ref=ref, visibility=ref["visibility"] if shadow else None, **kw)
-        got = {k: (t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape)))
-               for k, t in leaves.items()}
-        compare(f"scene {done} torch {kw} shadow={shadow}", got, want, 5e-3 if shadow else 5e-4)
+        assert_grads_close(leaf_grads(leaves), want, 5e-3 if shadow else 5e-4, f"scene {done} torch {kw} shadow={shadow}")
 
 
 def test_resident_scene_matches_render_and_sees_in_place_updates():

@@ -1,130 +1,61 @@
 """GPU: gradients of render(scene, shading='torch') with respect to the camera's eye, at and up (srh_render_bwd_camera:
-the kCam variants of k_render_bwd_tch and k_camera_finish) against the fp64 helper tests/camera_oracle.py, which
-tests/test_camera_grad_golden_cpu.py ties to the reference torch backend's autograd (tests/golden/c1_*.npz).
+the kCam variants of k_render_bwd_tch and k_camera_finish) against the fp64 oracle with the camera in its graph
+(oracle/torch_oracle.gradients_tch, camera=True), which tests/test_camera_grad_golden_cpu.py ties to the reference torch
+backend's autograd (tests/golden/c1_*.npz).
 
 Stated tolerances, the project's own: per array |got - want| <= 2e-4 * max|want| + 1e-6 against the helper fed the GPU
 frame's winners (tests/test_hip_backward.py), 2e-3 * max|ref| against the reference fixtures
 (tests/test_hip_aux_grad.py), 2e-5 of the largest entry between two runs of the fp32-atomic scene gradients."""
 import copy
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
-import camera_oracle
 from conftest import GOLDEN_DIR
+from grad_cases import (CAM, DEV, RUN_TO_RUN, TCH_KEYS, assert_grads_close, camera_leaves, full_scene, gpu_leaf_scene,
+                        grad_kwargs, leaf_grads, load, masked_loss, random_upstream, to_np, upstream, winners)
 from oracle.golden_io import unpack_scene
-from test_hip_backward import _leaf_scene_tch
+from oracle.torch_oracle import CAMERA_KEYS as CAM_KEYS, OUTPUTS, gradients_tch
 
 pytestmark = pytest.mark.gpu
 
 CASES = ["c1_camera_grad_phong", "c1_camera_grad_phong_ds_quartic", "c1_camera_grad_ortho"]
-OUTPUTS = ("image", "depth", "normal", "pos")
-CAM = ("eye", "at", "up")
-SHADING_LEAVES = ("lights.pos", "colors", "materials.albedo", "materials.coeffs", "lights.attenuation", "lights.ambient")
-RUN_TO_RUN = 2e-5
-DEV = "cuda:0"
 
 
-def _load(case):
-    npz = np.load(os.path.join(GOLDEN_DIR, case + ".npz"), allow_pickle=False)
-    return npz, unpack_scene(npz), json.loads(str(npz["kwargs"]))
-
-
-def _upstream(npz, *keys):
-    return {k: npz["grad_in/" + k].astype(np.float64) for k in keys}
-
-
-def _random_upstream(H=36, W=48):
-    rng = np.random.RandomState(7)
-    g = {"image": rng.uniform(-1, 1, size=(H, W, 3)), "depth": rng.uniform(-1, 1, size=(H, W))}
-    rng = np.random.RandomState(11)
-    g["normal"] = rng.uniform(-1, 1, size=(H, W, 3))
-    g["pos"] = rng.uniform(-1, 1, size=(H, W, 3))
-    return {k: v.astype(np.float32).astype(np.float64) for k, v in g.items()}
-
-
-def _full_scene(ortho=False, plane=True):
-    """The g10 / n1 fixture scene with its spheres (ndarray leaves, from the n1 fixtures); plane=False: without the
-    background plane."""
-    name = "n1_aux_grad_ortho" if ortho else "n1_aux_grad_phong"
-    sc = unpack_scene(np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False))
-    if not plane:
-        del sc["objects"]["plane"]
-    return sc
-
-
-def _camera_leaves(camera, device=DEV, dtype=torch.float32):
-    return {k: torch.tensor(np.asarray(camera[k], dtype=np.float64), dtype=dtype, device=device, requires_grad=True)
-            for k in CAM}
-
-
-def _loss(res, g, far, mask=True):
-    hit = res["depth"].detach() <= float(far)
-    loss = torch.zeros((), device=DEV)
-    for k, up in g.items():
-        term = res[k] * torch.as_tensor(up, dtype=torch.float32, device=DEV)
-        if k != "image" and mask:
-            term = torch.where(hit if k == "depth" else hit[..., None], term, torch.zeros_like(term))
-        loss = loss + term.sum()
-    return loss
-
-
-def _hip(scene, g, rows=None, mask=True, camera=True, scene_grad=True, **kw):
-    """render() with GPU leaves -- the scene's and, with ``camera``, eye / at / up -- and loss = sum image g_i + sum_hit
-    (depth g_d + normal . g_n + pos . g_p) over the outputs named in g; returns ({leaf: grad ndarray}, result)."""
+def _hip(scene, g, rows=None, mask=True, camera=True, **kw):
+    """render() with GPU leaves -- the scene's and, with ``camera``, eye / at / up -- and masked_loss over the outputs
+    named in g; returns ({leaf: grad ndarray}, result)."""
     from surf_renderer_amd import render
-    if scene_grad:
-        leaf_scene, leaves = _leaf_scene_tch(scene)
-    else:
-        leaf_scene, leaves = copy.deepcopy(scene), {}
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     cam_leaves = {}
     if camera:
-        cam_leaves = _camera_leaves(scene["camera"])
+        cam_leaves = camera_leaves(scene["camera"])
         leaf_scene["camera"] = dict(leaf_scene["camera"], **cam_leaves)
     res = render(leaf_scene, device=DEV, shading="torch", rows=rows, **kw)
-    _loss(res, g, scene["camera"]["far"], mask).backward()
+    masked_loss(res, g, scene["camera"]["far"], mask).backward()
     torch.cuda.synchronize()
-    grads = {k: (t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape)))
-             for k, t in leaves.items()}
+    grads = leaf_grads(leaves)
     for k, t in cam_leaves.items():
         assert t.grad is not None, f"camera.{k} got no gradient"
         assert t.grad.shape == t.shape and t.grad.dtype == t.dtype and t.grad.device == t.device
-        grads["camera." + k] = t.grad.cpu().numpy().astype(np.float64)
+        grads["camera." + k] = to_np(t.grad)
     return grads, res
 
 
-def _winners(res):
-    return {"nearest": res["nearest"].cpu().numpy(), "depth": res["depth"].detach().cpu().numpy().astype(np.float64)}
-
-
 def _helper(scene, g, res, **kw):
-    return camera_oracle.gradients_camera(scene, _winners(res), **{"grad_" + k: v for k, v in g.items()}, **kw)
-
-
-def _compare(got, want, tol=2e-4, tag="", keys=None):
-    for key, w in want.items():
-        if keys is not None and key not in keys:
-            continue
-        assert np.all(np.isfinite(w)), (tag, key)
-        g = got[key].reshape(w.shape)
-        print(tag, key, "max |got - want| / max |want| =", np.abs(g - w).max() / max(np.abs(w).max(), 1e-30))
-        np.testing.assert_allclose(g, w, rtol=0, atol=tol * np.abs(w).max() + 1e-6, err_msg=f"{tag} {key}")
-
-
-CAM_KEYS = camera_oracle.CAMERA_KEYS
+    return gradients_tch(scene, **grad_kwargs(g), ref=winners(res), camera=True, **kw)
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_reference_fixtures_through_render(case):
-    npz, scene, kw = _load(case)
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load(case)
+    g = upstream(npz)
     got, res = _hip(scene, g, **kw)
     same = (res["nearest"].cpu().numpy() == npz["ref/nearest"]) & (npz["ref/depth"] <= scene["camera"]["far"])
     assert same.mean() > 0.995
-    _compare(got, _helper(scene, g, res, **kw), tag=case)
+    assert_grads_close(got, _helper(scene, g, res, **kw), 2e-4, case)
     for key in CAM_KEYS:
         ref = npz["grad/" + key].astype(np.float64)
         print(case, key, "against the reference:", np.abs(got[key] - ref).max() / np.abs(ref).max())
@@ -137,45 +68,45 @@ def test_reference_fixtures_through_render(case):
 
 @pytest.mark.parametrize("ortho", [False, True])
 def test_full_scene_with_spheres(ortho):
-    scene = _full_scene(ortho)
-    g = _random_upstream()
+    scene = full_scene(ortho)
+    g = random_upstream()
     got, res = _hip(scene, g)
     for key in CAM_KEYS:
         assert np.all(np.isfinite(got[key])) and np.abs(got[key]).max() > 0.1, key
-    _compare(got, _helper(scene, g, res), tag=f"spheres ortho={ortho}")
+    assert_grads_close(got, _helper(scene, g, res), 2e-4, f"spheres ortho={ortho}")
 
 
 @pytest.mark.parametrize("case", ["c1_camera_grad_phong", "c1_camera_grad_ortho"])
 def test_each_output_alone_and_linearity(case):
-    npz, scene, kw = _load(case)
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load(case)
+    g = upstream(npz)
     parts = {}
     for which in OUTPUTS:
         parts[which], res = _hip(scene, {which: g[which]}, **kw)
-        _compare(parts[which], _helper(scene, {which: g[which]}, res, **kw), tag=f"{case} {which}")
+        assert_grads_close(parts[which], _helper(scene, {which: g[which]}, res, **kw), 2e-4, f"{case} {which}")
         if which != "image":                                # the geometry-only kernel: no light / colour / material term
-            for key in SHADING_LEAVES:
+            for key in TCH_KEYS:
                 assert np.all(parts[which][key] == 0), (which, key)
     both, _ = _hip(scene, g, **kw)
-    _compare(both, {k: sum(p[k] for p in parts.values()) for k in both}, tag="sum of parts")
+    assert_grads_close(both, {k: sum(p[k] for p in parts.values()) for k in both}, 2e-4, "sum of parts")
 
 
 def test_row_slabs_sum_to_the_whole_frame():
-    npz, scene, kw = _load("c1_camera_grad_phong_ds_quartic")
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load("c1_camera_grad_phong_ds_quartic")
+    g = upstream(npz)
     full, _ = _hip(scene, g, **kw)
     r = 17                                                  # not a multiple of the workgroup's four rows
     top, tres = _hip(scene, {k: v[:r] for k, v in g.items()}, rows=(0, r), **kw)
     bottom, _ = _hip(scene, {k: v[r:] for k, v in g.items()}, rows=(r, 36), **kw)
     assert tres["image"].shape == (r, 48, 3)
-    _compare({k: top[k] + bottom[k] for k in CAM_KEYS}, {k: full[k] for k in CAM_KEYS}, tag="slabs")
+    assert_grads_close({k: top[k] + bottom[k] for k in CAM_KEYS}, {k: full[k] for k in CAM_KEYS}, 2e-4, "slabs")
 
 
 def test_shadow_rays():
     """Visibility is a constant 0 / 1 factor per light: the helper is fed the GPU's own visibility bits."""
     from surf_renderer_amd import render
-    scene = _full_scene()
-    g = _random_upstream()
+    scene = full_scene()
+    g = random_upstream()
     got, res = _hip(scene, g, shadow=True)
     with torch.no_grad():
         plain = render(scene, device=DEV, shading="torch", shadow=True)
@@ -184,14 +115,14 @@ def test_shadow_rays():
     vis = np.stack([((bits >> l) & 1).astype(np.float64).reshape(-1) for l in range(nl)])
     assert 0.02 < 1.0 - vis.mean() < 0.98                   # some lights are shadowed somewhere
     want = _helper(scene, g, res, visibility=vis)
-    _compare(got, want, tag="shadow")
+    assert_grads_close(got, want, 2e-4, "shadow")
     unshadowed = _helper(scene, g, res)
     assert np.abs(want["camera.eye"] - unshadowed["camera.eye"]).max() > 1e-3 * np.abs(want["camera.eye"]).max()
 
 
 def test_structure_and_reproducibility():
-    npz, scene, kw = _load("c1_camera_grad_phong")
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load("c1_camera_grad_phong")
+    g = upstream(npz)
     a, _ = _hip(scene, g, **kw)
     b, _ = _hip(scene, g, **kw)
     for key in CAM_KEYS:
@@ -204,7 +135,7 @@ def test_structure_and_reproducibility():
     leaf_scene = copy.deepcopy(scene)
     up3 = torch.tensor(up, dtype=torch.float32, device=DEV, requires_grad=True)
     leaf_scene["camera"] = dict(leaf_scene["camera"], up=up3)
-    _loss(render(leaf_scene, device=DEV, shading="torch", **kw), g, scene["camera"]["far"]).backward()
+    masked_loss(render(leaf_scene, device=DEV, shading="torch", **kw), g, scene["camera"]["far"]).backward()
     assert up3.grad.shape == (3,)
     assert np.array_equal(up3.grad.cpu().numpy().astype(np.float64), a["camera.up"][:3])
 
@@ -220,7 +151,7 @@ def _bunny(ortho):
                                          requires_grad=True)}
     mesh["objects"]["triangle"] = dict(tri, face=leaves["triangle.face"])
     mesh["lights"]["pos"] = leaves["lights.pos"]
-    cam = _camera_leaves(mesh["camera"])
+    cam = camera_leaves(mesh["camera"])
     mesh["camera"] = dict(mesh["camera"], **cam)
     return mesh, leaves, cam
 
@@ -255,23 +186,23 @@ def test_translation_invariance_on_the_bunny(ortho):
 def test_camera_only():
     """Nothing but the camera requires grad: the render is differentiable and the scene's tensors get no .grad."""
     from surf_renderer_amd import render
-    npz, scene, kw = _load("c1_camera_grad_phong")
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load("c1_camera_grad_phong")
+    g = upstream(npz)
     want, _ = _hip(scene, g, **kw)
-    leaf_scene, leaves = _leaf_scene_tch(scene)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     for t in leaves.values():
         t.requires_grad_(False)
-    cam = _camera_leaves(scene["camera"])
+    cam = camera_leaves(scene["camera"])
     leaf_scene["camera"] = dict(leaf_scene["camera"], **cam)
     res = render(leaf_scene, device=DEV, shading="torch", **kw)
     assert res["image"].requires_grad and res["depth"].requires_grad
-    _loss(res, g, scene["camera"]["far"]).backward()
+    masked_loss(res, g, scene["camera"]["far"]).backward()
     for k, t in leaves.items():
         assert t.grad is None, k
     for k in CAM:
         assert np.array_equal(cam[k].grad.cpu().numpy().astype(np.float64), want["camera." + k]), k
     # norm_depth_image_only: the image is a function of depth alone
-    cam2 = _camera_leaves(scene["camera"])
+    cam2 = camera_leaves(scene["camera"])
     leaf_scene["camera"] = dict(leaf_scene["camera"], **cam2)
     res = render(leaf_scene, device=DEV, shading="torch", norm_depth_image_only=True, **kw)
     res["image"].sum().backward()
@@ -317,14 +248,14 @@ def test_resident_scene_descent_follows_the_reference():
 
 
 def test_float64_cpu_camera_leaf():
-    npz, scene, kw = _load("c1_camera_grad_ortho")
-    g = _upstream(npz, *OUTPUTS)
+    npz, scene, kw = load("c1_camera_grad_ortho")
+    g = upstream(npz)
     want, _ = _hip(scene, g, **kw)
     from surf_renderer_amd import render
     leaf_scene = copy.deepcopy(scene)
-    cam = _camera_leaves(scene["camera"], device="cpu", dtype=torch.float64)
+    cam = camera_leaves(scene["camera"], device="cpu", dtype=torch.float64)
     leaf_scene["camera"] = dict(leaf_scene["camera"], **cam)
-    _loss(render(leaf_scene, device=DEV, shading="torch", **kw), g, scene["camera"]["far"]).backward()
+    masked_loss(render(leaf_scene, device=DEV, shading="torch", **kw), g, scene["camera"]["far"]).backward()
     for k in CAM:
         assert cam[k].grad.dtype == torch.float64 and cam[k].grad.device.type == "cpu" and cam[k].grad.shape == (4,)
         assert np.array_equal(cam[k].grad.numpy(), want["camera." + k]), k
@@ -345,16 +276,16 @@ def test_misses_and_scratch_reuse():
     """Workgroups that leave early (no hit pixel) must not leave a previous frame's partial sums behind: a 48 x 36 frame
     with misses, differentiated right after a full-hit 256 x 192 frame through the same ResidentScene (same scratch)."""
     from surf_renderer_amd import ResidentScene
-    scene = _full_scene(plane=False)
+    scene = full_scene(plane=False)
     small_cam = dict(scene["camera"])
     # looking straight at the largest disc (centre (0.5, 2, -1), radius 2.2) from 4 units away: every pixel hits
     big_cam = dict(scene["camera"], viewport=[0, 0, 256, 192], eye=[0.5, 2.0, 3.0, 1.0], at=[0.5, 2.0, -1.0, 1.0],
                    fovy=float(np.deg2rad(30.0)))
-    g = _random_upstream()
+    g = random_upstream()
 
     def resident(camera):
-        leaf_scene, leaves = _leaf_scene_tch(scene)
-        cam = _camera_leaves(camera)
+        leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
+        cam = camera_leaves(camera)
         leaf_scene["camera"] = dict(camera, **cam)
         return ResidentScene(leaf_scene, device=DEV, shading="torch", aux=True), leaves, cam
 
@@ -362,7 +293,7 @@ def test_misses_and_scratch_reuse():
         for t in cam.values():
             t.grad = None
         res = rs.render()
-        _loss(res, upstream, scene["camera"]["far"], mask).backward()
+        masked_loss(res, upstream, scene["camera"]["far"], mask).backward()
         torch.cuda.synchronize()
         return {"camera." + k: cam[k].grad.cpu().numpy().astype(np.float64) for k in CAM}, res
 
@@ -374,7 +305,7 @@ def test_misses_and_scratch_reuse():
     assert bool((bres["depth"].detach() <= scene["camera"]["far"]).all())           # full hit: every slot written
     assert all(np.abs(big[k]).max() > 0.1 for k in CAM_KEYS)
     scratch = rs.buf.camera_scratch
-    cam_small = _camera_leaves(small_cam)
+    cam_small = camera_leaves(small_cam)
     rs.set_camera(dict(small_cam, **cam_small))
     got, res = backward(rs, cam_small, g)
     assert rs.buf.camera_scratch is scratch                                         # the same scratch
@@ -384,7 +315,7 @@ def test_misses_and_scratch_reuse():
     blocks = [miss[r:r + 4, :].all() for r in range(0, 36, 4)]
     print("miss share", miss.mean(), "workgroups without a hit:", sum(blocks), "of", len(blocks))
     assert sum(blocks) >= 1
-    _compare(got, _helper(scene, g, res), tag="misses", keys=CAM_KEYS)
+    assert_grads_close(got, _helper(scene, g, res), 2e-4, "misses", keys=CAM_KEYS)
     fresh_rs, _, cam_fresh = resident(small_cam)
     fresh, _ = backward(fresh_rs, cam_fresh, g)
     for k in CAM_KEYS:

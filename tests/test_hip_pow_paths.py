@@ -22,9 +22,9 @@ import numpy as np
 import pytest
 import torch
 
+from grad_cases import TCH_KEYS, gpu_leaf_scene, hip_gradients, leaf_grads, masked_loss
 from oracle import np_oracle, np_oracle_tch, torch_oracle
 from pow_scenes import EXPONENTS, GAMMAS, ladder_scene, lobe_scene, without_tonemap
-from test_hip_backward import _hip_gradients, _leaf_scene_tch
 from test_hip_parity import IMAGE_ATOL, IMAGE_RTOL, assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -146,14 +146,12 @@ def _gradients_tch(scene, g_img, **kw):
     """render(shading='torch') under autograd on GPU leaves, and the gradient oracle on the same winners."""
     from surf_renderer_amd import render
     ref = np_oracle_tch.render(scene, **kw)
-    leaf_scene, leaves = _leaf_scene_tch(scene)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     res = render(leaf_scene, device="cuda:0", shading="torch", **kw)
     np.testing.assert_array_equal(res["nearest"].cpu().numpy(), ref["nearest"])
-    torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device="cuda:0")).backward()
+    masked_loss(res, {"image": g_img}).backward()
     torch.cuda.synchronize()
-    got = {k: (t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape)))
-           for k, t in leaves.items()}
-    return got, torch_oracle.gradients_tch(scene, g_img, None, ref=ref, **kw)
+    return leaf_grads(leaves), torch_oracle.gradients_tch(scene, g_img, None, ref=ref, **kw)
 
 
 @pytest.mark.parametrize("shading", SHADINGS)
@@ -167,7 +165,7 @@ def test_tonemap_slope_sweep(gamma, shading):
     if shading == "torch":
         got, want = _gradients_tch(scene, g_img)
     else:
-        got, fwd = _hip_gradients(scene, g_img, None)
+        got, fwd = hip_gradients(scene, g_img, None)
         want = torch_oracle.gradients(scene, g_img, None, ref=fwd)
     w = want["materials.albedo"]
     assert np.all(w[0] == 0) and np.all(w[1:] > 0)          # albedo 0: the clip's side of the tonemap, gradient 0

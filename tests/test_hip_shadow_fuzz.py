@@ -238,23 +238,20 @@ def test_views_and_backward_use_the_high_bits():
 
     # one backward: the oracle is fed the kernel's own bits, so it sees the same decisions and the tolerance is the
     # unshadowed one of tests/test_hip_backward.py
-    from test_hip_backward import _leaf_scene_tch
+    from grad_cases import TCH_KEYS, assert_grads_close, gpu_leaf_scene, leaf_grads
     sc = S.oracle_input(scene)
     ref = np_oracle_tch.render(sc)
     H, W = ref["depth"].shape
     g_img = np.random.RandomState(9).uniform(-1, 1, size=(H, W, 3))
     words = render(scene, device="cuda:0", shading="torch", shadow=True)["light_visibility"].cpu().numpy()
     V = S.unpack_bits(words, n_l)
-    leaf_scene, leaves = _leaf_scene_tch(sc)
+    leaf_scene, leaves = gpu_leaf_scene(sc, TCH_KEYS)
     res = render(leaf_scene, device="cuda:0", shading="torch", shadow=True)
     assert np.array_equal(res["nearest"].cpu().numpy(), ref["nearest"])
     torch.sum(res["image"] * torch.as_tensor(g_img, dtype=torch.float32, device="cuda:0")).backward()
     want = torch_oracle.gradients_tch(sc, g_img, None, ref=ref, visibility=V)
     plain = torch_oracle.gradients_tch(sc, g_img, None, ref=ref)
-    for key, t in leaves.items():
-        got_g = t.grad.cpu().numpy().astype(np.float64) if t.grad is not None else np.zeros(tuple(t.shape))
-        w = want[key].reshape(got_g.shape)
-        np.testing.assert_allclose(got_g, w, atol=2e-4 * max(np.abs(w).max(), 1e-9) + 1e-6, err_msg=key)
+    assert_grads_close(leaf_grads(leaves), want, 2e-4, "34 lights", keys=leaves)
     # the shadows on lights >= 32 reach the backward: they move those lights' position gradients by more than that
     w, p = want["lights.pos"].reshape(n_l, -1)[32:], plain["lights.pos"].reshape(n_l, -1)[32:]
     tol = 2e-4 * max(np.abs(want["lights.pos"]).max(), 1e-9) + 1e-6

@@ -5,8 +5,6 @@ per-view leaves kept per view (the definition pinned to the reference by tests/t
 Tolerances are the project's: against the fp64 oracle  |got - want| <= 2e-4 * max|want| + 1e-6  per array
 (tests/test_hip_backward.py), against the float32 reference fixtures 2e-3 * max|want|.  Frames are 72 x 22: a partial
 64-lane workgroup in x, a partial 4-row workgroup in y, partial 16 x 16 tiles."""
-import copy
-import json
 import os
 
 import numpy as np
@@ -14,86 +12,23 @@ import pytest
 import torch
 
 from conftest import GOLDEN_DIR
+from grad_cases import (DEV, NP_KEYS, TCH_KEYS, assert_array_close, assert_grads_close, gpu_leaf_scene, gpu_tensor,
+                        leaf_grads, masked_loss, to_np, view_winners)
 from oracle import np_oracle_tch, torch_oracle
-from oracle.golden_io import load_case, unpack_scene
-from views_cases import V1_CASES, V1_PER_VIEW, batch_gradients, load_v1, oracle_batch_tch, set_leaf, view_scene
+from oracle.golden_io import load_case
+from views_cases import (AWAY3, KW3, OWN3, V1_CASES, V1_PER_VIEW, H, W, batch_gradients, batch_upstream, load_v1, ortho_case,
+                         oracle_batch_tch, scene3, shadow_case, view_cameras, view_scene, visibility_rows)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-W, H = 72, 22
-TCH_KEYS = ("lights.pos", "lights.attenuation", "lights.ambient", "colors", "materials.albedo", "materials.coeffs")
-NP_KEYS = ("lights.pos", "colors", "materials.albedo")
+
+def _upstream(n, seed, **size):
+    return batch_upstream(n, seed, outputs=("image", "depth"), **size)
 
 
-def _gpu(a, grad=True):
-    return torch.tensor(np.asarray(a, dtype=np.float32), device=DEV, requires_grad=grad)
-
-
-def _get(scene, key):
-    a, _, b = key.partition(".")
-    return scene[a] if not b else (scene[a][b] if a in ("lights", "materials") else scene["objects"][a][b])
-
-
-def _leaf_scene(scene, extra, skip=(), grad=True):
-    """Copy of `scene` whose differentiable arrays (the object leaves and `extra`) are GPU tensors; those not in `skip`
-    require grad.  Returns (scene, {key: tensor that requires grad})."""
-    sc = copy.deepcopy(scene)
-    leaves = {}
-    keys = [f"{kind}.{name}" for kind in sc["objects"] for name in torch_oracle.LEAF_KEYS[kind]] + list(extra)
-    for key in keys:
-        t = _gpu(_get(sc, key), grad and key not in skip)
-        set_leaf(sc, key, t)
-        if t.requires_grad:
-            leaves[key] = t
-    return sc, leaves
-
-
-def _upstream(n, seed, h=H, w=W):
-    rng = np.random.RandomState(seed)
-    g_img = rng.uniform(-1, 1, size=(n, h, w, 3)).astype(np.float32)
-    g_dep = rng.uniform(-1, 1, size=(n, h, w)).astype(np.float32)
-    return g_img, g_dep
-
-
-def _backward(out, g_img, g_dep, far=None):
-    """loss = sum image * g_img + sum over hit pixels of depth * g_dep; hit = depth <= far (torch shading) or finite."""
-    dep = out["depth"]
-    loss = torch.sum(out["image"] * torch.as_tensor(g_img, device=DEV))
-    if g_dep is not None:
-        hit = torch.isfinite(dep) if far is None else dep <= far
-        loss = loss + torch.sum(torch.where(hit, dep * torch.as_tensor(g_dep, device=DEV), torch.zeros_like(dep)))
-    loss.backward()
+def _backward(out, g, far=None):
+    masked_loss(out, g, far).backward()
     torch.cuda.synchronize()
-
-
-def _refs(out):
-    near, dep = out["nearest"].cpu().numpy(), out["depth"].detach().cpu().numpy().astype(np.float64)
-    return [{"nearest": near[v], "depth": dep[v]} for v in range(near.shape[0])]
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-def _close(got, want, tol, tag):
-    want = np.asarray(want, dtype=np.float64)
-    got = np.asarray(got, dtype=np.float64).reshape(want.shape)
-    assert np.all(np.isfinite(want)), tag
-    scale = np.abs(want).max()
-    err = np.abs(got - want).max()
-    print(f"{tag}: max|want| {scale:.4g}  max err {err:.3g}  ({err / max(scale, 1e-30):.2g} of max)")
-    np.testing.assert_allclose(got, want, rtol=0, atol=tol * scale + 1e-6, err_msg=tag)
-
-
-def _cameras(base, eyes, ats=None):
-    cams = []
-    for v, eye in enumerate(eyes):
-        cam = dict(base, viewport=[0, 0, W, H], eye=np.asarray(eye, dtype=np.float64))
-        if ats is not None:
-            cam["at"] = np.asarray(ats[v], dtype=np.float64)
-        cams.append(cam)
-    return cams
 
 
 # ---- 1. the reference's own batch loop ---------------------------------------------------------------------------------
@@ -102,20 +37,20 @@ def test_reference_batch_fixture(case):
     from surf_renderer_amd import render_views
     npz, scene, cams, own, kw = load_v1(case)
     n = len(cams)
-    leaf_scene, leaves = _leaf_scene(scene, TCH_KEYS, skip=V1_PER_VIEW)
-    per_view = [{k: _gpu(own[v][k]) for k in V1_PER_VIEW} for v in range(n)]
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS, skip=V1_PER_VIEW)
+    per_view = [{k: gpu_tensor(own[v][k]) for k in V1_PER_VIEW} for v in range(n)]
     cameras = [dict(scene["camera"], **cams[v]) for v in range(n)]
     out = render_views(leaf_scene, cameras, device=DEV, shading="torch", overrides=per_view, batch=3, **kw)
     assert out["image"].requires_grad and out["depth"].requires_grad and not out["nearest"].requires_grad
     far = float(scene["camera"]["far"])
-    got_dep, want_dep = _np(out["depth"]), npz["ref/depth"].astype(np.float64)
+    got_dep, want_dep = to_np(out["depth"]), npz["ref/depth"].astype(np.float64)
     assert np.array_equal(out["nearest"].cpu().numpy(), npz["ref/nearest"])
     hit = want_dep <= far
     assert np.array_equal(got_dep <= far, hit)
     np.testing.assert_allclose(got_dep[hit], want_dep[hit], rtol=2e-5)
     np.testing.assert_allclose(got_dep[~hit], far + 1.0)
-    np.testing.assert_allclose(_np(out["image"]), npz["ref/image"], atol=3e-4)
-    _backward(out, npz["grad_in/image"], npz["grad_in/depth"], far)
+    np.testing.assert_allclose(to_np(out["image"]), npz["ref/image"], atol=3e-4)
+    _backward(out, {"image": npz["grad_in/image"], "depth": npz["grad_in/depth"]}, far)
     checked = 0
     for key in npz.files:
         if not key.startswith("grad/"):
@@ -124,7 +59,7 @@ def test_reference_batch_fixture(case):
         want = npz[key].astype(np.float64)
         t = leaves[parts[0]] if len(parts) == 1 else per_view[int(parts[1])][parts[0]]
         assert t.grad is not None, key
-        got = _np(t.grad).reshape(want.shape)
+        got = to_np(t.grad).reshape(want.shape)
         if parts[0] in ("lights.pos", "plane.pos", "disk.pos"):
             got, want = got[..., :3], want[..., :3]
         np.testing.assert_allclose(got, want, rtol=0, atol=2e-3 * max(np.abs(want).max(), 1e-6), err_msg=key)
@@ -143,22 +78,21 @@ def test_numpy_shading_shared_leaves(case):
     scene, _, _ = load_case(os.path.join(GOLDEN_DIR, case + ".npz"))
     eye = np.asarray(scene["camera"]["eye"], dtype=np.float64)
     step = 0.05 if case.startswith("g8a") else 0.4
-    cameras = _cameras(scene["camera"], [eye, eye + step * np.array([1.0, 0.5, 0.0, 0.0]),
+    cameras = view_cameras(scene["camera"], [eye, eye + step * np.array([1.0, 0.5, 0.0, 0.0]),
                                          eye + step * np.array([-0.8, 0.4, 1.0, 0.0])])
     n = len(cameras)
-    leaf_scene, leaves = _leaf_scene(scene, NP_KEYS)
+    leaf_scene, leaves = gpu_leaf_scene(scene, NP_KEYS)
     out = render_views(leaf_scene, cameras, device=DEV)
     assert out["image"].requires_grad
-    g_img, g_dep = _upstream(n, 3)
-    _backward(out, g_img, g_dep)
-    refs = _refs(out)
+    g = _upstream(n, 3)
+    _backward(out, g)
+    refs = view_winners(out)
     assert all(np.isfinite(r["depth"]).any() for r in refs)
-    per_view = [torch_oracle.gradients(view_scene(scene, cameras[v]), g_img[v].astype(np.float64),
-                                       g_dep[v].astype(np.float64), ref=refs[v]) for v in range(n)]
+    per_view = [torch_oracle.gradients(view_scene(scene, cameras[v]), g["image"][v].astype(np.float64),
+                                       g["depth"][v].astype(np.float64), ref=refs[v]) for v in range(n)]
     want, _ = batch_gradients(per_view, ())
     assert set(want) == set(leaves)
-    for key, w in want.items():
-        _close(_np(leaves[key].grad), w, 2e-4, f"{case} {key}")
+    assert_grads_close(leaf_grads(leaves), want, 2e-4, case)
     assert any(np.abs(w).max() > 0 for w in want.values())
     if "disk.radius" in leaves:
         assert not leaves["disk.radius"].grad.any()
@@ -167,33 +101,12 @@ def test_numpy_shading_shared_leaves(case):
 
 
 # ---- 3. torch shading, everything at once -------------------------------------------------------------------------------
-OWN3 = ("disk.pos", "disk.normal", "lights.pos")
-KW3 = {"double_sided": True, "use_quartic": True}
-EYES3 = [[0.3, 1.0, 10.0, 1.0], [2.5, -0.5, 9.0, 1.0], [0.0, 0.5, 30.0, 1.0], [-3.0, 2.0, 8.5, 1.0], [1.0, 3.0, 9.5, 1.0]]
-ATS3 = [[0.0, 0.0, 0.0, 1.0], [0.5, 0.2, 0.0, 1.0], [0.0, 0.5, 60.0, 1.0], [-0.5, 0.3, -1.0, 1.0], [0.2, -0.2, 0.5, 1.0]]
-AWAY3 = 2
-
-
-def _scene3():
-    scene = unpack_scene(np.load(os.path.join(GOLDEN_DIR, "g10_torch_autograd_phong_ds_quartic.npz"), allow_pickle=False))
-    assert "sphere" in scene["objects"]
-    rng = np.random.RandomState(31)
-    n = len(EYES3)
-    own = {}
-    for key, amp in (("disk.pos", 0.4), ("disk.normal", 0.2), ("lights.pos", 0.8)):
-        base = np.asarray(_get(scene, key), dtype=np.float64)
-        off = rng.uniform(-amp, amp, size=(n,) + base.shape)
-        off[..., 3] = 0.0
-        own[key] = (base[None] + off).astype(np.float32).astype(np.float64)
-    return scene, _cameras(scene["camera"], EYES3, ATS3), own
-
-
 def _run3(scene, cameras, own, grad_own=OWN3, grad_shared=True, batch=2):
     """The batch of case 3; returns (out, shared leaves that require grad, stacked per-view parents)."""
     from surf_renderer_amd import render_views
     n = len(cameras)
-    leaf_scene, leaves = _leaf_scene(scene, TCH_KEYS, skip=OWN3, grad=grad_shared)
-    parents = {k: _gpu(own[k], k in grad_own) for k in OWN3}
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS, skip=OWN3, grad=grad_shared)
+    parents = {k: gpu_tensor(own[k], k in grad_own) for k in OWN3}
     overrides = [{k: parents[k][v] for k in OWN3} for v in range(n)]          # slices: not leaves
     out = render_views(leaf_scene, cameras, device=DEV, shading="torch", overrides=overrides, batch=batch, **KW3)
     return out, leaves, parents
@@ -201,19 +114,18 @@ def _run3(scene, cameras, own, grad_own=OWN3, grad_shared=True, batch=2):
 
 @pytest.fixture(scope="module")
 def case3():
-    scene, cameras, own = _scene3()
+    scene, cameras, own = scene3()
     n = len(cameras)
-    g_img, g_dep = _upstream(n, 5)
+    g = _upstream(n, 5)
     out, leaves, parents = _run3(scene, cameras, own)
     far = float(scene["camera"]["far"])
-    _backward(out, g_img, g_dep, far)
-    refs = _refs(out)
+    _backward(out, g, far)
+    refs = view_winners(out)
     scenes = [view_scene(scene, cameras[v], {k: own[k][v] for k in OWN3}) for v in range(n)]
-    shared, per_view = oracle_batch_tch(scenes, g_img.astype(np.float64), g_dep.astype(np.float64), refs, OWN3, **KW3)
-    got = {k: _np(t.grad) for k, t in leaves.items()}
-    got.update({k: _np(t.grad) for k, t in parents.items()})
+    shared, per_view = oracle_batch_tch(scenes, g, refs, OWN3, **KW3)
+    got = {k: to_np(t.grad) for k, t in {**leaves, **parents}.items()}
     fwd = {k: out[k].detach().clone() for k in ("image", "depth", "nearest")}
-    return dict(scene=scene, cameras=cameras, own=own, g_img=g_img, g_dep=g_dep, far=far, refs=refs, shared=shared,
+    return dict(scene=scene, cameras=cameras, own=own, g=g, far=far, refs=refs, shared=shared,
                 per_view=per_view, got=got, fwd=fwd, leaves=leaves)
 
 
@@ -226,12 +138,11 @@ def test_torch_shading_everything_at_once(case3):
         sc = view_scene(c["scene"], c["cameras"][v], {k: c["own"][k][v] for k in OWN3})
         assert np.array_equal(ref["nearest"], np_oracle_tch.render(sc, **KW3)["nearest"]), f"view {v}"
     assert len(c["shared"]) == 12 and set(c["shared"]) == set(c["leaves"])
-    for key, want in c["shared"].items():
-        _close(c["got"][key], want, 2e-4, f"shared {key}")
+    assert_grads_close(c["got"], c["shared"], 2e-4, "shared")
     for key in OWN3:
         assert c["got"][key].shape[0] == n
         for v in range(n):
-            _close(c["got"][key][v], c["per_view"][key][v], 2e-4, f"{key}[{v}]")
+            assert_array_close(c["got"][key][v], c["per_view"][key][v], 2e-4, f"{key}[{v}]")
         assert not c["got"][key][AWAY3].any() and all(c["got"][key][v].any() for v in range(n) if v != AWAY3)
     assert not c["got"]["disk.radius"].any()
     assert not c["got"]["triangle.face"][:, 1:, :].any()
@@ -240,61 +151,44 @@ def test_torch_shading_everything_at_once(case3):
 # ---- 4. shadow rays ---------------------------------------------------------------------------------------------------
 def test_shadow_rays_with_per_view_lights():
     from surf_renderer_amd import render_views
-    npz = np.load(os.path.join(GOLDEN_DIR, "s1a_mixed_shadow_64x48.npz"), allow_pickle=False)
-    scene = unpack_scene(npz)
-    kw = {k: v for k, v in json.loads(str(npz["kwargs"])).items() if k != "shadow"}
-    eye = np.asarray(scene["camera"]["eye"], dtype=np.float64)
-    cameras = _cameras(scene["camera"], [eye, eye + np.array([0.5, 0.2, 0.0, 0.0]), eye + np.array([-0.4, 0.3, 0.4, 0.0])])
+    scene, kw, cameras, lights = shadow_case()
     n = len(cameras)
-    rng = np.random.RandomState(17)
-    base = np.asarray(scene["lights"]["pos"], dtype=np.float64)
-    off = rng.uniform(-0.5, 0.5, size=(n,) + base.shape)
-    off[..., 3] = 0.0
-    lights = (base[None] + off).astype(np.float32).astype(np.float64)
-    leaf_scene, leaves = _leaf_scene(scene, TCH_KEYS, skip=("lights.pos",))
-    parent = _gpu(lights)
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS, skip=("lights.pos",))
+    parent = gpu_tensor(lights)
     out = render_views(leaf_scene, cameras, device=DEV, shading="torch", shadow=True,
                        overrides=[{"lights.pos": parent[v]} for v in range(n)], **kw)
     assert out["image"].requires_grad and not out["visibility"].requires_grad
-    g_img, g_dep = _upstream(n, 9)
+    g = _upstream(n, 9)
     far = float(scene["camera"]["far"])
-    _backward(out, g_img, g_dep, far)
-    bits = out["visibility"].cpu().numpy()
-    nl = base.shape[0]
-    vis = [np.stack([((bits[v] >> l) & 1).astype(np.float64).reshape(-1) for l in range(nl)]) for v in range(n)]
-    hit = _np(out["depth"]) <= far
+    _backward(out, g, far)
+    vis = visibility_rows(out["visibility"].cpu().numpy(), lights.shape[1])
+    hit = to_np(out["depth"]) <= far
     shadowed = 1.0 - np.mean([vis[v][:, hit[v].reshape(-1)].mean() for v in range(n)])
     assert 0.01 < shadowed < 0.99                           # the scene does cast shadows
     scenes = [view_scene(scene, cameras[v], {"lights.pos": lights[v]}) for v in range(n)]
-    shared, per_view = oracle_batch_tch(scenes, g_img.astype(np.float64), g_dep.astype(np.float64), _refs(out),
-                                        ("lights.pos",), visibility=vis, **kw)
-    for key, want in shared.items():
-        _close(_np(leaves[key].grad), want, 2e-4, f"shadow {key}")
+    shared, per_view = oracle_batch_tch(scenes, g, view_winners(out), ("lights.pos",), visibility=vis, **kw)
+    assert_grads_close(leaf_grads(leaves), shared, 2e-4, "shadow")
     for v in range(n):
-        _close(_np(parent.grad)[v], per_view["lights.pos"][v], 2e-4, f"shadow lights.pos[{v}]")
-    plain, _ = oracle_batch_tch(scenes, g_img.astype(np.float64), g_dep.astype(np.float64), _refs(out), ("lights.pos",), **kw)
+        assert_array_close(to_np(parent.grad)[v], per_view["lights.pos"][v], 2e-4, f"shadow lights.pos[{v}]")
+    plain, _ = oracle_batch_tch(scenes, g, view_winners(out), ("lights.pos",), **kw)
     assert np.abs(plain["materials.albedo"] - shared["materials.albedo"]).max() > 1e-3 * np.abs(shared["materials.albedo"]).max()
 
 
 # ---- 5. orthographic views ----------------------------------------------------------------------------------------------
 def test_orthographic_views():
     from surf_renderer_amd import render_views
-    scene = unpack_scene(np.load(os.path.join(GOLDEN_DIR, "g11_torch_autograd_ortho.npz"), allow_pickle=False))
-    assert scene["camera"]["proj_type"] == "ortho"
-    eye = np.asarray(scene["camera"]["eye"], dtype=np.float64)
-    cameras = _cameras(scene["camera"], [eye, eye + np.array([1.0, -0.5, 0.0, 0.0])])
-    leaf_scene, leaves = _leaf_scene(scene, TCH_KEYS)
+    scene, cameras = ortho_case()
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS)
     out = render_views(leaf_scene, cameras, device=DEV, shading="torch")
-    g_img, g_dep = _upstream(2, 13)
+    g = _upstream(2, 13)
     far = float(scene["camera"]["far"])
-    _backward(out, g_img, g_dep, far)
-    refs = _refs(out)
+    _backward(out, g, far)
+    refs = view_winners(out)
     assert all((r["depth"] <= far).mean() > 0.3 for r in refs)
     scenes = [view_scene(scene, cam) for cam in cameras]
-    want, _ = oracle_batch_tch(scenes, g_img.astype(np.float64), g_dep.astype(np.float64), refs, ())
+    want, _ = oracle_batch_tch(scenes, g, refs, ())
     assert set(want) == set(leaves)
-    for key, w in want.items():
-        _close(_np(leaves[key].grad), w, 2e-4, f"ortho {key}")
+    assert_grads_close(leaf_grads(leaves), want, 2e-4, "ortho")
 
 
 # ---- 6. large runs: the workgroup-merge path of scatter_primitive_grads -----------------------------------------------------
@@ -314,17 +208,16 @@ def test_plane_filling_every_workgroup():
                                    "material_idx": np.array([0])}},
              "tonemap": {"type": "gamma", "gamma": 0.8}}
     cameras = [dict(scene["camera"], eye=np.array(e, dtype=np.float64)) for e in ([0.3, 2.0, 6.0, 1.0], [-1.0, 1.0, 7.0, 1.0])]
-    leaf_scene, leaves = _leaf_scene(scene, NP_KEYS)
+    leaf_scene, leaves = gpu_leaf_scene(scene, NP_KEYS)
     out = render_views(leaf_scene, cameras, device=DEV)
     assert torch.isfinite(out["depth"]).all() and not out["nearest"].any()      # the plane wins every pixel
-    g_img, g_dep = _upstream(2, 19, h=8, w=128)
-    _backward(out, g_img, g_dep)
-    refs = _refs(out)
-    per_view = [torch_oracle.gradients(view_scene(scene, cameras[v]), g_img[v].astype(np.float64),
-                                       g_dep[v].astype(np.float64), ref=refs[v]) for v in range(2)]
+    g = _upstream(2, 19, h=8, w=128)
+    _backward(out, g)
+    refs = view_winners(out)
+    per_view = [torch_oracle.gradients(view_scene(scene, cameras[v]), g["image"][v].astype(np.float64),
+                                       g["depth"][v].astype(np.float64), ref=refs[v]) for v in range(2)]
     want, _ = batch_gradients(per_view, ())
-    for key, w in want.items():
-        _close(_np(leaves[key].grad), w, 2e-4, f"plane {key}")
+    assert_grads_close(leaf_grads(leaves), want, 2e-4, "plane")
     assert np.abs(want["plane.pos"]).max() > 0 and np.abs(want["plane.normal"]).max() > 0
 
 
@@ -334,11 +227,11 @@ def test_only_one_override_requires_grad(case3):
     out, leaves, parents = _run3(c["scene"], c["cameras"], c["own"], grad_own=("lights.pos",), grad_shared=False)
     assert not leaves and out["image"].requires_grad
     assert torch.equal(out["image"], c["fwd"]["image"]) and torch.equal(out["nearest"], c["fwd"]["nearest"])
-    _backward(out, c["g_img"], c["g_dep"], c["far"])
+    _backward(out, c["g"], c["far"])
     assert parents["disk.pos"].grad is None and parents["disk.normal"].grad is None
-    got = _np(parents["lights.pos"].grad)
+    got = to_np(parents["lights.pos"].grad)
     for v in range(got.shape[0]):
-        _close(got[v], c["per_view"]["lights.pos"][v], 2e-4, f"lights.pos[{v}] alone")
+        assert_array_close(got[v], c["per_view"]["lights.pos"][v], 2e-4, f"lights.pos[{v}] alone")
     # ... and the value of the full case, to the run-to-run spread of the atomic sums
     full = c["got"]["lights.pos"]
     assert np.abs(got - full).max() <= 2e-5 * np.abs(full).max()
@@ -363,8 +256,8 @@ def test_second_call_gives_the_same_frames_and_gradients(case3):
     out, leaves, parents = _run3(c["scene"], c["cameras"], c["own"])
     for k in ("image", "depth", "nearest"):
         assert torch.equal(out[k].detach(), c["fwd"][k]), k
-    _backward(out, c["g_img"], c["g_dep"], c["far"])
-    again = {k: _np(t.grad) for k, t in {**leaves, **parents}.items()}
+    _backward(out, c["g"], c["far"])
+    again = {k: to_np(t.grad) for k, t in {**leaves, **parents}.items()}
     assert set(again) == set(c["got"])
     for key, a in again.items():
         b = c["got"][key]
@@ -397,7 +290,7 @@ def test_backward_leaves_the_bin_counters_alone(case3):
     for v in range(n):
         grads[v].albedo = g_alb.data_ptr()
         grads[v].pos[buf.kinds.index("disk")] = g_pos.data_ptr()
-    g_img = torch.as_tensor(c["g_img"][:n], device=DEV).contiguous()
+    g_img = torch.as_tensor(c["g"]["image"][:n], device=DEV).contiguous()
     assert R.render_views_bwd_buffers(buf, cams, g_img, None, near_a, dep_a, grads, workspace=ws, **kw) is ws
     assert R._ws_state(ws) == state                          # still noted clean: the next forward clears nothing
     img_b, dep_b, near_b = frames()

@@ -1,57 +1,26 @@
 """GPU: render_views with the torch backend's normal / pos outputs (srh_render_views_aux) and, under autograd, with camera
 leaves and upstream gradients of all four outputs (srh_render_views_bwd_camera: the kAux / kCam instantiations of
 k_render_bwd_tch_views, then k_camera_finish_views -- one backward launch and one finish launch per chunk of views),
-against render() per view and against the fp64 helper tests/camera_oracle.py fed the GPU frames' winners.
+against render() per view and against the fp64 oracle with the camera in its graph (oracle/torch_oracle.gradients_tch,
+camera=True) fed the GPU frames' winners.
 
 Tolerances are the project's own (tests/test_hip_camera_grad.py): per array |got - want| <= 2e-4 * max|want| + 1e-6
 against the helper, 2e-5 of the largest entry between two runs of the fp32-atomic scene gradients; the camera gradients
 of a batch against render() per view 1e-6 * max|want| (float32 roundings of fp64 sums formed in the same fixed order).
 Frames are 72 x 22: a partial 64-lane workgroup in x, a partial 4-row workgroup in y, partial 16 x 16 tiles."""
 import copy
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-import camera_oracle
-from conftest import GOLDEN_DIR
-from oracle.golden_io import unpack_scene
-from test_hip_backward import _leaf_scene_tch
-from test_hip_views_backward import (AWAY3, EYES3, KW3, OWN3, TCH_KEYS, H, W, _cameras, _close, _gpu, _leaf_scene,
-                                     _np, _scene3)
-from views_cases import batch_gradients, view_scene
+from grad_cases import (CAM, DEV, RUN_TO_RUN, TCH_KEYS, assert_array_close, assert_grads_close, gpu_leaf_scene,
+                        gpu_tensor, leaf_grads, masked_loss, to_np, view_winners)
+from oracle.torch_oracle import CAMERA_KEYS as CAM_KEYS, OUTPUTS
+from views_cases import (AWAY3, EYES3, KW3, OWN3, H, W, batch_upstream, oracle_batch_tch, ortho_case, scene3, shadow_case, view_scene,
+                         visibility_rows)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-CAM = ("eye", "at", "up")
-CAM_KEYS = camera_oracle.CAMERA_KEYS
-OUTPUTS = ("image", "depth", "normal", "pos")
-SHADING_LEAVES = ("lights.pos", "colors", "materials.albedo", "materials.coeffs", "lights.attenuation", "lights.ambient")
-RUN_TO_RUN = 2e-5
-
-
-def _upstream(n, seed, h=H, w=W):
-    rng = np.random.RandomState(seed)
-    g = {"image": rng.uniform(-1, 1, size=(n, h, w, 3)), "depth": rng.uniform(-1, 1, size=(n, h, w)),
-         "normal": rng.uniform(-1, 1, size=(n, h, w, 3)), "pos": rng.uniform(-1, 1, size=(n, h, w, 3))}
-    return {k: v.astype(np.float32) for k, v in g.items()}
-
-
-def _loss(out, g, far, v=None):
-    """sum image g_i + sum over hit pixels of (depth g_d + normal . g_n + pos . g_p), over the outputs named in g; with
-    ``v`` the upstream arrays are sliced to that view (out is then one frame)."""
-    hit = out["depth"].detach() <= float(far)
-    loss = torch.zeros((), device=DEV)
-    for k, up in g.items():
-        term = out[k] * torch.as_tensor(up if v is None else up[v], dtype=torch.float32, device=DEV)
-        if k != "image":
-            term = torch.where(hit if k == "depth" else hit[..., None], term, torch.zeros_like(term))
-        loss = loss + term.sum()
-    return loss
-
 
 def _cam_tensors(cameras, which=None):
     """Per view: float32 GPU tensors of eye / at / up; those named by which(v) (default all three) require grad."""
@@ -68,8 +37,8 @@ def _run(scene, cameras, own, cam=None, grad_own=OWN3, grad_shared=True, batch=2
     (out, shared leaves that require grad, stacked per-view parents, per-view camera tensors)."""
     from surf_renderer_amd import render_views
     n = len(cameras)
-    leaf_scene, leaves = _leaf_scene(scene, TCH_KEYS, skip=tuple(own), grad=grad_shared)
-    parents = {k: _gpu(own[k], k in grad_own) for k in own}
+    leaf_scene, leaves = gpu_leaf_scene(scene, TCH_KEYS, skip=tuple(own), grad=grad_shared)
+    parents = {k: gpu_tensor(own[k], k in grad_own) for k in own}
     overrides = [{k: parents[k][v] for k in own} for v in range(n)] if own else None
     cams = cam_tensors if cam_tensors is not None else _cam_tensors(cameras, cam)
     out = render_views(leaf_scene, [dict(cameras[v], **cams[v]) for v in range(n)], device=DEV, shading="torch",
@@ -77,17 +46,9 @@ def _run(scene, cameras, own, cam=None, grad_own=OWN3, grad_shared=True, batch=2
     return out, leaves, parents, cams
 
 
-def _refs(out):
-    near, dep = out["nearest"].cpu().numpy(), out["depth"].detach().cpu().numpy().astype(np.float64)
-    return [{"nearest": near[v], "depth": dep[v]} for v in range(near.shape[0])]
-
-
-def _helper(scenes, g, refs, own_keys, visibility=None, **kw):
-    """camera_oracle per view -> (shared: summed over the views, own: {key: [per view]}; the camera keys are own)."""
-    per_view = [camera_oracle.gradients_camera(sc, refs[v], **{"grad_" + k: a[v].astype(np.float64) for k, a in g.items()},
-                                               visibility=None if visibility is None else visibility[v], **kw)
-                for v, sc in enumerate(scenes)]
-    return batch_gradients(per_view, tuple(own_keys) + CAM_KEYS)
+def _helper(scenes, g, refs, own_keys, **kw):
+    """The camera oracle per view -> (shared: summed over the views, own: {key: [per view]}; the camera keys are own)."""
+    return oracle_batch_tch(scenes, g, refs, own_keys, camera=True, **kw)
 
 
 def _cam_grads(cams):
@@ -121,7 +82,7 @@ def _compare_cameras(got, want, tag, away=None):
         for v, w in enumerate(want[key]):
             if got[key][v] is None:
                 continue
-            _close(got[key][v], w, 2e-4, f"{tag} {key}[{v}]")
+            assert_array_close(got[key][v], w, 2e-4, f"{tag} {key}[{v}]")
             assert got[key][v][3] == 0.0
             if v == away:
                 assert not got[key][v].any(), f"{tag} {key}[{v}]: the look-away view's gradient is not zero"
@@ -134,25 +95,24 @@ def _hits(refs, far):
 # ---- the five-view batch of tests/test_hip_views_backward.py case 3, once per module -----------------------------------------
 @pytest.fixture(scope="module")
 def base():
-    scene, cameras, own = _scene3()
+    scene, cameras, own = scene3()
     return dict(scene=scene, cameras=cameras, own=own, n=len(cameras), far=float(scene["camera"]["far"]),
-                g=_upstream(len(cameras), 5),
+                g=batch_upstream(len(cameras), 5),
                 scenes=[view_scene(scene, cameras[v], {k: own[k][v] for k in OWN3}) for v in range(len(cameras))])
 
 
 def _everything(b):
     out, leaves, parents, cams = _run(b["scene"], b["cameras"], b["own"])
-    _loss(out, b["g"], b["far"]).backward()
+    masked_loss(out, b["g"], b["far"]).backward()
     torch.cuda.synchronize()
-    got = {k: _np(t.grad) for k, t in leaves.items()}
-    got.update({k: _np(t.grad) for k, t in parents.items()})
+    got = {k: to_np(t.grad) for k, t in {**leaves, **parents}.items()}
     return out, got, _cam_grads(cams), cams
 
 
 @pytest.fixture(scope="module")
 def case2(base):
     out, got, got_cam, cams = _everything(base)
-    refs = _refs(out)
+    refs = view_winners(out)
     shared, per_view = _helper(base["scenes"], base["g"], refs, OWN3, **KW3)
     fwd = {k: out[k].detach().clone() for k in ("image", "depth", "nearest", "normal", "pos")}
     return dict(base, out=out, got=got, got_cam=got_cam, refs=refs, shared=shared, per_view=per_view, fwd=fwd)
@@ -171,7 +131,7 @@ def test_forward_aux_equals_render_per_view(base, batch):
         assert set(plain) == {"image", "depth", "nearest"} and set(out) == set(plain) | {"normal", "pos"}
         for k in plain:
             assert torch.equal(out[k], plain[k]), k
-        hits = _hits(_refs(out), b["far"])
+        hits = _hits(view_winners(out), b["far"])
         assert hits[AWAY3] == 0 and all(h > 0.5 for v, h in enumerate(hits) if v != AWAY3)
         for k in ("normal", "pos"):
             assert out[k].shape == (b["n"], H, W, 3) and out[k].dtype == torch.float32
@@ -184,16 +144,9 @@ def test_forward_aux_equals_render_per_view(base, batch):
             assert torch.equal(out["image"][v], one["image"]) and torch.equal(out["depth"][v], one["depth"])
 
 
-def _ortho_case():
-    scene = unpack_scene(np.load(os.path.join(GOLDEN_DIR, "g11_torch_autograd_ortho.npz"), allow_pickle=False))
-    assert scene["camera"]["proj_type"] == "ortho"
-    eye = np.asarray(scene["camera"]["eye"], dtype=np.float64)
-    return scene, _cameras(scene["camera"], [eye, eye + np.array([1.0, -0.5, 0.0, 0.0])])
-
-
 def test_forward_aux_orthographic_views():
     from surf_renderer_amd import render, render_views
-    scene, cameras = _ortho_case()
+    scene, cameras = ortho_case()
     with torch.no_grad():
         plain = render_views(scene, cameras, device=DEV, shading="torch")
         out = render_views(scene, cameras, device=DEV, shading="torch", aux=True)
@@ -216,14 +169,12 @@ def test_camera_gradients_everything_at_once(case2):
     _check_wanted(c["per_view"], AWAY3)
     _compare_cameras(c["got_cam"], c["per_view"], "all", AWAY3)
     assert len(c["shared"]) == 12
-    for key, want in c["shared"].items():
-        assert np.all(np.isfinite(want))
-        _close(c["got"][key], want, 2e-4, f"shared {key}")
+    assert_grads_close(c["got"], c["shared"], 2e-4, "shared")
     assert any(np.abs(w).max() > 0 for w in c["shared"].values())
     for key in OWN3:
         assert c["got"][key].shape[0] == n
         for v in range(n):
-            _close(c["got"][key][v], c["per_view"][key][v], 2e-4, f"{key}[{v}]")
+            assert_array_close(c["got"][key][v], c["per_view"][key][v], 2e-4, f"{key}[{v}]")
         assert not c["got"][key][AWAY3].any()
     assert not c["got"]["disk.radius"].any()
 
@@ -234,13 +185,13 @@ def test_batch_equals_render_per_view(case2):
     c = case2
     sums = {}
     for v in range(c["n"]):
-        leaf_scene, leaves = _leaf_scene_tch(c["scenes"][v])
+        leaf_scene, leaves = gpu_leaf_scene(c["scenes"][v], TCH_KEYS)
         cam = _cam_tensors([c["cameras"][v]])[0]
         leaf_scene["camera"] = dict(leaf_scene["camera"], **cam)
         res = render(leaf_scene, device=DEV, shading="torch", **KW3)
         for k in ("normal", "pos"):
             assert torch.equal(res[k].detach(), c["fwd"][k][v]), (v, k)
-        _loss(res, c["g"], c["far"], v).backward()
+        masked_loss(res, {k: a[v] for k, a in c["g"].items()}, c["far"]).backward()
         torch.cuda.synchronize()
         for k in CAM:
             want = cam[k].grad.cpu().numpy().astype(np.float64)
@@ -250,7 +201,7 @@ def test_batch_equals_render_per_view(case2):
             print(f"view {v} camera.{k}: bit-equal {np.array_equal(got, want)}, max |delta| {err:.3g} of {np.abs(want).max():.4g}")
             assert err <= 1e-6 * np.abs(want).max(), (v, k)
         for key, t in leaves.items():
-            g = _np(t.grad)
+            g = to_np(t.grad)
             if key in OWN3:
                 want, got = g, c["got"][key][v]
                 assert np.abs(got.reshape(want.shape) - want).max() <= RUN_TO_RUN * max(np.abs(want).max(), 1e-30), (v, key)
@@ -286,21 +237,21 @@ def test_geometry_only_losses(case2, outputs):
     g = {k: c["g"][k] for k in outputs}
     out, leaves, parents, cams = _run(c["scene"], c["cameras"], c["own"])
     assert torch.equal(out["image"].detach(), c["fwd"]["image"])
-    _loss(out, g, c["far"]).backward()
+    masked_loss(out, g, c["far"]).backward()
     torch.cuda.synchronize()
     shared, per_view = _helper(c["scenes"], g, c["refs"], OWN3, **KW3)
     _check_wanted({k: per_view[k] for k in CAM_KEYS + ("disk.pos", "disk.normal")}, AWAY3)
     _compare_cameras(_cam_grads(cams), per_view, "+".join(outputs), AWAY3)
     for key, want in shared.items():
-        got = _np(leaves[key].grad)
-        if key in SHADING_LEAVES:                           # they require grad; the geometry-only kernel leaves them alone
+        got = to_np(leaves[key].grad)
+        if key in TCH_KEYS:                                # they require grad; the geometry-only kernel leaves them alone
             assert not got.any() and not want.any(), key
         else:
-            _close(got, want, 2e-4, f"{'+'.join(outputs)} {key}")
+            assert_array_close(got, want, 2e-4, f"{'+'.join(outputs)} {key}")
     assert parents["lights.pos"].grad is not None and not parents["lights.pos"].grad.any()
     for key in ("disk.pos", "disk.normal"):
         for v in range(c["n"]):
-            _close(_np(parents[key].grad)[v], per_view[key][v], 2e-4, f"{'+'.join(outputs)} {key}[{v}]")
+            assert_array_close(to_np(parents[key].grad)[v], per_view[key][v], 2e-4, f"{'+'.join(outputs)} {key}[{v}]")
 
 
 # ---- 6. partial wants ----------------------------------------------------------------------------------------------------------
@@ -312,7 +263,7 @@ def test_only_two_camera_tensors_require_grad(case2):
     assert not leaves and not any(p.requires_grad for p in parents.values())
     assert out["image"].requires_grad and out["pos"].requires_grad
     assert torch.equal(out["image"].detach(), c["fwd"]["image"])
-    _loss(out, c["g"], c["far"]).backward()
+    masked_loss(out, c["g"], c["far"]).backward()
     torch.cuda.synchronize()
     for v, cam in enumerate(cams):
         for k in CAM:
@@ -331,12 +282,12 @@ def test_one_up_vector_shared_by_all_views(case2):
                        requires_grad=True)
     cams = [{"up": up3} for _ in range(c["n"])]
     out, _, _, _ = _run(c["scene"], c["cameras"], c["own"], grad_own=(), grad_shared=False, cam_tensors=cams)
-    _loss(out, c["g"], c["far"]).backward()
+    masked_loss(out, c["g"], c["far"]).backward()
     torch.cuda.synchronize()
     want = sum(c["per_view"]["camera.up"][v][:3] for v in range(c["n"]))
     assert up3.grad is not None and up3.grad.shape == (3,)
     assert np.all(np.isfinite(want)) and np.abs(want).max() > 0
-    _close(_np(up3.grad), want, 2e-4, "shared up")
+    assert_array_close(to_np(up3.grad), want, 2e-4, "shared up")
 
 
 def test_eyes_as_rows_of_one_pose_tensor(case2):
@@ -344,12 +295,12 @@ def test_eyes_as_rows_of_one_pose_tensor(case2):
     parent = torch.tensor(np.asarray(EYES3, dtype=np.float64), dtype=torch.float32, device=DEV, requires_grad=True)
     cams = [{"eye": parent[v]} for v in range(c["n"])]         # non-leaf slices
     out, _, _, _ = _run(c["scene"], c["cameras"], c["own"], grad_own=(), grad_shared=False, cam_tensors=cams)
-    _loss(out, c["g"], c["far"]).backward()
+    masked_loss(out, c["g"], c["far"]).backward()
     torch.cuda.synchronize()
     assert parent.grad is not None and parent.grad.shape == (c["n"], 4)
-    got = _np(parent.grad)
+    got = to_np(parent.grad)
     for v in range(c["n"]):
-        _close(got[v], c["per_view"]["camera.eye"][v], 2e-4, f"pose row {v}")
+        assert_array_close(got[v], c["per_view"]["camera.eye"][v], 2e-4, f"pose row {v}")
     assert not got[AWAY3].any() and all(got[v].any() for v in range(c["n"]) if v != AWAY3)
 
 
@@ -362,11 +313,11 @@ def test_no_grad_and_numpy_shading_leave_the_cameras_alone(case2):
         assert not out[k].requires_grad and out[k].grad_fn is None
         assert torch.equal(out[k], c["fwd"][k]), k
     # numpy shading: the camera tensors are read, never attached
-    leaf_scene, leaves = _leaf_scene(c["scene"], ("lights.pos",))
+    leaf_scene, leaves = gpu_leaf_scene(c["scene"], ("lights.pos",))
     cams = _cam_tensors(c["cameras"])
     cameras = [dict(c["cameras"][v], **cams[v]) for v in range(c["n"])]
     # (the numpy shading takes a camera array at full precision: the plain call gets the tensors' float32 values)
-    plain = render_views(c["scene"], [dict(c["cameras"][v], **{k: _np(t) for k, t in cams[v].items()}) for v in range(c["n"])],
+    plain = render_views(c["scene"], [dict(c["cameras"][v], **{k: to_np(t) for k, t in cams[v].items()}) for v in range(c["n"])],
                          device=DEV)
     out = render_views(leaf_scene, cameras, device=DEV)
     assert set(out) == {"image", "depth", "nearest"} and torch.equal(out["image"].detach(), plain["image"])
@@ -379,46 +330,35 @@ def test_no_grad_and_numpy_shading_leave_the_cameras_alone(case2):
 
 # ---- 7. shadows ----------------------------------------------------------------------------------------------------------------
 def test_shadow_rays_with_camera_leaves():
-    npz = np.load(os.path.join(GOLDEN_DIR, "s1a_mixed_shadow_64x48.npz"), allow_pickle=False)
-    scene = unpack_scene(npz)
-    kw = {k: v for k, v in json.loads(str(npz["kwargs"])).items() if k != "shadow"}
-    eye = np.asarray(scene["camera"]["eye"], dtype=np.float64)
-    cameras = _cameras(scene["camera"], [eye, eye + np.array([0.5, 0.2, 0.0, 0.0]), eye + np.array([-0.4, 0.3, 0.4, 0.0])])
+    scene, kw, cameras, lights = shadow_case()
     n = len(cameras)
-    rng = np.random.RandomState(17)
-    lbase = np.asarray(scene["lights"]["pos"], dtype=np.float64)
-    off = rng.uniform(-0.5, 0.5, size=(n,) + lbase.shape)
-    off[..., 3] = 0.0
-    own = {"lights.pos": (lbase[None] + off).astype(np.float32).astype(np.float64)}
-    g = _upstream(n, 9)
+    own = {"lights.pos": lights}
+    g = batch_upstream(n, 9)
     out, leaves, parents, cams = _run(scene, cameras, own, grad_own=("lights.pos",), kw=kw, shadow=True)
     assert out["image"].requires_grad and not out["visibility"].requires_grad
     far = float(scene["camera"]["far"])
-    _loss(out, g, far).backward()
+    masked_loss(out, g, far).backward()
     torch.cuda.synchronize()
-    bits = out["visibility"].cpu().numpy()
-    nl = lbase.shape[0]
-    vis = [np.stack([((bits[v] >> l) & 1).astype(np.float64).reshape(-1) for l in range(nl)]) for v in range(n)]
-    hit = _np(out["depth"]) <= far
+    vis = visibility_rows(out["visibility"].cpu().numpy(), lights.shape[1])
+    hit = to_np(out["depth"]) <= far
     assert all(h.mean() > 0.1 for h in hit)
     shadowed = 1.0 - np.mean([vis[v][:, hit[v].reshape(-1)].mean() for v in range(n)])
     assert 0.01 < shadowed < 0.99                           # the scene does cast shadows
     scenes = [view_scene(scene, cameras[v], {"lights.pos": own["lights.pos"][v]}) for v in range(n)]
-    refs = _refs(out)
+    refs = view_winners(out)
     shared, per_view = _helper(scenes, g, refs, ("lights.pos",), visibility=vis, **kw)
     _check_wanted(per_view)
     _compare_cameras(_cam_grads(cams), per_view, "shadow")
-    for key, want in shared.items():
-        _close(_np(leaves[key].grad), want, 2e-4, f"shadow {key}")
+    assert_grads_close(leaf_grads(leaves), shared, 2e-4, "shadow")
     for v in range(n):
-        _close(_np(parents["lights.pos"].grad)[v], per_view["lights.pos"][v], 2e-4, f"shadow lights.pos[{v}]")
+        assert_array_close(to_np(parents["lights.pos"].grad)[v], per_view["lights.pos"][v], 2e-4, f"shadow lights.pos[{v}]")
     # The bits are used.  Visibility is a factor on the light terms of the image alone: depth, normal and pos do not
     # depend on it, and with random upstream gradients on them the geometry terms of a camera gradient are hundreds of
     # times its image term, so the comparison is made where the bits act -- the same batch with a loss on the image alone.
     g_i = {"image": g["image"]}
     out_i, _, _, cams_i = _run(scene, cameras, own, grad_own=(), grad_shared=False, kw=kw, shadow=True)
     assert torch.equal(out_i["visibility"], out["visibility"]) and torch.equal(out_i["nearest"], out["nearest"])
-    _loss(out_i, g_i, far).backward()
+    masked_loss(out_i, g_i, far).backward()
     torch.cuda.synchronize()
     _, lit = _helper(scenes, g_i, refs, ("lights.pos",), visibility=vis, **kw)
     _, plain = _helper(scenes, g_i, refs, ("lights.pos",), **kw)
@@ -432,20 +372,19 @@ def test_shadow_rays_with_camera_leaves():
 
 # ---- 8. orthographic -----------------------------------------------------------------------------------------------------------
 def test_orthographic_views_with_camera_leaves():
-    scene, cameras = _ortho_case()
-    g = _upstream(2, 13)
+    scene, cameras = ortho_case()
+    g = batch_upstream(2, 13)
     out, leaves, _, cams = _run(scene, cameras, {}, kw={})
     far = float(scene["camera"]["far"])
-    _loss(out, g, far).backward()
+    masked_loss(out, g, far).backward()
     torch.cuda.synchronize()
-    refs = _refs(out)
+    refs = view_winners(out)
     assert all(h > 0.3 for h in _hits(refs, far))
     shared, per_view = _helper([view_scene(scene, cam) for cam in cameras], g, refs, ())
     _check_wanted(per_view)
     _compare_cameras(_cam_grads(cams), per_view, "ortho")
     assert set(shared) == set(leaves)
-    for key, want in shared.items():
-        _close(_np(leaves[key].grad), want, 2e-4, f"ortho {key}")
+    assert_grads_close(leaf_grads(leaves), shared, 2e-4, "ortho")
 
 
 # ---- 9. more workgroups than finish rows -----------------------------------------------------------------------------------------
@@ -455,18 +394,17 @@ def test_more_workgroups_than_finish_rows(base):
     w, h = 136, 120
     scene = copy.deepcopy(base["scene"])
     cameras = [dict(cam, viewport=[0, 0, w, h]) for cam in base["cameras"][:2]]
-    g = _upstream(2, 23, h, w)
+    g = batch_upstream(2, 23, h, w)
     out, leaves, _, cams = _run(scene, cameras, {})
     assert out["pos"].shape == (2, h, w, 3)
-    _loss(out, g, base["far"]).backward()
+    masked_loss(out, g, base["far"]).backward()
     torch.cuda.synchronize()
-    refs = _refs(out)
+    refs = view_winners(out)
     assert all(hh > 0.3 for hh in _hits(refs, base["far"]))
     shared, per_view = _helper([view_scene(scene, cam) for cam in cameras], g, refs, (), **KW3)
     _check_wanted(per_view)
     _compare_cameras(_cam_grads(cams), per_view, "136x120")
-    for key, want in shared.items():
-        _close(_np(leaves[key].grad), want, 2e-4, f"136x120 {key}")
+    assert_grads_close(leaf_grads(leaves), shared, 2e-4, "136x120")
 
 
 # ---- 10. workspace hygiene ---------------------------------------------------------------------------------------------------
@@ -522,5 +460,5 @@ def test_backward_leaves_the_bin_counters_alone_and_reads_nothing_stale(base):
     _check_wanted(per_view, AWAY3)
     for i, key in enumerate(CAM_KEYS):
         for v in range(n):
-            _close(got[v, i], per_view[key][v], 2e-4, f"buffers {key}[{v}]")
+            assert_array_close(got[v, i], per_view[key][v], 2e-4, f"buffers {key}[{v}]")
     assert not got[AWAY3].any()

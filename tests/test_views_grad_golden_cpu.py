@@ -17,8 +17,8 @@ def batch(request):
     npz, scene, cams, own, kw = load_v1(request.param)
     scenes = [view_scene(scene, cams[v], own[v]) for v in range(len(cams))]
     refs = [np_oracle_tch.render(sc, **kw) for sc in scenes]
-    g_img, g_dep = npz["grad_in/image"].astype(np.float64), npz["grad_in/depth"].astype(np.float64)
-    shared, per_view = oracle_batch_tch(scenes, g_img, g_dep, refs, V1_PER_VIEW, **kw)
+    g = {k: npz["grad_in/" + k].astype(np.float64) for k in ("image", "depth")}
+    shared, per_view = oracle_batch_tch(scenes, g, refs, V1_PER_VIEW, **kw)
     return npz, scenes, refs, shared, per_view
 
 
