@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What two keyword arguments of the reference torch backend really do (diffrend/torch/renderer.py:152-162,245-260),
-established by running the UNMODIFIED reference in the build container.  Test infrastructure; prints a short report.
+established by running the UNMODIFIED reference (oracle/ref_harness.py).  Test infrastructure; a hand-run probe that
+prints a short report:  python -m oracle.check_ref_kwargs
 
   backface_culling=True        only labels the primitives (torch/utils.py:515-536); nothing reads the labels, so every
                                output is unchanged -> the hip backend accepts the keyword as a no-op.
@@ -10,24 +11,15 @@ established by running the UNMODIFIED reference in the build container.  Test in
                                path can be generated.  The hip backend implements the formula of :245-249 from the
                                source text; that output is NOT pinned by a reference fixture.
 """
-import contextlib
-import io
-import os
-import sys
-
 import numpy as np
 
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-from oracle.gen_golden_tch import f32, ref_tch, to_torch  # noqa: E402  (imports the reference)
-from surf_renderer_amd import synthetic  # noqa: E402
+from oracle import ref_harness as R
+from oracle.ref_harness import f32
+from surf_renderer_amd import synthetic
 
 
 def run(sc, **kw):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return ref_tch.render(to_torch(sc), shadow=False, **kw)
+    return R.render(R.torch_scene(sc, requires_grad=False)[0], **kw)
 
 
 def main():

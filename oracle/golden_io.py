@@ -8,7 +8,7 @@ Only data -- no code of the reference travels in these files.
 from __future__ import annotations
 
 import json
-from typing import Any, Dict
+from typing import Any, Dict, List, Tuple
 
 import numpy as np
 
@@ -89,13 +89,38 @@ def unpack_scene(npz) -> Dict[str, Any]:
     return scene
 
 
-def save_case(path: str, scene: Dict[str, Any], out: Dict[str, np.ndarray], note: str = "") -> None:
+def diff_npz(a, b) -> List[Tuple[str, str]]:
+    """Differences between two loaded ``.npz`` as (key, what) pairs; empty when they hold the same data.
+
+    Same key set, and per key the same dtype, shape and values (NaN equal to NaN in float arrays; the
+    ``meta`` / ``note`` / ``kwargs`` strings compared as strings).
+    """
+    diffs = [(k, "only in the first") for k in a.files if k not in b.files]
+    diffs += [(k, "only in the second") for k in b.files if k not in a.files]
+    for k in a.files:
+        if k not in b.files:
+            continue
+        x, y = a[k], b[k]
+        if x.dtype.kind == "U" and y.dtype.kind == "U" and x.ndim == y.ndim == 0:
+            if str(x) != str(y):                  # a string's dtype is its length: report the text instead
+                diffs.append((k, f"{str(x)!r} != {str(y)!r}"))
+        elif x.dtype != y.dtype:
+            diffs.append((k, f"dtype {x.dtype} != {y.dtype}"))
+        elif x.shape != y.shape:
+            diffs.append((k, f"shape {x.shape} != {y.shape}"))
+        elif not np.array_equal(x, y, equal_nan=x.dtype.kind in "fc"):
+            bad = ~((x == y) | ((x != x) & (y != y)))
+            diffs.append((k, f"{int(bad.sum())} of {x.size} values differ, first at {tuple(int(i) for i in np.argwhere(bad)[0])}"))
+    return diffs
+
+
+def pack_case(scene: Dict[str, Any], out: Dict[str, np.ndarray], note: str = "") -> Dict[str, np.ndarray]:
     flat = pack_scene(scene)
     flat["out/image"] = np.asarray(out["image"], dtype=np.float64)
     flat["out/depth"] = np.asarray(out["depth"], dtype=np.float64)
     flat["out/nearest"] = np.asarray(out["nearest"], dtype=np.int64)
     flat["note"] = np.asarray(note)
-    np.savez_compressed(path, **flat)
+    return flat
 
 
 def load_case(path: str):

@@ -1,31 +1,23 @@
-#!/usr/bin/env python3
 """Generate tests/golden/p1_*.npz: forward outputs and gradients of the reference's splat renderer,
 render_splats_along_ray (diffrend/torch/renderer.py:537-751), running UNMODIFIED on the CPU under autograd:
 
     loss = sum image * g_i + sum depth * g_d + sum normal * g_n + sum pos * g_p
 
-Test infrastructure; needs the reference checkout (located as oracle/gen_golden_grad_tch.py locates it) and is run by
+Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by
 hand -- no test reads the reference.  Stored (tests/splat_oracle.pack / unpack): the inputs, the four upstream
 gradients, ref/{image, depth, normal, pos} and d loss / d leaf for every differentiable input (float32, as the
 reference computes).
-usage: tools/gen_golden_splats.py
 """
-import contextlib
-import io
 import json
 import os
 import sys
 
 import numpy as np
+import torch
 
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+from oracle import ref_harness as R
 
-import torch  # noqa: E402
-
-from oracle.gen_golden_grad_tch import ref_tch  # noqa: E402  (puts the reference on sys.path)
+sys.path.insert(0, os.path.join(R.REPO, "tests"))
 from splat_oracle import pack  # noqa: E402
 
 
@@ -57,33 +49,11 @@ def base_scene(H, W, seed=3):
 
 
 def emit(name, scene, **kw):
-    cam = scene["camera"]
-    vp = cam["viewport"]
-    W, H = vp[2] - vp[0], vp[3] - vp[1]
-
-    def leaf(a):
-        return torch.tensor(np.asarray(a, dtype=np.float32), requires_grad=True)
-
-    leaves = {}
-    disk = scene["objects"]["disk"]
-    tdisk = {"material_idx": torch.tensor(disk["material_idx"], dtype=torch.long)}
-    for k in ("pos", "normal", "light_vis"):
-        if k in disk:
-            tdisk[k] = leaves["disk." + k] = leaf(disk[k])
-    tsc = {"camera": dict(cam, **{k: torch.tensor(cam[k]) for k in ("eye", "at", "up")}),
-           "objects": {"disk": tdisk},
-           "lights": {"pos": leaf(scene["lights"]["pos"]), "color_idx": torch.tensor(scene["lights"]["color_idx"]),
-                      "attenuation": leaf(scene["lights"]["attenuation"]), "ambient": leaf(scene["lights"]["ambient"])},
-           "colors": leaf(scene["colors"]),
-           "materials": {"albedo": leaf(scene["materials"]["albedo"]), "coeffs": leaf(scene["materials"]["coeffs"])}}
-    for k in ("pos", "attenuation", "ambient"):
-        leaves["lights." + k] = tsc["lights"][k]
-    leaves["colors"] = tsc["colors"]
-    leaves["materials.albedo"] = tsc["materials"]["albedo"]
-    leaves["materials.coeffs"] = tsc["materials"]["coeffs"]
-
-    with contextlib.redirect_stdout(io.StringIO()):
-        res = ref_tch.render_splats_along_ray(tsc, normal_estimation_method="plane", **kw)
+    if not R.wanted(name):
+        return
+    tsc, leaves = R.torch_scene(scene)                 # the splat scene has the same leaves; its disk.pos is the z field
+    with R.quiet():
+        res = R.ref_tch.render_splats_along_ray(tsc, normal_estimation_method="plane", **kw)
     rng = np.random.RandomState(11)
     g = {k: rng.uniform(-1, 1, size=tuple(res[k].shape)).astype(np.float32) for k in ("image", "depth", "normal", "pos")}
     loss = sum(torch.sum(res[k] * torch.tensor(g[k])) for k in g)
@@ -94,12 +64,8 @@ def emit(name, scene, **kw):
         out["grad_in/" + k] = g[k]
         out["ref/" + k] = res[k].detach().numpy()
     out["kwargs"] = np.asarray(json.dumps(kw))
-    for k, v in leaves.items():
-        out["grad/" + k] = v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape), dtype=np.float32)
-        print(f"{name} {k:20s} |grad| max {np.abs(out['grad/' + k]).max():.4g}  finite {np.isfinite(out['grad/' + k]).all()}")
-    path = os.path.join(REPO, "tests", "golden", name + ".npz")
-    np.savez_compressed(path, **out)
-    print("->", path, os.path.getsize(path), "bytes")
+    R.pack_grads(out, leaves)
+    R.write(name, out)
 
 
 def given_normals(H, W, seed):
@@ -108,7 +74,7 @@ def given_normals(H, W, seed):
     return n.astype(np.float32)                     # deliberately not unit: the renderer takes them as they are
 
 
-if __name__ == "__main__":
+def main():
     H, W = 36, 48
     emit("p1_estimated_36x48", base_scene(H, W))
 

@@ -6,7 +6,7 @@ that the hip backend can be checked on the GPU box, where the reference itself i
 ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py`` may import
 it; nothing under ``surf_renderer_amd/`` does.
 
-Parity status: PINNED.  ``oracle/gen_golden.py`` ran the unmodified reference in the build
+Parity status: PINNED.  ``oracle/golden_g1_g8.py`` ran the unmodified reference in the build
 container and committed its outputs under ``tests/golden/``; ``tests/test_oracle_golden.py``
 checks this file against every one of them (image/depth to 1e-12, ``nearest`` exactly).
 

@@ -13,7 +13,7 @@ literal distance 1001, which becomes a hit when far >= 1001, torch/utils.py:323,
 negative is a miss (the reference substitutes max(t)+1 over the current pixel tile, torch/utils.py:266-268).
 
 Parity status: PINNED with an fp32 tolerance -- the reference computes this path in float32;
-``oracle/gen_golden_tch.py`` ran it unmodified and ``tests/test_oracle_tch.py`` compares.
+``oracle/golden_t1_t5.py`` ran it unmodified and ``tests/test_oracle_tch.py`` compares.
 """
 from __future__ import annotations
 
@@ -102,7 +102,7 @@ def light_visibility(scene, res):
     it; the light is visible unless some primitive OTHER than the fragment's own is hit closer than the light
     (distances measured from the shifted origin, the light's distance from the fragment itself, as the reference
     does).  Returns (L, H*W) bool.  PINNED by tests/golden/s1*.npz: outputs of the reference's render(shadow=True),
-    generated on the CPU by oracle/gen_golden_shadow.py, which aliases `torch.cuda.FloatTensor` to `torch.FloatTensor`
+    generated on the CPU by oracle/golden_s1.py, which aliases `torch.cuda.FloatTensor` to `torch.FloatTensor`
     in its own process because the reference casts the mask with `.type(torch.cuda.FloatTensor)` (:311); the
     reference returns only the shaded image, which is what tests/test_oracle_tch.py compares."""
     cam = scene['camera']

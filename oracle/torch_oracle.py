@@ -12,7 +12,7 @@ gradients.
 
 Parity status: forward PINNED by the golden vectors (``tests/test_oracle_golden.py``); gradients PINNED by
 ``tests/golden/g9_torch_autograd.npz``, produced by running the reference's torch backend under autograd on a scene
-where its shading model coincides with the numpy one (``oracle/gen_golden_grad.py``).
+where its shading model coincides with the numpy one (``oracle/golden_g9_g11.py``).
 """
 from __future__ import annotations
 
@@ -341,7 +341,7 @@ def render_aux(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Opti
                double_sided: bool = False, use_quartic: bool = False):
     """Differentiable normal (H,W,3), pos (H,W,3) and the hit mask (H,W), zeros at misses, on numpy rays: the torch
     backend's extra outputs (diffrend/torch/renderer.py:185-189, 342-355), without the shading.  Pinned to the
-    reference by tests/test_aux_grad_golden_cpu.py (tests/golden/n1_*.npz, tools/gen_golden_aux_grad.py)."""
+    reference by tests/test_aux_grad_golden_cpu.py (tests/golden/n1_*.npz, oracle/golden_n1.py)."""
     _, _, normal, pos, hit = _render_core(rays_np(scene["camera"]), scene, leaves, ref, double_sided, use_quartic, None,
                                           outputs=("normal", "pos"))
     return normal, pos, hit
@@ -351,7 +351,7 @@ def render_camera(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], cam_le
                   ref: Dict[str, np.ndarray], double_sided: bool = False, use_quartic: bool = False,
                   visibility: Optional[np.ndarray] = None):
     """Differentiable image, depth, normal, pos and the hit mask on the rays of the camera leaves.  Pinned to the
-    reference by tests/test_camera_grad_golden_cpu.py (tests/golden/c1_*.npz, tools/gen_golden_camera_grad.py)."""
+    reference by tests/test_camera_grad_golden_cpu.py (tests/golden/c1_*.npz, oracle/golden_c1_c2.py)."""
     return _render_core(rays(scene["camera"], cam_leaves), scene, leaves, ref, double_sided, use_quartic, visibility)
 
 

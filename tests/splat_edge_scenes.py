@@ -10,7 +10,7 @@ reach the branches of csrc/srh_splat.h that such inputs never take:
 
 Every builder is deterministic (fixed seeds) and returns (scene, kwargs, notes): a numpy scene dict in the format
 splat_oracle.unpack produces, the keywords of the call, and what the CPU test needs to know about the case.  The base
-depth field, camera, lights and materials are those of tools/gen_golden_splats.py.
+depth field, camera, lights and materials are those of oracle/golden_p1.py.
 
 tests/test_splat_edge_scenes_cpu.py asserts with the oracle alone that each case reaches the branch it is named for;
 tests/test_hip_splats_edges.py then compares the kernels with the oracle on them."""

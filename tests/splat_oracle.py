@@ -13,7 +13,7 @@ One view, W x H base pixels, f = focal_length, h = 2 f tan(fovy / 2), w = h W / 
     shading    the torch backend's Phong (fragment_shader) with double_sided off, lights in camera coordinates through
                the orthonormal lookat basis, light_vis multiplying colour x albedo, relu over the light sum
 Written in this project's own terms; pinned to the reference by tests/test_splat_oracle_cpu.py
-(tests/golden/p1_*.npz, tools/gen_golden_splats.py)."""
+(tests/golden/p1_*.npz, oracle/golden_p1.py)."""
 import json
 from typing import Any, Dict
 

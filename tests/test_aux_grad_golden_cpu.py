@@ -1,5 +1,5 @@
 """The normal / pos side of the gradient oracle (oracle/torch_oracle.py: render_aux, gradients_tch with grad_normal /
-grad_pos) against the reference torch backend under autograd (tests/golden/n1_*.npz, tools/gen_golden_aux_grad.py): forward normal and pos at hit pixels, and every leaf gradient of
+grad_pos) against the reference torch backend under autograd (tests/golden/n1_*.npz, oracle/golden_n1.py): forward normal and pos at hit pixels, and every leaf gradient of
 loss = sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p).  The reference's sphere gradients are NaN (sqrt
 under a mask, torch/utils.py:238-279), so the sphere leaves are pinned by central differences instead."""
 import copy

@@ -1,5 +1,5 @@
 """The gradient oracle with the camera in its graph (oracle/torch_oracle.py: rays, gradients_tch with camera=True)
-against the reference torch backend under autograd (tests/golden/c1_*.npz, tools/gen_golden_camera_grad.py -- the
+against the reference torch backend under autograd (tests/golden/c1_*.npz, oracle/golden_c1_c2.py -- the
 sphere-free fixture scene, camera eye / at / up as leaves beside all others), against the same oracle on its numpy rays
 (the camera outside the graph), and against central differences on the full scene with
 spheres (where the reference's own camera gradients are NaN).

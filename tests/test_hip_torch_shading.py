@@ -112,7 +112,7 @@ def test_shadow_pass_matches_the_oracle(case):
 @pytest.mark.parametrize("case", ["s1a_mixed_shadow_64x48", "s1a_mixed_shadow_64x48_ds", "s1b_disk_cloud_shadow_64x64_ds"])
 def test_shadow_pass_matches_reference_torch_backend(case):
     """render(shading='torch', shadow=True) against the reference's own render(shadow=True) (float32, CPU;
-    oracle/gen_golden_shadow.py): same tolerance as the unshadowed reference cases, a grazing shadow ray may flip on
+    oracle/golden_s1.py): same tolerance as the unshadowed reference cases, a grazing shadow ray may flip on
     <= 0.5 % of the pixels."""
     import json
     from conftest import GOLDEN_DIR

@@ -1,7 +1,7 @@
 """The CPU oracle (oracle/np_oracle.py) against every golden vector produced by the reference.
 
 This is what pins the oracle: the expected outputs in tests/golden/*.npz came from the unmodified
-``diffrend.numpy.renderer.render`` (oracle/gen_golden.py).  fp64 against fp64: image and depth must
+``diffrend.numpy.renderer.render`` (oracle/golden_g1_g8.py).  fp64 against fp64: image and depth must
 agree to 1e-12, ``nearest`` exactly, NaNs in the same places (g8f has one by construction).
 """
 import os

@@ -1,5 +1,5 @@
 """The torch-semantics oracle (oracle/np_oracle_tch.py) against outputs of the reference's torch backend
-(tests/golden/t*.npz, oracle/gen_golden_tch.py).  The reference computes this path in float32, the oracle in
+(tests/golden/t*.npz, oracle/golden_t1_t5.py).  The reference computes this path in float32, the oracle in
 float64, so: `nearest` may differ on a small fraction of silhouette pixels (<= 0.5 %), and where it agrees depth must
 match to 2e-5 relative, image / normal to 3e-4 absolute, pos to 2e-4."""
 import glob
@@ -57,7 +57,7 @@ def load_shadow_case(name):
 
 @pytest.mark.parametrize("case", SHADOW_CASES)
 def test_shadow_oracle_matches_reference_torch_backend(case):
-    """render(shadow=True) of the reference (oracle/gen_golden_shadow.py; the reference returns the shaded image, not
+    """render(shadow=True) of the reference (oracle/golden_s1.py; the reference returns the shaded image, not
     the visibility): the oracle's image must match on every pixel whose `nearest` agrees, and the fixture must
     really hold shadows (the unshadowed oracle image differs from it on > 20 % of the pixels)."""
     assert len(SHADOW_CASES) >= 3

@@ -1,5 +1,5 @@
 """Host-side scene / model IO against arrays captured from the reference's own loaders (the golden inputs
-of g3-g6 were produced by diffrend.model / diffrend.torch.render.load_scene, see oracle/gen_golden.py)."""
+of g3-g6 were produced by diffrend.model / diffrend.torch.render.load_scene, see oracle/golden_g1_g8.py)."""
 import copy
 import os
 

@@ -1,5 +1,5 @@
 """The fp64 splat-renderer restatement (tests/splat_oracle.py) against the reference's render_splats_along_ray under
-autograd (tests/golden/p1_*.npz, tools/gen_golden_splats.py): the four forward outputs and d loss / d leaf for every
+autograd (tests/golden/p1_*.npz, oracle/golden_p1.py): the four forward outputs and d loss / d leaf for every
 differentiable input, loss = sum image g_i + sum depth g_d + sum normal g_n + sum pos g_p.
 
 Tolerances: the reference computes in float32.  Image, depth and pos carry a few float32 roundings of values of order

@@ -1,6 +1,6 @@
 """The gradient oracle (oracle/torch_oracle.py): its forward against the reference's golden outputs, and its
 autograd against gradients the reference's own torch backend produced (tests/golden/g9_torch_autograd.npz,
-oracle/gen_golden_grad.py)."""
+oracle/golden_g9_g11.py)."""
 import os
 
 import numpy as np

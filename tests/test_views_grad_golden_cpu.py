@@ -1,6 +1,6 @@
 """The gradient of a batch of views = the per-view gradients, shared leaves summed: the definition the batched HIP
 backward (srh_render_views_bwd) is tested against, pinned here to the reference torch backend running its own batch loop
-under autograd with one summed loss (tests/golden/v1_views_grad_*.npz, tools/gen_golden_views_grad.py).  The per-view
+under autograd with one summed loss (tests/golden/v1_views_grad_*.npz, oracle/golden_v1.py).  The per-view
 side is oracle/torch_oracle.gradients_tch on the fixture's own scene, cameras and upstream gradients.
 
 Tolerance: 2e-3 of each array's largest entry, the project's figure for float32 reference fixtures (g9 / g10 / n1 / c1).

@@ -1,4 +1,4 @@
-"""Shared by the multi-view gradient tests: the v1 fixtures (tools/gen_golden_views_grad.py) as per-view scenes, the
+"""Shared by the multi-view gradient tests: the v1 fixtures (oracle/golden_v1.py) as per-view scenes, the
 batches several test modules render (the five-view batch, the orthographic pair, the shadow fixture with per-view
 lights), and the per-view gradient oracle summed / stacked the way a batch's gradients are defined -- a leaf all views
 share gets the sum over the views, a leaf a view overrides the gradient of that view alone."""
