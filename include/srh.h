@@ -465,6 +465,53 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
                   const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
                   const SrhSplatGrads* grads, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The geometric regularisers the reference's trainers put on every rendered splat view (diffrend/torch/GAN/gan.py:
+ * 601-640 with diffrend/torch/utils.py:731-851), for B views per call.  Inputs are what srh_splat_fwd writes: pos,
+ * normal, image (B, H, W, 3) and depth (B, H, W), dense, with H x W the OUTPUT grid (K H x K W at samples = K).
+ * d_k(x) = x[neighbour k] - x[centre] over the 3 x 3 stencil without its centre, reflected at the borders; N = H W.
+ * Terms, in this order (SRH_REG_TERMS of them per view):
+ *   0 z                        mean (s relu(z_min - |p_z|))^2 + (s relu(|p_z| - z_max))^2,  s = z_scale
+ *   1 unit_normal              mean (c (|n| - 1))^2,  c = unit_normal_scale
+ *   2 normal_consistency       mean over the 8 N pairs of |u_k . n|,  u_k = d_k(pos) / sqrt(|d_k|^2 + 3e-10)
+ *   3 spatial                  mean over the 8 N pairs of sum_c |d_k(pos)_c|
+ *   4 spatial_var              1 / (var p_x + var p_y + var p_z + 1e-4), unbiased variances over the N pixels
+ *   5 image_depth_consistency  mean over the 8 N pairs of | |d_k(mean_c image)| - |d_k(depth)| |
+ *   6 away_from_camera         SUM over the pixels of relu(n . p / sqrt(|p|^2 + 3e-10))
+ * fp64 arithmetic, fp32 results, no atomics: values and gradients are identical from run to run.  Gradients follow
+ * autograd's conventions (|.| and relu have gradient 0 at 0) except that a normal that is exactly zero gets no
+ * unit_normal gradient (autograd: NaN).  These entry points were added without an ABI version change.  Conventions as
+ * above: caller-owned device buffers, enqueue only, no synchronisation or allocation, argument checks before any HIP
+ * call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_REG_TERMS 7
+#define SRH_REG_STATS 4           /* doubles per view: mean p_x, p_y, p_z and the variance sum */
+
+typedef struct SrhRegularizerParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 2 each (reflection), W H <= 2^24 */
+  int32_t reserved;
+  double z_min, z_max;          /* z_min <= z_max */
+  double z_scale;               /* s */
+  double unit_normal_scale;     /* c */
+} SrhRegularizerParams;
+
+/* bytes of device scratch srh_regularizers_fwd needs (8-byte aligned): one row of partial sums per workgroup; 0 and
+ * srh_last_error on bad input */
+size_t srh_regularizers_workspace_bytes(int32_t n_views, int32_t width, int32_t height);
+
+/* terms (B, SRH_REG_TERMS) fp32; stats (B, SRH_REG_STATS) fp64, which srh_regularizers_bwd reads */
+int srh_regularizers_fwd(const SrhRegularizerParams* params, const float* pos, const float* normal, const float* image,
+                         const float* depth, void* workspace, size_t workspace_bytes, float* terms, double* stats,
+                         void* stream);
+
+/* Vector-Jacobian product for grad_terms (B, SRH_REG_TERMS) fp32 and the stats of the forward call on the same inputs.
+ * g_pos, g_normal, g_image (B, H, W, 3) and g_depth (B, H, W) are WRITTEN, every element once (no zero-fill needed);
+ * any may be NULL = not wanted, not all. */
+int srh_regularizers_bwd(const SrhRegularizerParams* params, const float* pos, const float* normal, const float* image,
+                         const float* depth, const double* stats, const float* grad_terms, float* g_pos,
+                         float* g_normal, float* g_image, float* g_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,8 +13,9 @@ _RENDERER = ("render", "render_views", "ResidentScene", "CapturedStep", "ViewSce
              "generate_rays")
 _SCENE = ("load_scene", "load_model", "load_obj", "load_splat", "obj_to_triangle_spec")
 _SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
+_REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS]
 
 
 def __getattr__(name):
@@ -24,6 +25,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".scene", __name__), name)
     if name in _SPLATS:
         return getattr(importlib.import_module(".splats", __name__), name)
+    if name in _REGULARIZERS:
+        return getattr(importlib.import_module(".regularizers", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -91,13 +91,22 @@ class SrhSplatGrads(C.Structure):
                                           "ambient", "albedo", "coeffs")]
 
 
+class SrhRegularizerParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("z_scale", C.c_double),
+                ("unit_normal_scale", C.c_double)]
+
+
+REG_TERMS, REG_STATS = 7, 4
+
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
            "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
            "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_render_views_aux",
            "srh_camera_grad_scratch_bytes_views", "srh_render_views_bwd_camera", "srh_shadow_shade",
            "srh_shadow_workspace_bytes", "srh_bin_counters",
            "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
-           "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd")
+           "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd",
+           "srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd")
 
 _lib: Optional[C.CDLL] = None
 
@@ -205,6 +214,15 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib.srh_splat_bwd.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs), C.POINTER(SrhLights),
                                   C.POINTER(SrhMaterials), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(SrhSplatGrads), C.c_void_p]
+    lib.srh_regularizers_workspace_bytes.restype = C.c_size_t
+    lib.srh_regularizers_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.srh_regularizers_fwd.restype = C.c_int
+    lib.srh_regularizers_fwd.argtypes = [C.POINTER(SrhRegularizerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.srh_regularizers_bwd.restype = C.c_int
+    lib.srh_regularizers_bwd.argtypes = [C.POINTER(SrhRegularizerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
     got = lib.srh_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {got}, this package expects {ABI_VERSION}; rebuild it")

@@ -1,6 +1,6 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
-// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h.
+// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -24,6 +24,7 @@
 #include "srh_backward.h"
 #include "srh_shadow.h"
 #include "srh_splat.h"
+#include "srh_regularizers.h"
 
 using namespace srh;
 
@@ -438,6 +439,36 @@ int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLigh
 }
 
 size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N * 9 * sizeof(double) : 0; }
+
+// ------------------------------------------------------------------------------------------------
+// the splat regularisers (srh_regularizers.h)
+// ------------------------------------------------------------------------------------------------
+int reg_check_grid(int32_t n_views, int32_t width, int32_t height) {
+  if (n_views < 1 || n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", n_views);
+  if (width < 2 || height < 2)
+    return fail(SRH_E_RANGE, "grid %d x %d: the reflected stencil needs at least 2 x 2", width, height);
+  if ((int64_t)width * height > (1 << 24)) return fail(SRH_E_RANGE, "grid %d x %d out of range", width, height);
+  return SRH_OK;
+}
+
+size_t reg_ws_bytes(int32_t n_views, int32_t width, int32_t height) {
+  const size_t nblk = ((size_t)width * height + kRegBlock - 1) / kRegBlock;
+  return (size_t)n_views * nblk * kRegSums * sizeof(double);
+}
+
+// argument checks (no HIP call) and the device view of a regulariser launch
+int reg_setup(const SrhRegularizerParams* p, const float* pos, const float* normal, const float* image,
+              const float* depth, RegDev* R) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = reg_check_grid(p->n_views, p->width, p->height)) return rc;
+  if (!(p->z_min <= p->z_max)) return fail(SRH_E_RANGE, "z_min = %g > z_max = %g", p->z_min, p->z_max);
+  if (!pos || !normal || !image || !depth) return fail(SRH_E_NULL, "pos / normal / image / depth is NULL");
+  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height;
+  R->nblk = (R->N + kRegBlock - 1) / kRegBlock;
+  R->z_min = p->z_min; R->z_max = p->z_max; R->z_scale = p->z_scale; R->n_scale = p->unit_normal_scale;
+  R->pos = pos; R->normal = normal; R->image = image; R->depth = depth;
+  return SRH_OK;
+}
 
 }  // namespace
 
@@ -1240,5 +1271,43 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
   return launch_status("splat backward launch");
 }
 
+
+// ---- the splat regularisers ------------------------------------------------------------------------------------
+size_t srh_regularizers_workspace_bytes(int32_t n_views, int32_t width, int32_t height) {
+  if (reg_check_grid(n_views, width, height)) return 0;
+  return reg_ws_bytes(n_views, width, height);
+}
+
+int srh_regularizers_fwd(const SrhRegularizerParams* params, const float* pos, const float* normal, const float* image,
+                         const float* depth, void* workspace, size_t workspace_bytes, float* terms, double* stats,
+                         void* stream) {
+  RegDev R;
+  int rc = reg_setup(params, pos, normal, image, depth, &R);
+  if (rc) return rc;
+  if (!terms || !stats) return fail(SRH_E_NULL, "terms / stats is NULL");
+  const size_t need = reg_ws_bytes(R.B, R.W, R.H);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double)))
+    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
+                workspace);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_reg_fwd, dim3(R.nblk, R.B), dim3(kRegBlock), 0, st, R, (double*)workspace);
+  hipLaunchKernelGGL(k_reg_finish, dim3(R.B), dim3(64), 0, st, R, (const double*)workspace, terms, stats);
+  return launch_status("regularizers forward launch");
+}
+
+int srh_regularizers_bwd(const SrhRegularizerParams* params, const float* pos, const float* normal, const float* image,
+                         const float* depth, const double* stats, const float* grad_terms, float* g_pos,
+                         float* g_normal, float* g_image, float* g_depth, void* stream) {
+  RegDev R;
+  int rc = reg_setup(params, pos, normal, image, depth, &R);
+  if (rc) return rc;
+  if (!stats || !grad_terms) return fail(SRH_E_NULL, "stats / grad_terms is NULL");
+  if (!g_pos && !g_normal && !g_image && !g_depth)
+    return fail(SRH_E_NULL, "g_pos, g_normal, g_image and g_depth are all NULL");
+  RegGradsDev G;
+  G.pos = g_pos; G.normal = g_normal; G.image = g_image; G.depth = g_depth;
+  hipLaunchKernelGGL(k_reg_bwd, dim3(R.nblk, R.B), dim3(kRegBlock), 0, (hipStream_t)stream, R, G, stats, grad_terms);
+  return launch_status("k_reg_bwd launch");
+}
 
 }  // extern "C"
