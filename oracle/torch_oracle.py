@@ -228,8 +228,17 @@ def rays(camera: Dict[str, Any], cam_leaves: Dict[str, torch.Tensor]):
     return eye, orig, d, H, W
 
 
+def _tap(taps, key: str, index, t: torch.Tensor) -> torch.Tensor:
+    """With ``taps``: keep the gradient of ``t`` -- the per-pixel copy of leaf ``key`` (rows ``index`` of it; None: the
+    whole leaf once per pixel) -- so that its rows are the pixels' own terms of the leaf's gradient."""
+    if taps is not None:
+        t.retain_grad()
+        taps.setdefault(key, []).append((index, t))
+    return t
+
+
 def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]],
-                 double_sided: bool, use_quartic: bool, visibility: Optional[np.ndarray], outputs=OUTPUTS):
+                 double_sided: bool, use_quartic: bool, visibility: Optional[np.ndarray], outputs=OUTPUTS, taps=None):
     """The one fp64 autograd restatement of the torch backend (diffrend/torch/renderer.py:82-125,136-355; see
     oracle/np_oracle_tch.py for the forward restatement and its two documented deviations) on the rays of rays_np or
     rays: (image (H,W,3), depth (H,W), normal (H,W,3), pos (H,W,3), hit (H,W)).  The shading is built -- and image is
@@ -264,8 +273,8 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
             ds = d[sel]
             mat[sel] = np.asarray(grp["material_idx"])[nearest[sel] - start]
             if kind == "sphere":
-                c = leaves["sphere.pos"][loc][:, :3]
-                r = leaves["sphere.radius"][loc]
+                c = _tap(taps, "sphere.pos", loc, leaves["sphere.pos"][loc])[:, :3]
+                r = _tap(taps, "sphere.radius", loc, leaves["sphere.radius"][loc])
                 oc = orig[sel] - c
                 a = torch.sum(ds * ds, dim=-1)
                 b = 2 * torch.sum(oc * ds, dim=-1)
@@ -276,8 +285,9 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
                 ts = torch.where(t1 >= 0, t1, t2)                             # the smaller non-negative root
                 n = _unit3_eps(orig[sel] + ts[:, None] * ds - c)
             else:
-                q = (leaves["triangle.face"][loc][:, 0, :3] if kind == "triangle" else leaves[f"{kind}.pos"][loc][:, :3])
-                n = _unit3_eps(leaves[f"{kind}.normal"][loc][:, :3])
+                q = (_tap(taps, "triangle.face", loc, leaves["triangle.face"][loc])[:, 0, :3] if kind == "triangle"
+                     else _tap(taps, f"{kind}.pos", loc, leaves[f"{kind}.pos"][loc])[:, :3])
+                n = _unit3_eps(_tap(taps, f"{kind}.normal", loc, leaves[f"{kind}.normal"][loc])[:, :3])
                 ts = torch.sum(n * (q - orig[sel]), dim=-1) / torch.sum(n * ds, dim=-1)
             t = t.index_put((torch.as_tensor(sel),), ts)
             nrm = nrm.index_put((torch.as_tensor(sel),), n)
@@ -287,17 +297,26 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
     p = orig + t[:, None] * d
     im = None
     if "image" in outputs:
-        lpos = leaves["lights.pos"][:, :3]
-        lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])]
-        att = leaves["lights.attenuation"]
-        amb = leaves["lights.ambient"]
-        alb = leaves["materials.albedo"][mat]
-        cf = leaves["materials.coeffs"][mat]
-        ldir = lpos[None, :, :] - p[:, None, :]                              # (N,L,3)
+        if taps is None:
+            lpos = leaves["lights.pos"][None, :, :3]
+            lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])][None, :, :]
+            att = leaves["lights.attenuation"][None]
+            amb = leaves["lights.ambient"][None, None, :]
+        else:                                                                # every pixel its own copy of the shared leaves
+            def per_pixel(key):
+                return _tap(taps, key, None, leaves[key][None].expand(npix, *leaves[key].shape))
+            lpos = per_pixel("lights.pos")[:, :, :3]
+            lcol = per_pixel("colors")[:, np.asarray(scene["lights"]["color_idx"])]
+            att = per_pixel("lights.attenuation")
+            amb = per_pixel("lights.ambient")[:, None, :]
+        mat_t = torch.as_tensor(mat)
+        alb = _tap(taps, "materials.albedo", mat_t, leaves["materials.albedo"][mat])
+        cf = _tap(taps, "materials.coeffs", mat_t, leaves["materials.coeffs"][mat])
+        ldir = lpos - p[:, None, :]                                          # (N,L,3)
         lnorm = _norm(ldir)                                                  # a light exactly at a fragment: gradient 0
         ldir = ldir / torch.where(lnorm > 0, lnorm, torch.ones_like(lnorm))
         powv = 4 if use_quartic else 2
-        den = att[None, :, 0:1] + lnorm * att[None, :, 1:2] + (lnorm ** powv) * att[None, :, 2:3]
+        den = att[:, :, 0:1] + lnorm * att[:, :, 1:2] + (lnorm ** powv) * att[:, :, 2:3]
         afac = 1.0 / torch.where(den.abs() > 0, den, torch.ones_like(den))
         ldn = torch.sum(nrm[:, None, :] * ldir, dim=-1)                      # (N,L)
         ndotl = afac[..., 0] * ldn
@@ -314,7 +333,7 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
         w = cf[:, None, 0] * ndotl + spec                                    # (N,L)
         if visibility is not None:                                           # (L,N) constants: shadow rays
             w = w * torch.as_tensor(np.asarray(visibility, dtype=np.float64).reshape(w.shape[1], -1).T)
-        col = w[:, :, None] * (lcol[None, :, :] * alb[:, None, :]) + amb[None, None, :] * alb[:, None, :]
+        col = w[:, :, None] * (lcol * alb[:, None, :]) + amb * alb[:, None, :]
         im = torch.sum(col, dim=1)
         im = torch.where(hit[:, None], im, torch.zeros_like(im))
         im = torch.relu(im)
@@ -356,13 +375,13 @@ def render_camera(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], cam_le
 
 
 def loss_camera(scene, leaves, cam_leaves, ref, grad_image=None, grad_depth=None, grad_normal=None, grad_pos=None,
-                double_sided=False, use_quartic=False, visibility=None) -> torch.Tensor:
+                double_sided=False, use_quartic=False, visibility=None, taps=None) -> torch.Tensor:
     """sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p) of ONE graph; None terms are left out, and so is
     the shading without g_i.  ``cam_leaves`` None: numpy rays, the camera outside the graph."""
     grads = dict(zip(OUTPUTS, (grad_image, grad_depth, grad_normal, grad_pos)))
     ray_set = rays_np(scene["camera"]) if cam_leaves is None else rays(scene["camera"], cam_leaves)
     *outs, hit = _render_core(ray_set, scene, leaves, ref, double_sided, use_quartic, visibility,
-                              outputs=[k for k, g in grads.items() if g is not None])
+                              outputs=[k for k, g in grads.items() if g is not None], taps=taps)
     loss = torch.zeros((), dtype=torch.float64)
     for out, (name, g) in zip(outs, grads.items()):
         if g is not None:
@@ -391,3 +410,31 @@ def gradients_tch(scene: Dict[str, Any], grad_image: Optional[np.ndarray] = None
         g = v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape))
         out[k] = np.append(g, 0.0) if (k in CAMERA_KEYS and g.size == 3) else g
     return out
+
+
+def gradient_terms_tch(scene: Dict[str, Any], grad_image: Optional[np.ndarray] = None,
+                       grad_depth: Optional[np.ndarray] = None, grad_normal: Optional[np.ndarray] = None,
+                       grad_pos: Optional[np.ndarray] = None, *, ref: Optional[Dict[str, np.ndarray]] = None,
+                       double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None):
+    """(total, absolute): per scene leaf the sum over the pixels of each pixel's own term of d loss_camera / d leaf --
+    gradients_tch's values -- and the sum of the terms' absolute values, which says how hard that sum cancels: an fp32
+    accumulation of the terms in an arbitrary order is uncertain by about ``absolute`` x 2^-23.  Numpy rays."""
+    leaves = make_leaves_tch(scene)
+    taps: Dict[str, Any] = {}
+    loss = loss_camera(scene, leaves, None, ref, grad_image, grad_depth, grad_normal, grad_pos, double_sided,
+                       use_quartic, visibility, taps=taps)
+    if loss.requires_grad:
+        loss.backward()
+    total = {k: torch.zeros_like(v) for k, v in leaves.items()}
+    absolute = {k: torch.zeros_like(v) for k, v in leaves.items()}
+    for key, copies in taps.items():
+        for index, t in copies:
+            if t.grad is None:
+                continue
+            if index is None:
+                total[key] += t.grad.sum(dim=0)
+                absolute[key] += t.grad.abs().sum(dim=0)
+            else:
+                total[key].index_add_(0, index, t.grad)
+                absolute[key].index_add_(0, index, t.grad.abs())
+    return {k: v.numpy() for k, v in total.items()}, {k: v.numpy() for k, v in absolute.items()}

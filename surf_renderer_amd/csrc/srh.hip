@@ -231,7 +231,7 @@ int camera_to_frame(const SrhCamera* cam, FrameDev* F, bool orthonormal = false)
     if (!(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] > 0))
       return fail(SRH_E_CAMERA, "degenerate camera: up is parallel to the view direction");
     auto unit_eps = [](double* v) {
-      const double l = sqrt(((v[0] * v[0] + 1e-10) + (v[1] * v[1] + 1e-10)) + (v[2] * v[2] + 1e-10));
+      const double l = eps_len(v);
       for (int i = 0; i < 3; ++i) v[i] /= l;
     };
     double u[3];
@@ -426,7 +426,7 @@ int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLigh
   S->sub_dx = p->samples > 1 ? w / (p->samples * p->width - 1) : 0.0;
   S->sub_dy = p->samples > 1 ? h / (p->samples * p->height - 1) : 0.0;
   S->sub_step = p->samples > 1 ? 2.0 / (p->samples - 1) : 0.0;
-  const double ui = 1.0 / sqrt(((p->up[0] * p->up[0] + 1e-10) + (p->up[1] * p->up[1] + 1e-10)) + (p->up[2] * p->up[2] + 1e-10));
+  const double ui = 1.0 / eps_len(p->up);
   for (int k = 0; k < 3; ++k) { S->at[k] = p->at[k]; S->up[k] = p->up[k] * ui; }
   S->pos = in->pos; S->pos_vs = in->pos_view_stride;
   S->normal = in->normal; S->nrm_vs = in->normal_view_stride;

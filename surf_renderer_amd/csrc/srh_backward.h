@@ -847,8 +847,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBwdTchWave
 // The frame's camera gradients from the workgroups' partial sums (one workgroup).  Thread (j, k) adds sum k of workgroups
 // j, j + kCamFinishRows, ... in that order, the rows are added in order through LDS, and thread 0 applies the chain rule
 // of the look-at basis in fp64 -- every addition has a fixed place, so two runs give the same bits.
-//     z = unit(eye - at), u^ = unit(up), x = unit(cross(u^, z)), y = cross(z, x)          (torch/utils.py:402-427, exact
-//     unit vectors as camera_to_frame builds them; the reference's +1e-10 inside its norms is 1e-10 relative)
+//     z = unit(eye - at), u^ = unit(up), x = unit(cross(u^, z)), y = cross(z, x)          (torch/utils.py:402-427), unit
+//     the reference's v / sqrt(sum(v_i^2 + 1e-10)) as camera_to_frame builds them: with `up` a fraction of a degree from
+//     the view direction |cross(u^, z)|^2 is 1e-5 or less, the 3e-10 is 1e-5 of it, and the chain rule divides by that
+//     length twice (tests/test_hip_grad_fuzz.py::test_up_a_tenth_of_a_degree_from_the_view_direction)
 // persp: g_x = S1, g_y = S2, g_z = -f S3;  ortho: g_x = S1, g_y = S2, g_z = -S3;  g_eye = S0 + chain, g_at = -chain.
 struct CamFinish {
   double eye[3], at[3], up[3], focal;
@@ -865,7 +867,8 @@ __device__ __forceinline__ void cross3(const double a[3], const double b[3], dou
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// g_v for u = v / |v| given g_u:  (g_u - u (u . g_u)) / |v|
+// g_v for u = v / len given g_u:  (g_u - u (u . g_u)) / len  -- exact for len = |v| and for len = eps_len(v) (srh_device.h) alike
+// (d(v / n) = dv / n - v (v . dv) / n^3 with n^2 = |v|^2 + 3e-10)
 __device__ __forceinline__ void unit_bwd(const double u[3], double len, const double g_u[3], double g_v[3]) {
   const double pr = dot3(u, g_u);
 #pragma unroll
@@ -896,10 +899,10 @@ __device__ __forceinline__ void camera_finish_body(const CamFinish& P, const dou
   if (tid != 0) return;
   double w[3], z[3], uh[3], cx[3], x[3];
   for (int k = 0; k < 3; ++k) w[k] = P.eye[k] - P.at[k];
-  const double wl = sqrt(dot3(w, w)), ul = sqrt(dot3(P.up, P.up));
+  const double wl = eps_len(w), ul = eps_len(P.up);
   for (int k = 0; k < 3; ++k) { z[k] = w[k] / wl; uh[k] = P.up[k] / ul; }
   cross3(uh, z, cx);
-  const double cl = sqrt(dot3(cx, cx));
+  const double cl = eps_len(cx);
   for (int k = 0; k < 3; ++k) x[k] = cx[k] / cl;
   double g_x[3], g_y[3], g_z[3];
   for (int k = 0; k < 3; ++k) { g_x[k] = S[3 + k]; g_y[k] = S[6 + k]; g_z[k] = -(P.ortho ? 1.0 : P.focal) * S[9 + k]; }

@@ -100,6 +100,13 @@ __device__ __forceinline__ double dot3(const double* a, const double* b) {
   return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
 }
 
+// |v| over xyz as the torch backend's normalize takes it (torch/utils.py:131-135): sqrt(sum(v_i^2 + 1e-10)).  The one
+// copy of the expression: the host's camera basis, k_prep's normals and the camera gradients' chain rule all divide by
+// it, and a forward and a backward that disagree about the 3e-10 show once `up` is nearly parallel to the view direction.
+__host__ __device__ __forceinline__ double eps_len(const double* v) {
+  return sqrt(((v[0] * v[0] + 1e-10) + (v[1] * v[1] + 1e-10)) + (v[2] * v[2] + 1e-10));
+}
+
 // Image-plane coordinates of pixel (column c, row r) of the full W x H grid: np.linspace(-1, 1, W)[c] and
 // np.linspace(1, -1, H)[r] -- start + i*step, last sample forced to stop -- times half the plane's width / height.
 // The one copy of the reference's end-point rule (srh_binned.h has a wave-uniform variant that needs no last-column test).

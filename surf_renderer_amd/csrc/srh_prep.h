@@ -16,7 +16,7 @@ __device__ __forceinline__ void prep_record64(const SegDev& S, int type, int i, 
     const double v[4] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3]};
     double len = sqrt(((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3]);
     // the torch backend normalises xyz only, with an eps inside the sum (torch/utils.py:131-135, :289)
-    if (tch) len = sqrt(((v[0] * v[0] + 1e-10) + (v[1] * v[1] + 1e-10)) + (v[2] * v[2] + 1e-10));
+    if (tch) len = eps_len(v);
     if (!(fabs(len) > 0.0)) len = 1.0;
     nh[0] = v[0] / len; nh[1] = v[1] / len; nh[2] = v[2] / len;
   }

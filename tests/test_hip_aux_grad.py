@@ -12,6 +12,7 @@ import torch
 
 from grad_cases import (RUN_TO_RUN, TCH_KEYS, assert_grads_close, gpu_leaf_scene, grad_kwargs, leaf_grads, load,
                         masked_loss, upstream, winners)
+from grad_fuzz_cases import _fuzz_scene
 from oracle import np_oracle_tch
 from oracle.torch_oracle import OUTPUTS, gradients_tch
 
@@ -113,50 +114,6 @@ def test_row_slab_equals_the_rows_of_the_full_frame():
     for k in ("normal", "pos"):
         assert torch.equal(sres[k].detach(), fres[k].detach()[r0:r1]), k
     assert_grads_close(slab, full, 2e-4, "slab")
-
-
-def _fuzz_scene(rng, ortho):
-    """All four primitive types, a random camera (perspective or orthographic) outside the cloud, small frames."""
-    f32 = lambda a: np.asarray(a, dtype=np.float32)          # noqa: E731
-    W, H = int(rng.choice([32, 48, 64])), int(rng.choice([24, 40, 56]))
-    eye = rng.normal(size=3)
-    back = eye / np.linalg.norm(eye)
-    eye = back * rng.choice([4.0, 6.0, 9.0])
-    cam = {"viewport": [0, 0, W, H], "fovy": float(np.deg2rad(rng.choice([30, 45, 70]))),
-           "focal_length": float(rng.choice([1.0, 3.0])), "eye": [*map(float, eye), 1.0],
-           "at": [*map(float, rng.normal(size=3) * 0.2), 1.0], "up": [*map(float, rng.normal(size=3)), 0.0],
-           "near": 0.1, "far": 100.0}
-    if ortho:
-        cam["proj_type"] = "ortho"
-    objs = {}
-    for k in rng.permutation(["disk", "triangle", "sphere", "plane"]):
-        n = int(rng.choice([1, 5, 40])) if k != "plane" else 1
-        pos = np.concatenate([rng.uniform(-1.5, 1.5, (n, 3)), np.ones((n, 1))], 1)
-        nrm = np.concatenate([rng.normal(size=(n, 3)), np.zeros((n, 1))], 1)
-        mat = rng.randint(0, 3, n)
-        if k == "disk":
-            objs[k] = {"pos": f32(pos), "normal": f32(nrm), "material_idx": mat,
-                       "radius": f32(np.exp(rng.uniform(np.log(0.05), np.log(1.2), n)))}
-        elif k == "sphere":
-            objs[k] = {"pos": f32(pos), "radius": f32(np.exp(rng.uniform(np.log(0.1), np.log(0.8), n))),
-                       "material_idx": mat}
-        elif k == "plane":                              # a wall behind the cloud, roughly facing the camera
-            objs[k] = {"pos": f32(np.concatenate([-3.0 * back, [1.0]])[None]),
-                       "normal": f32(np.concatenate([back + 0.2 * rng.normal(size=3), [0.0]])[None]),
-                       "material_idx": mat}
-        else:
-            c = rng.uniform(-1.5, 1.5, (n, 1, 3))
-            v = c + rng.normal(size=(n, 3, 3)) * np.exp(rng.uniform(np.log(0.1), np.log(0.8), (n, 1, 1)))
-            fn = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]) * rng.choice([-1, 1], (n, 1))
-            objs[k] = {"face": f32(np.concatenate([v, np.ones((n, 3, 1))], 2)),
-                       "normal": f32(np.concatenate([fn, np.zeros((n, 1))], 1)), "material_idx": mat}
-    return {"camera": cam,
-            "lights": {"pos": f32([[3, 4, 5, 1], [-4, 2, 3, 1]]), "color_idx": np.array([1, 2]),
-                       "attenuation": f32([[1, 0, 0], [0.5, 0.1, 0.01]]), "ambient": f32([0.01, 0.02, 0.01])},
-            "colors": f32([[0, 0, 0], [.8, .5, .4], [.3, .6, .9]]),
-            "materials": {"albedo": f32([[.5, .5, .5], [.9, .3, .2], [.2, .7, .4]]),
-                          "coeffs": f32([[1, 0, 0], [0.7, 0.3, 5], [0.5, 0.5, 20]])},
-            "objects": objs, "tonemap": {"type": "gamma", "gamma": 0.8}}
 
 
 def test_fuzz_against_the_helper():
