@@ -512,6 +512,73 @@ int srh_regularizers_bwd(const SrhRegularizerParams* params, const float* pos, c
                          const float* depth, const double* stats, const float* grad_terms, float* g_pos,
                          float* g_normal, float* g_image, float* g_depth, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's surfel re-projection layer, projection_renderer_differentiable_fast (diffrend/torch/
+ * projection_layer.py:170-278), for B views per call: N = W H surfels per view (world position and a D-channel value)
+ * are projected into the view's camera, spread bilinearly over four pixels with weighted-blended order-independent
+ * transparency, blurred with a separable Gaussian and optionally merged with a second image through the soft coverage
+ * mask.  Restated as gathers: no float atomic in either direction, fp64 arithmetic, fp32 results, values and gradients
+ * identical from run to run.  The camera is not differentiable.
+ *
+ * One forward is three steps, because the ordering is the caller's:
+ *   srh_projection_keys   writes one record per surfel into the workspace and keys (B, N) int32: the surfel's cell on
+ *                         the (W + 1) x (H + 1) grid of cells that reach the frame, (W + 1)(H + 1) for a surfel that
+ *                         does not
+ *   the caller            makes order (B, N) int32: per view a STABLE ASCENDING permutation of that view's keys (ties in
+ *                         ascending surfel index), which fixes the order of every sum
+ *   srh_projection_fwd    the rest.
+ * These entry points were added without an ABI version change.  Conventions as above: caller-owned device buffers,
+ * enqueue only, no synchronisation or allocation, argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_PROJ_MAX_CHANNELS 4
+#define SRH_PROJ_MAX_BLUR_HALF 64
+
+#define SRH_PROJ_USE_DEPTH 1            /* weight by exp(-2 z) */
+#define SRH_PROJ_USE_CENTER_DIST 2      /* weight by the Gaussian of the distance to the cell's pixel centre */
+#define SRH_PROJ_BLUR_ROTATED 4         /* blur the rotated image before the merge */
+#define SRH_PROJ_DETACH_MASK 8          /* the reference's detach_mask (wins over DETACH_MASK2, as there) */
+#define SRH_PROJ_DETACH_MASK2 16
+#define SRH_PROJ_DETACH_DEPTH_MERGE 32  /* no gradient through the depth, as a weight or as a blended value */
+
+/* the three buffers srh_projection_workspace_bytes sizes */
+#define SRH_PROJ_WS_FWD 0               /* scratch shared by srh_projection_keys and srh_projection_fwd */
+#define SRH_PROJ_WS_SAVED 1             /* written by srh_projection_fwd, read by srh_projection_bwd */
+#define SRH_PROJ_WS_BWD 2               /* scratch of srh_projection_bwd */
+
+typedef struct SrhProjectionParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24; N = W H surfels per view */
+  int32_t channels;             /* D in 1..SRH_PROJ_MAX_CHANNELS */
+  int32_t flags;                /* SRH_PROJ_* bits */
+  int32_t blur_half;            /* half-width of the blur in 0..SRH_PROJ_MAX_BLUR_HALF; 0 = no blur */
+  double fovy, focal_length;    /* shared by the views: 0 < fovy < pi, focal_length > 0 */
+  double taps[SRH_PROJ_MAX_BLUR_HALF + 1];   /* taps[|d|] for d in -blur_half..blur_half, finite; the caller normalises */
+} SrhProjectionParams;
+
+/* bytes of the buffer `which` (SRH_PROJ_WS_*; 8-byte aligned); 0 and srh_last_error on bad input */
+size_t srh_projection_workspace_bytes(const SrhProjectionParams* params, int32_t which);
+
+/* view (B, 12) fp64: each view's world-to-camera matrix, 3 rows of 4; surfels (B, N, 3) fp32; keys (B, N) int32 out */
+int srh_projection_keys(const SrhProjectionParams* params, const double* view, const float* surfels, void* workspace,
+                        size_t workspace_bytes, int32_t* keys, void* stream);
+
+/* rgb (B, N, D) fp32; rotated the same or NULL = no merge; keys and workspace as srh_projection_keys left them; order:
+ * per view a stable ascending permutation of the keys (an entry outside 0..N-1 is skipped).  saved (SRH_PROJ_WS_SAVED)
+ * may be NULL when no backward will follow.  out, image1 (B, N, D) and mask (B, N) fp32 are written; depth (B, N) may
+ * be NULL = not wanted. */
+int srh_projection_fwd(const SrhProjectionParams* params, const float* rgb, const float* rotated, const int32_t* keys,
+                       const int32_t* order, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes,
+                       float* out, float* mask, float* image1, float* depth, void* stream);
+
+/* Vector-Jacobian product.  view, surfels, rgb and the flags as in the forward call that wrote `saved`; `rotated` is
+ * only tested against NULL.  Upstream gradients g_out, g_image1 (B, N, D), g_mask, g_depth (B, N) fp32: NULL = none,
+ * not all.  grad_surfels (B, N, 3), grad_rgb, grad_rotated (B, N, D) are WRITTEN, every element once; any may be NULL
+ * = not wanted, not all; grad_rotated needs `rotated`. */
+int srh_projection_bwd(const SrhProjectionParams* params, const double* view, const float* surfels, const float* rgb,
+                       const float* rotated, const void* saved, size_t saved_bytes, void* workspace,
+                       size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
+                       const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,9 @@ _RENDERER = ("render", "render_views", "ResidentScene", "CapturedStep", "ViewSce
 _SCENE = ("load_scene", "load_model", "load_obj", "load_splat", "obj_to_triangle_spec")
 _SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
 _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
+_PROJECTION = ("projection_renderer_differentiable_fast",)
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION]
 
 
 def __getattr__(name):
@@ -27,6 +28,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".splats", __name__), name)
     if name in _REGULARIZERS:
         return getattr(importlib.import_module(".regularizers", __name__), name)
+    if name in _PROJECTION:
+        return getattr(importlib.import_module(".projection", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

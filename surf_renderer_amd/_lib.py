@@ -99,6 +99,18 @@ class SrhRegularizerParams(C.Structure):
 
 REG_TERMS, REG_STATS = 7, 4
 
+PROJ_MAX_CHANNELS, PROJ_MAX_BLUR_HALF = 4, 64
+(PROJ_USE_DEPTH, PROJ_USE_CENTER_DIST, PROJ_BLUR_ROTATED, PROJ_DETACH_MASK, PROJ_DETACH_MASK2,
+ PROJ_DETACH_DEPTH_MERGE) = 1, 2, 4, 8, 16, 32
+PROJ_WS_FWD, PROJ_WS_SAVED, PROJ_WS_BWD = 0, 1, 2
+
+
+class SrhProjectionParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("flags", C.c_int32), ("blur_half", C.c_int32), ("fovy", C.c_double), ("focal_length", C.c_double),
+                ("taps", C.c_double * (PROJ_MAX_BLUR_HALF + 1))]
+
+
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
            "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
            "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_render_views_aux",
@@ -106,7 +118,8 @@ EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_gene
            "srh_shadow_workspace_bytes", "srh_bin_counters",
            "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
            "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd",
-           "srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd")
+           "srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd",
+           "srh_projection_workspace_bytes", "srh_projection_keys", "srh_projection_fwd", "srh_projection_bwd")
 
 _lib: Optional[C.CDLL] = None
 
@@ -223,6 +236,19 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib.srh_regularizers_bwd.argtypes = [C.POINTER(SrhRegularizerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+    lib.srh_projection_workspace_bytes.restype = C.c_size_t
+    lib.srh_projection_workspace_bytes.argtypes = [C.POINTER(SrhProjectionParams), C.c_int32]
+    lib.srh_projection_keys.restype = C.c_int
+    lib.srh_projection_keys.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]
+    lib.srh_projection_fwd.restype = C.c_int
+    lib.srh_projection_fwd.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.srh_projection_bwd.restype = C.c_int
+    lib.srh_projection_bwd.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     got = lib.srh_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {got}, this package expects {ABI_VERSION}; rebuild it")

@@ -1,6 +1,6 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
-// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h.
+// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -25,6 +25,7 @@
 #include "srh_shadow.h"
 #include "srh_splat.h"
 #include "srh_regularizers.h"
+#include "srh_projection.h"
 
 using namespace srh;
 
@@ -467,6 +468,67 @@ int reg_setup(const SrhRegularizerParams* p, const float* pos, const float* norm
   R->nblk = (R->N + kRegBlock - 1) / kRegBlock;
   R->z_min = p->z_min; R->z_max = p->z_max; R->z_scale = p->z_scale; R->n_scale = p->unit_normal_scale;
   R->pos = pos; R->normal = normal; R->image = image; R->depth = depth;
+  return SRH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the surfel re-projection layer (srh_projection.h)
+// ------------------------------------------------------------------------------------------------
+static_assert(kProjMaxD == SRH_PROJ_MAX_CHANNELS && kProjMaxHalf == SRH_PROJ_MAX_BLUR_HALF, "srh.h and srh_projection.h");
+static_assert(kProjUseDepth == SRH_PROJ_USE_DEPTH && kProjUseCenterDist == SRH_PROJ_USE_CENTER_DIST &&
+              kProjBlurRotated == SRH_PROJ_BLUR_ROTATED && kProjDetachMask == SRH_PROJ_DETACH_MASK &&
+              kProjDetachMask2 == SRH_PROJ_DETACH_MASK2 && kProjDetachDepthMerge == SRH_PROJ_DETACH_DEPTH_MERGE,
+              "srh.h and srh_projection.h");
+
+// argument checks (no HIP call) and the device view of a projection launch
+int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
+  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
+    return fail(SRH_E_RANGE, "width x height = %d x %d out of range", p->width, p->height);
+  if (p->channels < 1 || p->channels > kProjMaxD)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (p->flags & ~63) return fail(SRH_E_TYPE, "flags = %d has unknown bits", p->flags);
+  if (p->blur_half < 0 || p->blur_half > kProjMaxHalf)
+    return fail(SRH_E_RANGE, "blur_half = %d, expected 0..%d", p->blur_half, kProjMaxHalf);
+  if (!(p->fovy > 0.0 && p->fovy < 3.14159265358979323846))
+    return fail(SRH_E_CAMERA, "fovy = %g, expected 0 < fovy < pi", p->fovy);
+  if (!(p->focal_length > 0.0 && std::isfinite(p->focal_length)))
+    return fail(SRH_E_CAMERA, "focal_length = %g, expected positive and finite", p->focal_length);
+  for (int k = 0; k <= p->blur_half; ++k)
+    if (!std::isfinite(p->taps[k])) return fail(SRH_E_RANGE, "taps[%d] is not finite", k);
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->W = p->width; P->H = p->height; P->N = p->width * p->height; P->D = p->channels;
+  P->P = 2 * P->D + 2; P->CS = P->D + 3; P->half = p->blur_half;
+  P->flags = p->flags | (has_rotated ? kProjHasRotated : 0);
+  P->ncell = (P->W + 1) * (P->H + 1);
+  P->nblk = (P->N + kProjBlock - 1) / kProjBlock;
+  // project_image_coordinates: h = 2 f tan(fovy / 2), w = h W / H, pixel = x (-(W - 1) / w) + W / 2 with x = f X / Z
+  const double h = tan(p->fovy / 2.0) * 2.0 * p->focal_length, w = h * ((double)P->W / (double)P->H);
+  P->fsx = p->focal_length * (-(double)(P->W - 1) / w);
+  P->fsy = p->focal_length * ((double)(P->H - 1) / h);
+  P->cx0 = P->W / 2.0 - 0.5;
+  P->cy0 = P->H / 2.0 - 0.5;
+  for (int k = 0; k <= P->half; ++k) P->taps[k] = p->taps[k];
+  return SRH_OK;
+}
+
+// SRH_PROJ_WS_FWD: rec (B, N, 4) | pre (B, P, N) | tmp (B, P, N) fp64 | range (B, ncell, 2) int32
+// SRH_PROJ_WS_SAVED: blr (B, P, N) | cor (B, 4, CS, N) fp64
+// SRH_PROJ_WS_BWD: gpl (B, P, N) | gtmp (B, P, N) | gcor (B, 4, CS, N) fp64
+size_t proj_ws_bytes(const ProjDev& P, int which) {
+  const size_t px = (size_t)P.B * P.N;
+  switch (which) {
+    case SRH_PROJ_WS_FWD: return px * (4 + 2 * P.P) * sizeof(double) + (size_t)P.B * P.ncell * 2 * sizeof(int32_t);
+    case SRH_PROJ_WS_SAVED: return px * (P.P + 4 * P.CS) * sizeof(double);
+    default: return px * (2 * P.P + 4 * P.CS) * sizeof(double);
+  }
+}
+
+int proj_check_ws(const ProjDev& P, int which, const char* name, const void* ws, size_t bytes) {
+  const size_t need = proj_ws_bytes(P, which);
+  if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
+    return fail(SRH_E_WORKSPACE, "%s: need %zu bytes, 8-byte aligned (got %zu at %p)", name, need, bytes, ws);
   return SRH_OK;
 }
 
@@ -1308,6 +1370,102 @@ int srh_regularizers_bwd(const SrhRegularizerParams* params, const float* pos, c
   G.pos = g_pos; G.normal = g_normal; G.image = g_image; G.depth = g_depth;
   hipLaunchKernelGGL(k_reg_bwd, dim3(R.nblk, R.B), dim3(kRegBlock), 0, (hipStream_t)stream, R, G, stats, grad_terms);
   return launch_status("k_reg_bwd launch");
+}
+
+// ---- the surfel re-projection layer ------------------------------------------------------------------------------
+size_t srh_projection_workspace_bytes(const SrhProjectionParams* params, int32_t which) {
+  ProjDev P;
+  if (proj_setup(params, false, &P)) return 0;
+  if (which < SRH_PROJ_WS_FWD || which > SRH_PROJ_WS_BWD) {
+    fail(SRH_E_TYPE, "which = %d, expected SRH_PROJ_WS_FWD, _SAVED or _BWD", which);
+    return 0;
+  }
+  return proj_ws_bytes(P, which);
+}
+
+int srh_projection_keys(const SrhProjectionParams* params, const double* view, const float* surfels, void* workspace,
+                        size_t workspace_bytes, int32_t* keys, void* stream) {
+  ProjDev P;
+  int rc = proj_setup(params, false, &P);
+  if (rc) return rc;
+  if (!view) return fail(SRH_E_NULL, "view is NULL");
+  if (!surfels) return fail(SRH_E_NULL, "surfels is NULL");
+  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
+  if ((rc = proj_check_ws(P, SRH_PROJ_WS_FWD, "workspace", workspace, workspace_bytes))) return rc;
+  hipLaunchKernelGGL(k_proj_keys, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, view, surfels,
+                     (double*)workspace, keys);
+  return launch_status("k_proj_keys launch");
+}
+
+int srh_projection_fwd(const SrhProjectionParams* params, const float* rgb, const float* rotated, const int32_t* keys,
+                       const int32_t* order, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes,
+                       float* out, float* mask, float* image1, float* depth, void* stream) {
+  ProjDev P;
+  int rc = proj_setup(params, rotated != nullptr, &P);
+  if (rc) return rc;
+  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
+  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
+  if (!order) return fail(SRH_E_NULL, "order is NULL");
+  if (!out || !mask || !image1) return fail(SRH_E_NULL, "out / mask / image1 is NULL");
+  if ((rc = proj_check_ws(P, SRH_PROJ_WS_FWD, "workspace", workspace, workspace_bytes))) return rc;
+  if (saved && (rc = proj_check_ws(P, SRH_PROJ_WS_SAVED, "saved", saved, saved_bytes))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t px = (size_t)P.B * P.N;
+  double* rec = (double*)workspace;
+  double* pre = rec + px * 4;
+  double* tmp = pre + px * P.P;
+  int32_t* range = (int32_t*)(tmp + px * P.P);
+  double* blr = (double*)saved;
+  double* cor = blr ? blr + px * P.P : nullptr;
+  const int nb = (rotated && (P.flags & kProjBlurRotated)) ? 2 * P.D + 1 : P.D + 1;
+  const dim3 grid(P.nblk, P.B), block(kProjBlock);
+  if (hipError_t e = hipMemsetAsync(range, 0, (size_t)P.B * P.ncell * 2 * sizeof(int32_t), st))
+    return hip_fail(e, "projection cell ranges memset");
+  hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, P, keys, order, range);
+  hipLaunchKernelGGL(k_proj_gather, grid, block, 0, st, P, (const double*)rec, order, (const int32_t*)range, rgb, rotated,
+                     pre, cor);
+  hipLaunchKernelGGL(k_proj_blur_h, dim3((P.N * nb + kProjBlock - 1) / kProjBlock, P.B), block, 0, st, P, nb,
+                     (const double*)pre, tmp);
+  hipLaunchKernelGGL(k_proj_blur_v_merge, grid, block, 0, st, P, nb, (const double*)tmp, (const double*)pre, rotated, blr,
+                     out, mask, image1, depth);
+  return launch_status("projection forward launch");
+}
+
+int srh_projection_bwd(const SrhProjectionParams* params, const double* view, const float* surfels, const float* rgb,
+                       const float* rotated, const void* saved, size_t saved_bytes, void* workspace,
+                       size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
+                       const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+  ProjDev P;
+  int rc = proj_setup(params, rotated != nullptr, &P);
+  if (rc) return rc;
+  if (!view) return fail(SRH_E_NULL, "view is NULL");
+  if (!surfels) return fail(SRH_E_NULL, "surfels is NULL");
+  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
+  if (!g_out && !g_mask && !g_image1 && !g_depth)
+    return fail(SRH_E_NULL, "g_out, g_mask, g_image1 and g_depth are all NULL");
+  if (!grad_surfels && !grad_rgb && !grad_rotated)
+    return fail(SRH_E_NULL, "grad_surfels, grad_rgb and grad_rotated are all NULL");
+  if (grad_rotated && !rotated) return fail(SRH_E_NULL, "grad_rotated without rotated");
+  if ((rc = proj_check_ws(P, SRH_PROJ_WS_SAVED, "saved", saved, saved_bytes))) return rc;
+  if ((rc = proj_check_ws(P, SRH_PROJ_WS_BWD, "workspace", workspace, workspace_bytes))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t px = (size_t)P.B * P.N;
+  const double* blr = (const double*)saved;
+  const double* cor = blr + px * P.P;
+  double* gpl = (double*)workspace;
+  double* gtmp = gpl + px * P.P;
+  double* gcor = (grad_surfels || grad_rgb) ? gtmp + px * P.P : nullptr;
+  const int nb = (grad_rotated && (P.flags & kProjBlurRotated)) ? 2 * P.D + 1 : P.D + 1;
+  const dim3 grid(P.nblk, P.B), block(kProjBlock);
+  hipLaunchKernelGGL(k_proj_merge_bwd, grid, block, 0, st, P, blr, g_out, g_mask, g_image1, g_depth, gpl);
+  hipLaunchKernelGGL(k_proj_blur_h, dim3((P.N * nb + kProjBlock - 1) / kProjBlock, P.B), block, 0, st, P, nb,
+                     (const double*)gpl, gtmp);
+  hipLaunchKernelGGL(k_proj_blur_v_corner, grid, block, 0, st, P, nb, (const double*)gtmp, (const double*)gpl, cor, gcor,
+                     grad_rotated);
+  if (gcor)
+    hipLaunchKernelGGL(k_proj_surfel_bwd, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
+                       grad_surfels);
+  return launch_status("projection backward launch");
 }
 
 }  // extern "C"

@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/projection/pr1_*.npz: the reference's OWN projection_renderer_differentiable_fast
+(diffrend/torch/projection_layer.py:170-278), imported UNMODIFIED and run on the CPU under autograd, on the seeded
+cases of tests/projection_cases.py and the flag variants of its 12x16 case.
+
+Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by hand -- no test reads
+the reference.  The reference runs this function in float32 only (its blur builds float32 taps, so the float64 shim of
+ref_harness.precision ends in a dtype error), so the fixtures hold float32 results; tests/
+test_projection_oracle_cpu.py states what that leaves of the comparison.  It also needs rgb as [B, H, W, D], so a
+[B, N, D] case is handed over reshaped.  A case of exactly three views is recorded view by view (see emit).
+
+Stored per fixture: in/{surfels, rgb, rotated_image}, in/camera/{eye, at, up, viewport, fovy, focal_length},
+in/blur_size, in/flags (JSON), grad_in/<output> (the case's upstream gradients), ref/<output> [B, H, W, .] and
+grad/<input> = d sum_outputs sum(output * grad_in) / d input, float32.  The subfolder keeps the fixtures out of the
+top-level globs (the golden drift check, conftest.golden_cases)."""
+import contextlib
+import io
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import ref_harness as R  # noqa: E402
+
+sys.path.insert(0, os.path.join(R.REPO, "tests"))
+import projection_cases as cases  # noqa: E402
+from projection_oracle import INPUTS  # noqa: E402
+
+with contextlib.redirect_stdout(io.StringIO()):
+    import diffrend.torch.projection_layer as ref_projection  # noqa: E402
+
+
+def emit(name, variant):
+    c = cases.case(name, variant)
+    B, H, W, D = c["shape"]
+    leaves = {k: torch.tensor(c[k], requires_grad=True) for k in INPUTS if c[k] is not None}
+    camera = {k: (torch.tensor(np.asarray(v, dtype=np.float32)) if k in ("eye", "at", "up") else v)
+              for k, v in c["camera"].items()}
+
+    def run(views):
+        with R.quiet():
+            out, proj_out = ref_projection.projection_renderer_differentiable_fast(
+                leaves["surfels"][views], leaves["rgb"][views].reshape(-1, H, W, D),
+                {k: (v[views] if k in ("eye", "at", "up") else v) for k, v in camera.items()},
+                rotated_image=leaves["rotated_image"][views].reshape(-1, H, W, D) if "rotated_image" in leaves else None,
+                blur_size=c["blur_size"], **c["flags"])
+        return dict(proj_out, out=out)
+
+    if B == 3:
+        # lookat_rot_inv calls torch.cross(up, z) without `dim`, which for [3, 3] operands -- three views, and only
+        # three -- still means dim 0: the cross product is taken ACROSS the views.  That is an accident of B == 3,
+        # not a meaning of the layer, so such a case is recorded view by view
+        per_view = [run(slice(b, b + 1)) for b in range(B)]
+        res = {k: torch.cat([r[k] for r in per_view]) for k in per_view[0]}
+    else:
+        res = run(slice(None))
+    assert set(res) == set(c["upstream"]), (sorted(res), sorted(c["upstream"]))
+    sum(torch.sum(res[k] * torch.tensor(g)) for k, g in c["upstream"].items()).backward()
+    flat = {"in/" + k: c[k] for k in leaves}
+    for k, v in c["camera"].items():
+        flat["in/camera/" + k] = np.asarray(v, dtype=np.float64 if k in ("fovy", "focal_length") else None)
+    flat["in/blur_size"] = np.asarray(c["blur_size"], dtype=np.float64)
+    flat["in/flags"] = np.asarray(json.dumps(c["flags"], sort_keys=True))
+    for k, g in c["upstream"].items():
+        assert res[k].dtype == torch.float32 and tuple(res[k].shape) == g.shape, k
+        flat["grad_in/" + k] = g
+        flat["ref/" + k] = res[k].detach().numpy()
+    for k, t in leaves.items():
+        flat["grad/" + k] = t.grad.numpy()
+    R.write("pr1_" + cases.tag(name, variant), flat)
+
+
+if __name__ == "__main__":
+    R.OUT = os.path.join(R.REPO, "tests", "golden", "projection")
+    for n, v in cases.ALL:
+        emit(n, v)
