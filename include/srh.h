@@ -579,6 +579,68 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
                        size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
                        const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's backward-warp ("pull") re-projection, projection_reverse_renderer (diffrend/torch/
+ * projection_layer.py:281-333), for B views per call.  Each of the N = W H pixels of the target view has a surfel
+ * (out_pos, world coordinates) that is projected into the source camera (camera 1), where the source image rgb is
+ * sampled bilinearly (zero padding, texel centres at integers of pixel coordinate - 1/2); a pixel that leaves the frame
+ * by the reference's 0.5-pixel test, or whose depth in camera 1 exceeds the twice-resampled depth of the source view's
+ * own surfels (in_pos, seen by camera 2) by more than depth_epsilon, is masked out, and `rotated` fills the holes.
+ * fp64 arithmetic, fp32 results, no float atomic in either direction, values and gradients identical from run to run.
+ * The cameras are not differentiable.
+ *
+ * The forward is one call.  A backward that wants grad_rgb or grad_in_pos is three steps, because the ordering is the
+ * caller's, as for srh_projection_*:
+ *   srh_reverse_projection_keys   keys (B, N) int32: each pixel's sample cell on the (W + 1) x (H + 1) grid of cells
+ *                                 that reach the frame, (W + 1)(H + 1) for a sample that does not; and one record per
+ *                                 pixel at the head of the backward workspace
+ *   the caller                    order (B, N) int32: per view a STABLE ASCENDING permutation of that view's keys
+ *   srh_reverse_projection_bwd    the rest.
+ * A backward that wants neither skips the first two and passes keys = order = workspace = NULL.  Added without an ABI
+ * version change.  Conventions as above: caller-owned device buffers, enqueue only, no synchronisation or allocation,
+ * argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_RPROJ_WS_FWD 0              /* scratch of srh_reverse_projection_fwd */
+#define SRH_RPROJ_WS_BWD 1              /* shared by srh_reverse_projection_keys and srh_reverse_projection_bwd */
+
+typedef struct SrhReverseProjectionParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24: the frame of rgb and of both cameras */
+  int32_t channels;             /* D in 1..SRH_PROJ_MAX_CHANNELS */
+  double fovy1, focal_length1;  /* camera 1, shared by the views: 0 < fovy < pi, focal_length > 0 */
+  double fovy2, focal_length2;  /* camera 2 */
+  double depth_epsilon;         /* finite */
+} SrhReverseProjectionParams;
+
+/* bytes of the buffer `which` (SRH_RPROJ_WS_*; 8-byte aligned); 0 and srh_last_error on bad input */
+size_t srh_reverse_projection_workspace_bytes(const SrhReverseProjectionParams* params, int32_t which);
+
+/* view1, view2 (B, 12) fp64: each view's world-to-camera matrices, 3 rows of 4; rgb (B, N, D), in_pos, out_pos (B, N, 3)
+ * fp32; rotated (B, N, D) or NULL = no merge; keep (B, N) fp32 or NULL: a plane the mask is multiplied by (dropout).
+ * mask (B, N) and image1 (B, N, D) are written; out (B, N, D) is written with `rotated` and not looked at without (the
+ * result is then image1); depth (B, N) may be NULL = not wanted.  Nothing is kept for the backward. */
+int srh_reverse_projection_fwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                               const float* rgb, const float* in_pos, const float* out_pos, const float* rotated,
+                               const float* keep, void* workspace, size_t workspace_bytes, float* out, float* mask,
+                               float* image1, float* depth, void* stream);
+
+/* keys (B, N) int32 out; workspace: SRH_RPROJ_WS_BWD */
+int srh_reverse_projection_keys(const SrhReverseProjectionParams* params, const double* view1, const float* out_pos,
+                                void* workspace, size_t workspace_bytes, int32_t* keys, void* stream);
+
+/* Vector-Jacobian product.  Inputs as in the forward call; mask as that call wrote it.  Upstream gradients g_out,
+ * g_image1 (B, N, D), g_depth (B, N) fp32: NULL = none, not all; g_out is the gradient of the `out` of a call with a
+ * rotated image (without one `out` is image1, and its gradient belongs in g_image1).  The mask carries no gradient.
+ * grad_rgb, grad_rotated (B, N, D), grad_in_pos, grad_out_pos (B, N, 3) are WRITTEN, every element once; any may be
+ * NULL = not wanted, not all.  grad_rgb and grad_in_pos need keys and workspace as srh_reverse_projection_keys left
+ * them and `order` (an entry outside 0..N-1 is skipped); without either of the two, keys, order and workspace are not
+ * looked at. */
+int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                               const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
+                               const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
+                               const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
+                               float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,9 @@ _SCENE = ("load_scene", "load_model", "load_obj", "load_splat", "obj_to_triangle
 _SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
 _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 _PROJECTION = ("projection_renderer_differentiable_fast",)
+_REVERSE_PROJECTION = ("projection_reverse_renderer",)
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION]
 
 
 def __getattr__(name):
@@ -30,6 +31,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".regularizers", __name__), name)
     if name in _PROJECTION:
         return getattr(importlib.import_module(".projection", __name__), name)
+    if name in _REVERSE_PROJECTION:
+        return getattr(importlib.import_module(".reverse_projection", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

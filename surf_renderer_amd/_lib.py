@@ -111,6 +111,15 @@ class SrhProjectionParams(C.Structure):
                 ("taps", C.c_double * (PROJ_MAX_BLUR_HALF + 1))]
 
 
+RPROJ_WS_FWD, RPROJ_WS_BWD = 0, 1
+
+
+class SrhReverseProjectionParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("fovy1", C.c_double), ("focal_length1", C.c_double), ("fovy2", C.c_double),
+                ("focal_length2", C.c_double), ("depth_epsilon", C.c_double)]
+
+
 EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
            "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
            "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_render_views_aux",
@@ -119,7 +128,9 @@ EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_gene
            "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
            "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd",
            "srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd",
-           "srh_projection_workspace_bytes", "srh_projection_keys", "srh_projection_fwd", "srh_projection_bwd")
+           "srh_projection_workspace_bytes", "srh_projection_keys", "srh_projection_fwd", "srh_projection_bwd",
+           "srh_reverse_projection_workspace_bytes", "srh_reverse_projection_fwd", "srh_reverse_projection_keys",
+           "srh_reverse_projection_bwd")
 
 _lib: Optional[C.CDLL] = None
 
@@ -249,6 +260,17 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib.srh_projection_bwd.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.srh_reverse_projection_workspace_bytes.restype = C.c_size_t
+    lib.srh_reverse_projection_workspace_bytes.argtypes = [C.POINTER(SrhReverseProjectionParams), C.c_int32]
+    lib.srh_reverse_projection_fwd.restype = C.c_int
+    lib.srh_reverse_projection_fwd.argtypes = [C.POINTER(SrhReverseProjectionParams)] + [C.c_void_p] * 8 + [
+        C.c_size_t] + [C.c_void_p] * 5
+    lib.srh_reverse_projection_keys.restype = C.c_int
+    lib.srh_reverse_projection_keys.argtypes = [C.POINTER(SrhReverseProjectionParams), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.srh_reverse_projection_bwd.restype = C.c_int
+    lib.srh_reverse_projection_bwd.argtypes = [C.POINTER(SrhReverseProjectionParams)] + [C.c_void_p] * 9 + [
+        C.c_size_t] + [C.c_void_p] * 8
     got = lib.srh_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {got}, this package expects {ABI_VERSION}; rebuild it")

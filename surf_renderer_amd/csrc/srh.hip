@@ -1,6 +1,7 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
-// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h.
+// srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
+// srh_reverse_projection.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -26,6 +27,7 @@
 #include "srh_splat.h"
 #include "srh_regularizers.h"
 #include "srh_projection.h"
+#include "srh_reverse_projection.h"
 
 using namespace srh;
 
@@ -529,6 +531,64 @@ int proj_check_ws(const ProjDev& P, int which, const char* name, const void* ws,
   const size_t need = proj_ws_bytes(P, which);
   if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
     return fail(SRH_E_WORKSPACE, "%s: need %zu bytes, 8-byte aligned (got %zu at %p)", name, need, bytes, ws);
+  return SRH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the reverse re-projection layer (srh_reverse_projection.h)
+// ------------------------------------------------------------------------------------------------
+// argument checks (no HIP call) and the device view of a reverse projection launch
+int rproj_setup(const SrhReverseProjectionParams* p, RProjDev* R) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
+  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
+    return fail(SRH_E_RANGE, "width x height = %d x %d out of range", p->width, p->height);
+  if (p->channels < 1 || p->channels > kProjMaxD)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  const double fovy[2] = {p->fovy1, p->fovy2}, focal[2] = {p->focal_length1, p->focal_length2};
+  for (int c = 0; c < 2; ++c) {
+    if (!(fovy[c] > 0.0 && fovy[c] < 3.14159265358979323846))
+      return fail(SRH_E_CAMERA, "fovy%d = %g, expected 0 < fovy < pi", c + 1, fovy[c]);
+    if (!(focal[c] > 0.0 && std::isfinite(focal[c])))
+      return fail(SRH_E_CAMERA, "focal_length%d = %g, expected positive and finite", c + 1, focal[c]);
+  }
+  if (!std::isfinite(p->depth_epsilon)) return fail(SRH_E_RANGE, "depth_epsilon = %g, expected finite", p->depth_epsilon);
+  memset(R, 0, sizeof(*R));
+  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height; R->D = p->channels;
+  R->ncell = (R->W + 1) * (R->H + 1);
+  R->nblk = (R->N + kProjBlock - 1) / kProjBlock;
+  for (int c = 0; c < 2; ++c) {      // as proj_setup
+    const double h = tan(fovy[c] / 2.0) * 2.0 * focal[c], w = h * ((double)R->W / (double)R->H);
+    R->fsx[c] = focal[c] * (-(double)(R->W - 1) / w);
+    R->fsy[c] = focal[c] * ((double)(R->H - 1) / h);
+  }
+  R->cx0 = R->W / 2.0 - 0.5;
+  R->cy0 = R->H / 2.0 - 0.5;
+  R->eps = p->depth_epsilon;
+  return SRH_OK;
+}
+
+// what k_proj_keys and k_proj_mark read of a ProjDev, for camera 1: no weights, so the record is (fx, fy, z, 1)
+ProjDev rproj_as_proj(const RProjDev& R) {
+  ProjDev P;
+  memset(&P, 0, sizeof(P));
+  P.B = R.B; P.W = R.W; P.H = R.H; P.N = R.N; P.D = R.D; P.ncell = R.ncell; P.nblk = R.nblk;
+  P.fsx = R.fsx[0]; P.fsy = R.fsy[0]; P.cx0 = R.cx0; P.cy0 = R.cy0;
+  return P;
+}
+
+// SRH_RPROJ_WS_FWD: d_in (B, N) fp64
+// SRH_RPROJ_WS_BWD: rec (B, N, 4) | gpl (B, D + 1, N) fp64 | range (B, ncell, 2) int32
+size_t rproj_ws_bytes(const RProjDev& R, int which) {
+  const size_t px = (size_t)R.B * R.N;
+  if (which == SRH_RPROJ_WS_FWD) return px * sizeof(double);
+  return px * (4 + R.D + 1) * sizeof(double) + (size_t)R.B * R.ncell * 2 * sizeof(int32_t);
+}
+
+int rproj_check_ws(const RProjDev& R, int which, const void* ws, size_t bytes) {
+  const size_t need = rproj_ws_bytes(R, which);
+  if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
+    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, bytes, ws);
   return SRH_OK;
 }
 
@@ -1466,6 +1526,98 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
     hipLaunchKernelGGL(k_proj_surfel_bwd, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
                        grad_surfels);
   return launch_status("projection backward launch");
+}
+
+// ---- the reverse re-projection layer -----------------------------------------------------------------------------
+size_t srh_reverse_projection_workspace_bytes(const SrhReverseProjectionParams* params, int32_t which) {
+  RProjDev R;
+  if (rproj_setup(params, &R)) return 0;
+  if (which != SRH_RPROJ_WS_FWD && which != SRH_RPROJ_WS_BWD) {
+    fail(SRH_E_TYPE, "which = %d, expected SRH_RPROJ_WS_FWD or _BWD", which);
+    return 0;
+  }
+  return rproj_ws_bytes(R, which);
+}
+
+int srh_reverse_projection_fwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                               const float* rgb, const float* in_pos, const float* out_pos, const float* rotated,
+                               const float* keep, void* workspace, size_t workspace_bytes, float* out, float* mask,
+                               float* image1, float* depth, void* stream) {
+  RProjDev R;
+  int rc = rproj_setup(params, &R);
+  if (rc) return rc;
+  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
+  if (!view2) return fail(SRH_E_NULL, "view2 is NULL");
+  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
+  if (!in_pos) return fail(SRH_E_NULL, "in_pos is NULL");
+  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
+  if (rotated && !out) return fail(SRH_E_NULL, "out is NULL with a rotated image");
+  if (!mask) return fail(SRH_E_NULL, "mask is NULL");
+  if (!image1) return fail(SRH_E_NULL, "image1 is NULL");
+  if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_FWD, workspace, workspace_bytes))) return rc;
+  const dim3 grid(R.nblk, R.B), block(kProjBlock);
+  hipStream_t st = (hipStream_t)stream;
+  double* d_in = (double*)workspace;
+  hipLaunchKernelGGL(k_rproj_depth_in, grid, block, 0, st, R, view1, view2, in_pos, out_pos, d_in);
+  hipLaunchKernelGGL(k_rproj_fwd, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, rotated, keep,
+                     (const double*)d_in, out, mask, image1, depth);
+  return launch_status("reverse projection forward launch");
+}
+
+int srh_reverse_projection_keys(const SrhReverseProjectionParams* params, const double* view1, const float* out_pos,
+                                void* workspace, size_t workspace_bytes, int32_t* keys, void* stream) {
+  RProjDev R;
+  int rc = rproj_setup(params, &R);
+  if (rc) return rc;
+  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
+  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
+  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
+  if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_BWD, workspace, workspace_bytes))) return rc;
+  hipLaunchKernelGGL(k_proj_keys, dim3(R.nblk, R.B), dim3(kProjBlock), 0, (hipStream_t)stream, rproj_as_proj(R), view1,
+                     out_pos, (double*)workspace, keys);
+  return launch_status("reverse projection k_proj_keys launch");
+}
+
+int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                               const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
+                               const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
+                               const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
+                               float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream) {
+  RProjDev R;
+  int rc = rproj_setup(params, &R);
+  if (rc) return rc;
+  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
+  if (!view2) return fail(SRH_E_NULL, "view2 is NULL");
+  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
+  if (!in_pos) return fail(SRH_E_NULL, "in_pos is NULL");
+  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
+  if (!mask) return fail(SRH_E_NULL, "mask is NULL");
+  if (!g_out && !g_image1 && !g_depth) return fail(SRH_E_NULL, "g_out, g_image1 and g_depth are all NULL");
+  if (!grad_rgb && !grad_in_pos && !grad_out_pos && !grad_rotated)
+    return fail(SRH_E_NULL, "grad_rgb, grad_in_pos, grad_out_pos and grad_rotated are all NULL");
+  const bool walk = grad_rgb || grad_in_pos;
+  if (walk) {
+    if (!keys) return fail(SRH_E_NULL, "keys is NULL");
+    if (!order) return fail(SRH_E_NULL, "order is NULL");
+    if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_BWD, workspace, workspace_bytes))) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t px = (size_t)R.B * R.N;
+  double* rec = (double*)workspace;
+  double* gpl = walk ? rec + px * 4 : nullptr;
+  int32_t* range = walk ? (int32_t*)(gpl + px * (R.D + 1)) : nullptr;
+  const dim3 grid(R.nblk, R.B), block(kProjBlock);
+  if (walk) {
+    if (hipError_t e = hipMemsetAsync(range, 0, (size_t)R.B * R.ncell * 2 * sizeof(int32_t), st))
+      return hip_fail(e, "reverse projection cell ranges memset");
+    hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, rproj_as_proj(R), keys, order, range);
+  }
+  hipLaunchKernelGGL(k_rproj_pixel_bwd, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, mask, g_out, g_image1,
+                     g_depth, gpl, grad_out_pos, grad_rotated);
+  if (walk)
+    hipLaunchKernelGGL(k_rproj_texel_bwd, grid, block, 0, st, R, view2, (const double*)rec, order, (const int32_t*)range,
+                       (const double*)gpl, grad_rgb, grad_in_pos);
+  return launch_status("reverse projection backward launch");
 }
 
 }  // extern "C"

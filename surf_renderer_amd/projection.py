@@ -114,36 +114,70 @@ def blur_taps(blur_size: float, height: int) -> Tuple[int, np.ndarray]:
     return half, (k / k.sum())[half:]
 
 
-def _as_tensor(name: str, x: Any) -> torch.Tensor:
+def as_float_tensor(name: str, x: Any, caller: str = _NAME) -> torch.Tensor:
     if x is None:
-        raise ValueError(f"{_NAME}: {name} is missing")
+        raise ValueError(f"{caller}: {name} is missing")
     t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
     if not t.is_floating_point():
-        raise ValueError(f"{_NAME}: {name} has dtype {t.dtype}, expected a floating-point type")
+        raise ValueError(f"{caller}: {name} has dtype {t.dtype}, expected a floating-point type")
     return t
+
+
+def _host(v):
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def camera_frame(name: str, camera: Mapping, label: str = "camera") -> Tuple[int, int]:
+    """The first half of the camera checks (ValueError, prefixed `name`, the camera called `label`): every entry is
+    there, none requires grad, and the viewport is a frame.  Returns (W, H)."""
+    for k in ("eye", "at", "up", "viewport", "fovy", "focal_length"):
+        if k not in camera or camera[k] is None:
+            raise ValueError(f"{name}: {label}['{k}'] is missing")
+    for k, v in camera.items():
+        if isinstance(v, torch.Tensor) and v.requires_grad:
+            raise ValueError(f"{name}: {label}['{k}'] requires grad, but the camera is not differentiable on this "
+                             "path (detach it)")
+    vp = _host(camera["viewport"]).reshape(-1)
+    if vp.size != 4:
+        raise ValueError(f"{name}: {label}['viewport']: expected 4 values, got {vp.size}")
+    W, H = int(vp[2] - vp[0]), int(vp[3] - vp[1])
+    if W < 1 or H < 1:
+        raise ValueError(f"{name}: {label}['viewport']: empty {W} x {H} frame")
+    return W, H
+
+
+def camera_views(name: str, camera: Mapping, B: int, label: str = "camera") -> Tuple[float, float, torch.Tensor]:
+    """The second half, once the batch size is known: fovy and focal_length in range, eye / at / up finite [B, 3] or
+    [B, 4] under the reference's w conventions and not degenerate.  Returns (fovy, focal_length, the per-view matrices
+    [B, 3, 4] float64 on the host)."""
+    fovy, focal = float(_host(camera["fovy"]).reshape(-1)[0]), float(_host(camera["focal_length"]).reshape(-1)[0])
+    if not 0 < fovy < math.pi:
+        raise ValueError(f"{name}: {label}['fovy'] = {fovy}, expected 0 < fovy < pi")
+    if not (math.isfinite(focal) and focal > 0):
+        raise ValueError(f"{name}: {label}['focal_length'] = {focal}, expected positive and finite")
+    cam = {}
+    for k in ("eye", "at", "up"):
+        v = np.asarray(_host(camera[k]), dtype=np.float64)
+        if v.ndim != 2 or v.shape[0] != B or v.shape[1] not in (3, 4) or not np.all(np.isfinite(v)):
+            raise ValueError(f"{name}: {label}['{k}'] is {list(v.shape)}, expected finite [{B}, 3] or [{B}, 4]")
+        if v.shape[1] == 4:          # lookat_rot_inv's conventions; world_to_cam_batched then drops w
+            if k == "up" and np.any(v[:, 3] != 0):
+                raise ValueError(f"{name}: {label}['up'] is a direction: w must be 0")
+            if k != "up" and np.any(v[:, 3] == 0):
+                raise ValueError(f"{name}: {label}['{k}'] is a point: w must not be 0")
+        cam[k] = torch.from_numpy(np.ascontiguousarray(v[:, :3]))
+    if torch.any(torch.all(cam["eye"] == cam["at"], dim=-1)):
+        raise ValueError(f"{name}: {label}['eye'] == {label}['at']")
+    if torch.any(torch.linalg.cross(cam["up"], cam["eye"] - cam["at"]).abs().amax(-1) == 0):
+        raise ValueError(f"{name}: {label}['up'] is zero or parallel to eye - at")
+    return fovy, focal, view_matrices(cam["eye"], cam["at"], cam["up"])
 
 
 def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
     """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError).  Returns the
     tensors, (B, H, W, D), the per-view matrices [B, 3, 4] float64 on the host, and the blur's half-width and taps."""
-    surfels, rgb = _as_tensor("surfels", surfels), _as_tensor("rgb", rgb)
-    for k in ("eye", "at", "up", "viewport", "fovy", "focal_length"):
-        if k not in camera or camera[k] is None:
-            raise ValueError(f"{_NAME}: camera['{k}'] is missing")
-    for k, v in camera.items():
-        if isinstance(v, torch.Tensor) and v.requires_grad:
-            raise ValueError(f"{_NAME}: camera['{k}'] requires grad, but the camera is not differentiable on this "
-                             "path (detach it)")
-
-    def host(v):
-        return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-
-    vp = host(camera["viewport"]).reshape(-1)
-    if vp.size != 4:
-        raise ValueError(f"{_NAME}: camera['viewport']: expected 4 values, got {vp.size}")
-    W, H = int(vp[2] - vp[0]), int(vp[3] - vp[1])
-    if W < 1 or H < 1:
-        raise ValueError(f"{_NAME}: camera['viewport']: empty {W} x {H} frame")
+    surfels, rgb = as_float_tensor("surfels", surfels), as_float_tensor("rgb", rgb)
+    W, H = camera_frame(_NAME, camera)
     if surfels.dim() != 3 or surfels.shape[-1] != 3:
         raise ValueError(f"{_NAME}: surfels is {list(surfels.shape)}, expected [B, N, 3]")
     B, N = surfels.shape[:2]
@@ -158,7 +192,7 @@ def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
     if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
         raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
     if rotated_image is not None:
-        rotated_image = _as_tensor("rotated_image", rotated_image)
+        rotated_image = as_float_tensor("rotated_image", rotated_image)
         if tuple(rotated_image.shape) != tuple(rgb.shape):
             raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
     blur_size = float(blur_size)
@@ -168,28 +202,8 @@ def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
         raise ValueError(f"{_NAME}: blur_size = {blur_size} at H = {H} gives a blur half-width of "
                          f"{math.floor(blur_size * H / 6 * 3)}, at most {_lib.PROJ_MAX_BLUR_HALF}")
     half, taps = blur_taps(blur_size, H)
-    fovy, focal = float(host(camera["fovy"]).reshape(-1)[0]), float(host(camera["focal_length"]).reshape(-1)[0])
-    if not 0 < fovy < math.pi:
-        raise ValueError(f"{_NAME}: camera['fovy'] = {fovy}, expected 0 < fovy < pi")
-    if not (math.isfinite(focal) and focal > 0):
-        raise ValueError(f"{_NAME}: camera['focal_length'] = {focal}, expected positive and finite")
-    cam = {}
-    for k in ("eye", "at", "up"):
-        v = np.asarray(host(camera[k]), dtype=np.float64)
-        if v.ndim != 2 or v.shape[0] != B or v.shape[1] not in (3, 4) or not np.all(np.isfinite(v)):
-            raise ValueError(f"{_NAME}: camera['{k}'] is {list(v.shape)}, expected finite [{B}, 3] or [{B}, 4]")
-        if v.shape[1] == 4:          # lookat_rot_inv's conventions; world_to_cam_batched then drops w
-            if k == "up" and np.any(v[:, 3] != 0):
-                raise ValueError(f"{_NAME}: camera['up'] is a direction: w must be 0")
-            if k != "up" and np.any(v[:, 3] == 0):
-                raise ValueError(f"{_NAME}: camera['{k}'] is a point: w must not be 0")
-        cam[k] = torch.from_numpy(np.ascontiguousarray(v[:, :3]))
-    if torch.any(torch.all(cam["eye"] == cam["at"], dim=-1)):
-        raise ValueError(f"{_NAME}: camera['eye'] == camera['at']")
-    if torch.any(torch.linalg.cross(cam["up"], cam["eye"] - cam["at"]).abs().amax(-1) == 0):
-        raise ValueError(f"{_NAME}: camera['up'] is zero or parallel to eye - at")
-    return surfels, rgb, rotated_image, (B, H, W, D), view_matrices(cam["eye"], cam["at"], cam["up"]), half, taps, \
-        fovy, focal
+    fovy, focal, view = camera_views(_NAME, camera, B)
+    return surfels, rgb, rotated_image, (B, H, W, D), view, half, taps, fovy, focal
 
 
 def projection_renderer_differentiable_fast(surfels, rgb, camera: Mapping, rotated_image=None, blur_size: float = 0.15,

@@ -1,0 +1,158 @@
+"""The reference's backward-warp ("pull") re-projection (diffrend/torch/projection_layer.py:281-333) under its own name,
+so the swap is one import:
+
+    # from diffrend.torch.projection_layer import projection_reverse_renderer
+    from surf_renderer_amd import projection_reverse_renderer
+    out, proj_out = projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image=None)
+
+The surfels of the target view (out_pos_wc) are projected into the source camera (camera1), and the source image rgb
+is sampled there bilinearly.  Pixels that leave the frame, or that a nearer surface of the source view (in_pos_wc, seen
+by camera2) hides, are masked out, and rotated_image fills the holes.  Forward and backward are HIP kernels
+(surf_renderer_amd/csrc/srh_reverse_projection.h): fp64 arithmetic, fp32 results, no float atomics, so values and
+gradients are identical from run to run.  Differentiable in rgb, rotated_image, out_pos_wc (through the sample
+coordinates) and in_pos_wc (through the values of the new depth); the mask and the cameras are not differentiable.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Mapping, Tuple
+
+import torch
+
+from . import _lib
+from .projection import as_float_tensor, camera_frame, camera_views
+
+_NAME = "projection_reverse_renderer"
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class _ReverseFunction(torch.autograd.Function):
+    """(rgb [B, N, D], in_pos, out_pos [B, N, 3], rotated [B, N, D] or None), fp32 contiguous -> out (None without a
+    rotated image: the result is image1), mask, image1, depth."""
+
+    @staticmethod
+    def forward(ctx, params, view1, view2, keep, want_depth, rgb, in_pos, out_pos, rotated):
+        lib = _lib.load()
+        B, N, D = rgb.shape
+        dev = rgb.device
+        ws = torch.empty((lib.srh_reverse_projection_workspace_bytes(C.byref(params), _lib.RPROJ_WS_FWD),),
+                         dtype=torch.uint8, device=dev)
+        image1 = torch.empty_like(rgb)
+        out = torch.empty_like(rgb) if rotated is not None else None
+        mask = torch.empty((B, N), dtype=torch.float32, device=dev)
+        depth = torch.empty_like(mask) if want_depth else None
+        _lib.check(lib.srh_reverse_projection_fwd(
+            C.byref(params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(), out_pos.data_ptr(),
+            _ptr(rotated), _ptr(keep), ws.data_ptr(), ws.numel(), _ptr(out), mask.data_ptr(), image1.data_ptr(),
+            _ptr(depth), torch.cuda.current_stream(dev).cuda_stream))
+        ctx.params = params
+        ctx.set_materialize_grads(False)
+        # the kernels keep nothing of their own: the backward reads the inputs and the mask
+        if any(ctx.needs_input_grad[5:]):
+            ctx.save_for_backward(view1, view2, rgb, in_pos, out_pos, mask)
+        return out, mask, image1, depth
+
+    @staticmethod
+    def backward(ctx, g_out, g_mask, g_image1, g_depth):
+        view1, view2, rgb, in_pos, out_pos, mask = ctx.saved_tensors
+        need = ctx.needs_input_grad[5:]
+        # an input that does not require grad gets no buffer, and the kernels skip the work only it would need
+        grads = [torch.empty_like(t) if need[k] else None for k, t in enumerate((rgb, in_pos, out_pos, rgb))]
+        ups = [None if g is None else g.to(torch.float32).contiguous() for g in (g_out, g_image1, g_depth)]
+        if any(g is not None for g in grads):
+            if all(u is None for u in ups):
+                for g in grads:
+                    if g is not None:
+                        g.zero_()
+            else:
+                lib = _lib.load()
+                stream = torch.cuda.current_stream(rgb.device).cuda_stream
+                keys = order = ws = None
+                if grads[0] is not None or grads[1] is not None:
+                    # grad rgb and grad in_pos gather over the pixels that sampled each texel: key, order, walk
+                    ws = torch.empty((lib.srh_reverse_projection_workspace_bytes(C.byref(ctx.params),
+                                                                                 _lib.RPROJ_WS_BWD),),
+                                     dtype=torch.uint8, device=rgb.device)
+                    keys = torch.empty(mask.shape, dtype=torch.int32, device=rgb.device)
+                    _lib.check(lib.srh_reverse_projection_keys(C.byref(ctx.params), view1.data_ptr(),
+                                                               out_pos.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                               keys.data_ptr(), stream))
+                    # the one step left to torch: a stable sort fixes the order inside every cell's list
+                    order = torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
+                _lib.check(lib.srh_reverse_projection_bwd(
+                    C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
+                    out_pos.data_ptr(), mask.data_ptr(), _ptr(keys), _ptr(order), _ptr(ws),
+                    0 if ws is None else ws.numel(), *[_ptr(u) for u in ups], *[_ptr(g) for g in grads], stream))
+        return (None, None, None, None, None, *grads)
+
+
+def _validate(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, rotated_image, depth_epsilon,
+              mask_dropout):
+    """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError)."""
+    rgb = as_float_tensor("rgb", rgb, _NAME)
+    pos = {k: as_float_tensor(k, v, _NAME) for k, v in (("in_pos_wc", in_pos_wc), ("out_pos_wc", out_pos_wc))}
+    if rgb.dim() != 4:
+        raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}, expected [B, H, W, D]")
+    B, H, W, D = rgb.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}: an empty batch or frame")
+    if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
+        raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
+    for k, t in pos.items():
+        if tuple(t.shape) != (B, H * W, 3):
+            raise ValueError(f"{_NAME}: {k} is {list(t.shape)}, expected [{B}, H W = {H * W}, 3]")
+    if rotated_image is not None:
+        rotated_image = as_float_tensor("rotated_image", rotated_image, _NAME)
+        if tuple(rotated_image.shape) != tuple(rgb.shape):
+            raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
+    cams = []
+    for label, camera in (("camera1", camera1), ("camera2", camera2)):
+        if camera_frame(_NAME, camera, label) != (W, H):
+            raise ValueError(f"{_NAME}: {label}['viewport'] is not the {W} x {H} (W x H) frame of rgb")
+        cams.append(camera_views(_NAME, camera, B, label))
+    depth_epsilon, mask_dropout = float(depth_epsilon), float(mask_dropout)
+    if not math.isfinite(depth_epsilon):
+        raise ValueError(f"{_NAME}: depth_epsilon = {depth_epsilon}, expected finite")
+    if not 0 <= mask_dropout < 1:
+        raise ValueError(f"{_NAME}: mask_dropout = {mask_dropout}, expected 0 <= mask_dropout < 1")
+    return rgb, pos["in_pos_wc"], pos["out_pos_wc"], rotated_image, cams, depth_epsilon, mask_dropout
+
+
+def projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, rotated_image=None,
+                                compute_new_depth: bool = False, depth_epsilon: float = 1e-1,
+                                mask_dropout: float = 0) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """The reference's call.  rgb [B, H, W, D], D in 1..4: the source view; in_pos_wc, out_pos_wc [B, H W, 3]: the world
+    positions of the source and of the target view's pixels; camera1 the source camera, camera2 the target camera (eye /
+    at / up [B, 3] or [B, 4], a viewport of W x H, fovy and focal_length each); rotated_image like rgb or None.  With
+    mask_dropout > 0 the mask is multiplied by F.dropout(ones, mask_dropout, training=True), drawn with torch on the
+    GPU, so it follows torch.manual_seed.  Returns (out, {'mask': [B, H, W, 1], 'image1': like rgb, and with
+    compute_new_depth 'depth': [B, H, W, 1]}), float32 on the GPU; without a rotated image out is image1."""
+    rgb, in_pos, out_pos, rotated_image, cams, depth_epsilon, mask_dropout = _validate(
+        rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image, depth_epsilon, mask_dropout)
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{_NAME}: the hip backend needs a GPU")
+    B, H, W, D = rgb.shape
+    leaves = [t for t in (rgb, in_pos, out_pos, rotated_image) if t is not None]
+    dev = next((t.device for t in leaves if t.device.type == "cuda"), torch.device("cuda"))
+    # autograd carries the gradient back through these conversions to the leaf's own dtype, layout and device
+    x = [None if t is None else t.to(device=dev, dtype=torch.float32).reshape(B, H * W, -1).contiguous()
+         for t in (rgb, in_pos, out_pos, rotated_image)]
+    (fovy1, focal1, view1), (fovy2, focal2, view2) = cams
+    params = _lib.SrhReverseProjectionParams(n_views=B, width=W, height=H, channels=D, fovy1=fovy1, focal_length1=focal1,
+                                             fovy2=fovy2, focal_length2=focal2, depth_epsilon=depth_epsilon)
+    keep = None
+    if mask_dropout > 0:
+        keep = torch.nn.functional.dropout(torch.ones((B, H * W), dtype=torch.float32, device=dev), mask_dropout,
+                                           training=True)
+    out, mask, image1, depth = _ReverseFunction.apply(
+        params, view1.reshape(B, 12).contiguous().to(dev), view2.reshape(B, 12).contiguous().to(dev), keep,
+        bool(compute_new_depth), *x)
+    image1 = image1.reshape(B, H, W, D)
+    proj_out = {"mask": mask.reshape(B, H, W, 1), "image1": image1}
+    if compute_new_depth:
+        proj_out["depth"] = depth.reshape(B, H, W, 1)
+    return (image1 if out is None else out.reshape(B, H, W, D)), proj_out

@@ -1,0 +1,131 @@
+"""srh_reverse_projection_workspace_bytes / _fwd / _keys / _bwd: exported, bound, and their argument checks -- which
+return before any HIP call, so they run without a GPU.  Host buffers stand in for device pointers: no call here reaches
+a launch."""
+import ctypes as C
+
+import pytest
+
+from surf_renderer_amd import _lib, build
+
+NULL, RANGE, TYPE, WORKSPACE, CAMERA = -1, -2, -3, -4, -5        # SRH_E_*
+BIG = 1 << 40
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build.build_lib()
+    return _lib.load()
+
+
+def _valid(**fields):
+    buf = (C.c_double * 64)()
+    p = _lib.SrhReverseProjectionParams(n_views=2, width=16, height=12, channels=3, fovy1=0.7, focal_length1=0.5,
+                                        fovy2=0.9, focal_length2=0.8, depth_epsilon=0.1)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p, C.addressof(buf), buf
+
+
+FWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "rotated", "keep", "workspace", "out", "mask", "image1", "depth")
+KEYS = ("view1", "out_pos", "workspace", "keys")
+BWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "mask", "keys", "order", "workspace", "g_out", "g_image1", "g_depth",
+       "grad_rgb", "grad_in_pos", "grad_out_pos", "grad_rotated")
+
+
+def _pick(names, a, null):
+    return {k: (None if k in null and null[k] is None else null.get(k, a)) for k in names}
+
+
+def _fwd(lib, p, a, ws_bytes=BIG, **null):
+    x = _pick(FWD, a, null)
+    return lib.srh_reverse_projection_fwd(C.byref(p), x["view1"], x["view2"], x["rgb"], x["in_pos"], x["out_pos"],
+                                          x["rotated"], x["keep"], x["workspace"], ws_bytes, x["out"], x["mask"],
+                                          x["image1"], x["depth"], None)
+
+
+def _keys(lib, p, a, ws_bytes=BIG, **null):
+    x = _pick(KEYS, a, null)
+    return lib.srh_reverse_projection_keys(C.byref(p), x["view1"], x["out_pos"], x["workspace"], ws_bytes, x["keys"], None)
+
+
+def _bwd(lib, p, a, ws_bytes=BIG, **null):
+    x = _pick(BWD, a, null)
+    return lib.srh_reverse_projection_bwd(C.byref(p), x["view1"], x["view2"], x["rgb"], x["in_pos"], x["out_pos"],
+                                          x["mask"], x["keys"], x["order"], x["workspace"], ws_bytes, x["g_out"],
+                                          x["g_image1"], x["g_depth"], x["grad_rgb"], x["grad_in_pos"],
+                                          x["grad_out_pos"], x["grad_rotated"], None)
+
+
+def test_entry_points_are_exported_and_bound(lib):
+    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    for name in ("srh_reverse_projection_workspace_bytes", "srh_reverse_projection_fwd", "srh_reverse_projection_keys",
+                 "srh_reverse_projection_bwd"):
+        assert name in _lib.EXPORTS and hasattr(lib, name)
+    assert len(lib.srh_reverse_projection_fwd.argtypes) == 15
+    assert len(lib.srh_reverse_projection_keys.argtypes) == 7
+    assert len(lib.srh_reverse_projection_bwd.argtypes) == 19
+    assert C.sizeof(_lib.SrhReverseProjectionParams) == 4 * 4 + 5 * 8
+    import surf_renderer_amd
+    assert "projection_reverse_renderer" in surf_renderer_amd.__all__
+    assert callable(surf_renderer_amd.projection_reverse_renderer)
+
+
+def test_workspace_sizes_follow_the_documented_layouts(lib):
+    p, _, _ = _valid()
+    px, D = 2 * 16 * 12, 3
+    size = lambda which: lib.srh_reverse_projection_workspace_bytes(C.byref(p), which)      # noqa: E731
+    assert size(_lib.RPROJ_WS_FWD) == px * 8
+    assert size(_lib.RPROJ_WS_BWD) == px * (4 + D + 1) * 8 + 2 * 17 * 13 * 2 * 4
+    assert size(2) == 0 and b"which" in lib.srh_last_error()
+    assert size(-1) == 0 and b"which" in lib.srh_last_error()
+    assert lib.srh_reverse_projection_workspace_bytes(None, 0) == 0 and b"params" in lib.srh_last_error()
+
+
+def test_null_arguments_are_refused_by_name(lib):
+    p, a, _ = _valid()
+    assert lib.srh_reverse_projection_keys(None, a, a, a, BIG, a, None) == NULL and b"params" in lib.srh_last_error()
+    optional = {"rotated", "keep", "depth"}
+    for k in FWD:
+        if k in optional:
+            continue
+        assert _fwd(lib, p, a, **{k: None}) == (WORKSPACE if k == "workspace" else NULL), k
+        assert k.encode() in lib.srh_last_error(), k
+    for k in KEYS:
+        assert _keys(lib, p, a, **{k: None}) == (WORKSPACE if k == "workspace" else NULL), k
+        assert k.encode() in lib.srh_last_error(), k
+    for k in ("view1", "view2", "rgb", "in_pos", "out_pos", "mask", "keys", "order"):
+        assert _bwd(lib, p, a, **{k: None}) == NULL and k.encode() in lib.srh_last_error(), k
+    assert _bwd(lib, p, a, workspace=None) == WORKSPACE and b"workspace" in lib.srh_last_error()
+
+
+def test_all_null_gradients_are_refused(lib):
+    p, a, _ = _valid()
+    assert _bwd(lib, p, a, g_out=None, g_image1=None, g_depth=None) == NULL
+    assert b"g_out" in lib.srh_last_error() and b"all NULL" in lib.srh_last_error()
+    assert _bwd(lib, p, a, grad_rgb=None, grad_in_pos=None, grad_out_pos=None, grad_rotated=None) == NULL
+    assert b"grad_rgb" in lib.srh_last_error() and b"all NULL" in lib.srh_last_error()
+
+
+@pytest.mark.parametrize("field,value,code", [
+    ("n_views", 0, RANGE), ("n_views", 65536, RANGE), ("width", 0, RANGE), ("height", 0, RANGE), ("width", 1 << 22, RANGE),
+    ("channels", 0, RANGE), ("channels", 5, RANGE), ("fovy1", 0.0, CAMERA), ("fovy2", 3.2, CAMERA),
+    ("fovy1", float("nan"), CAMERA), ("focal_length1", 0.0, CAMERA), ("focal_length2", float("inf"), CAMERA),
+    ("focal_length2", -1.0, CAMERA), ("depth_epsilon", float("nan"), RANGE), ("depth_epsilon", float("inf"), RANGE)])
+def test_out_of_range_parameters_are_refused_by_name(lib, field, value, code):
+    p, a, _ = _valid(**{field: value})
+    name = {"width": b"width x height", "height": b"width x height"}.get(field, field.encode())
+    for call in (_fwd, _keys, _bwd):
+        assert call(lib, p, a) == code, call.__name__
+        assert name in lib.srh_last_error(), (call.__name__, lib.srh_last_error())
+    assert lib.srh_reverse_projection_workspace_bytes(C.byref(p), 0) == 0
+
+
+def test_short_or_misaligned_buffers_are_refused(lib):
+    p, a, _ = _valid()
+    need = [lib.srh_reverse_projection_workspace_bytes(C.byref(p), w) for w in range(2)]
+    assert _fwd(lib, p, a, ws_bytes=need[0] - 1) == WORKSPACE and str(need[0]).encode() in lib.srh_last_error()
+    assert _keys(lib, p, a, ws_bytes=need[1] - 1) == WORKSPACE and str(need[1]).encode() in lib.srh_last_error()
+    assert _bwd(lib, p, a, ws_bytes=need[1] - 1) == WORKSPACE and str(need[1]).encode() in lib.srh_last_error()
+    assert _fwd(lib, p, a, workspace=a + 4) == WORKSPACE
+    assert _keys(lib, p, a, workspace=a + 4) == WORKSPACE
+    assert _bwd(lib, p, a, workspace=a + 4) == WORKSPACE
