@@ -1,0 +1,67 @@
+"""The host scaffold the fused layer modules share (splats, regularizers, projection, reverse_projection): device
+choice, scratch, the float32-contiguous conversion and the backward pattern.  The camera helpers of the two projection
+layers are in _camera.py.  A layer whose wording or steps differ keeps its own code."""
+from __future__ import annotations
+
+from typing import Any, Callable, Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+
+def ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def gpu_device(name: str, tensors: Iterable[Any]) -> torch.device:
+    """Where the layer `name` runs: the device of the first CUDA tensor among `tensors`, else the current GPU."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{name}: the hip backend needs a GPU")
+    return next((t.device for t in tensors if isinstance(t, torch.Tensor) and t.device.type == "cuda"),
+                torch.device("cuda"))
+
+
+def scratch(n_bytes: int, device) -> torch.Tensor:
+    return torch.empty((n_bytes,), dtype=torch.uint8, device=device)
+
+
+def stream(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def f32(t: torch.Tensor, device) -> torch.Tensor:
+    """float32, contiguous, on `device`; autograd carries the gradient back through these conversions to the leaf's own
+    dtype, layout and device"""
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def as_float_tensor(name: str, x: Any, caller: str) -> torch.Tensor:
+    if x is None:
+        raise ValueError(f"{caller}: {name} is missing")
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if not t.is_floating_point():
+        raise ValueError(f"{caller}: {name} has dtype {t.dtype}, expected a floating-point type")
+    return t
+
+
+def grad_buffers(inputs: Sequence[Optional[torch.Tensor]], needed: Sequence[bool]) -> List[Optional[torch.Tensor]]:
+    """An input that does not require grad gets no buffer, and the kernels skip the work only it would need."""
+    return [torch.empty_like(t) if t is not None and need else None for t, need in zip(inputs, needed)]
+
+
+def upstreams(grads: Iterable[Optional[torch.Tensor]]) -> List[Optional[torch.Tensor]]:
+    return [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+
+
+def fill_grads(grads: Iterable[Optional[torch.Tensor]], ups: Iterable[Optional[torch.Tensor]],
+               launch: Callable[[], None]) -> None:
+    """The backward of a layer whose kernels write every element of every buffer in `grads`: nothing without a buffer,
+    zeros without an upstream gradient, else `launch()`."""
+    grads = [g for g in grads if g is not None]
+    if not grads:
+        return
+    if all(u is None for u in ups):
+        for g in grads:
+            g.zero_()
+    else:
+        launch()

@@ -120,17 +120,54 @@ class SrhReverseProjectionParams(C.Structure):
                 ("focal_length2", C.c_double), ("depth_epsilon", C.c_double)]
 
 
-EXPORTS = ("srh_abi_version", "srh_last_error", "srh_workspace_bytes", "srh_generate_rays", "srh_render_fwd",
-           "srh_render_bwd", "srh_render_bwd_aux", "srh_render_bwd_camera", "srh_camera_grad_scratch_bytes",
-           "srh_workspace_bytes_views", "srh_render_views", "srh_render_views_bwd", "srh_render_views_aux",
-           "srh_camera_grad_scratch_bytes_views", "srh_render_views_bwd_camera", "srh_shadow_shade",
-           "srh_shadow_workspace_bytes", "srh_bin_counters",
-           "srh_event_create", "srh_event_destroy", "srh_event_elapsed_ms",
-           "srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd",
-           "srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd",
-           "srh_projection_workspace_bytes", "srh_projection_keys", "srh_projection_fwd", "srh_projection_bwd",
-           "srh_reverse_projection_workspace_bytes", "srh_reverse_projection_fwd", "srh_reverse_projection_keys",
-           "srh_reverse_projection_bwd")
+def _p(struct):
+    return C.POINTER(struct)
+
+
+_V, _I, _Z = C.c_void_p, C.c_int32, C.c_size_t
+# what the single-frame entry points start with, and the batched ones after their n_views
+_FRAME = [_p(SrhCamera), _p(SrhObjects), _p(SrhLights), _p(SrhMaterials), _p(SrhParams), _V, _Z]
+_SPLAT = [_p(SrhSplatParams), _p(SrhSplatInputs), _p(SrhLights), _p(SrhMaterials)]
+
+# name -> (restype, argtypes): every entry point of include/srh.h, in its order (tests/test_abi.py compares the two)
+SIGNATURES = {
+    "srh_abi_version": (C.c_int, []),
+    "srh_last_error": (C.c_char_p, []),
+    "srh_workspace_bytes": (_Z, [_p(SrhObjects), _I, _I]),
+    "srh_generate_rays": (C.c_int, [_p(SrhCamera), _I, _I, _V, _V]),
+    "srh_render_fwd": (C.c_int, _FRAME + [_V] * 4),
+    "srh_render_bwd": (C.c_int, _FRAME + [_V] * 4 + [_p(SrhGrads), _V]),
+    "srh_render_bwd_aux": (C.c_int, _FRAME + [_V] * 6 + [_p(SrhGrads), _V]),
+    "srh_camera_grad_scratch_bytes": (_Z, [_I, _I]),
+    "srh_render_bwd_camera": (C.c_int, _FRAME + [_V] * 6 + [_p(SrhGrads), _p(SrhCameraGrads), _V, _Z, _V]),
+    "srh_workspace_bytes_views": (_Z, [_p(SrhObjects), _I, _I, _I]),
+    "srh_render_views": (C.c_int, [_I] + _FRAME + [_V] * 4),
+    "srh_render_views_aux": (C.c_int, [_I] + _FRAME + [_V] * 6),
+    "srh_render_views_bwd": (C.c_int, [_I] + _FRAME + [_V] * 4 + [_p(SrhGrads), _V]),
+    "srh_camera_grad_scratch_bytes_views": (_Z, [_I, _I, _I]),
+    "srh_render_views_bwd_camera": (C.c_int, [_I] + _FRAME + [_V] * 6 + [_p(SrhGrads), _p(SrhCameraGrads), _V, _Z, _V]),
+    "srh_shadow_workspace_bytes": (_Z, [_p(SrhObjects), _I, _I, _I]),
+    "srh_shadow_shade": (C.c_int, _FRAME + [_V] * 5),
+    "srh_bin_counters": (C.c_int, [_p(SrhObjects), _I, _I, _I, _I, _p(_Z), _p(_I), _p(_I), _p(_I), _p(_I)]),
+    "srh_event_create": (C.c_int, [_p(_V)]),
+    "srh_event_destroy": (C.c_int, [_V]),
+    "srh_event_elapsed_ms": (C.c_int, [_V, _V, _p(C.c_float)]),
+    "srh_splat_workspace_bytes": (_Z, _SPLAT[:2]),
+    "srh_splat_fwd": (C.c_int, _SPLAT + [_V] * 5),
+    "srh_splat_bwd": (C.c_int, _SPLAT + [_V, _Z] + [_V] * 4 + [_p(SrhSplatGrads), _V]),
+    "srh_regularizers_workspace_bytes": (_Z, [_I, _I, _I]),
+    "srh_regularizers_fwd": (C.c_int, [_p(SrhRegularizerParams)] + [_V] * 5 + [_Z] + [_V] * 3),
+    "srh_regularizers_bwd": (C.c_int, [_p(SrhRegularizerParams)] + [_V] * 11),
+    "srh_projection_workspace_bytes": (_Z, [_p(SrhProjectionParams), _I]),
+    "srh_projection_keys": (C.c_int, [_p(SrhProjectionParams), _V, _V, _V, _Z, _V, _V]),
+    "srh_projection_fwd": (C.c_int, [_p(SrhProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 5),
+    "srh_projection_bwd": (C.c_int, [_p(SrhProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 8),
+    "srh_reverse_projection_workspace_bytes": (_Z, [_p(SrhReverseProjectionParams), _I]),
+    "srh_reverse_projection_fwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 8 + [_Z] + [_V] * 5),
+    "srh_reverse_projection_keys": (C.c_int, [_p(SrhReverseProjectionParams), _V, _V, _V, _Z, _V, _V]),
+    "srh_reverse_projection_bwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 9 + [_Z] + [_V] * 8),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib: Optional[C.CDLL] = None
 
@@ -163,114 +200,11 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     # every launch ends in "no ROCm-capable device is detected" (seen with build() followed by smoke() in one process)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in SIGNATURES.items():
         if not hasattr(lib, name):
             raise RuntimeError(f"{path} does not export {name}")
-    lib.srh_abi_version.restype = C.c_int
-    lib.srh_last_error.restype = C.c_char_p
-    lib.srh_workspace_bytes.restype = C.c_size_t
-    lib.srh_workspace_bytes.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32]
-    lib.srh_generate_rays.restype = C.c_int
-    lib.srh_generate_rays.argtypes = [C.POINTER(SrhCamera), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.srh_render_fwd.restype = C.c_int
-    lib.srh_render_fwd.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                   C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_render_bwd.restype = C.c_int
-    lib.srh_render_bwd.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                   C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrhGrads), C.c_void_p]
-    lib.srh_render_bwd_aux.restype = C.c_int
-    lib.srh_render_bwd_aux.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                       C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(SrhGrads), C.c_void_p]
-    lib.srh_camera_grad_scratch_bytes.restype = C.c_size_t
-    lib.srh_camera_grad_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.srh_render_bwd_camera.restype = C.c_int
-    lib.srh_render_bwd_camera.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                          C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(SrhGrads), C.POINTER(SrhCameraGrads), C.c_void_p, C.c_size_t,
-                                          C.c_void_p]
-    lib.srh_workspace_bytes_views.restype = C.c_size_t
-    lib.srh_workspace_bytes_views.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32, C.c_int32]
-    lib.srh_render_views.restype = C.c_int
-    lib.srh_render_views.argtypes = [C.c_int32, C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                     C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_render_views_bwd.restype = C.c_int
-    lib.srh_render_views_bwd.argtypes = [C.c_int32, C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                         C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrhGrads), C.c_void_p]
-    lib.srh_render_views_aux.restype = C.c_int
-    lib.srh_render_views_aux.argtypes = lib.srh_render_views.argtypes[:11] + [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_camera_grad_scratch_bytes_views.restype = C.c_size_t
-    lib.srh_camera_grad_scratch_bytes_views.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.srh_render_views_bwd_camera.restype = C.c_int
-    lib.srh_render_views_bwd_camera.argtypes = [C.c_int32, C.POINTER(SrhCamera), C.POINTER(SrhObjects),
-                                                C.POINTER(SrhLights), C.POINTER(SrhMaterials), C.POINTER(SrhParams),
-                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.POINTER(SrhGrads), C.POINTER(SrhCameraGrads),
-                                                C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.srh_shadow_workspace_bytes.restype = C.c_size_t
-    lib.srh_shadow_workspace_bytes.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32, C.c_int32]
-    lib.srh_shadow_shade.restype = C.c_int
-    lib.srh_shadow_shade.argtypes = [C.POINTER(SrhCamera), C.POINTER(SrhObjects), C.POINTER(SrhLights),
-                                     C.POINTER(SrhMaterials), C.POINTER(SrhParams), C.c_void_p, C.c_size_t,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_bin_counters.restype = C.c_int
-    lib.srh_bin_counters.argtypes = [C.POINTER(SrhObjects), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.srh_event_create.restype = C.c_int
-    lib.srh_event_create.argtypes = [C.POINTER(C.c_void_p)]
-    lib.srh_event_destroy.restype = C.c_int
-    lib.srh_event_destroy.argtypes = [C.c_void_p]
-    lib.srh_event_elapsed_ms.restype = C.c_int
-    lib.srh_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-    lib.srh_splat_workspace_bytes.restype = C.c_size_t
-    lib.srh_splat_workspace_bytes.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs)]
-    lib.srh_splat_fwd.restype = C.c_int
-    lib.srh_splat_fwd.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs), C.POINTER(SrhLights),
-                                  C.POINTER(SrhMaterials), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_splat_bwd.restype = C.c_int
-    lib.srh_splat_bwd.argtypes = [C.POINTER(SrhSplatParams), C.POINTER(SrhSplatInputs), C.POINTER(SrhLights),
-                                  C.POINTER(SrhMaterials), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.POINTER(SrhSplatGrads), C.c_void_p]
-    lib.srh_regularizers_workspace_bytes.restype = C.c_size_t
-    lib.srh_regularizers_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.srh_regularizers_fwd.restype = C.c_int
-    lib.srh_regularizers_fwd.argtypes = [C.POINTER(SrhRegularizerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_regularizers_bwd.restype = C.c_int
-    lib.srh_regularizers_bwd.argtypes = [C.POINTER(SrhRegularizerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p]
-    lib.srh_projection_workspace_bytes.restype = C.c_size_t
-    lib.srh_projection_workspace_bytes.argtypes = [C.POINTER(SrhProjectionParams), C.c_int32]
-    lib.srh_projection_keys.restype = C.c_int
-    lib.srh_projection_keys.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_void_p]
-    lib.srh_projection_fwd.restype = C.c_int
-    lib.srh_projection_fwd.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_projection_bwd.restype = C.c_int
-    lib.srh_projection_bwd.argtypes = [C.POINTER(SrhProjectionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.srh_reverse_projection_workspace_bytes.restype = C.c_size_t
-    lib.srh_reverse_projection_workspace_bytes.argtypes = [C.POINTER(SrhReverseProjectionParams), C.c_int32]
-    lib.srh_reverse_projection_fwd.restype = C.c_int
-    lib.srh_reverse_projection_fwd.argtypes = [C.POINTER(SrhReverseProjectionParams)] + [C.c_void_p] * 8 + [
-        C.c_size_t] + [C.c_void_p] * 5
-    lib.srh_reverse_projection_keys.restype = C.c_int
-    lib.srh_reverse_projection_keys.argtypes = [C.POINTER(SrhReverseProjectionParams), C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.srh_reverse_projection_bwd.restype = C.c_int
-    lib.srh_reverse_projection_bwd.argtypes = [C.POINTER(SrhReverseProjectionParams)] + [C.c_void_p] * 9 + [
-        C.c_size_t] + [C.c_void_p] * 8
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     got = lib.srh_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {got}, this package expects {ABI_VERSION}; rebuild it")

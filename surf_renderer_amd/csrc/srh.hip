@@ -13,6 +13,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 
@@ -56,6 +57,73 @@ int launch_status(const char* what) {
 
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
+
+// ------------------------------------------------------------------------------------------------
+// argument checks and camera arithmetic the entry points share (no HIP call)
+// ------------------------------------------------------------------------------------------------
+// the first NULL among a list of named pointers, in the order given
+struct NamedPtr {
+  const char* name;
+  const void* ptr;
+};
+int check_not_null(std::initializer_list<NamedPtr> ptrs) {
+  for (const NamedPtr& a : ptrs)
+    if (!a.ptr) return fail(SRH_E_NULL, "%s is NULL", a.name);
+  return SRH_OK;
+}
+
+// A fused layer's batch of frames: n_views in 1..65535 (grid dimension y), sides of at least 1, W H <= 1 << 24.  `what`
+// names the frame in the message.  In two halves, for a layer with a test of its own between them (reg_check_grid).
+int check_n_views(int32_t n_views) {
+  if (n_views < 1 || n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", n_views);
+  return SRH_OK;
+}
+int check_grid_size(int32_t width, int32_t height, const char* what) {
+  if (width < 1 || height < 1 || (int64_t)width * height > (1 << 24))
+    return fail(SRH_E_RANGE, "%s %d x %d out of range", what, width, height);
+  return SRH_OK;
+}
+int check_batch_grid(int32_t n_views, int32_t width, int32_t height, const char* what) {
+  if (int rc = check_n_views(n_views)) return rc;
+  return check_grid_size(width, height, what);
+}
+
+// a device scratch buffer of fp64 records: `name` for the message
+int check_scratch(const char* name, const void* ws, size_t bytes, size_t need) {
+  if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
+    return fail(SRH_E_WORKSPACE, "%s: need %zu bytes, 8-byte aligned (got %zu at %p)", name, need, bytes, ws);
+  return SRH_OK;
+}
+
+// The pinhole frame at the focal distance: h = 2 f tan(fovy / 2), w = h W / H, in the reference's order of operations
+// (numpy/renderer.py:145-163, torch/renderer.py, project_image_coordinates).  Every entry point that needs the frame
+// size takes it from here.
+struct FrameSize {
+  double w, h;
+};
+FrameSize frame_size(double fovy, double focal_length, int W, int H) {
+  const double h = tan(fovy / 2) * 2 * focal_length;
+  return {h * ((double)W / (double)H), h};
+}
+
+// project_image_coordinates: pixel = x (-(W - 1) / w) + W / 2 with x = f X / Z (y likewise, not mirrored), less the half
+// pixel: u = fsx X / Z + cx0, v = fsy Y / Z + cy0
+struct PixelScales {
+  double fsx, fsy, cx0, cy0;
+};
+PixelScales pixel_scales(double fovy, double focal_length, int W, int H) {
+  const FrameSize fs = frame_size(fovy, focal_length, W, H);
+  return {focal_length * (-(double)(W - 1) / fs.w), focal_length * ((double)(H - 1) / fs.h), W / 2.0 - 0.5, H / 2.0 - 0.5};
+}
+
+// the projection layers' camera: `suffix` completes the parameter names in the messages ("", "1", "2")
+int check_pinhole(const char* suffix, double fovy, double focal_length) {
+  if (!(fovy > 0.0 && fovy < 3.14159265358979323846))
+    return fail(SRH_E_CAMERA, "fovy%s = %g, expected 0 < fovy < pi", suffix, fovy);
+  if (!(focal_length > 0.0 && std::isfinite(focal_length)))
+    return fail(SRH_E_CAMERA, "focal_length%s = %g, expected positive and finite", suffix, focal_length);
+  return SRH_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // launch shapes and typed launches
@@ -249,11 +317,10 @@ int camera_to_frame(const SrhCamera* cam, FrameDev* F, bool orthonormal = false)
     y[1] = z[2] * x[0] - z[0] * x[2];
     y[2] = z[0] * x[1] - z[1] * x[0];
   }
-  const double h = tan(cam->fovy / 2) * 2 * cam->focal_length;
-  const double w = h * ((double)W / (double)H);
+  const FrameSize fs = frame_size(cam->fovy, cam->focal_length, W, H);
   for (int i = 0; i < 3; ++i) { F->o[i] = cam->eye[i]; F->bx[i] = x[i]; F->by[i] = y[i]; F->bz[i] = z[i]; }
-  F->half_w = w / 2;
-  F->half_h = h / 2;
+  F->half_w = fs.w / 2;
+  F->half_h = fs.h / 2;
   F->focal = cam->focal_length;
   F->step_x = W > 1 ? 2.0 / (W - 1) : 0.0;
   F->step_y = H > 1 ? -2.0 / (H - 1) : 0.0;
@@ -385,211 +452,6 @@ void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
       F.slab_cull = std::isfinite(F.slab_na) && std::isfinite(F.slab_ng) ? 1 : 0;
     }
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// the splat renderer (srh_splat.h)
-// ------------------------------------------------------------------------------------------------
-
-constexpr int kSplatMaxSamples = 8;
-// argument checks (no HIP call) and the device view of a splat launch
-int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLights* lights, const SrhMaterials* mats,
-                SplatDev* S) {
-  if (!p || !in) return fail(SRH_E_NULL, "params / inputs is NULL");
-  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
-  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
-    return fail(SRH_E_RANGE, "grid %d x %d out of range", p->width, p->height);
-  if (p->samples < 1 || p->samples > kSplatMaxSamples)
-    return fail(SRH_E_RANGE, "samples = %d, expected 1..%d", p->samples, kSplatMaxSamples);
-  if (p->pos_cols != 1 && p->pos_cols != 3) return fail(SRH_E_RANGE, "pos_cols = %d, expected 1 or 3", p->pos_cols);
-  if (!(p->focal_length > 0.0) || !(p->fovy > 0.0) || !(p->fovy < M_PI))
-    return fail(SRH_E_RANGE, "focal_length must be > 0 and fovy in (0, pi)");
-  if (!in->pos || !in->eye) return fail(SRH_E_NULL, "inputs.pos / inputs.eye is NULL");
-  if (!in->normal && (p->width < 2 || p->height < 2))
-    return fail(SRH_E_RANGE, "normal estimation needs a grid of at least 2 x 2 (got %d x %d)", p->width, p->height);
-  if (in->pos_view_stride < 0 || in->normal_view_stride < 0 || in->light_vis_view_stride < 0 ||
-      in->eye_view_stride < 0 || in->lights_pos_view_stride < 0)
-    return fail(SRH_E_RANGE, "negative view stride");
-  if (!lights || !mats) return fail(SRH_E_NULL, "lights / materials is NULL");
-  if (p->shade)
-    if (int rc = check_lights_materials(lights, mats)) return rc;
-  const double up2 = p->up[0] * p->up[0] + p->up[1] * p->up[1] + p->up[2] * p->up[2];
-  if (!(up2 > 0.0)) return fail(SRH_E_CAMERA, "camera.up is zero");
-  memset(S, 0, sizeof(*S));
-  S->B = p->n_views; S->W = p->width; S->H = p->height; S->K = p->samples; S->N = p->width * p->height;
-  S->pos_cols = p->pos_cols; S->use_quartic = p->use_quartic != 0; S->shade = p->shade != 0;
-  S->estimate = in->normal == nullptr;
-  S->nlights = p->shade ? lights->n_lights : 0;
-  S->ncolors = lights->n_colors; S->nmat = mats->n_materials;
-  // h = 2 f tan(fovy / 2), w = h W / H, in the reference's order of operations
-  const double h = tan(p->fovy / 2) * 2 * p->focal_length, w = h * ((double)p->width / (double)p->height);
-  S->f = p->focal_length; S->half_w = w / 2; S->half_h = h / 2;
-  S->step_x = p->width > 1 ? 2.0 / (p->width - 1) : 0.0;
-  S->step_y = p->height > 1 ? -2.0 / (p->height - 1) : 0.0;
-  S->sub_dx = p->samples > 1 ? w / (p->samples * p->width - 1) : 0.0;
-  S->sub_dy = p->samples > 1 ? h / (p->samples * p->height - 1) : 0.0;
-  S->sub_step = p->samples > 1 ? 2.0 / (p->samples - 1) : 0.0;
-  const double ui = 1.0 / eps_len(p->up);
-  for (int k = 0; k < 3; ++k) { S->at[k] = p->at[k]; S->up[k] = p->up[k] * ui; }
-  S->pos = in->pos; S->pos_vs = in->pos_view_stride;
-  S->normal = in->normal; S->nrm_vs = in->normal_view_stride;
-  S->vis = in->light_vis; S->vis_vs = in->light_vis_view_stride;
-  S->eye = in->eye; S->eye_vs = in->eye_view_stride;
-  S->lpos = lights->pos; S->lpos_vs = in->lights_pos_view_stride;
-  S->lcidx = lights->color_idx; S->colors = lights->colors; S->latt = lights->attenuation; S->amb = lights->ambient;
-  S->mat = in->material_idx; S->albedo = mats->albedo; S->coeffs = mats->coeffs;
-  return SRH_OK;
-}
-
-size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N * 9 * sizeof(double) : 0; }
-
-// ------------------------------------------------------------------------------------------------
-// the splat regularisers (srh_regularizers.h)
-// ------------------------------------------------------------------------------------------------
-int reg_check_grid(int32_t n_views, int32_t width, int32_t height) {
-  if (n_views < 1 || n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", n_views);
-  if (width < 2 || height < 2)
-    return fail(SRH_E_RANGE, "grid %d x %d: the reflected stencil needs at least 2 x 2", width, height);
-  if ((int64_t)width * height > (1 << 24)) return fail(SRH_E_RANGE, "grid %d x %d out of range", width, height);
-  return SRH_OK;
-}
-
-size_t reg_ws_bytes(int32_t n_views, int32_t width, int32_t height) {
-  const size_t nblk = ((size_t)width * height + kRegBlock - 1) / kRegBlock;
-  return (size_t)n_views * nblk * kRegSums * sizeof(double);
-}
-
-// argument checks (no HIP call) and the device view of a regulariser launch
-int reg_setup(const SrhRegularizerParams* p, const float* pos, const float* normal, const float* image,
-              const float* depth, RegDev* R) {
-  if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (int rc = reg_check_grid(p->n_views, p->width, p->height)) return rc;
-  if (!(p->z_min <= p->z_max)) return fail(SRH_E_RANGE, "z_min = %g > z_max = %g", p->z_min, p->z_max);
-  if (!pos || !normal || !image || !depth) return fail(SRH_E_NULL, "pos / normal / image / depth is NULL");
-  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height;
-  R->nblk = (R->N + kRegBlock - 1) / kRegBlock;
-  R->z_min = p->z_min; R->z_max = p->z_max; R->z_scale = p->z_scale; R->n_scale = p->unit_normal_scale;
-  R->pos = pos; R->normal = normal; R->image = image; R->depth = depth;
-  return SRH_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// the surfel re-projection layer (srh_projection.h)
-// ------------------------------------------------------------------------------------------------
-static_assert(kProjMaxD == SRH_PROJ_MAX_CHANNELS && kProjMaxHalf == SRH_PROJ_MAX_BLUR_HALF, "srh.h and srh_projection.h");
-static_assert(kProjUseDepth == SRH_PROJ_USE_DEPTH && kProjUseCenterDist == SRH_PROJ_USE_CENTER_DIST &&
-              kProjBlurRotated == SRH_PROJ_BLUR_ROTATED && kProjDetachMask == SRH_PROJ_DETACH_MASK &&
-              kProjDetachMask2 == SRH_PROJ_DETACH_MASK2 && kProjDetachDepthMerge == SRH_PROJ_DETACH_DEPTH_MERGE,
-              "srh.h and srh_projection.h");
-
-// argument checks (no HIP call) and the device view of a projection launch
-int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
-  if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
-  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
-    return fail(SRH_E_RANGE, "width x height = %d x %d out of range", p->width, p->height);
-  if (p->channels < 1 || p->channels > kProjMaxD)
-    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
-  if (p->flags & ~63) return fail(SRH_E_TYPE, "flags = %d has unknown bits", p->flags);
-  if (p->blur_half < 0 || p->blur_half > kProjMaxHalf)
-    return fail(SRH_E_RANGE, "blur_half = %d, expected 0..%d", p->blur_half, kProjMaxHalf);
-  if (!(p->fovy > 0.0 && p->fovy < 3.14159265358979323846))
-    return fail(SRH_E_CAMERA, "fovy = %g, expected 0 < fovy < pi", p->fovy);
-  if (!(p->focal_length > 0.0 && std::isfinite(p->focal_length)))
-    return fail(SRH_E_CAMERA, "focal_length = %g, expected positive and finite", p->focal_length);
-  for (int k = 0; k <= p->blur_half; ++k)
-    if (!std::isfinite(p->taps[k])) return fail(SRH_E_RANGE, "taps[%d] is not finite", k);
-  memset(P, 0, sizeof(*P));
-  P->B = p->n_views; P->W = p->width; P->H = p->height; P->N = p->width * p->height; P->D = p->channels;
-  P->P = 2 * P->D + 2; P->CS = P->D + 3; P->half = p->blur_half;
-  P->flags = p->flags | (has_rotated ? kProjHasRotated : 0);
-  P->ncell = (P->W + 1) * (P->H + 1);
-  P->nblk = (P->N + kProjBlock - 1) / kProjBlock;
-  // project_image_coordinates: h = 2 f tan(fovy / 2), w = h W / H, pixel = x (-(W - 1) / w) + W / 2 with x = f X / Z
-  const double h = tan(p->fovy / 2.0) * 2.0 * p->focal_length, w = h * ((double)P->W / (double)P->H);
-  P->fsx = p->focal_length * (-(double)(P->W - 1) / w);
-  P->fsy = p->focal_length * ((double)(P->H - 1) / h);
-  P->cx0 = P->W / 2.0 - 0.5;
-  P->cy0 = P->H / 2.0 - 0.5;
-  for (int k = 0; k <= P->half; ++k) P->taps[k] = p->taps[k];
-  return SRH_OK;
-}
-
-// SRH_PROJ_WS_FWD: rec (B, N, 4) | pre (B, P, N) | tmp (B, P, N) fp64 | range (B, ncell, 2) int32
-// SRH_PROJ_WS_SAVED: blr (B, P, N) | cor (B, 4, CS, N) fp64
-// SRH_PROJ_WS_BWD: gpl (B, P, N) | gtmp (B, P, N) | gcor (B, 4, CS, N) fp64
-size_t proj_ws_bytes(const ProjDev& P, int which) {
-  const size_t px = (size_t)P.B * P.N;
-  switch (which) {
-    case SRH_PROJ_WS_FWD: return px * (4 + 2 * P.P) * sizeof(double) + (size_t)P.B * P.ncell * 2 * sizeof(int32_t);
-    case SRH_PROJ_WS_SAVED: return px * (P.P + 4 * P.CS) * sizeof(double);
-    default: return px * (2 * P.P + 4 * P.CS) * sizeof(double);
-  }
-}
-
-int proj_check_ws(const ProjDev& P, int which, const char* name, const void* ws, size_t bytes) {
-  const size_t need = proj_ws_bytes(P, which);
-  if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
-    return fail(SRH_E_WORKSPACE, "%s: need %zu bytes, 8-byte aligned (got %zu at %p)", name, need, bytes, ws);
-  return SRH_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// the reverse re-projection layer (srh_reverse_projection.h)
-// ------------------------------------------------------------------------------------------------
-// argument checks (no HIP call) and the device view of a reverse projection launch
-int rproj_setup(const SrhReverseProjectionParams* p, RProjDev* R) {
-  if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (p->n_views < 1 || p->n_views > 65535) return fail(SRH_E_RANGE, "n_views = %d, expected 1..65535", p->n_views);
-  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1 << 24))
-    return fail(SRH_E_RANGE, "width x height = %d x %d out of range", p->width, p->height);
-  if (p->channels < 1 || p->channels > kProjMaxD)
-    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
-  const double fovy[2] = {p->fovy1, p->fovy2}, focal[2] = {p->focal_length1, p->focal_length2};
-  for (int c = 0; c < 2; ++c) {
-    if (!(fovy[c] > 0.0 && fovy[c] < 3.14159265358979323846))
-      return fail(SRH_E_CAMERA, "fovy%d = %g, expected 0 < fovy < pi", c + 1, fovy[c]);
-    if (!(focal[c] > 0.0 && std::isfinite(focal[c])))
-      return fail(SRH_E_CAMERA, "focal_length%d = %g, expected positive and finite", c + 1, focal[c]);
-  }
-  if (!std::isfinite(p->depth_epsilon)) return fail(SRH_E_RANGE, "depth_epsilon = %g, expected finite", p->depth_epsilon);
-  memset(R, 0, sizeof(*R));
-  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height; R->D = p->channels;
-  R->ncell = (R->W + 1) * (R->H + 1);
-  R->nblk = (R->N + kProjBlock - 1) / kProjBlock;
-  for (int c = 0; c < 2; ++c) {      // as proj_setup
-    const double h = tan(fovy[c] / 2.0) * 2.0 * focal[c], w = h * ((double)R->W / (double)R->H);
-    R->fsx[c] = focal[c] * (-(double)(R->W - 1) / w);
-    R->fsy[c] = focal[c] * ((double)(R->H - 1) / h);
-  }
-  R->cx0 = R->W / 2.0 - 0.5;
-  R->cy0 = R->H / 2.0 - 0.5;
-  R->eps = p->depth_epsilon;
-  return SRH_OK;
-}
-
-// what k_proj_keys and k_proj_mark read of a ProjDev, for camera 1: no weights, so the record is (fx, fy, z, 1)
-ProjDev rproj_as_proj(const RProjDev& R) {
-  ProjDev P;
-  memset(&P, 0, sizeof(P));
-  P.B = R.B; P.W = R.W; P.H = R.H; P.N = R.N; P.D = R.D; P.ncell = R.ncell; P.nblk = R.nblk;
-  P.fsx = R.fsx[0]; P.fsy = R.fsy[0]; P.cx0 = R.cx0; P.cy0 = R.cy0;
-  return P;
-}
-
-// SRH_RPROJ_WS_FWD: d_in (B, N) fp64
-// SRH_RPROJ_WS_BWD: rec (B, N, 4) | gpl (B, D + 1, N) fp64 | range (B, ncell, 2) int32
-size_t rproj_ws_bytes(const RProjDev& R, int which) {
-  const size_t px = (size_t)R.B * R.N;
-  if (which == SRH_RPROJ_WS_FWD) return px * sizeof(double);
-  return px * (4 + R.D + 1) * sizeof(double) + (size_t)R.B * R.ncell * 2 * sizeof(int32_t);
-}
-
-int rproj_check_ws(const RProjDev& R, int which, const void* ws, size_t bytes) {
-  const size_t need = rproj_ws_bytes(R, which);
-  if (!ws || bytes < need || ((uintptr_t)ws % sizeof(double)))
-    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, bytes, ws);
-  return SRH_OK;
 }
 
 }  // namespace
@@ -1329,8 +1191,70 @@ int srh_event_elapsed_ms(void* start, void* stop, float* ms) {
   return e == hipSuccess ? SRH_OK : hip_fail(e, "hipEventElapsedTime");
 }
 
+}  // extern "C"
 
-// ---- the splat renderer ----------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------------
+// The fused layers.  One section per layer: its argument checks and workspace sizes (no HIP call), then its entry
+// points.  What the checks share (check_not_null, check_batch_grid, check_scratch, frame_size, pixel_scales,
+// check_pinhole) is at the head of this file.
+// ------------------------------------------------------------------------------------------------
+
+// ---- the splat renderer (srh_splat.h) ----------------------------------------------------------------------------
+namespace {
+
+constexpr int kSplatMaxSamples = 8;
+// argument checks (no HIP call) and the device view of a splat launch
+int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLights* lights, const SrhMaterials* mats,
+                SplatDev* S) {
+  if (!p || !in) return fail(SRH_E_NULL, "params / inputs is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "grid")) return rc;
+  if (p->samples < 1 || p->samples > kSplatMaxSamples)
+    return fail(SRH_E_RANGE, "samples = %d, expected 1..%d", p->samples, kSplatMaxSamples);
+  if (p->pos_cols != 1 && p->pos_cols != 3) return fail(SRH_E_RANGE, "pos_cols = %d, expected 1 or 3", p->pos_cols);
+  if (!(p->focal_length > 0.0) || !(p->fovy > 0.0) || !(p->fovy < M_PI))
+    return fail(SRH_E_RANGE, "focal_length must be > 0 and fovy in (0, pi)");
+  if (!in->pos || !in->eye) return fail(SRH_E_NULL, "inputs.pos / inputs.eye is NULL");
+  if (!in->normal && (p->width < 2 || p->height < 2))
+    return fail(SRH_E_RANGE, "normal estimation needs a grid of at least 2 x 2 (got %d x %d)", p->width, p->height);
+  if (in->pos_view_stride < 0 || in->normal_view_stride < 0 || in->light_vis_view_stride < 0 ||
+      in->eye_view_stride < 0 || in->lights_pos_view_stride < 0)
+    return fail(SRH_E_RANGE, "negative view stride");
+  if (!lights || !mats) return fail(SRH_E_NULL, "lights / materials is NULL");
+  if (p->shade)
+    if (int rc = check_lights_materials(lights, mats)) return rc;
+  const double up2 = p->up[0] * p->up[0] + p->up[1] * p->up[1] + p->up[2] * p->up[2];
+  if (!(up2 > 0.0)) return fail(SRH_E_CAMERA, "camera.up is zero");
+  memset(S, 0, sizeof(*S));
+  S->B = p->n_views; S->W = p->width; S->H = p->height; S->K = p->samples; S->N = p->width * p->height;
+  S->pos_cols = p->pos_cols; S->use_quartic = p->use_quartic != 0; S->shade = p->shade != 0;
+  S->estimate = in->normal == nullptr;
+  S->nlights = p->shade ? lights->n_lights : 0;
+  S->ncolors = lights->n_colors; S->nmat = mats->n_materials;
+  const FrameSize fs = frame_size(p->fovy, p->focal_length, p->width, p->height);
+  S->f = p->focal_length; S->half_w = fs.w / 2; S->half_h = fs.h / 2;
+  S->step_x = p->width > 1 ? 2.0 / (p->width - 1) : 0.0;
+  S->step_y = p->height > 1 ? -2.0 / (p->height - 1) : 0.0;
+  S->sub_dx = p->samples > 1 ? fs.w / (p->samples * p->width - 1) : 0.0;
+  S->sub_dy = p->samples > 1 ? fs.h / (p->samples * p->height - 1) : 0.0;
+  S->sub_step = p->samples > 1 ? 2.0 / (p->samples - 1) : 0.0;
+  const double ui = 1.0 / eps_len(p->up);
+  for (int k = 0; k < 3; ++k) { S->at[k] = p->at[k]; S->up[k] = p->up[k] * ui; }
+  S->pos = in->pos; S->pos_vs = in->pos_view_stride;
+  S->normal = in->normal; S->nrm_vs = in->normal_view_stride;
+  S->vis = in->light_vis; S->vis_vs = in->light_vis_view_stride;
+  S->eye = in->eye; S->eye_vs = in->eye_view_stride;
+  S->lpos = lights->pos; S->lpos_vs = in->lights_pos_view_stride;
+  S->lcidx = lights->color_idx; S->colors = lights->colors; S->latt = lights->attenuation; S->amb = lights->ambient;
+  S->mat = in->material_idx; S->albedo = mats->albedo; S->coeffs = mats->coeffs;
+  return SRH_OK;
+}
+
+size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N * 9 * sizeof(double) : 0; }
+
+}  // namespace
+
+extern "C" {
+
 size_t srh_splat_workspace_bytes(const SrhSplatParams* params, const SrhSplatInputs* inputs) {
   SrhLights L;
   SrhMaterials M;
@@ -1371,11 +1295,8 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
     return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
   if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
   if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
-  const size_t need = splat_ws_bytes(S);
   const bool gather = S.estimate && grads->pos;
-  if (gather && (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double))))
-    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
-                workspace);
+  if (gather && (rc = check_scratch("workspace", workspace, workspace_bytes, splat_ws_bytes(S)))) return rc;
   SplatGradsDev G;
   G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
   G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
@@ -1393,8 +1314,42 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
   return launch_status("splat backward launch");
 }
 
+}  // extern "C"
 
-// ---- the splat regularisers ------------------------------------------------------------------------------------
+// ---- the splat regularisers (srh_regularizers.h) -----------------------------------------------------------------
+namespace {
+
+// the stencil's own refusal sits before the size test: a grid that fails both is refused with it
+int reg_check_grid(int32_t n_views, int32_t width, int32_t height) {
+  if (int rc = check_n_views(n_views)) return rc;
+  if (width < 2 || height < 2)
+    return fail(SRH_E_RANGE, "grid %d x %d: the reflected stencil needs at least 2 x 2", width, height);
+  return check_grid_size(width, height, "grid");
+}
+
+size_t reg_ws_bytes(int32_t n_views, int32_t width, int32_t height) {
+  const size_t nblk = ((size_t)width * height + kRegBlock - 1) / kRegBlock;
+  return (size_t)n_views * nblk * kRegSums * sizeof(double);
+}
+
+// argument checks (no HIP call) and the device view of a regulariser launch
+int reg_setup(const SrhRegularizerParams* p, const float* pos, const float* normal, const float* image,
+              const float* depth, RegDev* R) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = reg_check_grid(p->n_views, p->width, p->height)) return rc;
+  if (!(p->z_min <= p->z_max)) return fail(SRH_E_RANGE, "z_min = %g > z_max = %g", p->z_min, p->z_max);
+  if (!pos || !normal || !image || !depth) return fail(SRH_E_NULL, "pos / normal / image / depth is NULL");
+  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height;
+  R->nblk = (R->N + kRegBlock - 1) / kRegBlock;
+  R->z_min = p->z_min; R->z_max = p->z_max; R->z_scale = p->z_scale; R->n_scale = p->unit_normal_scale;
+  R->pos = pos; R->normal = normal; R->image = image; R->depth = depth;
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 size_t srh_regularizers_workspace_bytes(int32_t n_views, int32_t width, int32_t height) {
   if (reg_check_grid(n_views, width, height)) return 0;
   return reg_ws_bytes(n_views, width, height);
@@ -1407,10 +1362,7 @@ int srh_regularizers_fwd(const SrhRegularizerParams* params, const float* pos, c
   int rc = reg_setup(params, pos, normal, image, depth, &R);
   if (rc) return rc;
   if (!terms || !stats) return fail(SRH_E_NULL, "terms / stats is NULL");
-  const size_t need = reg_ws_bytes(R.B, R.W, R.H);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % sizeof(double)))
-    return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes, 8-byte aligned (got %zu at %p)", need, workspace_bytes,
-                workspace);
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, reg_ws_bytes(R.B, R.W, R.H)))) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_reg_fwd, dim3(R.nblk, R.B), dim3(kRegBlock), 0, st, R, (double*)workspace);
   hipLaunchKernelGGL(k_reg_finish, dim3(R.B), dim3(64), 0, st, R, (const double*)workspace, terms, stats);
@@ -1432,7 +1384,57 @@ int srh_regularizers_bwd(const SrhRegularizerParams* params, const float* pos, c
   return launch_status("k_reg_bwd launch");
 }
 
-// ---- the surfel re-projection layer ------------------------------------------------------------------------------
+}  // extern "C"
+
+// ---- the surfel re-projection layer (srh_projection.h) -----------------------------------------------------------
+namespace {
+
+static_assert(kProjMaxD == SRH_PROJ_MAX_CHANNELS && kProjMaxHalf == SRH_PROJ_MAX_BLUR_HALF, "srh.h and srh_projection.h");
+static_assert(kProjUseDepth == SRH_PROJ_USE_DEPTH && kProjUseCenterDist == SRH_PROJ_USE_CENTER_DIST &&
+              kProjBlurRotated == SRH_PROJ_BLUR_ROTATED && kProjDetachMask == SRH_PROJ_DETACH_MASK &&
+              kProjDetachMask2 == SRH_PROJ_DETACH_MASK2 && kProjDetachDepthMerge == SRH_PROJ_DETACH_DEPTH_MERGE,
+              "srh.h and srh_projection.h");
+
+// argument checks (no HIP call) and the device view of a projection launch
+int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
+  if (p->channels < 1 || p->channels > kProjMaxD)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (p->flags & ~63) return fail(SRH_E_TYPE, "flags = %d has unknown bits", p->flags);
+  if (p->blur_half < 0 || p->blur_half > kProjMaxHalf)
+    return fail(SRH_E_RANGE, "blur_half = %d, expected 0..%d", p->blur_half, kProjMaxHalf);
+  if (int rc = check_pinhole("", p->fovy, p->focal_length)) return rc;
+  for (int k = 0; k <= p->blur_half; ++k)
+    if (!std::isfinite(p->taps[k])) return fail(SRH_E_RANGE, "taps[%d] is not finite", k);
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->W = p->width; P->H = p->height; P->N = p->width * p->height; P->D = p->channels;
+  P->P = 2 * P->D + 2; P->CS = P->D + 3; P->half = p->blur_half;
+  P->flags = p->flags | (has_rotated ? kProjHasRotated : 0);
+  P->ncell = (P->W + 1) * (P->H + 1);
+  P->nblk = (P->N + kProjBlock - 1) / kProjBlock;
+  const PixelScales s = pixel_scales(p->fovy, p->focal_length, P->W, P->H);
+  P->fsx = s.fsx; P->fsy = s.fsy; P->cx0 = s.cx0; P->cy0 = s.cy0;
+  for (int k = 0; k <= P->half; ++k) P->taps[k] = p->taps[k];
+  return SRH_OK;
+}
+
+// SRH_PROJ_WS_FWD: rec (B, N, 4) | pre (B, P, N) | tmp (B, P, N) fp64 | range (B, ncell, 2) int32
+// SRH_PROJ_WS_SAVED: blr (B, P, N) | cor (B, 4, CS, N) fp64
+// SRH_PROJ_WS_BWD: gpl (B, P, N) | gtmp (B, P, N) | gcor (B, 4, CS, N) fp64
+size_t proj_ws_bytes(const ProjDev& P, int which) {
+  const size_t px = (size_t)P.B * P.N;
+  switch (which) {
+    case SRH_PROJ_WS_FWD: return px * (4 + 2 * P.P) * sizeof(double) + (size_t)P.B * P.ncell * 2 * sizeof(int32_t);
+    case SRH_PROJ_WS_SAVED: return px * (P.P + 4 * P.CS) * sizeof(double);
+    default: return px * (2 * P.P + 4 * P.CS) * sizeof(double);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
 size_t srh_projection_workspace_bytes(const SrhProjectionParams* params, int32_t which) {
   ProjDev P;
   if (proj_setup(params, false, &P)) return 0;
@@ -1448,10 +1450,8 @@ int srh_projection_keys(const SrhProjectionParams* params, const double* view, c
   ProjDev P;
   int rc = proj_setup(params, false, &P);
   if (rc) return rc;
-  if (!view) return fail(SRH_E_NULL, "view is NULL");
-  if (!surfels) return fail(SRH_E_NULL, "surfels is NULL");
-  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
-  if ((rc = proj_check_ws(P, SRH_PROJ_WS_FWD, "workspace", workspace, workspace_bytes))) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"keys", keys}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_FWD)))) return rc;
   hipLaunchKernelGGL(k_proj_keys, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, view, surfels,
                      (double*)workspace, keys);
   return launch_status("k_proj_keys launch");
@@ -1463,12 +1463,10 @@ int srh_projection_fwd(const SrhProjectionParams* params, const float* rgb, cons
   ProjDev P;
   int rc = proj_setup(params, rotated != nullptr, &P);
   if (rc) return rc;
-  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
-  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
-  if (!order) return fail(SRH_E_NULL, "order is NULL");
+  if ((rc = check_not_null({{"rgb", rgb}, {"keys", keys}, {"order", order}}))) return rc;
   if (!out || !mask || !image1) return fail(SRH_E_NULL, "out / mask / image1 is NULL");
-  if ((rc = proj_check_ws(P, SRH_PROJ_WS_FWD, "workspace", workspace, workspace_bytes))) return rc;
-  if (saved && (rc = proj_check_ws(P, SRH_PROJ_WS_SAVED, "saved", saved, saved_bytes))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_FWD)))) return rc;
+  if (saved && (rc = check_scratch("saved", saved, saved_bytes, proj_ws_bytes(P, SRH_PROJ_WS_SAVED)))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t px = (size_t)P.B * P.N;
   double* rec = (double*)workspace;
@@ -1498,16 +1496,14 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
   ProjDev P;
   int rc = proj_setup(params, rotated != nullptr, &P);
   if (rc) return rc;
-  if (!view) return fail(SRH_E_NULL, "view is NULL");
-  if (!surfels) return fail(SRH_E_NULL, "surfels is NULL");
-  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"rgb", rgb}}))) return rc;
   if (!g_out && !g_mask && !g_image1 && !g_depth)
     return fail(SRH_E_NULL, "g_out, g_mask, g_image1 and g_depth are all NULL");
   if (!grad_surfels && !grad_rgb && !grad_rotated)
     return fail(SRH_E_NULL, "grad_surfels, grad_rgb and grad_rotated are all NULL");
   if (grad_rotated && !rotated) return fail(SRH_E_NULL, "grad_rotated without rotated");
-  if ((rc = proj_check_ws(P, SRH_PROJ_WS_SAVED, "saved", saved, saved_bytes))) return rc;
-  if ((rc = proj_check_ws(P, SRH_PROJ_WS_BWD, "workspace", workspace, workspace_bytes))) return rc;
+  if ((rc = check_scratch("saved", saved, saved_bytes, proj_ws_bytes(P, SRH_PROJ_WS_SAVED)))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_BWD)))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t px = (size_t)P.B * P.N;
   const double* blr = (const double*)saved;
@@ -1528,7 +1524,54 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
   return launch_status("projection backward launch");
 }
 
-// ---- the reverse re-projection layer -----------------------------------------------------------------------------
+}  // extern "C"
+
+// ---- the reverse re-projection layer (srh_reverse_projection.h) --------------------------------------------------
+namespace {
+
+// argument checks (no HIP call) and the device view of a reverse projection launch
+int rproj_setup(const SrhReverseProjectionParams* p, RProjDev* R) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
+  if (p->channels < 1 || p->channels > kProjMaxD)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (int rc = check_pinhole("1", p->fovy1, p->focal_length1)) return rc;
+  if (int rc = check_pinhole("2", p->fovy2, p->focal_length2)) return rc;
+  if (!std::isfinite(p->depth_epsilon)) return fail(SRH_E_RANGE, "depth_epsilon = %g, expected finite", p->depth_epsilon);
+  memset(R, 0, sizeof(*R));
+  R->B = p->n_views; R->W = p->width; R->H = p->height; R->N = p->width * p->height; R->D = p->channels;
+  R->ncell = (R->W + 1) * (R->H + 1);
+  R->nblk = (R->N + kProjBlock - 1) / kProjBlock;
+  const PixelScales s[2] = {pixel_scales(p->fovy1, p->focal_length1, R->W, R->H),
+                            pixel_scales(p->fovy2, p->focal_length2, R->W, R->H)};
+  for (int c = 0; c < 2; ++c) { R->fsx[c] = s[c].fsx; R->fsy[c] = s[c].fsy; }
+  R->cx0 = s[0].cx0;
+  R->cy0 = s[0].cy0;
+  R->eps = p->depth_epsilon;
+  return SRH_OK;
+}
+
+// what k_proj_keys and k_proj_mark read of a ProjDev, for camera 1: no weights, so the record is (fx, fy, z, 1)
+ProjDev rproj_as_proj(const RProjDev& R) {
+  ProjDev P;
+  memset(&P, 0, sizeof(P));
+  P.B = R.B; P.W = R.W; P.H = R.H; P.N = R.N; P.D = R.D; P.ncell = R.ncell; P.nblk = R.nblk;
+  P.fsx = R.fsx[0]; P.fsy = R.fsy[0]; P.cx0 = R.cx0; P.cy0 = R.cy0;
+  return P;
+}
+
+// SRH_RPROJ_WS_FWD: d_in (B, N) fp64
+// SRH_RPROJ_WS_BWD: rec (B, N, 4) | gpl (B, D + 1, N) fp64 | range (B, ncell, 2) int32
+size_t rproj_ws_bytes(const RProjDev& R, int which) {
+  const size_t px = (size_t)R.B * R.N;
+  if (which == SRH_RPROJ_WS_FWD) return px * sizeof(double);
+  return px * (4 + R.D + 1) * sizeof(double) + (size_t)R.B * R.ncell * 2 * sizeof(int32_t);
+}
+
+}  // namespace
+
+extern "C" {
+
 size_t srh_reverse_projection_workspace_bytes(const SrhReverseProjectionParams* params, int32_t which) {
   RProjDev R;
   if (rproj_setup(params, &R)) return 0;
@@ -1546,15 +1589,11 @@ int srh_reverse_projection_fwd(const SrhReverseProjectionParams* params, const d
   RProjDev R;
   int rc = rproj_setup(params, &R);
   if (rc) return rc;
-  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
-  if (!view2) return fail(SRH_E_NULL, "view2 is NULL");
-  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
-  if (!in_pos) return fail(SRH_E_NULL, "in_pos is NULL");
-  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
+  if ((rc = check_not_null({{"view1", view1}, {"view2", view2}, {"rgb", rgb}, {"in_pos", in_pos}, {"out_pos", out_pos}})))
+    return rc;
   if (rotated && !out) return fail(SRH_E_NULL, "out is NULL with a rotated image");
-  if (!mask) return fail(SRH_E_NULL, "mask is NULL");
-  if (!image1) return fail(SRH_E_NULL, "image1 is NULL");
-  if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_FWD, workspace, workspace_bytes))) return rc;
+  if ((rc = check_not_null({{"mask", mask}, {"image1", image1}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_FWD)))) return rc;
   const dim3 grid(R.nblk, R.B), block(kProjBlock);
   hipStream_t st = (hipStream_t)stream;
   double* d_in = (double*)workspace;
@@ -1569,10 +1608,8 @@ int srh_reverse_projection_keys(const SrhReverseProjectionParams* params, const 
   RProjDev R;
   int rc = rproj_setup(params, &R);
   if (rc) return rc;
-  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
-  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
-  if (!keys) return fail(SRH_E_NULL, "keys is NULL");
-  if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_BWD, workspace, workspace_bytes))) return rc;
+  if ((rc = check_not_null({{"view1", view1}, {"out_pos", out_pos}, {"keys", keys}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_BWD)))) return rc;
   hipLaunchKernelGGL(k_proj_keys, dim3(R.nblk, R.B), dim3(kProjBlock), 0, (hipStream_t)stream, rproj_as_proj(R), view1,
                      out_pos, (double*)workspace, keys);
   return launch_status("reverse projection k_proj_keys launch");
@@ -1586,20 +1623,16 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
   RProjDev R;
   int rc = rproj_setup(params, &R);
   if (rc) return rc;
-  if (!view1) return fail(SRH_E_NULL, "view1 is NULL");
-  if (!view2) return fail(SRH_E_NULL, "view2 is NULL");
-  if (!rgb) return fail(SRH_E_NULL, "rgb is NULL");
-  if (!in_pos) return fail(SRH_E_NULL, "in_pos is NULL");
-  if (!out_pos) return fail(SRH_E_NULL, "out_pos is NULL");
-  if (!mask) return fail(SRH_E_NULL, "mask is NULL");
+  if ((rc = check_not_null({{"view1", view1}, {"view2", view2}, {"rgb", rgb}, {"in_pos", in_pos}, {"out_pos", out_pos},
+                            {"mask", mask}})))
+    return rc;
   if (!g_out && !g_image1 && !g_depth) return fail(SRH_E_NULL, "g_out, g_image1 and g_depth are all NULL");
   if (!grad_rgb && !grad_in_pos && !grad_out_pos && !grad_rotated)
     return fail(SRH_E_NULL, "grad_rgb, grad_in_pos, grad_out_pos and grad_rotated are all NULL");
   const bool walk = grad_rgb || grad_in_pos;
   if (walk) {
-    if (!keys) return fail(SRH_E_NULL, "keys is NULL");
-    if (!order) return fail(SRH_E_NULL, "order is NULL");
-    if ((rc = rproj_check_ws(R, SRH_RPROJ_WS_BWD, workspace, workspace_bytes))) return rc;
+    if ((rc = check_not_null({{"keys", keys}, {"order", order}}))) return rc;
+    if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_BWD)))) return rc;
   }
   hipStream_t st = (hipStream_t)stream;
   const size_t px = (size_t)R.B * R.N;

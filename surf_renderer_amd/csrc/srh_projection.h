@@ -24,7 +24,7 @@
 // Cells are indexed on the (W + 1) x (H + 1) grid of cell + (1, 1): a cell in column -1 or row -1 still reaches the
 // frame through its +1 corners.  A surfel none of whose corners is in the frame gets the key (W + 1)(H + 1).
 //
-// The per-element arithmetic (proj_surfel, proj_merge_fwd, proj_merge_bwd) is host-callable.
+// The per-element arithmetic (proj_point, proj_surfel, proj_merge_fwd, proj_merge_bwd) is host-callable.
 #pragma once
 #include "srh_device.h"   // as_constant
 
@@ -57,27 +57,47 @@ __host__ __device__ __forceinline__ size_t proj_corner(const ProjDev& P, int b, 
   return (((size_t)b * 4 + k) * P.CS + slot) * P.N + q;
 }
 
-struct ProjSurfel {
-  double X, Y, Z, Zd, fx, fy, z, alpha, w;
+// A world point seen by a camera with the pixel scales (fsx, fsy, cx0, cy0) in a W x H frame: camera coordinates,
+// (u, v), the cell floor(u, v) and the fractions.  The one copy of this arithmetic: the reverse layer walks the records
+// k_proj_keys writes with it, so both layers must get the same cell and fractions bit for bit.
+struct ProjPoint {
+  double X, Y, Z, Zd, u, v, fx, fy;
   int ix, iy;      // the cell
   bool live;       // at least one corner can be in the frame
 };
 
-__host__ __device__ inline ProjSurfel proj_surfel(const ProjDev& P, const double* M, const float* p) {
-  ProjSurfel S;
+__host__ __device__ __forceinline__ ProjPoint proj_point(double fsx, double fsy, double cx0, double cy0, int W, int H,
+                                                         const double* M, const float* p) {
+  ProjPoint S;
   const double x = p[0], y = p[1], z = p[2];
   S.X = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
   S.Y = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
   S.Z = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
   S.Zd = S.Z != 0.0 ? S.Z : 1.0;                       // nonzero_divide
-  const double u = P.fsx * (S.X / S.Zd) + P.cx0, v = P.fsy * (S.Y / S.Zd) + P.cy0;
-  const double cu = floor(u), cv = floor(v);
+  S.u = fsx * (S.X / S.Zd) + cx0;
+  S.v = fsy * (S.Y / S.Zd) + cy0;
+  const double cu = floor(S.u), cv = floor(S.v);
   // NaN and anything an int cannot hold fail these comparisons
-  S.live = cu >= -1.0 && cu <= (double)(P.W - 1) && cv >= -1.0 && cv <= (double)(P.H - 1);
+  S.live = cu >= -1.0 && cu <= (double)(W - 1) && cv >= -1.0 && cv <= (double)(H - 1);
   S.ix = S.live ? (int)cu : 0;
   S.iy = S.live ? (int)cv : 0;
-  S.fx = u - cu;
-  S.fy = v - cv;
+  S.fx = S.u - cu;
+  S.fy = S.v - cv;
+  return S;
+}
+
+// the projected point (without u, v: the cell and the fractions are all the kernels read) plus the surfel's depth and
+// its two weights
+struct ProjSurfel {
+  double X, Y, Z, Zd, fx, fy, z, alpha, w;
+  int ix, iy;
+  bool live;
+};
+
+__host__ __device__ inline ProjSurfel proj_surfel(const ProjDev& P, const double* M, const float* p) {
+  const ProjPoint Q = proj_point(P.fsx, P.fsy, P.cx0, P.cy0, P.W, P.H, M, p);
+  ProjSurfel S;
+  S.X = Q.X; S.Y = Q.Y; S.Z = Q.Z; S.Zd = Q.Zd; S.fx = Q.fx; S.fy = Q.fy; S.ix = Q.ix; S.iy = Q.iy; S.live = Q.live;
   S.z = -S.Z;
   S.alpha = (P.flags & kProjUseCenterDist) ? exp(-2.0 * (S.fx * S.fx + S.fy * S.fy)) * 0.63661977236758134308 : 1.0;
   S.w = (P.flags & kProjUseDepth) ? exp(-2.0 * S.z) : 1.0;

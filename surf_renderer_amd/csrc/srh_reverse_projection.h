@@ -40,34 +40,16 @@ __host__ __device__ __forceinline__ size_t rproj_plane(const RProjDev& R, int b,
   return ((size_t)b * (R.D + 1) + ch) * R.N + q;
 }
 
-struct RProjPoint {
-  double X, Y, Z, Zd, u, v;
-  double fx, fy;
-  int ix, iy;      // the sample cell: texels (ix, iy) .. (ix + 1, iy + 1)
-  bool live;       // at least one of them can be in the frame
-};
+// the sample cell is texels (ix, iy) .. (ix + 1, iy + 1); live = at least one of them can be in the frame
+using RProjPoint = ProjPoint;
 
 __host__ __device__ __forceinline__ double rproj_row(const double* M, int r, const float* p) {
   return ((M[4 * r] * (double)p[0] + M[4 * r + 1] * (double)p[1]) + M[4 * r + 2] * (double)p[2]) + M[4 * r + 3];
 }
 
-// proj_surfel's arithmetic for camera `cam`
+// proj_surfel's point for camera `cam`
 __host__ __device__ __forceinline__ RProjPoint rproj_point(const RProjDev& R, int cam, const double* M, const float* p) {
-  RProjPoint S;
-  S.X = rproj_row(M, 0, p);
-  S.Y = rproj_row(M, 1, p);
-  S.Z = rproj_row(M, 2, p);
-  S.Zd = S.Z != 0.0 ? S.Z : 1.0;                       // nonzero_divide
-  S.u = R.fsx[cam] * (S.X / S.Zd) + R.cx0;
-  S.v = R.fsy[cam] * (S.Y / S.Zd) + R.cy0;
-  const double cu = floor(S.u), cv = floor(S.v);
-  // NaN and anything an int cannot hold fail these comparisons
-  S.live = cu >= -1.0 && cu <= (double)(R.W - 1) && cv >= -1.0 && cv <= (double)(R.H - 1);
-  S.ix = S.live ? (int)cu : 0;
-  S.iy = S.live ? (int)cv : 0;
-  S.fx = S.u - cu;
-  S.fy = S.v - cv;
-  return S;
+  return proj_point(R.fsx[cam], R.fsy[cam], R.cx0, R.cy0, R.W, R.H, M, p);
 }
 
 // texel k = 2 dx + dy of the cell of S: its index in the frame, or -1

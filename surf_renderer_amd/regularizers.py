@@ -16,10 +16,10 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, Mapping
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._layer import as_float_tensor, fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
 
 REGULARIZER_TERMS = ("z", "unit_normal", "normal_consistency", "spatial", "spatial_var", "image_depth_consistency",
                      "away_from_camera")
@@ -33,14 +33,12 @@ class _RegFunction(torch.autograd.Function):
     def forward(ctx, params, pos, normal, image, depth):
         lib = _lib.load()
         B, dev = params.n_views, pos.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = torch.empty((lib.srh_regularizers_workspace_bytes(B, params.width, params.height),), dtype=torch.uint8,
-                         device=dev)
+        ws = scratch(lib.srh_regularizers_workspace_bytes(B, params.width, params.height), dev)
         terms = torch.empty((B, _lib.REG_TERMS), dtype=torch.float32, device=dev)
         stats = torch.empty((B, _lib.REG_STATS), dtype=torch.float64, device=dev)
         _lib.check(lib.srh_regularizers_fwd(C.byref(params), pos.data_ptr(), normal.data_ptr(), image.data_ptr(),
                                             depth.data_ptr(), ws.data_ptr(), ws.numel(), terms.data_ptr(),
-                                            stats.data_ptr(), stream))
+                                            stats.data_ptr(), stream(dev)))
         ctx.params = params
         ctx.save_for_backward(pos, normal, image, depth, stats)
         return terms
@@ -48,29 +46,22 @@ class _RegFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_terms):
         pos, normal, image, depth, stats = ctx.saved_tensors
-        # an input that does not require grad gets no buffer, and the kernel skips the work only it would need
-        grads = [torch.empty_like(t) if ctx.needs_input_grad[1 + k] else None
-                 for k, t in enumerate((pos, normal, image, depth))]
-        if any(g is not None for g in grads):
-            g_terms = g_terms.to(torch.float32).contiguous()
-            stream = torch.cuda.current_stream(pos.device).cuda_stream
+        grads = grad_buffers((pos, normal, image, depth), ctx.needs_input_grad[1:])
+        ups = upstreams((g_terms,))
+
+        def launch():
             _lib.check(_lib.load().srh_regularizers_bwd(
                 C.byref(ctx.params), pos.data_ptr(), normal.data_ptr(), image.data_ptr(), depth.data_ptr(),
-                stats.data_ptr(), g_terms.data_ptr(), *[g.data_ptr() if g is not None else None for g in grads], stream))
+                stats.data_ptr(), ups[0].data_ptr(), *[ptr(g) for g in grads], stream(pos.device)))
+
+        fill_grads(grads, ups, launch)
         return (None, *grads)
 
 
 def _validate(res: Mapping, z_min: float, z_max: float):
     """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError); returns
     the four inputs as tensors and whether they carry the view axis."""
-    t = {}
-    for k in _INPUTS:
-        if k not in res or res[k] is None:
-            raise ValueError(f"splat_regularizers: res['{k}'] is missing")
-        x = res[k] if isinstance(res[k], torch.Tensor) else torch.as_tensor(np.asarray(res[k]))
-        if not x.is_floating_point():
-            raise ValueError(f"splat_regularizers: res['{k}'] has dtype {x.dtype}, expected a floating-point type")
-        t[k] = x
+    t = {k: as_float_tensor(f"res['{k}']", res[k] if k in res else None, "splat_regularizers") for k in _INPUTS}
     shape = tuple(t["image"].shape)
     if len(shape) not in (3, 4) or shape[-1] != 3:
         raise ValueError(f"splat_regularizers: res['image'] is {list(shape)}, expected [B, H, W, 3] or [H, W, 3]")
@@ -98,14 +89,10 @@ def splat_regularizers(res: Mapping, z_min: float, z_max: float, z_scale: float 
     1 / (variance + 1e-4), the others means.  z_scale is the trainers' 2 (test_optimization.py: 10),
     unit_normal_scale their 10."""
     t, batched = _validate(res, z_min, z_max)
-    if not torch.cuda.is_available():
-        raise RuntimeError("splat_regularizers: the hip backend needs a GPU")
-    dev = next((x.device for x in t.values() if x.device.type == "cuda"), torch.device("cuda"))
-    # autograd carries the gradient back through these conversions to the leaf's own dtype, layout and device
-    x = [t[k].to(device=dev, dtype=torch.float32) for k in _INPUTS]
+    dev = gpu_device("splat_regularizers", t.values())
+    x = [f32(t[k], dev) for k in _INPUTS]
     if not batched:
         x = [v.unsqueeze(0) for v in x]
-    x = [v.contiguous() for v in x]
     B, H, W = x[3].shape
     params = _lib.SrhRegularizerParams(n_views=B, width=W, height=H, z_min=float(z_min), z_max=float(z_max),
                                        z_scale=float(z_scale), unit_normal_scale=float(unit_normal_scale))

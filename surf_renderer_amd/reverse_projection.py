@@ -21,13 +21,10 @@ from typing import Dict, Mapping, Tuple
 import torch
 
 from . import _lib
-from .projection import as_float_tensor, camera_frame, camera_views
+from ._camera import camera_frame, camera_views
+from ._layer import as_float_tensor, fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
 
 _NAME = "projection_reverse_renderer"
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class _ReverseFunction(torch.autograd.Function):
@@ -39,16 +36,15 @@ class _ReverseFunction(torch.autograd.Function):
         lib = _lib.load()
         B, N, D = rgb.shape
         dev = rgb.device
-        ws = torch.empty((lib.srh_reverse_projection_workspace_bytes(C.byref(params), _lib.RPROJ_WS_FWD),),
-                         dtype=torch.uint8, device=dev)
+        ws = scratch(lib.srh_reverse_projection_workspace_bytes(C.byref(params), _lib.RPROJ_WS_FWD), dev)
         image1 = torch.empty_like(rgb)
         out = torch.empty_like(rgb) if rotated is not None else None
         mask = torch.empty((B, N), dtype=torch.float32, device=dev)
         depth = torch.empty_like(mask) if want_depth else None
         _lib.check(lib.srh_reverse_projection_fwd(
             C.byref(params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(), out_pos.data_ptr(),
-            _ptr(rotated), _ptr(keep), ws.data_ptr(), ws.numel(), _ptr(out), mask.data_ptr(), image1.data_ptr(),
-            _ptr(depth), torch.cuda.current_stream(dev).cuda_stream))
+            ptr(rotated), ptr(keep), ws.data_ptr(), ws.numel(), ptr(out), mask.data_ptr(), image1.data_ptr(),
+            ptr(depth), stream(dev)))
         ctx.params = params
         ctx.set_materialize_grads(False)
         # the kernels keep nothing of their own: the backward reads the inputs and the mask
@@ -59,34 +55,28 @@ class _ReverseFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out, g_mask, g_image1, g_depth):
         view1, view2, rgb, in_pos, out_pos, mask = ctx.saved_tensors
-        need = ctx.needs_input_grad[5:]
-        # an input that does not require grad gets no buffer, and the kernels skip the work only it would need
-        grads = [torch.empty_like(t) if need[k] else None for k, t in enumerate((rgb, in_pos, out_pos, rgb))]
-        ups = [None if g is None else g.to(torch.float32).contiguous() for g in (g_out, g_image1, g_depth)]
-        if any(g is not None for g in grads):
-            if all(u is None for u in ups):
-                for g in grads:
-                    if g is not None:
-                        g.zero_()
-            else:
-                lib = _lib.load()
-                stream = torch.cuda.current_stream(rgb.device).cuda_stream
-                keys = order = ws = None
-                if grads[0] is not None or grads[1] is not None:
-                    # grad rgb and grad in_pos gather over the pixels that sampled each texel: key, order, walk
-                    ws = torch.empty((lib.srh_reverse_projection_workspace_bytes(C.byref(ctx.params),
-                                                                                 _lib.RPROJ_WS_BWD),),
-                                     dtype=torch.uint8, device=rgb.device)
-                    keys = torch.empty(mask.shape, dtype=torch.int32, device=rgb.device)
-                    _lib.check(lib.srh_reverse_projection_keys(C.byref(ctx.params), view1.data_ptr(),
-                                                               out_pos.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                               keys.data_ptr(), stream))
-                    # the one step left to torch: a stable sort fixes the order inside every cell's list
-                    order = torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
-                _lib.check(lib.srh_reverse_projection_bwd(
-                    C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
-                    out_pos.data_ptr(), mask.data_ptr(), _ptr(keys), _ptr(order), _ptr(ws),
-                    0 if ws is None else ws.numel(), *[_ptr(u) for u in ups], *[_ptr(g) for g in grads], stream))
+        grads = grad_buffers((rgb, in_pos, out_pos, rgb), ctx.needs_input_grad[5:])
+        ups = upstreams((g_out, g_image1, g_depth))
+
+        def launch():
+            lib = _lib.load()
+            st = stream(rgb.device)
+            keys = order = ws = None
+            if grads[0] is not None or grads[1] is not None:
+                # grad rgb and grad in_pos gather over the pixels that sampled each texel: key, order, walk
+                ws = scratch(lib.srh_reverse_projection_workspace_bytes(C.byref(ctx.params), _lib.RPROJ_WS_BWD),
+                             rgb.device)
+                keys = torch.empty(mask.shape, dtype=torch.int32, device=rgb.device)
+                _lib.check(lib.srh_reverse_projection_keys(C.byref(ctx.params), view1.data_ptr(), out_pos.data_ptr(),
+                                                           ws.data_ptr(), ws.numel(), keys.data_ptr(), st))
+                # the one step left to torch: a stable sort fixes the order inside every cell's list
+                order = torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
+            _lib.check(lib.srh_reverse_projection_bwd(
+                C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
+                out_pos.data_ptr(), mask.data_ptr(), ptr(keys), ptr(order), ptr(ws), 0 if ws is None else ws.numel(),
+                *[ptr(u) for u in ups], *[ptr(g) for g in grads], st))
+
+        fill_grads(grads, ups, launch)
         return (None, None, None, None, None, *grads)
 
 
@@ -133,14 +123,9 @@ def projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, ca
     compute_new_depth 'depth': [B, H, W, 1]}), float32 on the GPU; without a rotated image out is image1."""
     rgb, in_pos, out_pos, rotated_image, cams, depth_epsilon, mask_dropout = _validate(
         rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image, depth_epsilon, mask_dropout)
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{_NAME}: the hip backend needs a GPU")
+    dev = gpu_device(_NAME, (rgb, in_pos, out_pos, rotated_image))
     B, H, W, D = rgb.shape
-    leaves = [t for t in (rgb, in_pos, out_pos, rotated_image) if t is not None]
-    dev = next((t.device for t in leaves if t.device.type == "cuda"), torch.device("cuda"))
-    # autograd carries the gradient back through these conversions to the leaf's own dtype, layout and device
-    x = [None if t is None else t.to(device=dev, dtype=torch.float32).reshape(B, H * W, -1).contiguous()
-         for t in (rgb, in_pos, out_pos, rotated_image)]
+    x = [None if t is None else f32(t, dev).reshape(B, H * W, -1) for t in (rgb, in_pos, out_pos, rotated_image)]
     (fovy1, focal1, view1), (fovy2, focal2, view2) = cams
     params = _lib.SrhReverseProjectionParams(n_views=B, width=W, height=H, channels=D, fovy1=fovy1, focal_length1=focal1,
                                              fovy2=fovy2, focal_length2=focal2, depth_epsilon=depth_epsilon)

@@ -14,12 +14,13 @@ The camera is not differentiable; a camera tensor that requires grad is refused.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._layer import f32, fill_grads, gpu_device, ptr, scratch, stream
 
 _DIFF = ("pos", "normal", "light_vis", "lights_pos", "colors", "attenuation", "ambient", "albedo", "coeffs")
 
@@ -32,16 +33,12 @@ def _f32(x, device, name) -> torch.Tensor:
     if x is None:
         raise ValueError(f"render_splats_along_ray: scene value {name} is missing")
     t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float32))
-    return t.to(device=device, dtype=torch.float32).contiguous()
+    return f32(t, device)
 
 
 def _i32(x, device) -> torch.Tensor:
     t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
     return t.to(device=device, dtype=torch.int32).contiguous()
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 class _Splat:
@@ -57,18 +54,18 @@ class _Splat:
         N = p.width * p.height
         inp = _lib.SrhSplatInputs(
             pos=pos.data_ptr(), pos_view_stride=N * p.pos_cols,
-            normal=_ptr(normal), normal_view_stride=(N * 3 if self.batched["normal"] else 0),
-            light_vis=_ptr(light_vis), light_vis_view_stride=(self.n_lights * N if self.batched["light_vis"] else 0),
+            normal=ptr(normal), normal_view_stride=(N * 3 if self.batched["normal"] else 0),
+            light_vis=ptr(light_vis), light_vis_view_stride=(self.n_lights * N if self.batched["light_vis"] else 0),
             eye=self.eye.data_ptr(), eye_view_stride=(3 if self.batched["eye"] else 0),
             lights_pos_view_stride=(self.n_lights * 4 if self.batched["lights_pos"] else 0),
-            material_idx=_ptr(self.material_idx))
-        ls = _lib.SrhLights(n_lights=self.n_lights, n_colors=self.n_colors, pos=_ptr(lpos),
-                            color_idx=_ptr(self.color_idx), colors=_ptr(colors), attenuation=_ptr(att), ambient=_ptr(amb))
-        ms = _lib.SrhMaterials(n_materials=self.n_mat, albedo=_ptr(albedo), coeffs=_ptr(coeffs))
+            material_idx=ptr(self.material_idx))
+        ls = _lib.SrhLights(n_lights=self.n_lights, n_colors=self.n_colors, pos=ptr(lpos),
+                            color_idx=ptr(self.color_idx), colors=ptr(colors), attenuation=ptr(att), ambient=ptr(amb))
+        ms = _lib.SrhMaterials(n_materials=self.n_mat, albedo=ptr(albedo), coeffs=ptr(coeffs))
         return inp, ls, ms
 
     def stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return stream(self.device)
 
 
 class _SplatFunction(torch.autograd.Function):
@@ -86,7 +83,7 @@ class _SplatFunction(torch.autograd.Function):
         pos = torch.empty((B, KH, KW, 3), dtype=torch.float32, device=dev)
         normal = torch.empty((B, KH, KW, 3), dtype=torch.float32, device=dev)
         inp, ls, ms = cfg.structs(*inputs)
-        _lib.check(_lib.load().srh_splat_fwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), _ptr(image),
+        _lib.check(_lib.load().srh_splat_fwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ptr(image),
                                              depth.data_ptr(), pos.data_ptr(), normal.data_ptr(), cfg.stream()))
         ctx.cfg = cfg
         ctx.present = [t is not None for t in inputs]
@@ -123,16 +120,15 @@ class _SplatFunction(torch.autograd.Function):
         ups = [g.contiguous() if g is not None else None for g in (g_image, g_depth, g_pos, g_normal)]
         if not p.shade:
             ups[0] = None
-        if grads and any(u is not None for u in ups):
+
+        def launch():
             inp, ls, ms = cfg.structs(*inputs)
-            ws_bytes = _lib.load().srh_splat_workspace_bytes(C.byref(p), C.byref(inp))
-            ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)
+            ws = scratch(max(_lib.load().srh_splat_workspace_bytes(C.byref(p), C.byref(inp)), 8), dev)
             sg = _lib.SrhSplatGrads(**{k: v.data_ptr() for k, v in grads.items()})
             _lib.check(_lib.load().srh_splat_bwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ws.data_ptr(),
-                                                 ws.numel(), *[_ptr(u) for u in ups], C.byref(sg), cfg.stream()))
-        else:
-            for g in grads.values():
-                g.zero_()
+                                                 ws.numel(), *[ptr(u) for u in ups], C.byref(sg), cfg.stream()))
+
+        fill_grads(grads.values(), ups, launch)
         out = []
         for k, t in zip(_DIFF, inputs):
             g = grads.get(k)
@@ -153,8 +149,9 @@ def _shape(x):
     return None if x is None else (tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x))
 
 
-def _validate(scene: Dict[str, Any], batched: bool) -> None:
-    """Every shape the kernels index by, checked on the host before anything reaches the GPU (ValueError)."""
+def _validate(scene: Dict[str, Any], batched: bool) -> Tuple[int, int]:
+    """Every shape the kernels index by, checked on the host before anything reaches the GPU (ValueError).  Returns the
+    viewport's grid (W, H)."""
     cam, disk, lights = scene["camera"], scene["objects"]["disk"], scene["lights"]
     vp = np.asarray(_value(cam["viewport"])).reshape(-1)
     if vp.size != 4:
@@ -211,6 +208,7 @@ def _validate(scene: Dict[str, Any], batched: bool) -> None:
     for k in ("at", "up"):
         if np.asarray(_value(cam.get(k))).size not in (3, 4):
             raise ValueError(f"camera.{k}: expected 3 or 4 values")
+    return W, H
 
 
 def _render(scene: Dict[str, Any], batched: bool, samples: int = 1, normal_estimation_method: str = "plane",
@@ -221,16 +219,10 @@ def _render(scene: Dict[str, Any], batched: bool, samples: int = 1, normal_estim
                          "supported (only 'plane')")
     cam = scene["camera"]
     _refuse_camera_grads(cam)
-    _validate(scene, batched)
+    W, H = _validate(scene, batched)
     disk = scene["objects"]["disk"]
     pos_in = disk["pos"]
-    device = pos_in.device if isinstance(pos_in, torch.Tensor) else torch.device("cuda")
-    if device.type != "cuda":
-        device = torch.device("cuda")
-    if not torch.cuda.is_available():
-        raise RuntimeError("render_splats_along_ray: the hip backend needs a GPU")
-    vp = [int(v) for v in np.asarray(_value(cam["viewport"])).reshape(-1)]
-    W, H = vp[2] - vp[0], vp[3] - vp[1]
+    device = gpu_device("render_splats_along_ray", (pos_in,))
     N = W * H
     pos = _f32(pos_in, device, "objects.disk.pos")
     if not batched:

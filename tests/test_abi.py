@@ -36,6 +36,39 @@ def test_library_exports_every_declared_symbol(lib):
     assert set(_lib.EXPORTS) <= set(declared_symbols())
 
 
+def declared_prototypes():
+    """{name: (return type, [parameter declarations])} of every function include/srh.h declares"""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^(int|size_t|const char\s*\*)\s*(srh_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, re.M):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        protos[name] = (ret.replace(" ", ""), [] if params == ["void"] else params)
+    return protos
+
+
+def test_signature_table_matches_the_header():
+    """_lib.SIGNATURES is what ctypes converts every argument by: a wrong entry corrupts a call silently.  Count, kind
+    (pointer, int32_t, size_t) and return type of every prototype against the table."""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()                      # the expression missed no declaration
+    assert set(protos) == set(_lib.SIGNATURES) == set(_lib.EXPORTS)
+    returns = {"int": C.c_int, "size_t": C.c_size_t, "constchar*": C.c_char_p}
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is returns[ret], name
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters, {len(argtypes)} argtypes"
+        for k, (decl, ctype) in enumerate(zip(params, argtypes)):
+            where = f"{name}, parameter {k} ({decl})"
+            if "*" in decl:
+                assert ctype is C.c_void_p or issubclass(ctype, C._Pointer), where
+            elif decl.startswith("int32_t "):
+                assert ctype is C.c_int32, where
+            elif decl.startswith("size_t "):
+                assert ctype is C.c_size_t, where
+            else:
+                raise AssertionError(f"{where}: a kind of parameter this test does not know")
+
+
 def test_abi_version_matches_header(lib):
     text = open(HEADER).read()
     want = int(re.search(r"#define\s+SRH_ABI_VERSION\s+(\d+)", text).group(1))
