@@ -641,6 +641,53 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
                                const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
                                float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's dense Gaussian re-projection, projection_renderer_differentiable (diffrend/torch/projection_layer.py:
+ * 108-152), for B views per call: every one of the N = W H surfels of a view (world position and a D-channel value)
+ * contributes to every one of its W H pixels (i, j) with the weight exp(-((u - i)^2 + (v - j)^2) / (2 sigma^2)), (u, v)
+ * the surfel's pixel coordinate less 1/2 -- surfels outside the frame and behind the camera included.  mask = the sum
+ * of the weights (not normalised), S = the weighted sum of the values;
+ *   out = S / (mask + 1e-10)        without a rotated image
+ *   out = S + rotated (1 - mask)    with one.
+ * No buffer grows with W H x N: the weight is separable and is formed tile by tile.  fp64 arithmetic, fp32 results, no
+ * atomic in either direction, every sum in a fixed order: values and gradients are identical from run to run and a
+ * batch equals its views.  The camera is not differentiable.  Added without an ABI version change.  Conventions as
+ * above: caller-owned device buffers, enqueue only, no synchronisation or allocation, argument checks before any HIP
+ * call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_DPROJ_WS_FWD 0              /* scratch of srh_dense_projection_fwd */
+#define SRH_DPROJ_WS_SAVED 1            /* written by srh_dense_projection_fwd, read by srh_dense_projection_bwd */
+#define SRH_DPROJ_WS_BWD 2              /* scratch of srh_dense_projection_bwd */
+
+typedef struct SrhDenseProjectionParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24; N = W H surfels per view */
+  int32_t channels;             /* D in 1..SRH_PROJ_MAX_CHANNELS */
+  int32_t has_rotated;          /* 0: out = S / (mask + 1e-10); 1: out = S + rotated (1 - mask) */
+  int32_t reserved;             /* 0 */
+  double sigma;                 /* of the Gaussian, in pixels: positive and finite */
+  double fovy, focal_length;    /* shared by the views: 0 < fovy < pi, focal_length > 0 */
+} SrhDenseProjectionParams;
+
+/* bytes of the buffer `which` (SRH_DPROJ_WS_*; 8-byte aligned), each linear in B W H; 0 and srh_last_error on bad
+ * input */
+size_t srh_dense_projection_workspace_bytes(const SrhDenseProjectionParams* params, int32_t which);
+
+/* view (B, 12) fp64: each view's world-to-camera matrix, 3 rows of 4; surfels (B, N, 3), rgb (B, N, D) fp32; rotated
+ * (B, N, D) fp32 with has_rotated, NULL without.  saved (SRH_DPROJ_WS_SAVED) may be NULL when no backward will follow.
+ * out (B, N, D) and mask (B, N) fp32 are written, every element once. */
+int srh_dense_projection_fwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                             const float* rgb, const float* rotated, void* workspace, size_t workspace_bytes,
+                             void* saved, size_t saved_bytes, float* out, float* mask, void* stream);
+
+/* Vector-Jacobian product.  Inputs as in the forward call that wrote `saved`.  Upstream gradients g_out (B, N, D) and
+ * g_mask (B, N) fp32: NULL = none, not both.  grad_surfels (B, N, 3), grad_rgb, grad_rotated (B, N, D) are WRITTEN,
+ * every element once; any may be NULL = not wanted, not all; grad_rotated needs has_rotated. */
+int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                             const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                             void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                             float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

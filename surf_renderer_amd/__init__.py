@@ -16,8 +16,9 @@ _SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
 _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 _PROJECTION = ("projection_renderer_differentiable_fast",)
 _REVERSE_PROJECTION = ("projection_reverse_renderer",)
+_DENSE_PROJECTION = ("projection_renderer_differentiable",)
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION]
 
 
 def __getattr__(name):
@@ -33,6 +34,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".projection", __name__), name)
     if name in _REVERSE_PROJECTION:
         return getattr(importlib.import_module(".reverse_projection", __name__), name)
+    if name in _DENSE_PROJECTION:
+        return getattr(importlib.import_module(".dense_projection", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -120,6 +120,15 @@ class SrhReverseProjectionParams(C.Structure):
                 ("focal_length2", C.c_double), ("depth_epsilon", C.c_double)]
 
 
+DPROJ_WS_FWD, DPROJ_WS_SAVED, DPROJ_WS_BWD = 0, 1, 2
+
+
+class SrhDenseProjectionParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("has_rotated", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_double), ("fovy", C.c_double),
+                ("focal_length", C.c_double)]
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -166,6 +175,9 @@ SIGNATURES = {
     "srh_reverse_projection_fwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 8 + [_Z] + [_V] * 5),
     "srh_reverse_projection_keys": (C.c_int, [_p(SrhReverseProjectionParams), _V, _V, _V, _Z, _V, _V]),
     "srh_reverse_projection_bwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 9 + [_Z] + [_V] * 8),
+    "srh_dense_projection_workspace_bytes": (_Z, [_p(SrhDenseProjectionParams), _I]),
+    "srh_dense_projection_fwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 3),
+    "srh_dense_projection_bwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 6),
 }
 EXPORTS = tuple(SIGNATURES)
 

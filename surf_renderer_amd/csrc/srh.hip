@@ -1,7 +1,7 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
-// srh_reverse_projection.h.
+// srh_reverse_projection.h, srh_dense_projection.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -29,6 +29,7 @@
 #include "srh_regularizers.h"
 #include "srh_projection.h"
 #include "srh_reverse_projection.h"
+#include "srh_dense_projection.h"
 
 using namespace srh;
 
@@ -1651,6 +1652,130 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
     hipLaunchKernelGGL(k_rproj_texel_bwd, grid, block, 0, st, R, view2, (const double*)rec, order, (const int32_t*)range,
                        (const double*)gpl, grad_rgb, grad_in_pos);
   return launch_status("reverse projection backward launch");
+}
+
+}  // extern "C"
+
+// ---- the dense Gaussian re-projection layer (srh_dense_projection.h) ---------------------------------------------
+namespace {
+
+// argument checks (no HIP call) and the device view of a dense projection launch
+int dproj_setup(const SrhDenseProjectionParams* p, DProjDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
+  if (p->channels < 1 || p->channels > kProjMaxD)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (p->has_rotated != 0 && p->has_rotated != 1)
+    return fail(SRH_E_TYPE, "has_rotated = %d, expected 0 or 1", p->has_rotated);
+  if (!(p->sigma > 0.0 && std::isfinite(p->sigma)))
+    return fail(SRH_E_RANGE, "sigma = %g, expected positive and finite", p->sigma);
+  if (int rc = check_pinhole("", p->fovy, p->focal_length)) return rc;
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->W = p->width; P->H = p->height; P->N = p->width * p->height; P->D = p->channels;
+  P->flags = p->has_rotated ? kDProjHasRotated : 0;
+  P->Wp = (P->W + kDProjStrip - 1) / kDProjStrip * kDProjStrip;
+  const PixelScales s = pixel_scales(p->fovy, p->focal_length, P->W, P->H);
+  P->fsx = s.fsx; P->fsy = s.fsy; P->cx0 = s.cx0; P->cy0 = s.cy0;
+  P->h = 1.0 / (2.0 * p->sigma * p->sigma);
+  P->q = exp(-2.0 * P->h);
+  return SRH_OK;
+}
+
+// the rotated image is there exactly when the parameters say so
+int dproj_check_rotated(const DProjDev& P, const float* rotated) {
+  if ((P.flags & kDProjHasRotated) && !rotated) return fail(SRH_E_NULL, "rotated is NULL with has_rotated = 1");
+  if (!(P.flags & kDProjHasRotated) && rotated) return fail(SRH_E_TYPE, "rotated is given with has_rotated = 0");
+  return SRH_OK;
+}
+
+// SRH_DPROJ_WS_FWD: uv (B, N, 2) fp64
+// SRH_DPROJ_WS_SAVED: S, m (B, D + 1, N) fp64
+// SRH_DPROJ_WS_BWD: gt (B, H, Wp, D + 1) fp64
+size_t dproj_ws_bytes(const DProjDev& P, int which) {
+  switch (which) {
+    case SRH_DPROJ_WS_FWD: return (size_t)P.B * P.N * 2 * sizeof(double);
+    case SRH_DPROJ_WS_SAVED: return (size_t)P.B * P.N * (P.D + 1) * sizeof(double);
+    default: return (size_t)P.B * P.H * P.Wp * (P.D + 1) * sizeof(double);
+  }
+}
+
+// f(std::integral_constant<int, D>) for the channel count D (validated by dproj_setup)
+template <class Fn>
+void with_channels(int D, Fn f) {
+  switch (D) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t srh_dense_projection_workspace_bytes(const SrhDenseProjectionParams* params, int32_t which) {
+  DProjDev P;
+  if (dproj_setup(params, &P)) return 0;
+  if (which < SRH_DPROJ_WS_FWD || which > SRH_DPROJ_WS_BWD) {
+    fail(SRH_E_TYPE, "which = %d, expected SRH_DPROJ_WS_FWD, _SAVED or _BWD", which);
+    return 0;
+  }
+  return dproj_ws_bytes(P, which);
+}
+
+int srh_dense_projection_fwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                             const float* rgb, const float* rotated, void* workspace, size_t workspace_bytes,
+                             void* saved, size_t saved_bytes, float* out, float* mask, void* stream) {
+  DProjDev P;
+  int rc = dproj_setup(params, &P);
+  if (rc || (rc = dproj_check_rotated(P, rotated))) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"rgb", rgb}, {"out", out}, {"mask", mask}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_FWD)))) return rc;
+  if (saved && (rc = check_scratch("saved", saved, saved_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_SAVED)))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  double* uv = (double*)workspace;
+  hipLaunchKernelGGL(k_dproj_uv, dim3((P.N + kDProjBlock - 1) / kDProjBlock, P.B), dim3(kDProjBlock), 0, st, P, view,
+                     surfels, uv);
+  const int tiles = ((P.W + kDProjTile - 1) / kDProjTile) * ((P.H + kDProjTile - 1) / kDProjTile);
+  with_channels(P.D, [&](auto d) {
+    hipLaunchKernelGGL(k_dproj_fwd<decltype(d)::value>, dim3(tiles, P.B), dim3(kDProjFwdBlock), 0, st, P,
+                       (const double*)uv, rgb, rotated, (double*)saved, out, mask);
+  });
+  return launch_status("dense projection forward launch");
+}
+
+int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                             const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                             void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                             float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+  DProjDev P;
+  int rc = dproj_setup(params, &P);
+  if (rc || (rc = dproj_check_rotated(P, rotated))) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"rgb", rgb}}))) return rc;
+  if (!g_out && !g_mask) return fail(SRH_E_NULL, "g_out and g_mask are both NULL");
+  if (!grad_surfels && !grad_rgb && !grad_rotated)
+    return fail(SRH_E_NULL, "grad_surfels, grad_rgb and grad_rotated are all NULL");
+  if (grad_rotated && !rotated) return fail(SRH_E_NULL, "grad_rotated without rotated");
+  if ((rc = check_scratch("saved", saved, saved_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_SAVED)))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_BWD)))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  double* gt = (double*)workspace;
+  hipLaunchKernelGGL(k_dproj_pixel_bwd, dim3((P.H * P.Wp + kDProjBlock - 1) / kDProjBlock, P.B), dim3(kDProjBlock), 0, st,
+                     P, (const double*)saved, rotated, g_out, g_mask, gt, grad_rotated);
+  if (grad_surfels || grad_rgb) {
+    const dim3 grid((P.N + kDProjBwdBlock - 1) / kDProjBwdBlock, P.B), block(kDProjBwdBlock);
+    with_channels(P.D, [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      if (grad_surfels)
+        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, true>), grid, block, 0, st, P, view, surfels, rgb, (const double*)gt,
+                           grad_rgb, grad_surfels);
+      else
+        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, false>), grid, block, 0, st, P, view, surfels, rgb, (const double*)gt,
+                           grad_rgb, grad_surfels);
+    });
+  }
+  return launch_status("dense projection backward launch");
 }
 
 }  // extern "C"

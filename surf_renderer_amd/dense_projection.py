@@ -1,0 +1,132 @@
+"""The reference's dense Gaussian re-projection (diffrend/torch/projection_layer.py:108-152) under its own name, so the
+swap is one import:
+
+    # from diffrend.torch.projection_layer import projection_renderer_differentiable
+    from surf_renderer_amd import projection_renderer_differentiable
+    out, mask = projection_renderer_differentiable(surfels, rgb, camera, rotated_image=None, blur_size=0.15)
+
+A view's surfels (W H world-space points with a D-channel value each) are projected into another camera, and EVERY
+surfel contributes to EVERY pixel with the weight exp(-d^2 / (2 sigma^2)), d the distance between the surfel's pixel
+coordinate and the pixel's centre -- surfels outside the frame and behind the camera included.  There is no cell
+choice, no floor and no drop at the frame's edge: the layer is smooth in the surfel positions everywhere except Z = 0.
+The reference materialises the weights as a [B, W H, N] tensor; here forward and backward are HIP kernels
+(surf_renderer_amd/csrc/srh_dense_projection.h) that form the separable weight tile by tile and need memory linear in
+B W H: fp64 arithmetic, fp32 results, no atomics, so values and gradients are identical from run to run.
+Differentiable in surfels, rgb and rotated_image; the camera is not differentiable.
+
+Two things follow the reference to the letter, and one cannot:
+  - sigma = blur_size * rgb.shape[-2] / 6: the WIDTH for rgb [B, H, W, D] and the SURFEL COUNT for rgb [B, N, D].  An
+    accident of the reference's indexing, but it is the function under this name; the two layouts of one image give
+    different results.
+  - mask is the plain sum of the weights: not normalised, and well above 1 wherever surfels are dense.
+  - with a rotated image the reference's line `sum(...) + rotated_image * (1 - mask)` multiplies [B, N, D] by [B, N] and
+    raises for every frame of more than one pixel.  Here the mask is broadcast over the channels, the line's evident
+    meaning: out = S + rotated_image * (1 - mask)[..., None].
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Mapping, Tuple
+
+import torch
+
+from . import _layer, _lib
+from ._camera import camera_frame, camera_views
+from ._layer import fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+
+_NAME = "projection_renderer_differentiable"
+
+
+class _DenseProjFunction(torch.autograd.Function):
+    """(surfels [B, N, 3], rgb [B, N, D], rotated [B, N, D] or None), fp32 contiguous -> out [B, N, D], mask [B, N]."""
+
+    @staticmethod
+    def forward(ctx, params, view, surfels, rgb, rotated):
+        lib = _lib.load()
+        B, N, D = rgb.shape
+        dev = rgb.device
+        ws = scratch(lib.srh_dense_projection_workspace_bytes(C.byref(params), _lib.DPROJ_WS_FWD), dev)
+        # without a backward to come the kernels keep nothing
+        saved = None
+        if any(ctx.needs_input_grad[2:]):
+            saved = scratch(lib.srh_dense_projection_workspace_bytes(C.byref(params), _lib.DPROJ_WS_SAVED), dev)
+        out = torch.empty_like(rgb)
+        mask = torch.empty((B, N), dtype=torch.float32, device=dev)
+        _lib.check(lib.srh_dense_projection_fwd(C.byref(params), view.data_ptr(), surfels.data_ptr(), rgb.data_ptr(),
+                                                ptr(rotated), ws.data_ptr(), ws.numel(), ptr(saved),
+                                                0 if saved is None else saved.numel(), out.data_ptr(), mask.data_ptr(),
+                                                stream(dev)))
+        ctx.params = params
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(view, surfels, rgb, rotated, saved)
+        return out, mask
+
+    @staticmethod
+    def backward(ctx, g_out, g_mask):
+        view, surfels, rgb, rotated, saved = ctx.saved_tensors
+        grads = grad_buffers((surfels, rgb, rotated), ctx.needs_input_grad[2:])
+        ups = upstreams((g_out, g_mask))
+
+        def launch():
+            lib = _lib.load()
+            ws = scratch(lib.srh_dense_projection_workspace_bytes(C.byref(ctx.params), _lib.DPROJ_WS_BWD), rgb.device)
+            _lib.check(lib.srh_dense_projection_bwd(
+                C.byref(ctx.params), view.data_ptr(), surfels.data_ptr(), rgb.data_ptr(), ptr(rotated),
+                saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(), *[ptr(u) for u in ups],
+                *[ptr(g) for g in grads], stream(rgb.device)))
+
+        fill_grads(grads, ups, launch)
+        return (None, None, *grads)
+
+
+def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
+    """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError).  Returns the
+    tensors, (B, H, W, D), sigma, and the camera's fovy, focal length and per-view matrices [B, 3, 4] float64."""
+    surfels = _layer.as_float_tensor("surfels", surfels, _NAME)
+    rgb = _layer.as_float_tensor("rgb", rgb, _NAME)
+    W, H = camera_frame(_NAME, camera)
+    if surfels.dim() != 3 or surfels.shape[-1] != 3:
+        raise ValueError(f"{_NAME}: surfels is {list(surfels.shape)}, expected [B, N, 3]")
+    B, N = surfels.shape[:2]
+    if B < 1:
+        raise ValueError(f"{_NAME}: an empty batch")
+    if N != W * H:
+        raise ValueError(f"{_NAME}: {N} surfels per view, expected W x H = {W} x {H} = {W * H} (one per pixel of the "
+                         "frame: the result is shaped like rgb)")
+    D = rgb.shape[-1] if rgb.dim() else 0
+    if tuple(rgb.shape) not in ((B, N, D), (B, H, W, D)):
+        raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}, expected [{B}, {N}, D] or [{B}, {H}, {W}, D]")
+    if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
+        raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
+    if rotated_image is not None:
+        rotated_image = _layer.as_float_tensor("rotated_image", rotated_image, _NAME)
+        if tuple(rotated_image.shape) != tuple(rgb.shape):
+            raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
+    blur_size = float(blur_size)
+    if not (math.isfinite(blur_size) and blur_size > 0):
+        raise ValueError(f"{_NAME}: blur_size = {blur_size}, expected positive and finite")
+    sigma = blur_size * rgb.shape[-2] / 6          # the reference's rgb.size(-2): W for [B, H, W, D], N for [B, N, D]
+    fovy, focal, view = camera_views(_NAME, camera, B)
+    return surfels, rgb, rotated_image, (B, H, W, D), sigma, fovy, focal, view
+
+
+def projection_renderer_differentiable(surfels, rgb, camera: Mapping, rotated_image=None,
+                                       blur_size: float = 0.15) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's call.  surfels [B, N, 3] in world coordinates with N = W H; rgb [B, N, D] or [B, H, W, D], D in
+    1..4; rotated_image like rgb or None; camera: eye / at / up [B, 3] or [B, 4] and one shared viewport, fovy and
+    focal_length.  Returns (out like rgb, mask [*rgb.shape[:-1], 1]), float32 on the GPU, differentiable in surfels, rgb
+    and rotated_image through both.
+
+    sigma = blur_size * rgb.shape[-2] / 6 as in the reference: W for [B, H, W, D] input, N for [B, N, D] input.  With
+    rotated_image, out = S + rotated_image * (1 - mask) with the mask broadcast over the channels (the reference raises
+    there unless B = N = 1); without, out = S / (mask + 1e-10).  See the module docstring."""
+    surfels, rgb, rotated_image, (B, H, W, D), sigma, fovy, focal, view = _validate(
+        surfels, rgb, camera, rotated_image, blur_size)
+    dev = gpu_device(_NAME, (surfels, rgb, rotated_image))
+    x = [None if t is None else f32(t, dev).reshape(B, H * W, -1) for t in (surfels, rgb, rotated_image)]
+    params = _lib.SrhDenseProjectionParams(n_views=B, width=W, height=H, channels=D,
+                                           has_rotated=int(rotated_image is not None), sigma=sigma, fovy=fovy,
+                                           focal_length=focal)
+    out, mask = _DenseProjFunction.apply(params, view.reshape(B, 12).contiguous().to(dev), *x)
+    return out.reshape(rgb.shape), mask.reshape(*rgb.shape[:-1], 1)
