@@ -59,6 +59,7 @@ class SrhParams(C.Structure):
                 ("per_view", C.c_int32), ("reserved1", C.c_int32)]
 
 STAGE_BIN, STAGE_RENDER, STAGE_KEEP_BINS = 1, 2, 4
+E_NOT_APPLICABLE = -6
 VIEWS_OBJECTS, VIEWS_LIGHTS, VIEWS_MATERIALS = 1, 2, 4
 
 
@@ -158,6 +159,7 @@ SIGNATURES = {
     "srh_shadow_workspace_bytes": (_Z, [_p(SrhObjects), _I, _I, _I]),
     "srh_shadow_shade": (C.c_int, _FRAME + [_V] * 5),
     "srh_bin_counters": (C.c_int, [_p(SrhObjects), _I, _I, _I, _I, _p(_Z), _p(_I), _p(_I), _p(_I), _p(_I)]),
+    "srh_tile_rlen": (C.c_int, [_p(SrhObjects), _I, _I, _I, _I, _p(_Z), _p(_I), _p(_I)]),
     "srh_event_create": (C.c_int, [_p(_V)]),
     "srh_event_destroy": (C.c_int, [_V]),
     "srh_event_elapsed_ms": (C.c_int, [_V, _V, _p(C.c_float)]),

@@ -999,6 +999,29 @@ __device__ __forceinline__ const FrameDev& round_frame(const FrameDev& F) {
   return *(const FrameDev*)p;
 }
 
+// The occlusion cull's `rlen_lo` of tile (tx, ty): a lower bound of 1 / |D| over the tile's pixels.  1 / |D| is smallest
+// where |D| is largest, and |D| is convex in the pixel coordinates: at a corner of the tile (clamped to the frame and the
+// row slab).  0 where no usable bound exists: T = 0 then, and nothing is skipped.  It depends on the camera, the slab and
+// the tile only.  The one copy of the expression: k_prep evaluates it once per tile, one tile per lane, into
+// FrameDev::tile_rlen (fill_tile_rlen); a render kernel whose frame has no table evaluates it itself.
+__device__ __forceinline__ float tile_rlen_lo(const FrameDev& F, int tx, int ty) {
+  const int px0 = tx * kTile, py0 = F.row0 + ty * kTile;
+  const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
+  const double m2 = fmax(fmax(pixel_len2(F, ca, ra), pixel_len2(F, cb, ra)),
+                         fmax(pixel_len2(F, ca, rb), pixel_len2(F, cb, rb)));
+  const float rl = (float)(1.0 / sqrt(m2));
+  return (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;
+}
+
+// k_prep's blocks behind the primitives' (launch_prep): block `block` of them writes the table entries of tiles
+// 64 block .. 64 block + 63, with plain vector stores.  The render kernel is a later launch on the stream.
+__device__ __forceinline__ void fill_tile_rlen(const FrameDev& F, unsigned block) {
+  const int tile = (int)(block * kBinBlock + threadIdx.x);
+  if (!F.tile_rlen || tile >= F.ntiles) return;
+  const int ty = tile / F.tiles_x, tx = tile - ty * F.tiles_x;
+  const_cast<float*>(F.tile_rlen)[tile] = tile_rlen_lo(F, tx, ty);
+}
+
 template <bool TCH, int WPT, int BATCH = -1>
 __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ F, float* __restrict__ image,
                                                    float* __restrict__ depth, int32_t* __restrict__ nearest) {
@@ -1036,10 +1059,14 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
     // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
     int32_t gs[2] = {0, 0}, us[2] = {-1, -1};   // sorted entries and their bounds (occl_sort)
+    float rlen_lo = 0.0f;                       // the sorted sweep's lower bound of 1 / |D| over the tile (tile_rlen_lo)
 #if SRH_OCCLUSION_CULL
     if (WPT == 1 && BATCH == SRH_PRIM_DISK && pretest) {
       const TileLists L{F, tile};
       if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
+        // from the frame's table (k_prep wrote it, an earlier launch: as_constant's contract), one scalar load whose
+        // latency the sort hides
+        if (F.tile_rlen) rlen_lo = as_constant(F.tile_rlen)[tile];
         if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         sorted = true;
@@ -1078,13 +1105,9 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     }
     const uint32_t part = WPT == 1 ? 0u : (uint32_t)wave;     // which share of the tile's entries this wave sweeps
     if (sorted) {
-      // 1 / |D| is smallest where |D| is largest: |D| is convex in the pixel coordinates, so at a corner of the tile
-      const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
-      const double m2 = fmax(fmax(pixel_len2(F, ca, ra), pixel_len2(F, cb, ra)),
-                             fmax(pixel_len2(F, ca, rb), pixel_len2(F, cb, rb)));
-      float rl = (float)(1.0 / sqrt(m2));
-      rl = (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;           // (0: T = 0, nothing is skipped)
-      const float rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rl)));
+      // a frame without a table (many views per launch, one wave per tile forced on a small frame): every lane computes
+      // the same value here
+      if (!F.tile_rlen) rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tile_rlen_lo(F, tx, ty))));
       if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, rlen_lo, Q);
       else sweep_sorted<2>(F.seg[0], listed, gs, us, rlen_lo, Q);
     } else if (pretest) {

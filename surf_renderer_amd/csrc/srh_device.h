@@ -52,7 +52,8 @@ struct FrameDev {
   // SRH_SHADING_TORCH extras (torch/renderer.py:82-125)
   int32_t shading, double_sided, use_quartic;
   int32_t div_shared;                // pixel_ray may share one reciprocal between its three divisions (see there)
-  int32_t ortho, pad4;               // orthographic projection (torch semantics only; k_render_ortho)
+  int32_t ortho;                     // orthographic projection (torch semantics only; k_render_ortho)
+  int32_t slab_cull;                 // the row pre-cull below is on (in a former padding word, see tile_rlen)
   const float* latt;                 // (L,3) attenuation or NULL
   const float* coeffs;               // (K,3) material coefficients or NULL
   const float* ambient;              // (3) or NULL
@@ -65,7 +66,11 @@ struct FrameDev {
   // image row g / a; slab_ma / slab_mg are the rows of [D0 Dc Dr]^-1 that give a and g, slab_na / slab_ng their
   // lengths.  slab_cull = 0 switches the test off (full frame, or a singular basis).
   double slab_ma[3], slab_mg[3], slab_na, slab_ng;
-  int32_t slab_cull, pad3;
+  const float* tile_rlen;            // (ntiles_pad) per tile the occlusion cull's lower bound of 1 / |D| (srh_binned.h:
+                                     // tile_rlen_lo), written by k_prep of batch 0; NULL: the frame has no table and the
+                                     // render kernel computes the bound itself.  In the 8 bytes that held slab_cull and a
+                                     // padding word: sizeof(FrameDev) -- the views' workspace header -- and every other
+                                     // field's offset stay what they were
   uint16_t* tilerange;               // (total,4) tx0,ty0,tx1,ty1 inclusive; tx0 > tx1 = not binned
   uint32_t* counters;                // [4p + s] n_large of batch s, set p | [8] set of the NEXT frame | [9] set of this frame |
                                      // [64, 64+nbins) bin counts   (see kLargeNext below)
@@ -89,6 +94,11 @@ struct FrameDev {
   const float* colors;
   const float* albedo;
 };
+
+// tile_rlen took the place of slab_cull and a padding word: the struct's size (the views' workspace header is an array of
+// it) and the fields around it are where they were
+static_assert(sizeof(FrameDev) == 784 && offsetof(FrameDev, tile_rlen) == 376 && offsetof(FrameDev, tilerange) == 384 &&
+              offsetof(FrameDev, slab_cull) + 4 == offsetof(FrameDev, latt), "FrameDev layout");
 
 // rec64 layouts
 //   disk     [0..2] n^ (unit normal)  [3] k = sum(pos*n^) - n^.eye  [4..6] c = pos  [7] r^2
@@ -335,8 +345,9 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 //     an invalidated scalar cache, so it sees that data;
 //   - the RUNNING kernel never writes it -- hipcc treats the loads as invariant, and the scalar cache is not coherent
 //     with the kernel's own vector stores.
-// So: frame inputs (lights, colours, attenuation, ambient) and what k_prep left for the render kernels (lights64) --
-// never in k_prep itself, which writes lights64, and never the bin counters, which the render kernel zeroes at its end.
+// So: frame inputs (lights, colours, attenuation, ambient) and what k_prep left for the render kernels (lights64,
+// tile_rlen) -- never in k_prep itself, which writes both, and never the bin counters, which the render kernel zeroes at
+// its end.
 template <class T>
 __device__ __forceinline__ const __attribute__((address_space(4))) T* as_constant(const T* p) {
   return (const __attribute__((address_space(4))) T*)p;

@@ -201,6 +201,15 @@ __global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrep
     uint32_t* dst = reinterpret_cast<uint32_t*>(F.self);
     for (unsigned i = threadIdx.x; i < sizeof(FrameDev) / 4; i += kBinBlock) dst[i] = src[i];
   }
+  // blocks behind the primitives' (launch_prep adds them to batch 0 of a frame with a table; only a one-batch disc frame
+  // has one): the per-tile bound of the render kernel's occlusion cull, 64 tiles each
+  if constexpr (TYPE == SRH_PRIM_DISK) {
+    const unsigned prim_blocks = ((unsigned)F.seg[s].count + kBinBlock - 1) / kBinBlock;
+    if (blockIdx.x >= prim_blocks) {
+      fill_tile_rlen(F, blockIdx.x - prim_blocks);
+      return;
+    }
+  }
   prep_body<TYPE>(F, s, rec64, rec32);
 }
 

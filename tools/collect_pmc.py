@@ -31,12 +31,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", required=True)
     ap.add_argument("--out", required=True)
+    ap.add_argument("--only", default=None, metavar="COUNTER",
+                    help="collect only the group(s) that hold this counter, e.g. SQ_INSTS_VALU (one pass instead of six)")
     args = ap.parse_args()
     lib = os.environ.get("SRH_LIB") or os.path.join(REPO, "surf_renderer_amd", "libsrh.so")
     sha = hashlib.sha256(open(lib, "rb").read()).hexdigest()
     kernels = collections.defaultdict(dict)
     env = dict(os.environ, TMPDIR="/tmp")
     for group in GROUPS:
+        if args.only and args.only not in group.split():
+            continue
         tmp = os.path.join(REPO, "gpurun_out", "pmc_tmp")
         shutil.rmtree(tmp, ignore_errors=True)
         cmd = ["rocprofv3", "--pmc", *group.split(), "--output-format", "csv", "-d", tmp, "--", sys.executable,
