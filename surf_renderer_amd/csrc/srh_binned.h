@@ -1022,6 +1022,53 @@ __device__ __forceinline__ void fill_tile_rlen(const FrameDev& F, unsigned block
   const_cast<float*>(F.tile_rlen)[tile] = tile_rlen_lo(F, tx, ty);
 }
 
+// ---- what a finish round needs of its TILE, computed once in front of the round loop -------------------------------
+// Each part has a build switch so that it can be compiled and counted alone (0 = the per-pixel form of the round).
+// The output addresses are not among them: built, measured and dropped (DESIGN Part II).
+#ifndef SRH_FINISH_RAYTAB
+#define SRH_FINISH_RAYTAB 1
+#endif
+#ifndef SRH_FINISH_TONE
+#define SRH_FINISH_TONE 1
+#endif
+
+// The ray numerator of pixel_ray, v[i] = (bx[i] X(c) + by[i] Y(r)) + bz[i] Z, has one addend that depends on the column
+// only, one on the row only and one on neither, and a tile has 16 columns and 16 rows.  A wave keeps the 33 addend
+// triples of its tile in LDS: entry k < 16 is bx[.] X(px0 + k), entry 16 + k is by[.] Y(py0 + k), entry 32 is
+// bz[.] (-focal).  A round reads three entries and adds them in pixel_ray's order: with contraction off these are the
+// products and sums pixel_ray rounds, so the direction is the same bit for bit.  Three doubles per entry, not four: 792 B
+// per wave, which the six-wave plane kernel's 24 resident workgroups still have room for.
+constexpr int kRayCols = 0, kRayRows = kTile, kRayZ = 2 * kTile, kRayEntries = 2 * kTile + 1;
+typedef double RayTable[kRayEntries][3];
+
+// Lanes 0-15 fill the column entries, 16-31 the row entries, lane 32 the last one.  X and Y come from pixel_plane_xy, the
+// one copy of the end-point rule; each branch uses one of its two results, so a column lane does column work only.
+// Columns >= W and rows >= row1 of an edge tile get finite values that no live pixel reads.
+__device__ __forceinline__ void ray_table_fill(const FrameDev& F, int px0, int py0, int lane, RayTable& T) {
+  double X, Y;
+  if (lane < kTile) {
+    pixel_plane_xy(F, px0 + lane, py0, X, Y);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[kRayCols + lane][i] = F.bx[i] * X;
+  } else if (lane < 2 * kTile) {
+    pixel_plane_xy(F, px0, py0 + (lane - kTile), X, Y);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[lane][i] = F.by[i] * Y;
+  } else if (lane == 2 * kTile) {
+    const double Z = -F.focal;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[kRayZ][i] = F.bz[i] * Z;
+  }
+}
+
+// pixel_ray for column px0 + kc, row py0 + kr of the tile whose table T is
+__device__ __forceinline__ double ray_from_table(const FrameDev& F, const RayTable& T, int kc, int kr, double d[3]) {
+  double v[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v[i] = (T[kRayCols + kc][i] + T[kRayRows + kr][i]) + T[kRayZ][i];
+  return ray_normalise(F, v, d);
+}
+
 template <bool TCH, int WPT, int BATCH = -1>
 __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ F, float* __restrict__ image,
                                                    float* __restrict__ depth, int32_t* __restrict__ nearest) {
@@ -1031,6 +1078,9 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   __shared__ int32_t front[kWaves][4][64];    // global index of each pixel's front candidate (-1: none / saturated)
   __shared__ uint8_t queue[kWaves][256];      // [wave]: ids j * 64 + lane of the pixels with a candidate, row-major
   __shared__ int32_t occl_g[kWaves][kSortCap];  // occlusion cull: the tile's list in front-to-back order
+#if SRH_FINISH_RAYTAB
+  __shared__ RayTable raytab[kWaves];         // the finish rounds' ray numerator addends of this tile (ray_table_fill)
+#endif
   const int wave = kWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   int tx, ty;
@@ -1206,7 +1256,14 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     }
   }
 
-  wave_lds_fence();                           // park / queue writes of other lanes
+  // per tile, not per round: the ray table and the tonemap's constants
+#if SRH_FINISH_RAYTAB
+  if (n1 > 0) ray_table_fill(F, px0, py0, lane, raytab[wave]);
+#endif
+#if SRH_FINISH_TONE
+  const ToneHint tone = tone_hint(F);
+#endif
+  wave_lds_fence();                           // park / queue / ray table writes of other lanes
 #pragma unroll 1
   for (int base = 0; base < n1; base += 64) {
     {
@@ -1222,7 +1279,11 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       FrontRecord<TCH, BATCH> fr;
       fr.fetch(F, gfront);
       double d[3];
+#if SRH_FINISH_RAYTAB
+      const float len = (float)ray_from_table(F, raytab[wave], 4 * (src & 3) + j, src >> 2, d);
+#else
       const float len = (float)pixel_ray(F, c, r, d);
+#endif
       double best = __builtin_inf();
       int besti = 0x7fffffff;
       float bound = __builtin_inff();
@@ -1287,7 +1348,14 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
         if (besti == 0x7fffffff) besti = 0;   // nothing hit: np.argmin of an all-inf column
         float rgb[3], aux[6];
         const ShadeHint hint = fr.hint();
+#if SRH_FINISH_TONE
+        // Lambert kernels only: in the one-wave Phong kernels the hint's register is the 97th, one more than five waves
+        // per SIMD allow
+        shade_pixel_t<TCH, BATCH, true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint, nullptr, ~0ull,
+                                        TCH ? nullptr : &tone);
+#else
         shade_pixel_t<TCH, BATCH, true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint);
+#endif
         const size_t row = (size_t)(r - F.row0);
         float* px = image + row * F.img_stride + 3 * (size_t)c;
         out_store(px, rgb[0]); out_store(px + 1, rgb[1]); out_store(px + 2, rgb[2]);

@@ -129,13 +129,22 @@ __device__ __forceinline__ void pixel_plane_xy(const FrameDev& F, int c, int r, 
 
 // numpy/renderer.py:145-169 for pixel (column c, row r) of the full W x H grid.
 // Returns |D|, the length of the un-normalised direction.
-__device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, double d[3]) {
-  double X, Y;
-  pixel_plane_xy(F, c, r, X, Y);
-  const double Z = -F.focal;
+// GIVEN: the numerator v[i] = (bx[i] X + by[i] Y) + bz[i] Z comes from the caller (`given`; c and r are unused) and only
+// the tail runs -- ray_normalise below.  The tail has one copy, and it stays in this function: with it in a function of
+// its own the per-pixel kernels (exact, fast, ortho, shadow, backward) compile to other text (commuted operands).
+template <bool GIVEN = false>
+__device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, double d[3], const double* given = nullptr) {
   double v[3];
+  if constexpr (GIVEN) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
+    for (int i = 0; i < 3; ++i) v[i] = given[i];
+  } else {
+    double X, Y;
+    pixel_plane_xy(F, c, r, X, Y);
+    const double Z = -F.focal;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
+  }
   const double len = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
   if (F.div_shared) {
     // The three IEEE divisions by |D| as hipcc expands each of them (v_rcp_f64, two Newton steps, quotient, residual
@@ -159,6 +168,12 @@ __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, dou
     for (int i = 0; i < 3; ++i) d[i] = v[i] / len;
   }
   return len;
+}
+
+// The tail of pixel_ray alone: d = v / |v| for a numerator v formed elsewhere by the same rounded operations (the binned
+// finish rounds read its three addends from a per-tile table, srh_binned.h: RayTable); returns |v|.
+__device__ __forceinline__ double ray_normalise(const FrameDev& F, const double v[3], double d[3]) {
+  return pixel_ray<true>(F, 0, 0, d, v);
 }
 
 // |D|^2 of the un-normalised direction of pixel (c, r): the part of pixel_ray the fp32 sweep needs (its 1 / |D| comes
@@ -418,6 +433,25 @@ __device__ __forceinline__ float tonemap_f32(const FrameDev& F, double v) {
   return powf(x, g);
 }
 
+// What the tonemap needs of the frame, for a caller that evaluates it once in front of a loop over pixels (the binned
+// finish rounds, one per tile) instead of per pixel and channel: the fp32 gamma and which arm F.tonemap and gamma > 0
+// select.  tonemap_f32(T, v) == tonemap_f32(F, v) bit for bit, NaN gamma and gamma <= 0 included (both fail g > 0).
+struct ToneHint {
+  float g;            // (float)F.gamma
+  int mode;           // 0: F.tonemap off | 1: gamma > 0, the direct path while y <= 12 | 2: always the library powf
+};
+__device__ __forceinline__ ToneHint tone_hint(const FrameDev& F) {
+  const float g = (float)F.gamma;
+  return ToneHint{g, !F.tonemap ? 0 : (g > 0.0f ? 1 : 2)};
+}
+__device__ __forceinline__ float tonemap_f32(const ToneHint& T, double v) {
+  if (T.mode == 0) return (float)v;
+  const float x = (float)v;
+  const float y = T.g * __builtin_amdgcn_logf(x);
+  if (T.mode == 1 && y <= 12.0f) return __builtin_amdgcn_exp2f(y);
+  return powf(x, T.g);
+}
+
 // tonemap_f32(F, 0.0) in closed form: what every all-miss or depth-masked pixel stores.  0 ** gamma is 0 for gamma > 0
 // (the direct path: exp2(gamma * -inf)), 1 for gamma == 0, +inf for gamma < 0 and NaN for a NaN gamma (powf's special
 // values, the same ones numpy's ** gives).  Spelled out because hipcc hoists the inlined powf(0, gamma) -- ~190 vector
@@ -450,7 +484,8 @@ struct ShadeHint {
 template <bool TCH, int BATCH = -1, bool UNIFORM = false>
 __device__ __forceinline__ void shade_pixel_t(const FrameDev& F, const double d[3], double z, int win,
                                               float rgb[3], float aux[6] = nullptr, const ShadeHint* hint = nullptr,
-                                              const double* origin = nullptr, uint64_t vis = ~0ull) {
+                                              const double* origin = nullptr, uint64_t vis = ~0ull,
+                                              const ToneHint* tone = nullptr) {
   const bool masked = (z < F.near_clip) || (z > F.far_clip);      // :256
   if (aux) {
 #pragma unroll
@@ -570,7 +605,7 @@ __device__ __forceinline__ void shade_pixel_t(const FrameDev& F, const double d[
   for (int ch = 0; ch < 3; ++ch) {
     double v = im[ch];
     if (v < 0.0) v = 0.0;                                         // :259, NaN stays NaN
-    rgb[ch] = tonemap_f32(F, v);                                  // :262-263
+    rgb[ch] = tone ? tonemap_f32(*tone, v) : tonemap_f32(F, v);   // :262-263
   }
 }
 
