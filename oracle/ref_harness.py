@@ -7,6 +7,7 @@ silenced; the generator modules (``oracle/golden_<fixture prefixes>.py``) reach 
 names.  Nothing of the reference's code is written anywhere: fixtures hold arrays and the ``meta`` / ``note`` /
 ``kwargs`` strings only.
 """
+import argparse
 import contextlib
 import io
 import json
@@ -174,6 +175,55 @@ def pack_run(sc, ups, res, leaves, kw=None):
         out["kwargs"] = np.asarray(json.dumps(kw))
     pack_grads(out, leaves)
     return out
+
+
+def layer_camera(camera, dtype=torch.float32):
+    """A seeded case's camera (tests/*projection_cases.py) for the reference's projection layers: eye / at / up as tensors
+    of the case's float32 values in ``dtype``."""
+    return {k: (torch.tensor(np.asarray(v, dtype=np.float32), dtype=dtype) if k in ("eye", "at", "up") else v)
+            for k, v in camera.items()}
+
+
+def camera_views(camera, views):
+    return {k: (v[views] if k in ("eye", "at", "up") else v) for k, v in camera.items()}
+
+
+def run_views(run, n_views):
+    """{output: tensor} of ``run(views)`` (``views`` a slice of the batch) over the whole batch."""
+    if n_views != 3:
+        return run(slice(None))
+    # lookat_rot_inv calls torch.cross(up, z) without `dim`, which for [3, 3] operands -- three views, and only three --
+    # still means dim 0: the cross product is taken ACROSS the views.  That is an accident of B == 3, not a meaning of
+    # the layer, so such a case is recorded view by view
+    per_view = [run(slice(b, b + 1)) for b in range(n_views)]
+    return {k: torch.cat([r[k] for r in per_view]) for k in per_view[0]}
+
+
+def pack_layer(c, leaves, res, cameras=("camera",), dtype=torch.float32):
+    """A projection layer's fixture from case ``c``, its leaf tensors and the reference's outputs: backward of
+    sum_outputs sum(output * upstream), then in/<input>, in/<camera>/<entry>, grad_in/<output>, ref/<output> and
+    grad/<input> (zeros where autograd left None).  The caller adds its layer's own in/ keys."""
+    assert set(res) == set(c["upstream"]), (sorted(res), sorted(c["upstream"]))
+    sum(torch.sum(res[k] * torch.tensor(g, dtype=dtype)) for k, g in c["upstream"].items()).backward()
+    flat = {"in/" + k: c[k] for k in leaves}
+    for cam in cameras:
+        for k, v in c[cam].items():
+            flat[f"in/{cam}/{k}"] = np.asarray(v, dtype=np.float64 if k in ("fovy", "focal_length") else None)
+    for k, g in c["upstream"].items():
+        assert res[k].dtype == dtype and tuple(res[k].shape) == g.shape, k
+        flat["grad_in/" + k] = g
+        flat["ref/" + k] = res[k].detach().numpy()
+    for k, t in leaves.items():
+        flat["grad/" + k] = t.grad.numpy() if t.grad is not None else np.zeros(tuple(t.shape), np.float32)
+    return flat
+
+
+def fixture_dir(subfolder, argv=None):
+    """Where a layer's generator writes: tests/golden/<subfolder>, or the directory given with --out (a fresh run to
+    compare with the committed fixtures)."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", help="write the fixtures here instead of tests/golden/" + subfolder)
+    return ap.parse_args(argv).out or os.path.join(REPO, "tests", "golden", subfolder)
 
 
 def wanted(name):

@@ -1,5 +1,5 @@
-"""The camera of the two re-projection layers (projection, reverse_projection): the host-side checks of a camera dict and
-the reference's lookat as per-view world-to-camera matrices."""
+"""The camera of the re-projection layers (projection, dense_projection, reverse_projection): the host-side checks of a
+camera dict and the reference's lookat as per-view world-to-camera matrices."""
 from __future__ import annotations
 
 import math

@@ -1,6 +1,7 @@
-"""The host scaffold the fused layer modules share (splats, regularizers, projection, reverse_projection): device
-choice, scratch, the float32-contiguous conversion and the backward pattern.  The camera helpers of the two projection
-layers are in _camera.py.  A layer whose wording or steps differ keeps its own code."""
+"""The host scaffold the fused layer modules share (splats, regularizers and the three projection layers): device
+choice, scratch, the float32-contiguous conversion and the backward pattern.  The camera helpers of the projection
+layers are in _camera.py, what else those three share in _projection.py.  A layer whose wording or steps differ keeps
+its own code."""
 from __future__ import annotations
 
 from typing import Any, Callable, Iterable, List, Optional, Sequence

@@ -1440,12 +1440,30 @@ static_assert(kProjUseDepth == SRH_PROJ_USE_DEPTH && kProjUseCenterDist == SRH_P
               kProjDetachMask2 == SRH_PROJ_DETACH_MASK2 && kProjDetachDepthMerge == SRH_PROJ_DETACH_DEPTH_MERGE,
               "srh.h and srh_projection.h");
 
+// what the parameters of the three projection layers share: the batch, the frame and the channel count
+int check_proj_frame(int32_t n_views, int32_t width, int32_t height, int32_t channels) {
+  if (int rc = check_batch_grid(n_views, width, height, "width x height =")) return rc;
+  if (channels < 1 || channels > kProjMaxD) return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", channels, kProjMaxD);
+  return SRH_OK;
+}
+
+// A layer's workspace as consecutive regions: each *_ws function below is the one statement of a layout, and both the
+// size the caller must bring (`bytes`, from no base) and the entry points' pointers come from it.
+struct Regions {
+  char* base;
+  size_t bytes = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* at = base ? (T*)(base + bytes) : nullptr;
+    bytes += count * sizeof(T);
+    return at;
+  }
+};
+
 // argument checks (no HIP call) and the device view of a projection launch
 int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
   if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
-  if (p->channels < 1 || p->channels > kProjMaxD)
-    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (int rc = check_proj_frame(p->n_views, p->width, p->height, p->channels)) return rc;
   if (p->flags & ~63) return fail(SRH_E_TYPE, "flags = %d has unknown bits", p->flags);
   if (p->blur_half < 0 || p->blur_half > kProjMaxHalf)
     return fail(SRH_E_RANGE, "blur_half = %d, expected 0..%d", p->blur_half, kProjMaxHalf);
@@ -1467,14 +1485,35 @@ int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
 // SRH_PROJ_WS_FWD: rec (B, N, 4) | pre (B, P, N) | tmp (B, P, N) fp64 | range (B, ncell, 2) int32
 // SRH_PROJ_WS_SAVED: blr (B, P, N) | cor (B, 4, CS, N) fp64
 // SRH_PROJ_WS_BWD: gpl (B, P, N) | gtmp (B, P, N) | gcor (B, 4, CS, N) fp64
-size_t proj_ws_bytes(const ProjDev& P, int which) {
+struct ProjWs {
+  double *rec, *pre, *tmp, *blr, *cor, *gpl, *gtmp, *gcor;
+  int32_t* range;
+  size_t bytes;
+};
+ProjWs proj_ws(const ProjDev& P, int which, const void* base = nullptr) {
   const size_t px = (size_t)P.B * P.N;
+  Regions r{(char*)base};
+  ProjWs w = {};
   switch (which) {
-    case SRH_PROJ_WS_FWD: return px * (4 + 2 * P.P) * sizeof(double) + (size_t)P.B * P.ncell * 2 * sizeof(int32_t);
-    case SRH_PROJ_WS_SAVED: return px * (P.P + 4 * P.CS) * sizeof(double);
-    default: return px * (2 * P.P + 4 * P.CS) * sizeof(double);
+    case SRH_PROJ_WS_FWD:
+      w.rec = r.take<double>(px * 4);
+      w.pre = r.take<double>(px * P.P);
+      w.tmp = r.take<double>(px * P.P);
+      w.range = r.take<int32_t>((size_t)P.B * P.ncell * 2);
+      break;
+    case SRH_PROJ_WS_SAVED:
+      w.blr = r.take<double>(px * P.P);
+      w.cor = r.take<double>(px * 4 * P.CS);
+      break;
+    default:
+      w.gpl = r.take<double>(px * P.P);
+      w.gtmp = r.take<double>(px * P.P);
+      w.gcor = r.take<double>(px * 4 * P.CS);
   }
+  w.bytes = r.bytes;
+  return w;
 }
+size_t proj_ws_bytes(const ProjDev& P, int which) { return proj_ws(P, which).bytes; }
 
 }  // namespace
 
@@ -1498,7 +1537,7 @@ int srh_projection_keys(const SrhProjectionParams* params, const double* view, c
   if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"keys", keys}}))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_FWD)))) return rc;
   hipLaunchKernelGGL(k_proj_keys, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, view, surfels,
-                     (double*)workspace, keys);
+                     proj_ws(P, SRH_PROJ_WS_FWD, workspace).rec, keys);
   return launch_status("k_proj_keys launch");
 }
 
@@ -1513,24 +1552,18 @@ int srh_projection_fwd(const SrhProjectionParams* params, const float* rgb, cons
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_FWD)))) return rc;
   if (saved && (rc = check_scratch("saved", saved, saved_bytes, proj_ws_bytes(P, SRH_PROJ_WS_SAVED)))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const size_t px = (size_t)P.B * P.N;
-  double* rec = (double*)workspace;
-  double* pre = rec + px * 4;
-  double* tmp = pre + px * P.P;
-  int32_t* range = (int32_t*)(tmp + px * P.P);
-  double* blr = (double*)saved;
-  double* cor = blr ? blr + px * P.P : nullptr;
+  const ProjWs w = proj_ws(P, SRH_PROJ_WS_FWD, workspace), s = proj_ws(P, SRH_PROJ_WS_SAVED, saved);
   const int nb = (rotated && (P.flags & kProjBlurRotated)) ? 2 * P.D + 1 : P.D + 1;
   const dim3 grid(P.nblk, P.B), block(kProjBlock);
-  if (hipError_t e = hipMemsetAsync(range, 0, (size_t)P.B * P.ncell * 2 * sizeof(int32_t), st))
+  if (hipError_t e = hipMemsetAsync(w.range, 0, (size_t)P.B * P.ncell * 2 * sizeof(int32_t), st))
     return hip_fail(e, "projection cell ranges memset");
-  hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, P, keys, order, range);
-  hipLaunchKernelGGL(k_proj_gather, grid, block, 0, st, P, (const double*)rec, order, (const int32_t*)range, rgb, rotated,
-                     pre, cor);
+  hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, P, keys, order, w.range);
+  hipLaunchKernelGGL(k_proj_gather, grid, block, 0, st, P, (const double*)w.rec, order, (const int32_t*)w.range, rgb,
+                     rotated, w.pre, s.cor);
   hipLaunchKernelGGL(k_proj_blur_h, dim3((P.N * nb + kProjBlock - 1) / kProjBlock, P.B), block, 0, st, P, nb,
-                     (const double*)pre, tmp);
-  hipLaunchKernelGGL(k_proj_blur_v_merge, grid, block, 0, st, P, nb, (const double*)tmp, (const double*)pre, rotated, blr,
-                     out, mask, image1, depth);
+                     (const double*)w.pre, w.tmp);
+  hipLaunchKernelGGL(k_proj_blur_v_merge, grid, block, 0, st, P, nb, (const double*)w.tmp, (const double*)w.pre, rotated,
+                     s.blr, out, mask, image1, depth);
   return launch_status("projection forward launch");
 }
 
@@ -1550,19 +1583,16 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
   if ((rc = check_scratch("saved", saved, saved_bytes, proj_ws_bytes(P, SRH_PROJ_WS_SAVED)))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_BWD)))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const size_t px = (size_t)P.B * P.N;
-  const double* blr = (const double*)saved;
-  const double* cor = blr + px * P.P;
-  double* gpl = (double*)workspace;
-  double* gtmp = gpl + px * P.P;
-  double* gcor = (grad_surfels || grad_rgb) ? gtmp + px * P.P : nullptr;
+  const ProjWs s = proj_ws(P, SRH_PROJ_WS_SAVED, saved), w = proj_ws(P, SRH_PROJ_WS_BWD, workspace);
+  double* gcor = (grad_surfels || grad_rgb) ? w.gcor : nullptr;
   const int nb = (grad_rotated && (P.flags & kProjBlurRotated)) ? 2 * P.D + 1 : P.D + 1;
   const dim3 grid(P.nblk, P.B), block(kProjBlock);
-  hipLaunchKernelGGL(k_proj_merge_bwd, grid, block, 0, st, P, blr, g_out, g_mask, g_image1, g_depth, gpl);
+  hipLaunchKernelGGL(k_proj_merge_bwd, grid, block, 0, st, P, (const double*)s.blr, g_out, g_mask, g_image1, g_depth,
+                     w.gpl);
   hipLaunchKernelGGL(k_proj_blur_h, dim3((P.N * nb + kProjBlock - 1) / kProjBlock, P.B), block, 0, st, P, nb,
-                     (const double*)gpl, gtmp);
-  hipLaunchKernelGGL(k_proj_blur_v_corner, grid, block, 0, st, P, nb, (const double*)gtmp, (const double*)gpl, cor, gcor,
-                     grad_rotated);
+                     (const double*)w.gpl, w.gtmp);
+  hipLaunchKernelGGL(k_proj_blur_v_corner, grid, block, 0, st, P, nb, (const double*)w.gtmp, (const double*)w.gpl,
+                     (const double*)s.cor, gcor, grad_rotated);
   if (gcor)
     hipLaunchKernelGGL(k_proj_surfel_bwd, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
                        grad_surfels);
@@ -1577,9 +1607,7 @@ namespace {
 // argument checks (no HIP call) and the device view of a reverse projection launch
 int rproj_setup(const SrhReverseProjectionParams* p, RProjDev* R) {
   if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
-  if (p->channels < 1 || p->channels > kProjMaxD)
-    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (int rc = check_proj_frame(p->n_views, p->width, p->height, p->channels)) return rc;
   if (int rc = check_pinhole("1", p->fovy1, p->focal_length1)) return rc;
   if (int rc = check_pinhole("2", p->fovy2, p->focal_length2)) return rc;
   if (!std::isfinite(p->depth_epsilon)) return fail(SRH_E_RANGE, "depth_epsilon = %g, expected finite", p->depth_epsilon);
@@ -1607,11 +1635,27 @@ ProjDev rproj_as_proj(const RProjDev& R) {
 
 // SRH_RPROJ_WS_FWD: d_in (B, N) fp64
 // SRH_RPROJ_WS_BWD: rec (B, N, 4) | gpl (B, D + 1, N) fp64 | range (B, ncell, 2) int32
-size_t rproj_ws_bytes(const RProjDev& R, int which) {
+// rec is first: srh_reverse_projection_keys writes it through the same workspace
+struct RProjWs {
+  double *d_in, *rec, *gpl;
+  int32_t* range;
+  size_t bytes;
+};
+RProjWs rproj_ws(const RProjDev& R, int which, const void* base = nullptr) {
   const size_t px = (size_t)R.B * R.N;
-  if (which == SRH_RPROJ_WS_FWD) return px * sizeof(double);
-  return px * (4 + R.D + 1) * sizeof(double) + (size_t)R.B * R.ncell * 2 * sizeof(int32_t);
+  Regions r{(char*)base};
+  RProjWs w = {};
+  if (which == SRH_RPROJ_WS_FWD) {
+    w.d_in = r.take<double>(px);
+  } else {
+    w.rec = r.take<double>(px * 4);
+    w.gpl = r.take<double>(px * (R.D + 1));
+    w.range = r.take<int32_t>((size_t)R.B * R.ncell * 2);
+  }
+  w.bytes = r.bytes;
+  return w;
 }
+size_t rproj_ws_bytes(const RProjDev& R, int which) { return rproj_ws(R, which).bytes; }
 
 }  // namespace
 
@@ -1641,7 +1685,7 @@ int srh_reverse_projection_fwd(const SrhReverseProjectionParams* params, const d
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_FWD)))) return rc;
   const dim3 grid(R.nblk, R.B), block(kProjBlock);
   hipStream_t st = (hipStream_t)stream;
-  double* d_in = (double*)workspace;
+  double* d_in = rproj_ws(R, SRH_RPROJ_WS_FWD, workspace).d_in;
   hipLaunchKernelGGL(k_rproj_depth_in, grid, block, 0, st, R, view1, view2, in_pos, out_pos, d_in);
   hipLaunchKernelGGL(k_rproj_fwd, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, rotated, keep,
                      (const double*)d_in, out, mask, image1, depth);
@@ -1656,7 +1700,7 @@ int srh_reverse_projection_keys(const SrhReverseProjectionParams* params, const 
   if ((rc = check_not_null({{"view1", view1}, {"out_pos", out_pos}, {"keys", keys}}))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_BWD)))) return rc;
   hipLaunchKernelGGL(k_proj_keys, dim3(R.nblk, R.B), dim3(kProjBlock), 0, (hipStream_t)stream, rproj_as_proj(R), view1,
-                     out_pos, (double*)workspace, keys);
+                     out_pos, rproj_ws(R, SRH_RPROJ_WS_BWD, workspace).rec, keys);
   return launch_status("reverse projection k_proj_keys launch");
 }
 
@@ -1680,21 +1724,18 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
     if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_BWD)))) return rc;
   }
   hipStream_t st = (hipStream_t)stream;
-  const size_t px = (size_t)R.B * R.N;
-  double* rec = (double*)workspace;
-  double* gpl = walk ? rec + px * 4 : nullptr;
-  int32_t* range = walk ? (int32_t*)(gpl + px * (R.D + 1)) : nullptr;
+  const RProjWs w = rproj_ws(R, SRH_RPROJ_WS_BWD, walk ? workspace : nullptr);   // without the walk, no region is used
   const dim3 grid(R.nblk, R.B), block(kProjBlock);
   if (walk) {
-    if (hipError_t e = hipMemsetAsync(range, 0, (size_t)R.B * R.ncell * 2 * sizeof(int32_t), st))
+    if (hipError_t e = hipMemsetAsync(w.range, 0, (size_t)R.B * R.ncell * 2 * sizeof(int32_t), st))
       return hip_fail(e, "reverse projection cell ranges memset");
-    hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, rproj_as_proj(R), keys, order, range);
+    hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, rproj_as_proj(R), keys, order, w.range);
   }
   hipLaunchKernelGGL(k_rproj_pixel_bwd, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, mask, g_out, g_image1,
-                     g_depth, gpl, grad_out_pos, grad_rotated);
+                     g_depth, w.gpl, grad_out_pos, grad_rotated);
   if (walk)
-    hipLaunchKernelGGL(k_rproj_texel_bwd, grid, block, 0, st, R, view2, (const double*)rec, order, (const int32_t*)range,
-                       (const double*)gpl, grad_rgb, grad_in_pos);
+    hipLaunchKernelGGL(k_rproj_texel_bwd, grid, block, 0, st, R, view2, (const double*)w.rec, order,
+                       (const int32_t*)w.range, (const double*)w.gpl, grad_rgb, grad_in_pos);
   return launch_status("reverse projection backward launch");
 }
 
@@ -1706,9 +1747,7 @@ namespace {
 // argument checks (no HIP call) and the device view of a dense projection launch
 int dproj_setup(const SrhDenseProjectionParams* p, DProjDev* P) {
   if (!p) return fail(SRH_E_NULL, "params is NULL");
-  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
-  if (p->channels < 1 || p->channels > kProjMaxD)
-    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kProjMaxD);
+  if (int rc = check_proj_frame(p->n_views, p->width, p->height, p->channels)) return rc;
   if (p->has_rotated != 0 && p->has_rotated != 1)
     return fail(SRH_E_TYPE, "has_rotated = %d, expected 0 or 1", p->has_rotated);
   if (!(p->sigma > 0.0 && std::isfinite(p->sigma)))
@@ -1733,15 +1772,24 @@ int dproj_check_rotated(const DProjDev& P, const float* rotated) {
 }
 
 // SRH_DPROJ_WS_FWD: uv (B, N, 2) fp64
-// SRH_DPROJ_WS_SAVED: S, m (B, D + 1, N) fp64
+// SRH_DPROJ_WS_SAVED: sm = S, m (B, D + 1, N) fp64
 // SRH_DPROJ_WS_BWD: gt (B, H, Wp, D + 1) fp64
-size_t dproj_ws_bytes(const DProjDev& P, int which) {
+struct DProjWs {
+  double *uv, *sm, *gt;
+  size_t bytes;
+};
+DProjWs dproj_ws(const DProjDev& P, int which, const void* base = nullptr) {
+  Regions r{(char*)base};
+  DProjWs w = {};
   switch (which) {
-    case SRH_DPROJ_WS_FWD: return (size_t)P.B * P.N * 2 * sizeof(double);
-    case SRH_DPROJ_WS_SAVED: return (size_t)P.B * P.N * (P.D + 1) * sizeof(double);
-    default: return (size_t)P.B * P.H * P.Wp * (P.D + 1) * sizeof(double);
+    case SRH_DPROJ_WS_FWD: w.uv = r.take<double>((size_t)P.B * P.N * 2); break;
+    case SRH_DPROJ_WS_SAVED: w.sm = r.take<double>((size_t)P.B * P.N * (P.D + 1)); break;
+    default: w.gt = r.take<double>((size_t)P.B * P.H * P.Wp * (P.D + 1));
   }
+  w.bytes = r.bytes;
+  return w;
 }
+size_t dproj_ws_bytes(const DProjDev& P, int which) { return dproj_ws(P, which).bytes; }
 
 // f(std::integral_constant<int, D>) for the channel count D (validated by dproj_setup)
 template <class Fn>
@@ -1778,13 +1826,13 @@ int srh_dense_projection_fwd(const SrhDenseProjectionParams* params, const doubl
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_FWD)))) return rc;
   if (saved && (rc = check_scratch("saved", saved, saved_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_SAVED)))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  double* uv = (double*)workspace;
+  double* uv = dproj_ws(P, SRH_DPROJ_WS_FWD, workspace).uv;
   hipLaunchKernelGGL(k_dproj_uv, dim3((P.N + kDProjBlock - 1) / kDProjBlock, P.B), dim3(kDProjBlock), 0, st, P, view,
                      surfels, uv);
   const int tiles = ((P.W + kDProjTile - 1) / kDProjTile) * ((P.H + kDProjTile - 1) / kDProjTile);
   with_channels(P.D, [&](auto d) {
     hipLaunchKernelGGL(k_dproj_fwd<decltype(d)::value>, dim3(tiles, P.B), dim3(kDProjFwdBlock), 0, st, P,
-                       (const double*)uv, rgb, rotated, (double*)saved, out, mask);
+                       (const double*)uv, rgb, rotated, dproj_ws(P, SRH_DPROJ_WS_SAVED, saved).sm, out, mask);
   });
   return launch_status("dense projection forward launch");
 }
@@ -1804,9 +1852,10 @@ int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const doubl
   if ((rc = check_scratch("saved", saved, saved_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_SAVED)))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_BWD)))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  double* gt = (double*)workspace;
+  const double* sm = dproj_ws(P, SRH_DPROJ_WS_SAVED, saved).sm;
+  double* gt = dproj_ws(P, SRH_DPROJ_WS_BWD, workspace).gt;
   hipLaunchKernelGGL(k_dproj_pixel_bwd, dim3((P.H * P.Wp + kDProjBlock - 1) / kDProjBlock, P.B), dim3(kDProjBlock), 0, st,
-                     P, (const double*)saved, rotated, g_out, g_mask, gt, grad_rotated);
+                     P, sm, rotated, g_out, g_mask, gt, grad_rotated);
   if (grad_surfels || grad_rgb) {
     const dim3 grid((P.N + kDProjBwdBlock - 1) / kDProjBwdBlock, P.B), block(kDProjBwdBlock);
     with_channels(P.D, [&](auto d) {

@@ -26,14 +26,14 @@ Two things follow the reference to the letter, and one cannot:
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Mapping, Tuple
 
 import torch
 
-from . import _layer, _lib
-from ._camera import camera_frame, camera_views
-from ._layer import fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from . import _lib
+from ._camera import camera_views
+from ._layer import fill_grads, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._projection import flat, shaped_like, upload_view, validate_surfels
 
 _NAME = "projection_renderer_differentiable"
 
@@ -83,29 +83,9 @@ class _DenseProjFunction(torch.autograd.Function):
 def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
     """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError).  Returns the
     tensors, (B, H, W, D), sigma, and the camera's fovy, focal length and per-view matrices [B, 3, 4] float64."""
-    surfels = _layer.as_float_tensor("surfels", surfels, _NAME)
-    rgb = _layer.as_float_tensor("rgb", rgb, _NAME)
-    W, H = camera_frame(_NAME, camera)
-    if surfels.dim() != 3 or surfels.shape[-1] != 3:
-        raise ValueError(f"{_NAME}: surfels is {list(surfels.shape)}, expected [B, N, 3]")
-    B, N = surfels.shape[:2]
-    if B < 1:
-        raise ValueError(f"{_NAME}: an empty batch")
-    if N != W * H:
-        raise ValueError(f"{_NAME}: {N} surfels per view, expected W x H = {W} x {H} = {W * H} (one per pixel of the "
-                         "frame: the result is shaped like rgb)")
-    D = rgb.shape[-1] if rgb.dim() else 0
-    if tuple(rgb.shape) not in ((B, N, D), (B, H, W, D)):
-        raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}, expected [{B}, {N}, D] or [{B}, {H}, {W}, D]")
-    if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
-        raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
-    if rotated_image is not None:
-        rotated_image = _layer.as_float_tensor("rotated_image", rotated_image, _NAME)
-        if tuple(rotated_image.shape) != tuple(rgb.shape):
-            raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
-    blur_size = float(blur_size)
-    if not (math.isfinite(blur_size) and blur_size > 0):
-        raise ValueError(f"{_NAME}: blur_size = {blur_size}, expected positive and finite")
+    surfels, rgb, rotated_image, (B, H, W, D), blur_size = validate_surfels(
+        _NAME, surfels, rgb, camera, rotated_image, blur_size,
+        "one per pixel of the frame: the result is shaped like rgb")
     sigma = blur_size * rgb.shape[-2] / 6          # the reference's rgb.size(-2): W for [B, H, W, D], N for [B, N, D]
     fovy, focal, view = camera_views(_NAME, camera, B)
     return surfels, rgb, rotated_image, (B, H, W, D), sigma, fovy, focal, view
@@ -124,9 +104,9 @@ def projection_renderer_differentiable(surfels, rgb, camera: Mapping, rotated_im
     surfels, rgb, rotated_image, (B, H, W, D), sigma, fovy, focal, view = _validate(
         surfels, rgb, camera, rotated_image, blur_size)
     dev = gpu_device(_NAME, (surfels, rgb, rotated_image))
-    x = [None if t is None else f32(t, dev).reshape(B, H * W, -1) for t in (surfels, rgb, rotated_image)]
+    x = flat((surfels, rgb, rotated_image), B, H * W, dev)
     params = _lib.SrhDenseProjectionParams(n_views=B, width=W, height=H, channels=D,
                                            has_rotated=int(rotated_image is not None), sigma=sigma, fovy=fovy,
                                            focal_length=focal)
-    out, mask = _DenseProjFunction.apply(params, view.reshape(B, 12).contiguous().to(dev), *x)
-    return out.reshape(rgb.shape), mask.reshape(*rgb.shape[:-1], 1)
+    out, mask = _DenseProjFunction.apply(params, upload_view(view, dev), *x)
+    return out.reshape(rgb.shape), shaped_like(rgb.shape, mask)["mask"]

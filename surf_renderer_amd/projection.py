@@ -22,8 +22,9 @@ import numpy as np
 import torch
 
 from . import _layer, _lib
-from ._camera import camera_frame, camera_views, view_matrices  # noqa: F401  (view_matrices stays importable from here)
-from ._layer import fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._camera import camera_views, view_matrices  # noqa: F401  (view_matrices stays importable from here)
+from ._layer import fill_grads, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._projection import flat, shaped_like, sorted_order, upload_view, validate_surfels
 
 _NAME = "projection_renderer_differentiable_fast"
 
@@ -44,8 +45,7 @@ class _ProjFunction(torch.autograd.Function):
         keys = torch.empty((B, N), dtype=torch.int32, device=dev)
         _lib.check(lib.srh_projection_keys(C.byref(params), view.data_ptr(), surfels.data_ptr(), ws.data_ptr(),
                                            ws.numel(), keys.data_ptr(), stream(dev)))
-        # the one step left to torch: a stable sort fixes the order inside every cell's list, and with it every sum
-        order = torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
+        order = sorted_order(keys)
         # without a backward to come the kernels keep nothing
         saved = None
         if any(ctx.needs_input_grad[3:]):
@@ -91,28 +91,9 @@ def blur_taps(blur_size: float, height: int) -> Tuple[int, np.ndarray]:
 def _validate(surfels, rgb, camera: Mapping, rotated_image, blur_size):
     """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError).  Returns the
     tensors, (B, H, W, D), the per-view matrices [B, 3, 4] float64 on the host, and the blur's half-width and taps."""
-    surfels, rgb = as_float_tensor("surfels", surfels), as_float_tensor("rgb", rgb)
-    W, H = camera_frame(_NAME, camera)
-    if surfels.dim() != 3 or surfels.shape[-1] != 3:
-        raise ValueError(f"{_NAME}: surfels is {list(surfels.shape)}, expected [B, N, 3]")
-    B, N = surfels.shape[:2]
-    if B < 1:
-        raise ValueError(f"{_NAME}: an empty batch")
-    if N != W * H:
-        raise ValueError(f"{_NAME}: {N} surfels per view, expected W x H = {W} x {H} = {W * H} (one per pixel of the "
-                         "frame, as the reference's scatter needs)")
-    D = rgb.shape[-1] if rgb.dim() else 0
-    if tuple(rgb.shape) not in ((B, N, D), (B, H, W, D)):
-        raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}, expected [{B}, {N}, D] or [{B}, {H}, {W}, D]")
-    if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
-        raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
-    if rotated_image is not None:
-        rotated_image = as_float_tensor("rotated_image", rotated_image)
-        if tuple(rotated_image.shape) != tuple(rgb.shape):
-            raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
-    blur_size = float(blur_size)
-    if not (math.isfinite(blur_size) and blur_size > 0):
-        raise ValueError(f"{_NAME}: blur_size = {blur_size}, expected positive and finite")
+    surfels, rgb, rotated_image, (B, H, W, D), blur_size = validate_surfels(
+        _NAME, surfels, rgb, camera, rotated_image, blur_size,
+        "one per pixel of the frame, as the reference's scatter needs")
     if math.floor(blur_size * H / 6 * 3) > _lib.PROJ_MAX_BLUR_HALF:
         raise ValueError(f"{_NAME}: blur_size = {blur_size} at H = {H} gives a blur half-width of "
                          f"{math.floor(blur_size * H / 6 * 3)}, at most {_lib.PROJ_MAX_BLUR_HALF}")
@@ -133,16 +114,12 @@ def projection_renderer_differentiable_fast(surfels, rgb, camera: Mapping, rotat
     surfels, rgb, rotated_image, (B, H, W, D), view, half, taps, fovy, focal = _validate(
         surfels, rgb, camera, rotated_image, blur_size)
     dev = gpu_device(_NAME, (surfels, rgb, rotated_image))
-    x = [None if t is None else f32(t, dev).reshape(B, H * W, -1) for t in (surfels, rgb, rotated_image)]
+    x = flat((surfels, rgb, rotated_image), B, H * W, dev)
     flags = (_lib.PROJ_USE_DEPTH * bool(use_depth) | _lib.PROJ_USE_CENTER_DIST * bool(use_center_dist)
              | _lib.PROJ_BLUR_ROTATED * bool(blur_rotated_image) | _lib.PROJ_DETACH_MASK * bool(detach_mask)
              | _lib.PROJ_DETACH_MASK2 * bool(detach_mask2) | _lib.PROJ_DETACH_DEPTH_MERGE * bool(detach_depth_merge))
     params = _lib.SrhProjectionParams(n_views=B, width=W, height=H, channels=D, flags=flags, blur_half=half, fovy=fovy,
                                       focal_length=focal)
     params.taps[:half + 1] = taps.tolist()
-    out, mask, image1, depth = _ProjFunction.apply(params, view.reshape(B, 12).contiguous().to(dev),
-                                                   bool(compute_new_depth), *x)
-    proj_out = {"mask": mask.reshape(*rgb.shape[:-1], 1), "image1": image1.reshape(rgb.shape)}
-    if compute_new_depth:
-        proj_out["depth"] = depth.reshape(*rgb.shape[:-1], 1)
-    return out.reshape(rgb.shape), proj_out
+    out, mask, image1, depth = _ProjFunction.apply(params, upload_view(view, dev), bool(compute_new_depth), *x)
+    return out.reshape(rgb.shape), shaped_like(rgb.shape, mask, image1, depth)

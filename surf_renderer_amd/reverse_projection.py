@@ -22,7 +22,8 @@ import torch
 
 from . import _lib
 from ._camera import camera_frame, camera_views
-from ._layer import as_float_tensor, fill_grads, f32, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._layer import as_float_tensor, fill_grads, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._projection import check_channels, flat, rotated_like, shaped_like, sorted_order, upload_view
 
 _NAME = "projection_reverse_renderer"
 
@@ -69,8 +70,7 @@ class _ReverseFunction(torch.autograd.Function):
                 keys = torch.empty(mask.shape, dtype=torch.int32, device=rgb.device)
                 _lib.check(lib.srh_reverse_projection_keys(C.byref(ctx.params), view1.data_ptr(), out_pos.data_ptr(),
                                                            ws.data_ptr(), ws.numel(), keys.data_ptr(), st))
-                # the one step left to torch: a stable sort fixes the order inside every cell's list
-                order = torch.sort(keys, dim=1, stable=True).indices.to(torch.int32)
+                order = sorted_order(keys)
             _lib.check(lib.srh_reverse_projection_bwd(
                 C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
                 out_pos.data_ptr(), mask.data_ptr(), ptr(keys), ptr(order), ptr(ws), 0 if ws is None else ws.numel(),
@@ -90,15 +90,11 @@ def _validate(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, ro
     B, H, W, D = rgb.shape
     if B < 1 or H < 1 or W < 1:
         raise ValueError(f"{_NAME}: rgb is {list(rgb.shape)}: an empty batch or frame")
-    if not 1 <= D <= _lib.PROJ_MAX_CHANNELS:
-        raise ValueError(f"{_NAME}: rgb has {D} channels, expected 1..{_lib.PROJ_MAX_CHANNELS}")
+    check_channels(_NAME, rgb)
     for k, t in pos.items():
         if tuple(t.shape) != (B, H * W, 3):
             raise ValueError(f"{_NAME}: {k} is {list(t.shape)}, expected [{B}, H W = {H * W}, 3]")
-    if rotated_image is not None:
-        rotated_image = as_float_tensor("rotated_image", rotated_image, _NAME)
-        if tuple(rotated_image.shape) != tuple(rgb.shape):
-            raise ValueError(f"{_NAME}: rotated_image is {list(rotated_image.shape)}, rgb is {list(rgb.shape)}")
+    rotated_image = rotated_like(_NAME, rotated_image, rgb)
     cams = []
     for label, camera in (("camera1", camera1), ("camera2", camera2)):
         if camera_frame(_NAME, camera, label) != (W, H):
@@ -125,7 +121,7 @@ def projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, ca
         rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image, depth_epsilon, mask_dropout)
     dev = gpu_device(_NAME, (rgb, in_pos, out_pos, rotated_image))
     B, H, W, D = rgb.shape
-    x = [None if t is None else f32(t, dev).reshape(B, H * W, -1) for t in (rgb, in_pos, out_pos, rotated_image)]
+    x = flat((rgb, in_pos, out_pos, rotated_image), B, H * W, dev)
     (fovy1, focal1, view1), (fovy2, focal2, view2) = cams
     params = _lib.SrhReverseProjectionParams(n_views=B, width=W, height=H, channels=D, fovy1=fovy1, focal_length1=focal1,
                                              fovy2=fovy2, focal_length2=focal2, depth_epsilon=depth_epsilon)
@@ -133,11 +129,7 @@ def projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, ca
     if mask_dropout > 0:
         keep = torch.nn.functional.dropout(torch.ones((B, H * W), dtype=torch.float32, device=dev), mask_dropout,
                                            training=True)
-    out, mask, image1, depth = _ReverseFunction.apply(
-        params, view1.reshape(B, 12).contiguous().to(dev), view2.reshape(B, 12).contiguous().to(dev), keep,
-        bool(compute_new_depth), *x)
-    image1 = image1.reshape(B, H, W, D)
-    proj_out = {"mask": mask.reshape(B, H, W, 1), "image1": image1}
-    if compute_new_depth:
-        proj_out["depth"] = depth.reshape(B, H, W, 1)
-    return (image1 if out is None else out.reshape(B, H, W, D)), proj_out
+    out, mask, image1, depth = _ReverseFunction.apply(params, upload_view(view1, dev), upload_view(view2, dev), keep,
+                                                      bool(compute_new_depth), *x)
+    proj_out = shaped_like(rgb.shape, mask, image1, depth)
+    return (proj_out["image1"] if out is None else out.reshape(rgb.shape)), proj_out

@@ -23,7 +23,7 @@ import functools
 import numpy as np
 
 import dense_projection_oracle as do
-from projection_cases import FOCAL, FOVY, lift
+from projection_cases import FOCAL, FOVY, draw_camera, f32, jittered_grid, lift
 
 FRAMES = ("2x2", "3x5", "12x16", "17x9", "36x48", "35x37")
 _SPEC = {  # B, H, W, D, sigma of the grid layout (pixels), jitter (pixels)
@@ -41,28 +41,20 @@ ALL = [(f, layout, rotated) for f in FRAMES for layout in LAYOUTS for rotated in
 RECORDED = [(f, "grid") for f in FRAMES] + [(f, "flat") for f in FRAMES[:4]]
 
 
-def _f32(a):
-    return np.asarray(a, dtype=np.float32)
-
-
 def _draw(frame, seed):
     B, H, W, D, sigma, jitter = _SPEC[frame]
     rng = np.random.RandomState(seed)
     N = H * W
-    eye = _f32(rng.uniform(-0.5, 0.5, (B, 3)) + [0.0, 0.5, 4.0])
-    at = _f32(rng.uniform(-0.3, 0.3, (B, 3)))
-    up = _f32(rng.uniform(-0.2, 0.2, (B, 3)) + [0.0, 1.0, 0.0])
-    gy, gx = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
-    px = np.broadcast_to(gx.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
-    py = np.broadcast_to(gy.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
+    eye, at, up = draw_camera(rng, B)
+    px, py = jittered_grid(rng, B, H, W, jitter)
     z = rng.uniform(1.5, 3.0, (B, N))
     if frame == "17x9":
         z[:, rng.permutation(N)[:4]] = -rng.uniform(0.5, 1.5, (B, 4))          # behind the camera
-    return {"surfels": _f32(lift(px, py, z, eye, at, up, W, H)), "rgb": _f32(rng.uniform(0, 1, (B, H, W, D))),
-            "rotated_image": _f32(rng.uniform(0, 1, (B, H, W, D))),
+    return {"surfels": f32(lift(px, py, z, eye, at, up, W, H)), "rgb": f32(rng.uniform(0, 1, (B, H, W, D))),
+            "rotated_image": f32(rng.uniform(0, 1, (B, H, W, D))),
             "camera": {"eye": eye, "at": at, "up": up, "viewport": [0, 0, W, H], "fovy": float(FOVY), "focal_length": FOCAL},
             "blur_size": float(np.float32(6 * sigma / W)), "shape": (B, H, W, D),
-            "upstream": {"out": _f32(rng.uniform(-1, 1, (B, H, W, D))), "mask": _f32(rng.uniform(-1, 1, (B, H, W, 1)))}}
+            "upstream": {"out": f32(rng.uniform(-1, 1, (B, H, W, D))), "mask": f32(rng.uniform(-1, 1, (B, H, W, 1)))}}
 
 
 @functools.lru_cache(maxsize=None)

@@ -10,12 +10,12 @@ the CPU test that the two agree.  The projection is tests/projection_oracle.py's
 
 With a rotated image the reference's own line raises (it multiplies [B, N, D] by [B, N]); the restatement broadcasts
 the mask over the channels, out = S + rotated (1 - mask)[..., None], as surf_renderer_amd/dense_projection.py does."""
-from typing import Dict, Mapping, Optional
+from typing import Dict, Mapping
 
 import numpy as np
 import torch
 
-from projection_oracle import frame, pixel_coordinates
+from projection_oracle import autograd, frame, pixel_coordinates
 
 OUTPUTS = ("out", "mask")
 INPUTS = ("surfels", "rgb", "rotated_image")
@@ -84,17 +84,7 @@ def z_margin(surfels, camera: Mapping) -> float:
     return float(px[..., 2].abs().min())
 
 
-def gradients(inputs: Mapping[str, Optional[np.ndarray]], camera: Mapping, upstream: Mapping[str, np.ndarray],
-              blur_size=0.15, wrt=INPUTS, fn=project, **kw):
-    """({output: value}, {input: d loss / d input}) in fp64 for loss = sum over the outputs present in `upstream` of
-    sum(output * upstream[output]); arrays keep the inputs' shapes."""
-    leaves = {k: torch.tensor(np.asarray(inputs[k], dtype=np.float64), requires_grad=k in wrt)
-              for k in INPUTS if inputs.get(k) is not None}
-    res = fn(leaves["surfels"], leaves["rgb"], camera, leaves.get("rotated_image"), blur_size, **kw)
-    loss = sum(torch.sum(res[k] * torch.as_tensor(np.asarray(upstream[k], dtype=np.float64)).reshape(res[k].shape))
-               for k in res if k in upstream)
-    if any(t.requires_grad for t in leaves.values()):
-        loss.backward()
-    return ({k: v.detach().numpy() for k, v in res.items()},
-            {k: (leaves[k].grad.numpy() if leaves[k].grad is not None else np.zeros(leaves[k].shape))
-             for k in wrt if k in leaves})
+def gradients(inputs, camera: Mapping, upstream, blur_size=0.15, wrt=INPUTS, fn=project, **kw):
+    """projection_oracle.autograd() of `fn`."""
+    return autograd(lambda x: fn(x["surfels"], x["rgb"], camera, x.get("rotated_image"), blur_size, **kw),
+                    inputs, INPUTS, upstream, wrt)

@@ -44,37 +44,56 @@ VARIANT_OF = "12x16"
 FOVY, FOCAL = np.deg2rad(40.0), 0.5
 
 
-def _f32(a):
+def f32(a):
     return np.asarray(a, dtype=np.float32)
 
 
-def lift(px, py, z, eye, at, up, W, H):
-    """World positions [B, N, 3] (fp64) of the points that the cameras (eye, at, up: [B, 3]) see at pixel coordinates
-    (px, py) and depth z, each [B, N]."""
-    h = np.tan(FOVY / 2) * 2 * FOCAL
+def draw_camera(rng, B, side=0.0, spread=0.5):
+    """eye, at, up [B, 3] fp32 of B cameras above the origin, `side` to its right."""
+    eye = f32(rng.uniform(-spread, spread, (B, 3)) + [side, 0.5, 4.0])
+    at = f32(rng.uniform(-0.3, 0.3, (B, 3)) + [0.25 * side, 0.0, 0.0])
+    up = f32(rng.uniform(-0.2, 0.2, (B, 3)) + [0.0, 1.0, 0.0])
+    return eye, at, up
+
+
+def pixel_centres(B, H, W):
+    """(px, py) [B, H W]: the pixel coordinates of the frame's pixel centres, row by row."""
+    gy, gx = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
+    return np.broadcast_to(gx.reshape(1, H * W), (B, H * W)), np.broadcast_to(gy.reshape(1, H * W), (B, H * W))
+
+
+def jittered_grid(rng, B, H, W, jitter):
+    """(px, py) [B, H W]: a pixel coordinate within `jitter` pixels of each pixel's centre (px is drawn first)."""
+    cx, cy = pixel_centres(B, H, W)
+    return cx + rng.uniform(-jitter, jitter, (B, H * W)), cy + rng.uniform(-jitter, jitter, (B, H * W))
+
+
+def rays(px, py, eye, at, up, W, H, fovy, focal):
+    """Per pixel coordinate (px, py) [B, N] the direction r [B, N, 3] with world point = eye - depth * r.  Along an axis
+    of one pixel the coordinate carries nothing: the ray goes through the centre."""
+    h = np.tan(fovy / 2) * 2 * focal
     w = h * W / H
-    Z = -z
-    X = (px - W / 2.0) / (-(W - 1) / w) * Z / FOCAL
-    Y = (py - H / 2.0) / ((H - 1) / h) * Z / FOCAL
+    a = (px - W / 2.0) / (-(W - 1) / w) / focal if W > 1 else np.zeros_like(px)
+    b = (py - H / 2.0) / ((H - 1) / h) / focal if H > 1 else np.zeros_like(py)
     zc = eye.astype(np.float64) - at
     zc /= np.linalg.norm(zc, axis=-1, keepdims=True)
     xc = np.cross(up.astype(np.float64), zc)
     xc /= np.linalg.norm(xc, axis=-1, keepdims=True)
-    yc = np.cross(zc, xc)
-    return X[..., None] * xc[:, None] + Y[..., None] * yc[:, None] + Z[..., None] * zc[:, None] + eye[:, None]
+    return a[..., None] * xc[:, None] + b[..., None] * np.cross(zc, xc)[:, None] + zc[:, None]
+
+
+def lift(px, py, z, eye, at, up, W, H, fovy=FOVY, focal=FOCAL):
+    """World positions [B, N, 3] (fp64) of the points that the cameras (eye, at, up: [B, 3]) see at pixel coordinates
+    (px, py) and depth z, each [B, N]."""
+    return eye[:, None].astype(np.float64) - z[..., None] * rays(px, py, eye, at, up, W, H, fovy, focal)
 
 
 def _draw(name, seed):
     B, H, W, D, blur_size, rotated, flat, jitter = _SPEC[name]
     rng = np.random.RandomState(seed)
     N = H * W
-    eye = _f32(rng.uniform(-0.5, 0.5, (B, 3)) + [0.0, 0.5, 4.0])
-    at = _f32(rng.uniform(-0.3, 0.3, (B, 3)))
-    up = _f32(rng.uniform(-0.2, 0.2, (B, 3)) + [0.0, 1.0, 0.0])
-    # the pixel coordinate and the depth each surfel is aimed at
-    gy, gx = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
-    px = np.broadcast_to(gx.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
-    py = np.broadcast_to(gy.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
+    eye, at, up = draw_camera(rng, B)
+    px, py = jittered_grid(rng, B, H, W, jitter)           # the pixel coordinate and the depth each surfel is aimed at
     z = rng.uniform(1.5, 3.0, (B, N))
     if name == "cluster_8x8":
         px, py = 3.5 + rng.uniform(0.15, 0.85, (B, N)), 3.5 + rng.uniform(0.15, 0.85, (B, N))     # cell (3, 3)
@@ -87,14 +106,14 @@ def _draw(name, seed):
     world = lift(px, py, z, eye, at, up, W, H)
     shape = (B, N, D) if flat else (B, H, W, D)
     hom = name == "17x9"
-    case = {"surfels": _f32(world), "rgb": _f32(rng.uniform(0, 1, shape)),
-            "rotated_image": _f32(rng.uniform(0, 1, shape)) if rotated else None,
+    case = {"surfels": f32(world), "rgb": f32(rng.uniform(0, 1, shape)),
+            "rotated_image": f32(rng.uniform(0, 1, shape)) if rotated else None,
             "camera": {"eye": np.concatenate((eye, np.ones((B, 1), np.float32)), -1) if hom else eye,
                        "at": np.concatenate((at, np.ones((B, 1), np.float32)), -1) if hom else at,
                        "up": np.concatenate((up, np.zeros((B, 1), np.float32)), -1) if hom else up,
                        "viewport": [0, 0, W, H], "fovy": float(FOVY), "focal_length": FOCAL},
             "blur_size": blur_size, "flags": dict(_FLAGS.get(name, {})), "shape": (B, H, W, D)}
-    case["upstream"] = {k: _f32(rng.uniform(-1, 1, (B, H, W, D if k in ("out", "image1") else 1))) for k in po.OUTPUTS
+    case["upstream"] = {k: f32(rng.uniform(-1, 1, (B, H, W, D if k in ("out", "image1") else 1))) for k in po.OUTPUTS
                         if k != "depth" or case["flags"].get("compute_new_depth")}
     return case
 

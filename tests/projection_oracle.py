@@ -157,16 +157,23 @@ def decision_margin(surfels, rgb, camera: Mapping, rotated_image=None, blur_size
     return min(worst)
 
 
-def gradients(inputs: Mapping[str, Optional[np.ndarray]], camera: Mapping, upstream: Mapping[str, np.ndarray],
-              blur_size=0.15, wrt=INPUTS, **flags):
+def autograd(fn, inputs: Mapping[str, Optional[np.ndarray]], names, upstream: Mapping[str, np.ndarray], wrt):
     """({output: value}, {input: d loss / d input}) in fp64 for loss = sum over the outputs present in `upstream` of
-    sum(output * upstream[output]); arrays keep the inputs' shapes ([B, H, W, .] for the outputs)."""
+    sum(output * upstream[output]), with fn(leaves) -> {output: tensor} and leaves the inputs among `names` that are
+    there; arrays keep the inputs' shapes.  An input the loss does not depend on gets zeros."""
     leaves = {k: torch.tensor(np.asarray(inputs[k], dtype=np.float64), requires_grad=k in wrt)
-              for k in INPUTS if inputs.get(k) is not None}
-    res = project(leaves["surfels"], leaves["rgb"], camera, leaves.get("rotated_image"), blur_size, **flags)
+              for k in names if inputs.get(k) is not None}
+    res = fn(leaves)
     loss = sum(torch.sum(res[k] * torch.as_tensor(np.asarray(upstream[k], dtype=np.float64)).reshape(res[k].shape))
                for k in res if k in upstream)
-    loss.backward()
+    if loss.requires_grad:
+        loss.backward()
     return ({k: v.detach().numpy() for k, v in res.items()},
             {k: (leaves[k].grad.numpy() if leaves[k].grad is not None else np.zeros(leaves[k].shape))
              for k in wrt if k in leaves})
+
+
+def gradients(inputs, camera: Mapping, upstream, blur_size=0.15, wrt=INPUTS, **flags):
+    """autograd() of project(): outputs as [B, H, W, .]."""
+    return autograd(lambda x: project(x["surfels"], x["rgb"], camera, x.get("rotated_image"), blur_size, **flags),
+                    inputs, INPUTS, upstream, wrt)

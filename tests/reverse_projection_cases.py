@@ -36,6 +36,8 @@ import functools
 import numpy as np
 
 import reverse_projection_oracle as ro
+from projection_cases import draw_camera, f32, jittered_grid, lift, pixel_centres, rays
+from projection_checks import one_view
 
 NAMES = ("1x1", "2x2", "3x5", "12x16", "17x9", "cluster_8x8", "36x48")
 _SPEC = {  # B, H, W, D, rotated, compute_new_depth, jitter (pixels)
@@ -55,34 +57,6 @@ VARIANT_OF = "12x16"
 CAMERAS = ((np.deg2rad(40.0), 0.5), (np.deg2rad(50.0), 0.8))        # (fovy, focal_length) of camera1, camera2
 
 
-def _f32(a):
-    return np.asarray(a, dtype=np.float32)
-
-
-def _axes(eye, at, up):
-    zc = eye.astype(np.float64) - at
-    zc /= np.linalg.norm(zc, axis=-1, keepdims=True)
-    xc = np.cross(up.astype(np.float64), zc)
-    xc /= np.linalg.norm(xc, axis=-1, keepdims=True)
-    return xc, np.cross(zc, xc), zc
-
-
-def _rays(px, py, eye, at, up, W, H, fovy, focal):
-    """Per pixel coordinate (px, py) [B, N] the direction r [B, N, 3] with world point = eye - depth * r."""
-    h = np.tan(fovy / 2) * 2 * focal
-    w = h * W / H
-    a = (px - W / 2.0) / (-(W - 1) / w) / focal if W > 1 else np.zeros_like(px)
-    b = (py - H / 2.0) / ((H - 1) / h) / focal if H > 1 else np.zeros_like(py)
-    xc, yc, zc = _axes(eye, at, up)
-    return a[..., None] * xc[:, None] + b[..., None] * yc[:, None] + zc[:, None]
-
-
-def lift(px, py, z, eye, at, up, W, H, fovy, focal):
-    """World positions [B, N, 3] (fp64) of the points that the cameras (eye, at, up: [B, 3]) see at pixel coordinates
-    (px, py) and depth z, each [B, N]."""
-    return eye[:, None].astype(np.float64) - z[..., None] * _rays(px, py, eye, at, up, W, H, fovy, focal)
-
-
 # the two-layer surface: the plane z = 0, and z = RAISED over |x|, |y| < SQUARE; on both a relief of amplitude RELIEF,
 # well under the default depth_epsilon and a few pixels long, so that no pixel's depth agrees with its twice-resampled
 # depth to 1e-4 (on a plane the two differ by the interpolation error alone, which passes through 0)
@@ -91,10 +65,7 @@ SQUARE, RAISED, RELIEF = 0.7, 1.0, 0.04
 
 def seen(eye, at, up, W, H, fovy, focal):
     """What each pixel centre of the cameras sees of the two-layer surface: world positions [B, H W, 3]."""
-    B = eye.shape[0]
-    gy, gx = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
-    r = _rays(np.broadcast_to(gx.reshape(1, -1), (B, H * W)), np.broadcast_to(gy.reshape(1, -1), (B, H * W)), eye, at,
-              up, W, H, fovy, focal)
+    r = rays(*pixel_centres(eye.shape[0], H, W), eye, at, up, W, H, fovy, focal)
     e = eye[:, None].astype(np.float64)
     top = e - ((e[..., 2:] - RAISED) / r[..., 2:]) * r
     ground = e - (e[..., 2:] / r[..., 2:]) * r
@@ -102,13 +73,6 @@ def seen(eye, at, up, W, H, fovy, focal):
     p = np.where(hit, top, ground)
     p[..., 2] += RELIEF * np.sin(9.0 * p[..., 0] + 1.0) * np.sin(9.0 * p[..., 1] + 2.0)
     return p
-
-
-def draw_camera(rng, B, side, spread=0.5):
-    eye = _f32(rng.uniform(-spread, spread, (B, 3)) + [side, 0.5, 4.0])
-    at = _f32(rng.uniform(-0.3, 0.3, (B, 3)) + [0.25 * side, 0.0, 0.0])
-    up = _f32(rng.uniform(-0.2, 0.2, (B, 3)) + [0.0, 1.0, 0.0])
-    return eye, at, up
 
 
 def _draw(name, seed):
@@ -121,10 +85,8 @@ def _draw(name, seed):
         pos = {"in_pos_wc": pos[0], "out_pos_wc": pos[1]}
     else:
         pos = {}
-        gy, gx = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
         for key, k in (("out_pos_wc", 0), ("in_pos_wc", 1)):             # out_pos is projected by camera1, in_pos by 2
-            px = np.broadcast_to(gx.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
-            py = np.broadcast_to(gy.reshape(1, N), (B, N)) + rng.uniform(-jitter, jitter, (B, N))
+            px, py = jittered_grid(rng, B, H, W, jitter)
             z = rng.uniform(1.5, 3.0, (B, N))
             if name == "cluster_8x8" and k == 0:
                 px, py = 3.5 + rng.uniform(0.15, 0.85, (B, N)), 3.5 + rng.uniform(0.15, 0.85, (B, N))   # cell (3, 3)
@@ -141,13 +103,13 @@ def _draw(name, seed):
                 "up": np.concatenate((up, zero), -1) if hom else up, "viewport": [0, 0, W, H],
                 "fovy": float(CAMERAS[k][0]), "focal_length": CAMERAS[k][1]}
 
-    case = {"rgb": _f32(rng.uniform(0, 1, (B, H, W, D))), "in_pos_wc": _f32(pos["in_pos_wc"]),
-            "out_pos_wc": _f32(pos["out_pos_wc"]),
-            "rotated_image": _f32(rng.uniform(0, 1, (B, H, W, D))) if rotated else None,
+    case = {"rgb": f32(rng.uniform(0, 1, (B, H, W, D))), "in_pos_wc": f32(pos["in_pos_wc"]),
+            "out_pos_wc": f32(pos["out_pos_wc"]),
+            "rotated_image": f32(rng.uniform(0, 1, (B, H, W, D))) if rotated else None,
             "camera1": camera(0), "camera2": camera(1),
             "flags": {"compute_new_depth": new_depth, "depth_epsilon": 0.1}, "shape": (B, H, W, D),
             "wrt": ro.INPUTS, "only": None}
-    case["upstream"] = {k: _f32(rng.uniform(-1, 1, (B, H, W, D if k in ("out", "image1") else 1))) for k in ro.OUTPUTS
+    case["upstream"] = {k: f32(rng.uniform(-1, 1, (B, H, W, D if k in ("out", "image1") else 1))) for k in ro.OUTPUTS
                         if k != "depth" or new_depth}
     return case
 
@@ -198,11 +160,7 @@ def inputs(c):
 
 def view(c, b):
     """View b of a case as a case of its own."""
-    one = dict(c, **{k: (c[k][b:b + 1] if c[k] is not None else None) for k in ro.INPUTS},
-               upstream={k: u[b:b + 1] for k, u in c["upstream"].items()}, shape=(1, *c["shape"][1:]))
-    for cam in ("camera1", "camera2"):
-        one[cam] = dict(c[cam], **{k: c[cam][k][b:b + 1] for k in ("eye", "at", "up")})
-    return one
+    return one_view(c, b, ro.INPUTS, ("camera1", "camera2"))
 
 
 ALL = [(n, None) for n in NAMES] + [(VARIANT_OF, v) for v in VARIANTS]

@@ -8,13 +8,13 @@ It keeps the reference's formulation -- four F.grid_sample calls on NCHW tensors
 zero padding, align_corners=False (the defaults of the torch the reference's results were recorded under, spelled out)
 -- and not the kernels' per-texel gather, so the two are independent statements of the same function.  `dtype` and
 `device` follow the inputs: tools/bench_reverse_projection.py times this composition in float32 on the GPU."""
-from typing import Dict, Mapping, Optional
+from typing import Dict, Mapping
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from projection_oracle import frame, pixel_coordinates
+from projection_oracle import autograd, frame, pixel_coordinates
 
 OUTPUTS = ("out", "mask", "image1", "depth")
 INPUTS = ("rgb", "in_pos_wc", "out_pos_wc", "rotated_image")
@@ -80,21 +80,10 @@ def decision_margin(in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, d
     return min(worst)
 
 
-def gradients(inputs: Mapping[str, Optional[np.ndarray]], camera1: Mapping, camera2: Mapping,
-              upstream: Mapping[str, np.ndarray], wrt=INPUTS, **flags):
-    """({output: value}, {input: d loss / d input}) in fp64 for loss = sum over the outputs present in `upstream` of
-    sum(output * upstream[output]); arrays keep the inputs' shapes ([B, H, W, .] for the outputs).  An input the loss
-    does not depend on gets zeros (the mask is a comparison: a loss on it alone depends on nothing)."""
-    leaves = {k: torch.tensor(np.asarray(inputs[k], dtype=np.float64), requires_grad=k in wrt)
-              for k in INPUTS if inputs.get(k) is not None}
+def gradients(inputs, camera1: Mapping, camera2: Mapping, upstream, wrt=INPUTS, **flags):
+    """projection_oracle.autograd() of project(): outputs as [B, H, W, .].  The mask is a comparison: a loss on it alone
+    depends on nothing."""
     if flags.get("keep") is not None:
         flags = dict(flags, keep=torch.as_tensor(np.asarray(flags["keep"], dtype=np.float64)))
-    res = project(leaves["rgb"], leaves["in_pos_wc"], leaves["out_pos_wc"], camera1, camera2,
-                  leaves.get("rotated_image"), **flags)
-    loss = sum(torch.sum(res[k] * torch.as_tensor(np.asarray(upstream[k], dtype=np.float64)).reshape(res[k].shape))
-               for k in res if k in upstream)
-    if loss.requires_grad:
-        loss.backward()
-    return ({k: v.detach().numpy() for k, v in res.items()},
-            {k: (leaves[k].grad.numpy() if leaves[k].grad is not None else np.zeros(leaves[k].shape))
-             for k in wrt if k in leaves})
+    return autograd(lambda x: project(x["rgb"], x["in_pos_wc"], x["out_pos_wc"], camera1, camera2,
+                                      x.get("rotated_image"), **flags), inputs, INPUTS, upstream, wrt)

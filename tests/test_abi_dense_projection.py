@@ -6,10 +6,10 @@ import re
 
 import pytest
 
+from projection_abi import (BIG, FRAME_ROWS, NULL, PINHOLE_ROWS, RANGE, TYPE, WORKSPACE, assert_refused_by_name, call, pointers,
+                            valid_params)
 from surf_renderer_amd import _lib, build
 
-NULL, RANGE, TYPE, WORKSPACE, CAMERA = -1, -2, -3, -4, -5        # SRH_E_*
-BIG = 1 << 40
 NAMES = ("srh_dense_projection_workspace_bytes", "srh_dense_projection_fwd", "srh_dense_projection_bwd")
 
 
@@ -20,30 +20,21 @@ def lib():
 
 
 def _valid(**fields):
-    buf = (C.c_double * 64)()
-    p = _lib.SrhDenseProjectionParams(n_views=2, width=16, height=12, channels=3, has_rotated=1, sigma=1.2, fovy=0.7,
-                                      focal_length=0.5)
-    for k, v in fields.items():
-        setattr(p, k, v)
-    return p, C.addressof(buf), buf
+    return valid_params(_lib.SrhDenseProjectionParams, **dict(dict(n_views=2, width=16, height=12, channels=3, has_rotated=1,
+                                                                   sigma=1.2, fovy=0.7, focal_length=0.5), **fields))
 
 
-FWD = ("view", "surfels", "rgb", "rotated", "workspace", "saved", "out", "mask")
-BWD = ("view", "surfels", "rgb", "rotated", "saved", "workspace", "g_out", "g_mask", "grad_surfels", "grad_rgb",
-       "grad_rotated")
+FWD = ("view", "surfels", "rgb", "rotated", "workspace", "ws_bytes", "saved", "saved_bytes", "out", "mask")
+BWD = ("view", "surfels", "rgb", "rotated", "saved", "saved_bytes", "workspace", "ws_bytes", "g_out", "g_mask",
+       "grad_surfels", "grad_rgb", "grad_rotated")
 
 
-def _fwd(lib, p, a, ws_bytes=BIG, saved_bytes=BIG, **null):
-    x = {k: (None if null.get(k) is None and k in null else null.get(k, a)) for k in FWD}
-    return lib.srh_dense_projection_fwd(C.byref(p), x["view"], x["surfels"], x["rgb"], x["rotated"], x["workspace"],
-                                        ws_bytes, x["saved"], saved_bytes, x["out"], x["mask"], None)
+def _fwd(lib, p, a, **given):
+    return call(lib.srh_dense_projection_fwd, FWD, p, a, **given)
 
 
-def _bwd(lib, p, a, ws_bytes=BIG, saved_bytes=BIG, **null):
-    x = {k: (None if null.get(k) is None and k in null else null.get(k, a)) for k in BWD}
-    return lib.srh_dense_projection_bwd(C.byref(p), x["view"], x["surfels"], x["rgb"], x["rotated"], x["saved"],
-                                        saved_bytes, x["workspace"], ws_bytes, x["g_out"], x["g_mask"],
-                                        x["grad_surfels"], x["grad_rgb"], x["grad_rotated"], None)
+def _bwd(lib, p, a, **given):
+    return call(lib.srh_dense_projection_bwd, BWD, p, a, **given)
 
 
 def test_entry_points_are_exported_bound_and_declared(lib):
@@ -94,7 +85,7 @@ def test_null_arguments_are_refused_by_name(lib):
     p, a, _ = _valid()
     assert lib.srh_dense_projection_fwd(None, a, a, a, a, a, BIG, a, BIG, a, a, None) == NULL
     assert b"params" in lib.srh_last_error()
-    for k in FWD:
+    for k in pointers(FWD):
         want = {"workspace": WORKSPACE, "saved": None}.get(k, NULL)
         if want is not None:                          # saved is optional
             assert _fwd(lib, p, a, **{k: None}) == want, k
@@ -123,19 +114,12 @@ def test_all_null_gradients_are_refused(lib):
     assert b"grad_surfels" in lib.srh_last_error() and b"all NULL" in lib.srh_last_error()
 
 
-@pytest.mark.parametrize("field,value,code", [
-    ("n_views", 0, RANGE), ("n_views", 65536, RANGE), ("width", 0, RANGE), ("height", 0, RANGE), ("width", 1 << 22, RANGE),
-    ("channels", 0, RANGE), ("channels", 5, RANGE), ("has_rotated", 2, TYPE), ("has_rotated", -1, TYPE),
-    ("sigma", 0.0, RANGE), ("sigma", -1.0, RANGE), ("sigma", float("nan"), RANGE), ("sigma", float("inf"), RANGE),
-    ("fovy", 0.0, CAMERA), ("fovy", 3.2, CAMERA), ("fovy", float("nan"), CAMERA),
-    ("focal_length", 0.0, CAMERA), ("focal_length", float("inf"), CAMERA)])
+@pytest.mark.parametrize("field,value,code", FRAME_ROWS + [
+    ("has_rotated", 2, TYPE), ("has_rotated", -1, TYPE), ("sigma", 0.0, RANGE), ("sigma", -1.0, RANGE),
+    ("sigma", float("nan"), RANGE), ("sigma", float("inf"), RANGE)] + PINHOLE_ROWS)
 def test_out_of_range_parameters_are_refused_by_name(lib, field, value, code):
     p, a, _ = _valid(**{field: value})
-    name = {"width": b"width x height", "height": b"width x height"}.get(field, field.encode())
-    for call in (_fwd, _bwd):
-        assert call(lib, p, a) == code, call.__name__
-        assert name in lib.srh_last_error(), (call.__name__, lib.srh_last_error())
-    assert lib.srh_dense_projection_workspace_bytes(C.byref(p), 0) == 0
+    assert_refused_by_name(lib, (_fwd, _bwd), lib.srh_dense_projection_workspace_bytes, p, a, field, code)
 
 
 def test_short_or_misaligned_buffers_are_refused(lib):

@@ -5,10 +5,9 @@ import ctypes as C
 
 import pytest
 
+from projection_abi import (BIG, FRAME_ROWS, NULL, PINHOLE_ROWS, RANGE, TYPE, WORKSPACE, assert_refused_by_name, call, pointers,
+                            valid_params)
 from surf_renderer_amd import _lib, build
-
-NULL, RANGE, TYPE, WORKSPACE, CAMERA = -1, -2, -3, -4, -5        # SRH_E_*
-BIG = 1 << 40
 
 
 @pytest.fixture(scope="module")
@@ -18,37 +17,28 @@ def lib():
 
 
 def _valid(**fields):
-    buf = (C.c_double * 64)()
-    p = _lib.SrhProjectionParams(n_views=2, width=16, height=12, channels=3, flags=3, blur_half=3, fovy=0.7,
-                                 focal_length=0.5)
+    p, a, buf = valid_params(_lib.SrhProjectionParams, **dict(dict(n_views=2, width=16, height=12, channels=3, flags=3,
+                                                                   blur_half=3, fovy=0.7, focal_length=0.5), **fields))
     p.taps[:4] = [0.4, 0.2, 0.08, 0.02]
-    for k, v in fields.items():
-        setattr(p, k, v)
-    return p, C.addressof(buf), buf
+    return p, a, buf
 
 
-KEYS = ("view", "surfels", "workspace", "keys")
-FWD = ("rgb", "rotated", "keys", "order", "workspace", "saved", "out", "mask", "image1", "depth")
-BWD = ("view", "surfels", "rgb", "rotated", "saved", "workspace", "g_out", "g_mask", "g_image1", "g_depth", "grad_surfels",
-       "grad_rgb", "grad_rotated")
+KEYS = ("view", "surfels", "workspace", "ws_bytes", "keys")
+FWD = ("rgb", "rotated", "keys", "order", "workspace", "ws_bytes", "saved", "saved_bytes", "out", "mask", "image1", "depth")
+BWD = ("view", "surfels", "rgb", "rotated", "saved", "saved_bytes", "workspace", "ws_bytes", "g_out", "g_mask", "g_image1",
+       "g_depth", "grad_surfels", "grad_rgb", "grad_rotated")
 
 
-def _keys(lib, p, a, ws_bytes=BIG, **null):
-    x = {k: (None if null.get(k) is None and k in null else null.get(k, a)) for k in KEYS}
-    return lib.srh_projection_keys(C.byref(p), x["view"], x["surfels"], x["workspace"], ws_bytes, x["keys"], None)
+def _keys(lib, p, a, **given):
+    return call(lib.srh_projection_keys, KEYS, p, a, **given)
 
 
-def _fwd(lib, p, a, ws_bytes=BIG, saved_bytes=BIG, **null):
-    x = {k: (None if null.get(k) is None and k in null else null.get(k, a)) for k in FWD}
-    return lib.srh_projection_fwd(C.byref(p), x["rgb"], x["rotated"], x["keys"], x["order"], x["workspace"], ws_bytes,
-                                  x["saved"], saved_bytes, x["out"], x["mask"], x["image1"], x["depth"], None)
+def _fwd(lib, p, a, **given):
+    return call(lib.srh_projection_fwd, FWD, p, a, **given)
 
 
-def _bwd(lib, p, a, ws_bytes=BIG, saved_bytes=BIG, **null):
-    x = {k: (None if null.get(k) is None and k in null else null.get(k, a)) for k in BWD}
-    return lib.srh_projection_bwd(C.byref(p), x["view"], x["surfels"], x["rgb"], x["rotated"], x["saved"], saved_bytes,
-                                  x["workspace"], ws_bytes, x["g_out"], x["g_mask"], x["g_image1"], x["g_depth"],
-                                  x["grad_surfels"], x["grad_rgb"], x["grad_rotated"], None)
+def _bwd(lib, p, a, **given):
+    return call(lib.srh_projection_bwd, BWD, p, a, **given)
 
 
 def test_entry_points_are_exported_and_bound(lib):
@@ -79,10 +69,10 @@ def test_workspace_sizes_follow_the_documented_layouts(lib):
 def test_null_arguments_are_refused_by_name(lib):
     p, a, _ = _valid()
     assert lib.srh_projection_keys(None, a, a, a, BIG, a, None) == NULL and b"params" in lib.srh_last_error()
-    for k in KEYS:
+    for k in pointers(KEYS):
         assert _keys(lib, p, a, **{k: None}) == (WORKSPACE if k == "workspace" else NULL), k
         assert k.encode() in lib.srh_last_error(), k
-    for k in FWD:
+    for k in pointers(FWD):
         want = {"workspace": WORKSPACE, "rotated": None, "saved": None, "depth": None}.get(k, NULL)
         if want is not None:                          # rotated, saved and depth are optional
             assert _fwd(lib, p, a, **{k: None}) == want, k
@@ -102,18 +92,11 @@ def test_all_null_gradients_are_refused(lib):
     assert _bwd(lib, p, a, rotated=None) == NULL and b"grad_rotated without rotated" in lib.srh_last_error()
 
 
-@pytest.mark.parametrize("field,value,code", [
-    ("n_views", 0, RANGE), ("n_views", 65536, RANGE), ("width", 0, RANGE), ("height", 0, RANGE), ("width", 1 << 22, RANGE),
-    ("channels", 0, RANGE), ("channels", 5, RANGE), ("blur_half", -1, RANGE), ("blur_half", 65, RANGE),
-    ("flags", 64, TYPE), ("flags", -1, TYPE), ("fovy", 0.0, CAMERA), ("fovy", 3.2, CAMERA), ("fovy", float("nan"), CAMERA),
-    ("focal_length", 0.0, CAMERA), ("focal_length", float("inf"), CAMERA)])
+@pytest.mark.parametrize("field,value,code", FRAME_ROWS + [
+    ("blur_half", -1, RANGE), ("blur_half", 65, RANGE), ("flags", 64, TYPE), ("flags", -1, TYPE)] + PINHOLE_ROWS)
 def test_out_of_range_parameters_are_refused_by_name(lib, field, value, code):
     p, a, _ = _valid(**{field: value})
-    name = {"width": b"width x height", "height": b"width x height"}.get(field, field.encode())
-    for call in (_keys, _fwd, _bwd):
-        assert call(lib, p, a) == code, call.__name__
-        assert name in lib.srh_last_error(), (call.__name__, lib.srh_last_error())
-    assert lib.srh_projection_workspace_bytes(C.byref(p), 0) == 0
+    assert_refused_by_name(lib, (_keys, _fwd, _bwd), lib.srh_projection_workspace_bytes, p, a, field, code)
 
 
 def test_a_tap_that_is_not_finite_is_refused(lib):

@@ -5,10 +5,9 @@ import ctypes as C
 
 import pytest
 
+from projection_abi import (BIG, CAMERA, FRAME_ROWS, NULL, RANGE, WORKSPACE, assert_refused_by_name, call,
+                            pointers, valid_params)
 from surf_renderer_amd import _lib, build
-
-NULL, RANGE, TYPE, WORKSPACE, CAMERA = -1, -2, -3, -4, -5        # SRH_E_*
-BIG = 1 << 40
 
 
 @pytest.fixture(scope="module")
@@ -18,42 +17,28 @@ def lib():
 
 
 def _valid(**fields):
-    buf = (C.c_double * 64)()
-    p = _lib.SrhReverseProjectionParams(n_views=2, width=16, height=12, channels=3, fovy1=0.7, focal_length1=0.5,
-                                        fovy2=0.9, focal_length2=0.8, depth_epsilon=0.1)
-    for k, v in fields.items():
-        setattr(p, k, v)
-    return p, C.addressof(buf), buf
+    return valid_params(_lib.SrhReverseProjectionParams, **dict(dict(n_views=2, width=16, height=12, channels=3, fovy1=0.7,
+                                                                     focal_length1=0.5, fovy2=0.9, focal_length2=0.8,
+                                                                     depth_epsilon=0.1), **fields))
 
 
-FWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "rotated", "keep", "workspace", "out", "mask", "image1", "depth")
-KEYS = ("view1", "out_pos", "workspace", "keys")
-BWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "mask", "keys", "order", "workspace", "g_out", "g_image1", "g_depth",
-       "grad_rgb", "grad_in_pos", "grad_out_pos", "grad_rotated")
+FWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "rotated", "keep", "workspace", "ws_bytes", "out", "mask", "image1",
+       "depth")
+KEYS = ("view1", "out_pos", "workspace", "ws_bytes", "keys")
+BWD = ("view1", "view2", "rgb", "in_pos", "out_pos", "mask", "keys", "order", "workspace", "ws_bytes", "g_out", "g_image1",
+       "g_depth", "grad_rgb", "grad_in_pos", "grad_out_pos", "grad_rotated")
 
 
-def _pick(names, a, null):
-    return {k: (None if k in null and null[k] is None else null.get(k, a)) for k in names}
+def _fwd(lib, p, a, **given):
+    return call(lib.srh_reverse_projection_fwd, FWD, p, a, **given)
 
 
-def _fwd(lib, p, a, ws_bytes=BIG, **null):
-    x = _pick(FWD, a, null)
-    return lib.srh_reverse_projection_fwd(C.byref(p), x["view1"], x["view2"], x["rgb"], x["in_pos"], x["out_pos"],
-                                          x["rotated"], x["keep"], x["workspace"], ws_bytes, x["out"], x["mask"],
-                                          x["image1"], x["depth"], None)
+def _keys(lib, p, a, **given):
+    return call(lib.srh_reverse_projection_keys, KEYS, p, a, **given)
 
 
-def _keys(lib, p, a, ws_bytes=BIG, **null):
-    x = _pick(KEYS, a, null)
-    return lib.srh_reverse_projection_keys(C.byref(p), x["view1"], x["out_pos"], x["workspace"], ws_bytes, x["keys"], None)
-
-
-def _bwd(lib, p, a, ws_bytes=BIG, **null):
-    x = _pick(BWD, a, null)
-    return lib.srh_reverse_projection_bwd(C.byref(p), x["view1"], x["view2"], x["rgb"], x["in_pos"], x["out_pos"],
-                                          x["mask"], x["keys"], x["order"], x["workspace"], ws_bytes, x["g_out"],
-                                          x["g_image1"], x["g_depth"], x["grad_rgb"], x["grad_in_pos"],
-                                          x["grad_out_pos"], x["grad_rotated"], None)
+def _bwd(lib, p, a, **given):
+    return call(lib.srh_reverse_projection_bwd, BWD, p, a, **given)
 
 
 def test_entry_points_are_exported_and_bound(lib):
@@ -85,12 +70,12 @@ def test_null_arguments_are_refused_by_name(lib):
     p, a, _ = _valid()
     assert lib.srh_reverse_projection_keys(None, a, a, a, BIG, a, None) == NULL and b"params" in lib.srh_last_error()
     optional = {"rotated", "keep", "depth"}
-    for k in FWD:
+    for k in pointers(FWD):
         if k in optional:
             continue
         assert _fwd(lib, p, a, **{k: None}) == (WORKSPACE if k == "workspace" else NULL), k
         assert k.encode() in lib.srh_last_error(), k
-    for k in KEYS:
+    for k in pointers(KEYS):
         assert _keys(lib, p, a, **{k: None}) == (WORKSPACE if k == "workspace" else NULL), k
         assert k.encode() in lib.srh_last_error(), k
     for k in ("view1", "view2", "rgb", "in_pos", "out_pos", "mask", "keys", "order"):
@@ -106,18 +91,13 @@ def test_all_null_gradients_are_refused(lib):
     assert b"grad_rgb" in lib.srh_last_error() and b"all NULL" in lib.srh_last_error()
 
 
-@pytest.mark.parametrize("field,value,code", [
-    ("n_views", 0, RANGE), ("n_views", 65536, RANGE), ("width", 0, RANGE), ("height", 0, RANGE), ("width", 1 << 22, RANGE),
-    ("channels", 0, RANGE), ("channels", 5, RANGE), ("fovy1", 0.0, CAMERA), ("fovy2", 3.2, CAMERA),
-    ("fovy1", float("nan"), CAMERA), ("focal_length1", 0.0, CAMERA), ("focal_length2", float("inf"), CAMERA),
-    ("focal_length2", -1.0, CAMERA), ("depth_epsilon", float("nan"), RANGE), ("depth_epsilon", float("inf"), RANGE)])
+@pytest.mark.parametrize("field,value,code", FRAME_ROWS + [
+    ("fovy1", 0.0, CAMERA), ("fovy2", 3.2, CAMERA), ("fovy1", float("nan"), CAMERA), ("focal_length1", 0.0, CAMERA),
+    ("focal_length2", float("inf"), CAMERA), ("focal_length2", -1.0, CAMERA), ("depth_epsilon", float("nan"), RANGE),
+    ("depth_epsilon", float("inf"), RANGE)])
 def test_out_of_range_parameters_are_refused_by_name(lib, field, value, code):
     p, a, _ = _valid(**{field: value})
-    name = {"width": b"width x height", "height": b"width x height"}.get(field, field.encode())
-    for call in (_fwd, _keys, _bwd):
-        assert call(lib, p, a) == code, call.__name__
-        assert name in lib.srh_last_error(), (call.__name__, lib.srh_last_error())
-    assert lib.srh_reverse_projection_workspace_bytes(C.byref(p), 0) == 0
+    assert_refused_by_name(lib, (_fwd, _keys, _bwd), lib.srh_reverse_projection_workspace_bytes, p, a, field, code)
 
 
 def test_short_or_misaligned_buffers_are_refused(lib):

@@ -12,13 +12,10 @@ import torch
 
 import dense_projection_cases as cases
 import dense_projection_oracle as do
+from projection_checks import assert_bit_identical, compare_grads, compare_values, one_view, to_np
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _np(t):
-    return None if t is None else t.detach().cpu().numpy().astype(np.float64)
 
 
 def _hip(c, wrt=do.INPUTS, only=None, no_grad=False):
@@ -35,60 +32,29 @@ def _hip(c, wrt=do.INPUTS, only=None, no_grad=False):
         sum((res[k] * torch.tensor(g, device=DEV)).sum() for k, g in c["upstream"].items()
             if only is None or k == only).backward()
     torch.cuda.synchronize()
-    return {k: _np(v) for k, v in res.items()}, {k: _np(t.grad) for k, t in x.items()}
-
-
-def _compare_values(got, want, tag):
-    assert set(got) == set(want), tag
-    for k, w in want.items():
-        assert got[k].shape == w.shape and np.all(np.isfinite(w)), (tag, k)
-        tol = 2e-6 * np.abs(w) + 2e-7 * max(np.abs(w).max(), 1.0)
-        print(f"{tag} {k}: max err / max|want| {np.abs(got[k] - w).max() / np.abs(w).max():.3g}, "
-              f"worst err / tolerance {(np.abs(got[k] - w) / tol).max():.3g}")
-        np.testing.assert_allclose(got[k], w, rtol=2e-6, atol=2e-7 * max(np.abs(w).max(), 1.0), err_msg=f"{tag} {k}")
-
-
-def _compare_grads(got, want, tag):
-    for k, w in want.items():
-        assert np.all(np.isfinite(w)) and np.abs(w).max() > 0 and got[k].shape == w.shape, (tag, k)
-        tol = 2e-6 * np.abs(w) + 2e-7 * np.abs(w).max()
-        print(f"{tag} grad {k}: max err / max|want| {np.abs(got[k] - w).max() / np.abs(w).max():.3g}, "
-              f"worst err / tolerance {(np.abs(got[k] - w) / tol).max():.3g}")
-        np.testing.assert_allclose(got[k], w, rtol=2e-6, atol=2e-7 * np.abs(w).max(), err_msg=f"{tag} grad {k}")
+    return {k: to_np(v) for k, v in res.items()}, {k: to_np(t.grad) for k, t in x.items()}
 
 
 @pytest.mark.parametrize("frame,layout,rotated", cases.ALL)
 def test_values_and_gradients_match_the_restatement(frame, layout, rotated):
     got, got_g = _hip(cases.case(frame, layout, rotated))
     want, want_g = cases.expected(frame, layout, rotated)
-    _compare_values(got, want, cases.tag(frame, layout, rotated))
-    _compare_grads(got_g, want_g, cases.tag(frame, layout, rotated))
+    compare_values(got, want, cases.tag(frame, layout, rotated))
+    compare_grads(got_g, want_g, cases.tag(frame, layout, rotated))
 
 
 @pytest.mark.parametrize("frame,rotated", [("35x37", False), ("12x16", True)])
 def test_two_runs_are_bit_identical(frame, rotated):
     c = cases.case(frame, "grid", rotated)
-    v1, g1 = _hip(c)
-    v2, g2 = _hip(c)
-    for k in v1:
-        assert np.array_equal(v1[k], v2[k]), k
-    for k in g1:
-        assert np.array_equal(g1[k], g2[k]), k
+    assert_bit_identical(_hip(c), _hip(c))
 
 
 @pytest.mark.parametrize("frame,layout,rotated", [("17x9", "flat", False), ("36x48", "grid", True)])
 def test_a_batch_equals_its_views_bit_for_bit(frame, layout, rotated):
     c = cases.case(frame, layout, rotated)
-    v, g = _hip(c)
+    whole = _hip(c)
     for b in range(c["shape"][0]):
-        one = dict(c, **{k: (c[k][b:b + 1] if c[k] is not None else None) for k in do.INPUTS},
-                   camera=dict(c["camera"], **{k: c["camera"][k][b:b + 1] for k in ("eye", "at", "up")}),
-                   upstream={k: u[b:b + 1] for k, u in c["upstream"].items()}, shape=(1, *c["shape"][1:]))
-        v1, g1 = _hip(one)
-        for k in v:
-            assert np.array_equal(v[k][b:b + 1], v1[k]), (b, k)
-        for k in g:
-            assert np.array_equal(g[k][b:b + 1], g1[k]), (b, k)
+        assert_bit_identical(whole, _hip(one_view(c, b, do.INPUTS)), slice(b, b + 1))
 
 
 @pytest.mark.parametrize("wrt", [("surfels",), ("rgb",), ("rotated_image",), ("surfels", "rgb"), ("rgb", "rotated_image"),
@@ -96,20 +62,20 @@ def test_a_batch_equals_its_views_bit_for_bit(frame, layout, rotated):
 def test_inputs_that_do_not_require_grad_get_none(wrt):
     got, got_g = _hip(cases.case("12x16", "grid", True), wrt=wrt)
     want, want_g = cases.expected("12x16", "grid", True, wrt=wrt)
-    _compare_values(got, want, "12x16")
+    compare_values(got, want, "12x16")
     for k in do.INPUTS:
         if k not in wrt:
             assert got_g[k] is None, k
-    _compare_grads({k: got_g[k] for k in wrt}, want_g, f"12x16 wrt {wrt}")
+    compare_grads({k: got_g[k] for k in wrt}, want_g, f"12x16 wrt {wrt}")
 
 
 def test_no_input_requires_grad_and_a_forward_under_no_grad():
     want = cases.expected("17x9")[0]
     got, got_g = _hip(cases.case("17x9"), wrt=())
-    _compare_values(got, want, "17x9 forward only")
+    compare_values(got, want, "17x9 forward only")
     assert all(g is None for g in got_g.values())
     got, got_g = _hip(cases.case("17x9"), no_grad=True)
-    _compare_values(got, want, "17x9 under no_grad")
+    compare_values(got, want, "17x9 under no_grad")
     assert all(g is None for g in got_g.values())
 
 
@@ -123,7 +89,7 @@ def test_a_loss_on_one_output_alone_reaches_the_surfels(only, rotated):
     if only == "mask":                                  # the mask reads neither the values nor the rotated image
         for k in ("rgb", "rotated_image")[:1 + rotated]:
             assert np.all(want_g.pop(k) == 0) and np.all(got_g[k] == 0)
-    _compare_grads(got_g, want_g, f"12x16 loss on {only}")
+    compare_grads(got_g, want_g, f"12x16 loss on {only}")
 
 
 def test_other_dtypes_devices_and_layouts_are_converted_and_the_gradient_comes_back_in_the_leafs_own():
@@ -139,11 +105,11 @@ def test_other_dtypes_devices_and_layouts_are_converted_and_the_gradient_comes_b
     res = {"out": out, "mask": mask}
     sum((res[k] * torch.tensor(g, device=DEV)).sum() for k, g in c["upstream"].items()).backward()
     want, want_g = cases.expected("12x16", "grid", True)
-    _compare_values({k: _np(v) for k, v in res.items()}, want, "12x16 converted")
+    compare_values({k: to_np(v) for k, v in res.items()}, want, "12x16 converted")
     assert surfels.grad.dtype == torch.float64 and surfels.grad.shape == surfels.shape
     assert rgb_t.grad.shape == rgb_t.shape and rotated.grad.device.type == "cpu"
-    _compare_grads({"surfels": _np(surfels.grad), "rgb": _np(rgb_t.grad.permute(0, 2, 1, 3)),
-                    "rotated_image": _np(rotated.grad)}, want_g, "12x16 converted")
+    compare_grads({"surfels": to_np(surfels.grad), "rgb": to_np(rgb_t.grad.permute(0, 2, 1, 3)),
+                    "rotated_image": to_np(rotated.grad)}, want_g, "12x16 converted")
 
 
 def test_the_two_layouts_of_one_image_differ_by_the_sigma_quirk():
@@ -156,4 +122,4 @@ def test_the_two_layouts_of_one_image_differ_by_the_sigma_quirk():
     assert np.abs(v_flat["mask"].reshape(-1) - v_grid["mask"].reshape(-1)).max() > 0.1 * np.abs(v_grid["mask"]).max()
     # blur_size / H is not the same float as blur_size * W / N in general, so this is a comparison to the bound
     v_same, _ = _hip(dict(flat, blur_size=grid["blur_size"] * W / (H * W)), wrt=())
-    _compare_values({k: v.reshape(v_grid[k].shape) for k, v in v_same.items()}, cases.expected("3x5")[0], "3x5 flat, sigma of the grid")
+    compare_values({k: v.reshape(v_grid[k].shape) for k, v in v_same.items()}, cases.expected("3x5")[0], "3x5 flat, sigma of the grid")

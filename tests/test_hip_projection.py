@@ -12,13 +12,10 @@ import torch
 
 import projection_cases as cases
 import projection_oracle as po
+from projection_checks import assert_bit_identical, compare_grads, compare_values, one_view, to_np
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _np(t):
-    return None if t is None else t.detach().cpu().numpy().astype(np.float64)
 
 
 def _hip(c, wrt=po.INPUTS, only=None):
@@ -36,72 +33,45 @@ def _hip(c, wrt=po.INPUTS, only=None):
         sum((res[k].reshape(B, H, W, -1) * torch.tensor(g, device=DEV)).sum() for k, g in c["upstream"].items()
             if only is None or k == only).backward()
     torch.cuda.synchronize()
-    return {k: _np(v).reshape(B, H, W, -1) for k, v in res.items()}, {k: _np(t.grad) for k, t in x.items()}
-
-
-def _compare_values(got, want, tag):
-    assert set(got) == set(want), tag
-    for k, w in want.items():
-        assert got[k].shape == w.shape, (tag, k)
-        print(f"{tag} {k}: max err / max|want| {np.abs(got[k] - w).max() / np.abs(w).max():.3g}")
-        np.testing.assert_allclose(got[k], w, rtol=2e-6, atol=2e-7 * max(np.abs(w).max(), 1.0), err_msg=f"{tag} {k}")
-
-
-def _compare_grads(got, want, tag):
-    for k, w in want.items():
-        assert np.all(np.isfinite(w)) and np.abs(w).max() > 0 and got[k].shape == w.shape, (tag, k)
-        print(f"{tag} grad {k}: max err / max|want| {np.abs(got[k] - w).max() / np.abs(w).max():.3g}")
-        np.testing.assert_allclose(got[k], w, rtol=2e-6, atol=2e-7 * np.abs(w).max(), err_msg=f"{tag} grad {k}")
+    return {k: to_np(v).reshape(B, H, W, -1) for k, v in res.items()}, {k: to_np(t.grad) for k, t in x.items()}
 
 
 @pytest.mark.parametrize("name,variant", cases.ALL)
 def test_values_and_gradients_match_the_restatement(name, variant):
     got, got_g = _hip(cases.case(name, variant))
     want, want_g = cases.expected(name, variant)
-    _compare_values(got, want, cases.tag(name, variant))
-    _compare_grads(got_g, want_g, cases.tag(name, variant))
+    compare_values(got, want, cases.tag(name, variant))
+    compare_grads(got_g, want_g, cases.tag(name, variant))
 
 
 @pytest.mark.parametrize("name", ["cluster_8x8", "12x16"])
 def test_two_runs_are_bit_identical(name):
     c = cases.case(name)
-    v1, g1 = _hip(c)
-    v2, g2 = _hip(c)
-    for k in v1:
-        assert np.array_equal(v1[k], v2[k]), k
-    for k in g1:
-        assert np.array_equal(g1[k], g2[k]), k
+    assert_bit_identical(_hip(c), _hip(c))
 
 
 @pytest.mark.parametrize("name", ["12x16", "17x9"])
 def test_a_batch_equals_its_views_bit_for_bit(name):
     c = cases.case(name)
-    v, g = _hip(c)
+    whole = _hip(c)
     for b in range(c["shape"][0]):
-        one = dict(c, **{k: (c[k][b:b + 1] if c[k] is not None else None) for k in po.INPUTS},
-                   camera=dict(c["camera"], **{k: c["camera"][k][b:b + 1] for k in ("eye", "at", "up")}),
-                   upstream={k: u[b:b + 1] for k, u in c["upstream"].items()}, shape=(1, *c["shape"][1:]))
-        v1, g1 = _hip(one)
-        for k in v:
-            assert np.array_equal(v[k][b:b + 1], v1[k]), (b, k)
-        for k in g:
-            assert np.array_equal(g[k][b:b + 1], g1[k]), (b, k)
+        assert_bit_identical(whole, _hip(one_view(c, b, po.INPUTS)), slice(b, b + 1))
 
 
 @pytest.mark.parametrize("wrt", [("surfels",), ("rgb",), ("rotated_image",), ("rgb", "rotated_image")])
 def test_inputs_that_do_not_require_grad_get_none(wrt):
     got, got_g = _hip(cases.case("12x16"), wrt=wrt)
     want, want_g = cases.expected("12x16", wrt=wrt)
-    _compare_values(got, want, "12x16")
+    compare_values(got, want, "12x16")
     for k in po.INPUTS:
         if k not in wrt:
             assert got_g[k] is None, k
-    _compare_grads({k: got_g[k] for k in wrt}, want_g, f"12x16 wrt {wrt}")
+    compare_grads({k: got_g[k] for k in wrt}, want_g, f"12x16 wrt {wrt}")
 
 
 def test_no_input_requires_grad():
     got, got_g = _hip(cases.case("17x9"), wrt=())
-    _compare_values(got, cases.expected("17x9")[0], "17x9 forward only")
+    compare_values(got, cases.expected("17x9")[0], "17x9 forward only")
     assert all(g is None for g in got_g.values())
 
 
@@ -115,7 +85,7 @@ def test_a_loss_on_one_output_alone_reaches_the_surfels(only):
         assert np.all(want_g.pop("rotated_image") == 0) and np.all(got_g["rotated_image"] == 0)
     if only in ("depth", "mask"):                       # neither reads the values
         assert np.all(want_g.pop("rgb") == 0) and np.all(got_g["rgb"] == 0)
-    _compare_grads(got_g, want_g, f"12x16 loss on {only}")
+    compare_grads(got_g, want_g, f"12x16 loss on {only}")
 
 
 def test_other_dtypes_devices_and_layouts_are_converted_and_the_gradient_comes_back_in_the_leafs_own():
@@ -132,11 +102,11 @@ def test_other_dtypes_devices_and_layouts_are_converted_and_the_gradient_comes_b
     res = dict(proj_out, out=out)
     sum((res[k] * torch.tensor(g, device=DEV)).sum() for k, g in c["upstream"].items()).backward()
     want, want_g = cases.expected("12x16")
-    _compare_values({k: _np(v) for k, v in res.items()}, want, "12x16 converted")
+    compare_values({k: to_np(v) for k, v in res.items()}, want, "12x16 converted")
     assert surfels.grad.dtype == torch.float64 and surfels.grad.shape == surfels.shape
     assert rgb_t.grad.shape == rgb_t.shape and rotated.grad.device.type == "cpu"
-    _compare_grads({"surfels": _np(surfels.grad), "rgb": _np(rgb_t.grad.permute(0, 2, 1, 3)),
-                    "rotated_image": _np(rotated.grad)}, want_g, "12x16 converted")
+    compare_grads({"surfels": to_np(surfels.grad), "rgb": to_np(rgb_t.grad.permute(0, 2, 1, 3)),
+                    "rotated_image": to_np(rotated.grad)}, want_g, "12x16 converted")
 
 
 def test_end_to_end_from_the_renderer_to_a_second_view():
@@ -166,7 +136,7 @@ def test_end_to_end_from_the_renderer_to_a_second_view():
     assert geometry and all(g is not None and bool(torch.isfinite(g).all()) for g in geometry.values())
     assert any(float(g.abs().max()) > 0 for g in geometry.values())
     # the oracle fed the same surfels and values
-    want, want_g = po.gradients({"surfels": _np(pos).reshape(1, H * W, 3), "rgb": _np(image)[None], "rotated_image": None},
+    want, want_g = po.gradients({"surfels": to_np(pos).reshape(1, H * W, 3), "rgb": to_np(image)[None], "rotated_image": None},
                                 second, {"out": upstream})
-    _compare_values({"out": _np(out)}, {"out": want["out"]}, "e2e")
-    _compare_grads({"surfels": _np(pos.grad).reshape(1, H * W, 3), "rgb": _np(image.grad)[None]}, want_g, "e2e")
+    compare_values({"out": to_np(out)}, {"out": want["out"]}, "e2e")
+    compare_grads({"surfels": to_np(pos.grad).reshape(1, H * W, 3), "rgb": to_np(image.grad)[None]}, want_g, "e2e")

@@ -3,7 +3,7 @@
 
 Workload: B = 64 views at 128 x 128 with D = 3, a rotated image and compute_new_depth, surfels / rgb / rotated_image all
 requiring grad, the loss a random weighting of out, mask, image1 and depth.  The surfels are a jittered depth map seen
-from the target cameras (tests/projection_cases.lift), about one per cell.  Two forms, in one process, alternating
+from the target cameras (tools/projection_bench.surfel_workload), about one per cell.  Two forms, in one process, alternating
 round by round after a warm-up so that both see the same machine state:
     fused        one projection_renderer_differentiable_fast call and its backward (HIP kernels and one torch.sort)
     composition  the reference's formulation -- 24 scatter-adds, dense convolutions -- as tests/projection_oracle.py
@@ -20,13 +20,10 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
-import projection_cases as cases  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import projection_bench as pb  # noqa: E402  (puts the repository and tests/ on the path)
 import projection_oracle as po  # noqa: E402
 from surf_renderer_amd import projection_renderer_differentiable_fast  # noqa: E402
 
@@ -40,89 +37,42 @@ if not torch.cuda.is_available():
     sys.exit("bench_projection: no GPU")
 dev = torch.device("cuda:0")
 B, S, D = args.views, args.size, 3
-N = S * S
 FLAGS = {"compute_new_depth": True}
-rng = np.random.RandomState(0)
-eye = (rng.uniform(-0.5, 0.5, (B, 3)) + [0.0, 0.5, 4.0]).astype(np.float32)
-at = rng.uniform(-0.3, 0.3, (B, 3)).astype(np.float32)
-up = (rng.uniform(-0.2, 0.2, (B, 3)) + [0.0, 1.0, 0.0]).astype(np.float32)
-gy, gx = np.meshgrid(np.arange(S) + 0.5, np.arange(S) + 0.5, indexing="ij")
-world = cases.lift(gx.reshape(1, N) + rng.uniform(-1.2, 1.2, (B, N)), gy.reshape(1, N) + rng.uniform(-1.2, 1.2, (B, N)),
-                   rng.uniform(1.5, 3.0, (B, N)), eye, at, up, S, S)
-camera = {"eye": eye, "at": at, "up": up, "viewport": [0, 0, S, S], "fovy": float(cases.FOVY), "focal_length": cases.FOCAL}
-host = {"surfels": world, "rgb": rng.uniform(0, 1, (B, S, S, D)), "rotated_image": rng.uniform(0, 1, (B, S, S, D))}
-x = {k: torch.tensor(v.astype(np.float32), device=dev, requires_grad=True) for k, v in host.items()}
-ups = {k: torch.tensor(rng.uniform(-1, 1, (B, S, S, D if k in ("out", "image1") else 1)).astype(np.float32), device=dev)
-       for k in po.OUTPUTS}
+rng, camera, host = pb.surfel_workload(B, S, D)
+x = pb.leaves(host, dev)
+ups = pb.upstreams(rng, po.OUTPUTS, B, S, D, dev)
 values = {}
 
 
-def clear():
-    for t in x.values():
-        t.grad = None
-
-
-def loss(res):
-    return sum((res[k] * ups[k]).sum() for k in po.OUTPUTS)
-
-
 def fused():
-    clear()
+    pb.clear(x)
     out, proj_out = projection_renderer_differentiable_fast(x["surfels"], x["rgb"], camera, x["rotated_image"], **FLAGS)
     values["fused"] = dict(proj_out, out=out)
-    loss(values["fused"]).backward()
+    pb.loss(values["fused"], ups).backward()
+
+
+def project(x):
+    return po.project(x["surfels"], x["rgb"], camera, x["rotated_image"], **FLAGS)
 
 
 def composition():
-    clear()
-    values["composition"] = po.project(x["surfels"], x["rgb"], camera, x["rotated_image"], **FLAGS)
-    loss(values["composition"]).backward()
-
-
-def composition_fp64():
-    """({output: value}, {input: gradient}) of the composition in float64 on the same float32 inputs; not timed."""
-    x64 = {k: t.detach().double().requires_grad_(True) for k, t in x.items()}
-    res = po.project(x64["surfels"], x64["rgb"], camera, x64["rotated_image"], **FLAGS)
-    sum((res[k] * ups[k].double()).sum() for k in po.OUTPUTS).backward()
-    return {k: v.detach() for k, v in res.items()}, {k: t.grad for k, t in x64.items()}
-
-
-def window(fn, n):
-    """ms per call over n calls, by device events."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(n):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop) / n
+    pb.clear(x)
+    values["composition"] = project(x)
+    pb.loss(values["composition"], ups).backward()
 
 
 forms = {"fused": fused, "composition": composition}
-want_v, want_g = composition_fp64()
+want_v, want_g = pb.composition_fp64(project, x, ups)
 agree = {}
 for name, fn in forms.items():                                # warm-up, and each form against float64
     fn(); fn()
     torch.cuda.synchronize()
-    got = {"value_" + k: (values[name][k].detach().double(), want_v[k]) for k in po.OUTPUTS}
-    got.update({"grad_" + k: (t.grad.double(), want_g[k]) for k, t in x.items()})
-    agree[name] = {k: {"max_err_over_max": float(f"{float((a - b).abs().max() / b.abs().max()):.3g}"),
-                       "share_off_by_1e-4_of_max": float(f"{float(((a - b).abs() > 1e-4 * b.abs().max()).double().mean()):.3g}")}
-                   for k, (a, b) in got.items()}
+    agree[name] = pb.agreement(values[name], x, want_v, want_g, po.OUTPUTS)
 del want_v, want_g
-calls = {name: max(1, int(np.ceil(1e3 * args.window / window(fn, 3)))) for name, fn in forms.items()}
-times = {name: [] for name in forms}
-for _ in range(args.rounds):
-    for name, fn in forms.items():
-        times[name].append(window(fn, calls[name]))
-med = {name: float(np.median(ts)) for name, ts in times.items()}
+calls, times, med = pb.timed(forms, args.rounds, args.window)
 out = {"workload": "projection_fwd_bwd", "views": B, "size": S, "channels": D, "rounds": args.rounds,
        "window_s_at_least": args.window, "calls_per_window": calls}
-for name, ts in times.items():
-    out[name] = {"ms_per_batch": round(med[name], 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
-                 "spread_ms": round(max(ts) - min(ts), 4)}
-out["speedup_median"] = round(med["composition"] / med["fused"], 2)
-# faster by more than the spread: the slowest fused round against the fastest round of the composition
-out["fused_faster_beyond_spread"] = bool(max(times["fused"]) < min(times["composition"]))
+out.update({name: pb.spread(ts) for name, ts in times.items()})
+out.update(pb.against_composition(times, med))
 out["against_float64_composition"] = agree
 print(json.dumps(out))

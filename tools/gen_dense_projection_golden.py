@@ -8,7 +8,7 @@ one pixel, so that branch has no reference result to record.
 Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by hand -- no test reads
 the reference.  The function is tried in float64 first (ref_harness.precision); PRECISION below records which precision
 the unedited function ran in, and every fixture carries it as in/precision.  A case of exactly three views is recorded
-view by view (see emit).
+view by view (ref_harness.run_views).
 
 Stored per fixture: in/{surfels, rgb}, in/camera/{eye, at, up, viewport, fovy, focal_length}, in/blur_size,
 in/precision, grad_in/{out, mask} (the case's upstream gradients), ref/{out, mask} and grad/{surfels, rgb} = d
@@ -34,37 +34,27 @@ with contextlib.redirect_stdout(io.StringIO()):
 
 
 def run_reference(c, dtype):
-    """({output: tensor}, {input: leaf}) of the reference on case `c` in `dtype`, gradients left in the leaves."""
-    B = c["shape"][0]
+    """({output: tensor}, {input: leaf}) of the reference on case `c` in `dtype`."""
     leaves = {k: torch.tensor(c[k], dtype=dtype, requires_grad=True) for k in ("surfels", "rgb")}
-    camera = {k: (torch.tensor(np.asarray(v, dtype=np.float32), dtype=dtype) if k in ("eye", "at", "up") else v)
-              for k, v in c["camera"].items()}
+    camera = R.layer_camera(c["camera"], dtype)
 
     def run(views):
         with R.quiet(), R.precision(dtype):
             out, mask = ref_projection.projection_renderer_differentiable(
-                leaves["surfels"][views], leaves["rgb"][views],
-                {k: (v[views] if k in ("eye", "at", "up") else v) for k, v in camera.items()},
-                rotated_image=None, blur_size=c["blur_size"])
+                leaves["surfels"][views], leaves["rgb"][views], R.camera_views(camera, views), rotated_image=None,
+                blur_size=c["blur_size"])
         return {"out": out, "mask": mask}
 
-    if B == 3:
-        # lookat_rot_inv calls torch.cross(up, z) without `dim`, which for [3, 3] operands -- three views, and only
-        # three -- still means dim 0: the cross product is taken ACROSS the views.  That is an accident of B == 3,
-        # not a meaning of the layer, so such a case is recorded view by view
-        per_view = [run(slice(b, b + 1)) for b in range(B)]
-        res = {k: torch.cat([r[k] for r in per_view]) for k in per_view[0]}
-    else:
-        res = run(slice(None))
-    sum(torch.sum(res[k] * torch.tensor(g, dtype=dtype)) for k, g in c["upstream"].items()).backward()
-    return res, leaves
+    return R.run_views(run, c["shape"][0]), leaves
 
 
 def pick_precision():
-    """float64 if the unedited function runs in it and returns float64, else float32."""
+    """float64 if the unedited function runs in it, forward and backward, and returns float64, else float32."""
     try:
-        res, _ = run_reference(cases.case("3x5"), torch.float64)
+        c = cases.case("3x5")
+        res, leaves = run_reference(c, torch.float64)
         if all(v.dtype == torch.float64 for v in res.values()):
+            R.pack_layer(c, leaves, res, dtype=torch.float64)
             return torch.float64
     except (RuntimeError, TypeError) as e:
         print(f"float64 run failed: {e}")
@@ -74,22 +64,14 @@ def pick_precision():
 def emit(frame, layout, dtype):
     c = cases.case(frame, layout)
     res, leaves = run_reference(c, dtype)
-    flat = {"in/" + k: c[k] for k in leaves}
-    for k, v in c["camera"].items():
-        flat["in/camera/" + k] = np.asarray(v, dtype=np.float64 if k in ("fovy", "focal_length") else None)
+    flat = R.pack_layer(c, leaves, res, dtype=dtype)
     flat["in/blur_size"] = np.asarray(c["blur_size"], dtype=np.float64)
     flat["in/precision"] = np.asarray(str(dtype).replace("torch.", ""))
-    for k, g in c["upstream"].items():
-        assert res[k].dtype == dtype and tuple(res[k].shape) == g.shape, k
-        flat["grad_in/" + k] = g
-        flat["ref/" + k] = res[k].detach().numpy()
-    for k, t in leaves.items():
-        flat["grad/" + k] = t.grad.numpy()
     R.write("dp1_" + cases.tag(frame, layout), flat)
 
 
 if __name__ == "__main__":
-    R.OUT = os.path.join(R.REPO, "tests", "golden", "dense_projection")
+    R.OUT = R.fixture_dir("dense_projection")
     PRECISION = pick_precision()
     print(f"recording in {PRECISION}")
     for f, layout in cases.RECORDED:

@@ -7,7 +7,7 @@ Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates
 the reference.  The reference runs this function in float32 only (its blur builds float32 taps, so the float64 shim of
 ref_harness.precision ends in a dtype error), so the fixtures hold float32 results; tests/
 test_projection_oracle_cpu.py states what that leaves of the comparison.  It also needs rgb as [B, H, W, D], so a
-[B, N, D] case is handed over reshaped.  A case of exactly three views is recorded view by view (see emit).
+[B, N, D] case is handed over reshaped.  A case of exactly three views is recorded view by view (ref_harness.run_views).
 
 Stored per fixture: in/{surfels, rgb, rotated_image}, in/camera/{eye, at, up, viewport, fovy, focal_length},
 in/blur_size, in/flags (JSON), grad_in/<output> (the case's upstream gradients), ref/<output> [B, H, W, .] and
@@ -37,43 +37,23 @@ def emit(name, variant):
     c = cases.case(name, variant)
     B, H, W, D = c["shape"]
     leaves = {k: torch.tensor(c[k], requires_grad=True) for k in INPUTS if c[k] is not None}
-    camera = {k: (torch.tensor(np.asarray(v, dtype=np.float32)) if k in ("eye", "at", "up") else v)
-              for k, v in c["camera"].items()}
+    camera = R.layer_camera(c["camera"])
 
     def run(views):
         with R.quiet():
             out, proj_out = ref_projection.projection_renderer_differentiable_fast(
-                leaves["surfels"][views], leaves["rgb"][views].reshape(-1, H, W, D),
-                {k: (v[views] if k in ("eye", "at", "up") else v) for k, v in camera.items()},
+                leaves["surfels"][views], leaves["rgb"][views].reshape(-1, H, W, D), R.camera_views(camera, views),
                 rotated_image=leaves["rotated_image"][views].reshape(-1, H, W, D) if "rotated_image" in leaves else None,
                 blur_size=c["blur_size"], **c["flags"])
         return dict(proj_out, out=out)
 
-    if B == 3:
-        # lookat_rot_inv calls torch.cross(up, z) without `dim`, which for [3, 3] operands -- three views, and only
-        # three -- still means dim 0: the cross product is taken ACROSS the views.  That is an accident of B == 3,
-        # not a meaning of the layer, so such a case is recorded view by view
-        per_view = [run(slice(b, b + 1)) for b in range(B)]
-        res = {k: torch.cat([r[k] for r in per_view]) for k in per_view[0]}
-    else:
-        res = run(slice(None))
-    assert set(res) == set(c["upstream"]), (sorted(res), sorted(c["upstream"]))
-    sum(torch.sum(res[k] * torch.tensor(g)) for k, g in c["upstream"].items()).backward()
-    flat = {"in/" + k: c[k] for k in leaves}
-    for k, v in c["camera"].items():
-        flat["in/camera/" + k] = np.asarray(v, dtype=np.float64 if k in ("fovy", "focal_length") else None)
+    flat = R.pack_layer(c, leaves, R.run_views(run, B))
     flat["in/blur_size"] = np.asarray(c["blur_size"], dtype=np.float64)
     flat["in/flags"] = np.asarray(json.dumps(c["flags"], sort_keys=True))
-    for k, g in c["upstream"].items():
-        assert res[k].dtype == torch.float32 and tuple(res[k].shape) == g.shape, k
-        flat["grad_in/" + k] = g
-        flat["ref/" + k] = res[k].detach().numpy()
-    for k, t in leaves.items():
-        flat["grad/" + k] = t.grad.numpy()
     R.write("pr1_" + cases.tag(name, variant), flat)
 
 
 if __name__ == "__main__":
-    R.OUT = os.path.join(R.REPO, "tests", "golden", "projection")
+    R.OUT = R.fixture_dir("projection")
     for n, v in cases.ALL:
         emit(n, v)
