@@ -60,11 +60,22 @@ def _norm(v: torch.Tensor) -> torch.Tensor:
     return torch.where(pos, torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))), torch.zeros_like(sq))
 
 
-def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None):
+def _tap(taps, key: str, index, t: torch.Tensor) -> torch.Tensor:
+    """With ``taps``: keep the gradient of ``t`` -- the per-pixel copy of leaf ``key`` (rows ``index`` of it; None: the
+    whole leaf once per pixel; ('columns', index): per pixel the rows ``index`` of it, one term per pixel and column)
+    -- so that its rows are the pixels' own terms of the leaf's gradient."""
+    if taps is not None:
+        t.retain_grad()
+        taps.setdefault(key, []).append((index, t))
+    return t
+
+
+def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]] = None,
+           taps=None):
     """Differentiable image (H,W,3) and depth (H,W).  ``ref`` = {'nearest', 'depth'} of the same scene (which
     primitive wins each pixel, and -- through depth being finite -- whether the pixel is hit at all); computed with
     the numpy oracle if not given.  ``scene`` supplies camera, index arrays and tonemap; ``leaves`` the
-    differentiable arrays."""
+    differentiable arrays.  ``taps``: see _tap (gradient_terms)."""
     cam = scene["camera"]
     eye_np, ray_np, H, W = np_oracle.generate_rays(cam)
     if ref is None:
@@ -88,8 +99,8 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional
             ds = d[sel]
             mat[sel] = np.asarray(grp["material_idx"])[nearest[sel] - start]
             if kind == "sphere":
-                c = leaves["sphere.pos"][loc][:, :3]
-                r = leaves["sphere.radius"][loc]
+                c = _tap(taps, "sphere.pos", loc, leaves["sphere.pos"][loc])[:, :3]
+                r = _tap(taps, "sphere.radius", loc, leaves["sphere.radius"][loc])
                 oc = orig[sel] - c
                 a = torch.sum(ds * ds, dim=-1)
                 b = 2 * torch.sum(oc * ds, dim=-1)
@@ -108,8 +119,9 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional
                 n = v / torch.sqrt(torch.sum(v * v, dim=-1, keepdim=True))
                 n = torch.where(ok[:, None], n, torch.zeros_like(n))
             else:
-                q = (leaves["triangle.face"][loc][:, 0, :3] if kind == "triangle" else leaves[f"{kind}.pos"][loc][:, :3])
-                n = _unit(leaves[f"{kind}.normal"][loc])[:, :3]
+                q = (_tap(taps, "triangle.face", loc, leaves["triangle.face"][loc])[:, 0, :3] if kind == "triangle"
+                     else _tap(taps, f"{kind}.pos", loc, leaves[f"{kind}.pos"][loc])[:, :3])
+                n = _unit(_tap(taps, f"{kind}.normal", loc, leaves[f"{kind}.normal"][loc]))[:, :3]
                 ts = torch.sum(n * (q - orig[sel]), dim=-1) / torch.sum(n * ds, dim=-1)
             t = t.index_put((torch.as_tensor(sel),), ts)
             nrm = nrm.index_put((torch.as_tensor(sel),), n)
@@ -118,14 +130,22 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional
     hit = torch.as_tensor(hit_np)
     # pixels that are not hit are background: depth inf, image tonemap(0)
     p = orig + t[:, None] * d
-    lpos = leaves["lights.pos"][:, :3]
-    lcol = leaves["colors"][np.asarray(scene["lights"]["color_idx"])]
-    alb = leaves["materials.albedo"][mat]
-    l = lpos[None, :, :] - p[:, None, :]
+    cidx = torch.as_tensor(np.asarray(scene["lights"]["color_idx"]).astype(np.int64))
+    if taps is None:
+        lpos = leaves["lights.pos"][None, :, :3]
+        lcol = leaves["colors"][cidx][None, :, :]
+        alb = leaves["materials.albedo"][mat]
+    else:
+        # every pixel its own copy of the lights, and every (pixel, light) its own copy of the light's colour row: the
+        # numpy shading has no per-light clip, so two lights that share a colour row can cancel within one pixel
+        lpos = _tap(taps, "lights.pos", None, leaves["lights.pos"][None].expand(npix, *leaves["lights.pos"].shape))[:, :, :3]
+        lcol = _tap(taps, "colors", ("columns", cidx), leaves["colors"][cidx][None].expand(npix, cidx.numel(), 3))
+        alb = _tap(taps, "materials.albedo", torch.as_tensor(mat), leaves["materials.albedo"][mat])
+    l = lpos - p[:, None, :]
     ln = _norm(l)
     l = l / torch.where(ln > 0, ln, torch.ones_like(ln))
     s = torch.sum(nrm[:, None, :] * l, dim=-1)                               # (N,L)
-    im = torch.sum(s[:, :, None] * lcol[None, :, :] * alb[:, None, :], dim=1)
+    im = torch.sum(s[:, :, None] * lcol * alb[:, None, :], dim=1)
     im = torch.where(hit[:, None], im, torch.zeros_like(im))
     im = torch.where(im < 0, torch.zeros_like(im), im)
     if "tonemap" in scene:
@@ -146,6 +166,45 @@ def gradients(scene: Dict[str, Any], grad_image: np.ndarray, grad_depth: Optiona
         loss = loss + torch.sum(torch.where(hit, depth * gd, torch.zeros_like(gd)))
     loss.backward()
     return {k: (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape))) for k, v in leaves.items()}
+
+
+def _sum_taps(leaves: Dict[str, torch.Tensor], taps):
+    """(total, absolute) per leaf from the retained gradients of its per-pixel copies."""
+    total = {k: torch.zeros_like(v) for k, v in leaves.items()}
+    absolute = {k: torch.zeros_like(v) for k, v in leaves.items()}
+    for key, copies in taps.items():
+        for index, t in copies:
+            if t.grad is None:
+                continue
+            if index is None:
+                total[key] += t.grad.sum(dim=0)
+                absolute[key] += t.grad.abs().sum(dim=0)
+            elif isinstance(index, tuple):
+                total[key].index_add_(0, index[1], t.grad.sum(dim=0))
+                absolute[key].index_add_(0, index[1], t.grad.abs().sum(dim=0))
+            else:
+                total[key].index_add_(0, index, t.grad)
+                absolute[key].index_add_(0, index, t.grad.abs())
+    return {k: v.numpy() for k, v in total.items()}, {k: v.numpy() for k, v in absolute.items()}
+
+
+def gradient_terms(scene: Dict[str, Any], grad_image: Optional[np.ndarray], grad_depth: Optional[np.ndarray] = None,
+                   ref: Optional[Dict[str, np.ndarray]] = None):
+    """gradient_terms_tch for ``render`` (numpy shading): (total, absolute) per leaf -- the sum over the pixels of each
+    pixel's own term of gradients()'s loss, and the sum of the terms' absolute values.  A light's colour row has one
+    term per pixel AND light that reads it.  ``grad_image`` None: the depth term alone."""
+    leaves = make_leaves(scene)
+    taps: Dict[str, Any] = {}
+    image, depth, hit = render(scene, leaves, ref, taps=taps)
+    loss = torch.zeros((), dtype=torch.float64)
+    if grad_image is not None:
+        loss = loss + torch.sum(image * torch.as_tensor(np.asarray(grad_image, dtype=np.float64)))
+    if grad_depth is not None:
+        gd = torch.as_tensor(np.asarray(grad_depth, dtype=np.float64))
+        loss = loss + torch.sum(torch.where(hit, depth * gd, torch.zeros_like(gd)))
+    if loss.requires_grad:
+        loss.backward()
+    return _sum_taps(leaves, taps)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -228,17 +287,9 @@ def rays(camera: Dict[str, Any], cam_leaves: Dict[str, torch.Tensor]):
     return eye, orig, d, H, W
 
 
-def _tap(taps, key: str, index, t: torch.Tensor) -> torch.Tensor:
-    """With ``taps``: keep the gradient of ``t`` -- the per-pixel copy of leaf ``key`` (rows ``index`` of it; None: the
-    whole leaf once per pixel) -- so that its rows are the pixels' own terms of the leaf's gradient."""
-    if taps is not None:
-        t.retain_grad()
-        taps.setdefault(key, []).append((index, t))
-    return t
-
-
 def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], ref: Optional[Dict[str, np.ndarray]],
-                 double_sided: bool, use_quartic: bool, visibility: Optional[np.ndarray], outputs=OUTPUTS, taps=None):
+                 double_sided: bool, use_quartic: bool, visibility: Optional[np.ndarray], outputs=OUTPUTS, taps=None,
+                 only_light: Optional[int] = None):
     """The one fp64 autograd restatement of the torch backend (diffrend/torch/renderer.py:82-125,136-355; see
     oracle/np_oracle_tch.py for the forward restatement and its two documented deviations) on the rays of rays_np or
     rays: (image (H,W,3), depth (H,W), normal (H,W,3), pos (H,W,3), hit (H,W)).  The shading is built -- and image is
@@ -251,7 +302,12 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
     inside the shading; pos = origin + t d (per-pixel origin for orthographic cameras).  Misses: normal and pos are 0,
     depth is far + 1, and upstream gradients there are ignored (the reference differentiates object 0's intersection
     there; the hip backend does not -- the one deliberate difference).  Misses contribute nothing, which is also how
-    the sphere case is defined where the reference itself yields NaN."""
+    the sphere case is defined where the reference itself yields NaN.
+
+    ``only_light`` = l: the image is replaced by its linearisation in light l's own contribution (its weight times
+    colour times albedo plus its share of the ambient term) -- d out / d im, taken at the full image and held constant,
+    times that contribution -- so a loss on it has light l's share of the image path's gradients, and the shares of all
+    lights add up to the whole (gradient_terms_tch)."""
     from . import np_oracle_tch
     cam = scene["camera"]
     eye, orig, d, H, W = ray_set
@@ -336,10 +392,18 @@ def _render_core(ray_set, scene: Dict[str, Any], leaves: Dict[str, torch.Tensor]
         col = w[:, :, None] * (lcol * alb[:, None, :]) + amb * alb[:, None, :]
         im = torch.sum(col, dim=1)
         im = torch.where(hit[:, None], im, torch.zeros_like(im))
-        im = torch.relu(im)
-        if "tonemap" in scene:
-            g = float(np.ravel(scene["tonemap"]["gamma"])[0])
-            im = torch.where(im > 0, im.clamp_min(1e-300) ** g, torch.zeros_like(im) if g > 0 else torch.ones_like(im))
+        if only_light is not None:
+            full = im.detach()
+            slope = (full > 0).to(full.dtype)
+            if "tonemap" in scene:
+                g = float(np.ravel(scene["tonemap"]["gamma"])[0])
+                slope = torch.where(full > 0, g * full.clamp_min(1e-300) ** (g - 1.0), torch.zeros_like(full))
+            im = slope * torch.where(hit[:, None], col[:, only_light], torch.zeros_like(full))
+        else:
+            im = torch.relu(im)
+            if "tonemap" in scene:
+                g = float(np.ravel(scene["tonemap"]["gamma"])[0])
+                im = torch.where(im > 0, im.clamp_min(1e-300) ** g, torch.zeros_like(im) if g > 0 else torch.ones_like(im))
         im = im.reshape(H, W, 3)
     # after the shading: autograd runs later-created nodes first, so this placement fixes the order in which p collects
     # its gradients (profiles/grad_oracle_unify_ab.txt)
@@ -375,13 +439,13 @@ def render_camera(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], cam_le
 
 
 def loss_camera(scene, leaves, cam_leaves, ref, grad_image=None, grad_depth=None, grad_normal=None, grad_pos=None,
-                double_sided=False, use_quartic=False, visibility=None, taps=None) -> torch.Tensor:
+                double_sided=False, use_quartic=False, visibility=None, taps=None, only_light=None) -> torch.Tensor:
     """sum image g_i + sum_hit (depth g_d + normal . g_n + pos . g_p) of ONE graph; None terms are left out, and so is
     the shading without g_i.  ``cam_leaves`` None: numpy rays, the camera outside the graph."""
     grads = dict(zip(OUTPUTS, (grad_image, grad_depth, grad_normal, grad_pos)))
     ray_set = rays_np(scene["camera"]) if cam_leaves is None else rays(scene["camera"], cam_leaves)
     *outs, hit = _render_core(ray_set, scene, leaves, ref, double_sided, use_quartic, visibility,
-                              outputs=[k for k, g in grads.items() if g is not None], taps=taps)
+                              outputs=[k for k, g in grads.items() if g is not None], taps=taps, only_light=only_light)
     loss = torch.zeros((), dtype=torch.float64)
     for out, (name, g) in zip(outs, grads.items()):
         if g is not None:
@@ -415,26 +479,16 @@ def gradients_tch(scene: Dict[str, Any], grad_image: Optional[np.ndarray] = None
 def gradient_terms_tch(scene: Dict[str, Any], grad_image: Optional[np.ndarray] = None,
                        grad_depth: Optional[np.ndarray] = None, grad_normal: Optional[np.ndarray] = None,
                        grad_pos: Optional[np.ndarray] = None, *, ref: Optional[Dict[str, np.ndarray]] = None,
-                       double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None):
+                       double_sided: bool = False, use_quartic: bool = False, visibility: Optional[np.ndarray] = None,
+                       only_light: Optional[int] = None):
     """(total, absolute): per scene leaf the sum over the pixels of each pixel's own term of d loss_camera / d leaf --
     gradients_tch's values -- and the sum of the terms' absolute values, which says how hard that sum cancels: an fp32
-    accumulation of the terms in an arbitrary order is uncertain by about ``absolute`` x 2^-23.  Numpy rays."""
+    accumulation of the terms in an arbitrary order is uncertain by about ``absolute`` x 2^-23.  Numpy rays.
+    ``only_light``: one light's share of the image path (_render_core); the shares' totals add up to the whole's."""
     leaves = make_leaves_tch(scene)
     taps: Dict[str, Any] = {}
     loss = loss_camera(scene, leaves, None, ref, grad_image, grad_depth, grad_normal, grad_pos, double_sided,
-                       use_quartic, visibility, taps=taps)
+                       use_quartic, visibility, taps=taps, only_light=only_light)
     if loss.requires_grad:
         loss.backward()
-    total = {k: torch.zeros_like(v) for k, v in leaves.items()}
-    absolute = {k: torch.zeros_like(v) for k, v in leaves.items()}
-    for key, copies in taps.items():
-        for index, t in copies:
-            if t.grad is None:
-                continue
-            if index is None:
-                total[key] += t.grad.sum(dim=0)
-                absolute[key] += t.grad.abs().sum(dim=0)
-            else:
-                total[key].index_add_(0, index, t.grad)
-                absolute[key].index_add_(0, index, t.grad.abs())
-    return {k: v.numpy() for k, v in total.items()}, {k: v.numpy() for k, v in absolute.items()}
+    return _sum_taps(leaves, taps)

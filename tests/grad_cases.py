@@ -144,3 +144,32 @@ def assert_grads_close(got, want, tol, tag="", keys=None):
     for key, w in want.items():
         if keys is None or key in keys:
             assert_array_close(got[key], w, tol, f"{tag} {key}")
+
+
+def entry_bounds(absolute, atomics, eps_term):
+    """(bound, accumulation part) per gradient entry for the backward kernels' fp32 sums (csrc/srh_backward.h):
+    (eps_term + D 2^-24) absolute (1 + 2^-20) and D 2^-24 absolute (1 + 2^-20), where `absolute` is the fp64 oracle's
+    sum of the |per-pixel terms| of the entry (torch_oracle.gradient_terms / gradient_terms_tch), eps_term the relative
+    error of one term and D = 1 (the cast of the term) + 6 (the run scan or wave_sum) + 2 (the workgroup merge) +
+    `atomics` (the atomic additions the entry receives, backward_run_cases.atomic_counts) counts the sequential fp32
+    additions on the way to the address."""
+    absolute = np.asarray(absolute, dtype=np.float64)
+    d = 9.0 + np.broadcast_to(np.asarray(atomics, dtype=np.float64), absolute.shape)
+    acc = d * 2.0 ** -24 * absolute * (1.0 + 2.0 ** -20)
+    return eps_term * absolute * (1.0 + 2.0 ** -20) + acc, acc
+
+
+def assert_entries_close(got, want, bound, tag=""):
+    """|got - want| <= bound for every entry on its own (an entry whose bound is 0 must be equal); prints and returns the
+    largest error over its bound."""
+    want = np.asarray(want, dtype=np.float64)
+    got = np.asarray(got, dtype=np.float64).reshape(want.shape)
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), want.shape)
+    assert np.all(np.isfinite(want)) and np.all(np.isfinite(got)), tag
+    err = np.abs(got - want)
+    ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0)), initial=0.0))
+    bad = np.argwhere(err > bound)
+    print(f"{tag}: worst error / bound {ratio:.3g} over {want.size} entries")
+    assert not len(bad), (f"{tag}: {len(bad)} entries over their bound, first {tuple(bad[0])}: got {got[tuple(bad[0])]:.9g} "
+                          f"want {want[tuple(bad[0])]:.9g} bound {bound[tuple(bad[0])]:.3g}")
+    return ratio

@@ -388,7 +388,8 @@ def test_fuzz_small_winners_are_not_hidden(camera_cases, views_cases):
     wholly wrong gradient.  For the three primitives that win the fewest pixels of a frame (winner_masks, from the GPU
     frame) the backward runs again with every upstream zeroed outside that primitive's pixels, on the GPU and in the
     oracle alike: max|want| is then that primitive's own row, and every other object row of the GPU result is exactly
-    zero.  First eight camera scenes, first four batches."""
+    zero.  First eight camera scenes, first four batches.  tests/test_hip_backward_runs.py holds every entry of every
+    leaf to a bound of its own (grad_cases.entry_bounds), numpy shading and the kernels without camera leaves included."""
     worst = _Worst()
     for it, case in enumerate(camera_cases[:G.N_MASKED_CAMERA]):
         scene, far = case["scene"], case["scene"]["camera"]["far"]

@@ -148,3 +148,46 @@ def test_phong_gradients_are_consistent_with_finite_differences():
             vals.append(loss(sc))
         fd = (vals[0] - vals[1]) / (2 * eps)
         np.testing.assert_allclose(grads[key][idx], fd, rtol=5e-5, atol=2e-7, err_msg=f"{key}{idx}")
+
+
+@pytest.mark.parametrize("case", ["g1_demo_64x48", "g2_demo_planes_64x48"])
+def test_gradient_terms_sum_to_the_gradients(case):
+    """gradient_terms (numpy shading) on two scenes that together hold all four primitive kinds: `total` is
+    gradients() within 1e-12 of `absolute` entrywise, `absolute` >= |total|, and `absolute` is exactly 0 where no pixel
+    reads the entry -- a primitive that wins no pixel, triangle vertices 1 and 2, every w, a colour row no light uses."""
+    scene, want, _ = load_case(os.path.join(GOLDEN_DIR, case + ".npz"))
+    H, W = want["depth"].shape
+    rng = np.random.RandomState(5)
+    g_img, g_dep = rng.uniform(-1, 1, size=(H, W, 3)), rng.uniform(-1, 1, size=(H, W))
+    if case.startswith("g2"):
+        assert set(scene["objects"]) == {"plane", "disk", "sphere", "triangle"}
+    for gi, gd in ((g_img, g_dep), (g_img, None), (None, g_dep)):
+        total, absolute = torch_oracle.gradient_terms(scene, gi, gd, ref=want)
+        grads = torch_oracle.gradients(scene, np.zeros_like(g_img) if gi is None else gi, gd, ref=want)
+        assert set(total) == set(absolute) == set(grads)
+        for key, g in grads.items():
+            assert total[key].shape == g.shape == absolute[key].shape
+            assert np.all(np.abs(total[key] - g) <= 1e-12 * absolute[key]), key
+            assert np.all(absolute[key] >= np.abs(total[key])), key
+    total, absolute = torch_oracle.gradient_terms(scene, g_img, g_dep, ref=want)
+    hit = np.isfinite(want["depth"])
+    winners = set(np.unique(want["nearest"][hit]).tolist())
+    start = 0
+    for kind, grp in scene["objects"].items():
+        count = len(grp["material_idx"])
+        lost = np.array([start + i not in winners for i in range(count)])
+        for name in torch_oracle.LEAF_KEYS[kind]:
+            a = absolute[f"{kind}.{name}"]
+            assert not a[lost].any(), f"{kind}.{name}: a primitive that wins no pixel"
+            if (kind, name) == ("disk", "radius"):
+                assert not a.any()                          # a disc's radius only selects: no gradient
+            else:
+                assert a[~lost].reshape(int((~lost).sum()), -1).any(axis=1).all(), f"{kind}.{name}: a winner without a term"
+            if name == "face":
+                assert not a[:, 1:].any() and not a[..., 3].any()
+            elif a.ndim == 2:
+                assert not a[:, 3].any(), f"{kind}.{name}: w"
+        start += count
+    assert not absolute["lights.pos"][:, 3].any()
+    unused = np.setdiff1d(np.arange(len(scene["colors"])), np.asarray(scene["lights"]["color_idx"]))
+    assert not absolute["colors"][unused].any() and absolute["colors"][np.asarray(scene["lights"]["color_idx"])].all()
