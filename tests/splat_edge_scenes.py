@@ -6,14 +6,16 @@ reach the branches of csrc/srh_splat.h that such inputs never take:
   reflect_idx on a side of length 2 (two stencil slots of one splat on the same neighbour), grid_x / grid_y with W == 1
   or H == 1, sub_shift for K = 4 .. 8, the light_vis read-modify-write over up to 64 sub-pixels, dead lanes of a partial
   wave or workgroup, splat_pow's 0 ** 0 = 1 and the cf[2] != 0 guard, the im > 0 mask of the relu over the light sum,
-  lights with w != 1, pos_cols == 3.
+  lights with w != 1, pos_cols == 3, the material reduction's uniform path per wave (m0 of the wave, live lanes only),
+  den_ok false at a light with attenuation (0, 0, 0), g_rn = -g_t t / rn at ray . n near -0.1.
 
 Every builder is deterministic (fixed seeds) and returns (scene, kwargs, notes): a numpy scene dict in the format
 splat_oracle.unpack produces, the keywords of the call, and what the CPU test needs to know about the case.  The base
 depth field, camera, lights and materials are those of oracle/golden_p1.py.
 
 tests/test_splat_edge_scenes_cpu.py asserts with the oracle alone that each case reaches the branch it is named for;
-tests/test_hip_splats_edges.py then compares the kernels with the oracle on them."""
+tests/test_hip_splats_edges.py then compares the kernels with the oracle on them, and tests/test_hip_splat_entries.py
+holds every entry to its own bound (the last four cases are pinned by tests/test_splat_entry_bounds_cpu.py)."""
 import functools
 
 import numpy as np
@@ -146,6 +148,66 @@ def _quartic_k2():
     return base_scene(5, 7, seed=47), {"samples": 2, "use_quartic": True}, {"grid": (5, 7), "given": False}
 
 
+def _three_materials(scene):
+    scene["materials"] = {"albedo": np.array([[0.7, 0.6, 0.5], [0.3, 0.8, 0.4], [0.5, 0.5, 0.9]], np.float32),
+                          "coeffs": np.array([[0.8, 0.2, 5.0], [0.6, 0.4, 12.0], [0.7, 0.3, 3.0]], np.float32)}
+
+
+def _materials_by_wave():
+    """2 x 64: row 0 (wave 0) is material 0, row 1 (wave 1) material 1 -- every wave takes k_splat_bwd's uniform path, to a
+    row of its own (m0 is the wave's, not the workgroup's).  Material 2 is used by nobody."""
+    scene = base_scene(2, 64, seed=58)
+    _three_materials(scene)
+    scene["objects"]["disk"]["material_idx"] = np.repeat(np.array([0, 1], np.int64), 64)
+    return scene, {}, {"grid": (2, 64), "given": False}
+
+
+def _materials_mixed_tail():
+    """1 x 70: material 1 only in the six live lanes of the last wave, material 0 in wave 0 and at pixel 0, as which the
+    58 dead lanes of the last wave run: that wave is uniform over its LIVE lanes only, with m0 = 1.  The row is 70 times
+    as wide as high, so its right-hand end is seen at 88 degrees: the six normals there are turned towards the eye and a
+    third light stands beside it, which gives material 1 a specular term."""
+    scene = base_scene(1, 70, seed=59, given=True)
+    _three_materials(scene)
+    scene["objects"]["disk"]["normal"][64:] = (np.array([-0.9, 0.1, 0.3]) + np.random.RandomState(65).uniform(-0.05, 0.05, (6, 3))) \
+        .astype(np.float32)
+    scene["lights"].update(pos=np.array([[3.0, 4.0, 8.0, 1.0], [-4.0, 1.0, 5.0, 1.0], [1.1, 1.7, 6.0, 1.0]], np.float32),
+                           color_idx=np.array([1, 2, 1]),
+                           attenuation=np.array([[1.0, 0.0, 0.0], [0.6, 0.04, 0.003], [0.8, 0.02, 0.02]], np.float32))
+    scene["objects"]["disk"]["material_idx"] = (np.arange(70) >= 64).astype(np.int64)
+    return scene, {"samples": 2}, {"grid": (1, 70), "given": True}
+
+
+def _zero_attenuation():
+    """6 x 6, three lights, the second with attenuation (0, 0, 0): den = 0, so afac = 1 (den_ok false) and the light's
+    attenuation gradient is exactly 0 while it still lights the frame."""
+    scene = base_scene(6, 6, seed=62)
+    scene["lights"].update(pos=np.array([[3.0, 4.0, 8.0, 1.0], [-4.0, 1.0, 5.0, 1.0], [2.0, -3.0, 6.0, 1.0]], np.float32),
+                           color_idx=np.array([1, 2, 1]),
+                           attenuation=np.array([[1.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.6, 0.04, 0.003]], np.float32))
+    return scene, {}, {"grid": (6, 6), "given": False}
+
+
+def _steep_given_k2():
+    """5 x 7, K = 2, given normals tilted 52 degrees towards -x: ray . n runs from about -0.1 at the left edge to -1 at the
+    right, so that g_rn = -g_t t / rn dominates the normal gradient on the left columns."""
+    scene = base_scene(5, 7, seed=63, given=True)
+    rng = np.random.RandomState(64)
+    th = np.deg2rad(52.0)
+    n = np.array([-np.sin(th), 0.0, np.cos(th)]) + rng.uniform(-0.02, 0.02, (35, 3))
+    scene["objects"]["disk"]["normal"] = n.astype(np.float32)
+    return scene, {"samples": 2}, {"grid": (5, 7), "given": True}
+
+
+def sub_ray_dot_normal(scene, kwargs):
+    """ray . n of every sub-pixel, (KH, KW), from the oracle's outputs: pos = t ray and the rays point to -z, so
+    ray = -sign(pos_z) unit(pos)."""
+    out = splat_oracle.render(scene, splat_oracle.make_leaves(scene, requires_grad=False), **kwargs)
+    pos, n = out["pos"].numpy(), out["normal"].numpy()
+    ray = pos / np.linalg.norm(pos, axis=-1, keepdims=True) * -np.sign(pos[..., 2:3])
+    return np.sum(ray * n, -1)
+
+
 BUILDERS = {
     "k4_given": _samples(4, True), "k4_est": _samples(4, False),
     "k8_given": _samples(8, True), "k8_est": _samples(8, False),
@@ -159,6 +221,9 @@ BUILDERS = {
     "clamped_est": _clamped(False, 1), "clamped_given_k2": _clamped(True, 2),
     "zpos_cols3": _zpos_cols3,
     "quartic_k2": _quartic_k2,
+    "materials_by_wave": _materials_by_wave, "materials_mixed_tail": _materials_mixed_tail,
+    "zero_attenuation": _zero_attenuation,
+    "steep_given_k2": _steep_given_k2,
 }
 CASES = tuple(BUILDERS)
 
@@ -187,6 +252,17 @@ def reference(name):
     for a in list(out.values()) + list(grads.values()) + list(up.values()):
         a.setflags(write=False)
     return scene, kwargs, notes, up, out, grads
+
+
+@functools.lru_cache(maxsize=None)
+def terms(name):
+    """(total, absolute) of splat_oracle.gradient_terms for a case under reference(name)'s upstream, computed once per
+    process; the arrays must not be written to."""
+    scene, kwargs, notes, up, out, grads = reference(name)
+    total, absolute = splat_oracle.gradient_terms(scene, up, **kwargs)
+    for a in list(total.values()) + list(absolute.values()):
+        a.setflags(write=False)
+    return total, absolute
 
 
 def shininess_rd(scene, kwargs):

@@ -74,8 +74,14 @@ def plane_fit_normals(P: torch.Tensor) -> torch.Tensor:
 
 
 def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], samples: int = 1, use_quartic: bool = False,
-           norm_depth_image_only: bool = False, **_ignored) -> Dict[str, torch.Tensor]:
-    """The reference's outputs for one view, in fp64, differentiable in `leaves` (fp64 tensors named as LEAVES)."""
+           norm_depth_image_only: bool = False, _copies: Dict[str, torch.Tensor] = None, _probe: Dict[str, Any] = None,
+           **_ignored) -> Dict[str, torch.Tensor]:
+    """The reference's outputs for one view, in fp64, differentiable in `leaves` (fp64 tensors named as LEAVES).
+    `_copies` (gradient_terms) replaces shading leaves by one copy per pixel, the arithmetic unchanged: lights.pos
+    (KH, KW, L, 4), colors (KH, KW, L, 3: the lights' rows), lights.attenuation (KH, KW, L, 3) per output pixel and light;
+    lights.ambient, materials.albedo, materials.coeffs (H, W, 3: the splat's row) per base pixel; disk.light_vis (L, KH, KW)
+    per sub-pixel.  `_probe` (decision_margin) receives the argument of every relu."""
+    cp = _copies or {}
     cam = scene["camera"]
     x, y, f, w, h, W, H = grid(cam)
     K = int(samples)
@@ -92,6 +98,11 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], samples: int 
     mat = scene["objects"]["disk"].get("material_idx")
     mat = torch.as_tensor(np.asarray(_np(mat), dtype=np.int64), device=dev).view(H, W) if mat is not None else \
         torch.zeros((H, W), dtype=torch.int64, device=dev)
+    if _probe is not None:
+        _probe["-z"] = -z
+
+    def up(a):
+        return a.repeat_interleave(K, 0).repeat_interleave(K, 1) if K > 1 else a
     if K > 1:
         dx, dy = w / (K * W - 1), h / (K * H - 1)
         d0 = torch.sum(P * N, dim=-1)
@@ -106,9 +117,6 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], samples: int 
                 cols.append(t[..., None] * ray)                # (H, W, 3) for sub-pixel (c, r)
             rows.append(torch.stack(cols, dim=2))             # (H, W, K_r, 3)
         pos = torch.stack(rows, dim=1).reshape(H * K, W * K, 3)        # (H, K_c, W, K_r, 3)
-
-        def up(a):
-            return a.repeat_interleave(K, 0).repeat_interleave(K, 1)
         N, mat = up(N), up(mat)
         vis = up(vis.permute(1, 2, 0)).permute(2, 0, 1) if vis is not None else None
         H, W = H * K, W * K
@@ -122,30 +130,39 @@ def render(scene: Dict[str, Any], leaves: Dict[str, torch.Tensor], samples: int 
                 "normal": N.reshape(-1, 3)}
     R, eye = camera_basis(_np(cam["eye"]), _np(cam["at"]), _np(cam["up"]))
     R, eye = R.to(dtype=dt, device=dev), eye.to(dtype=dt, device=dev)
-    lp = leaves["lights.pos"]
-    lcc = (lp[:, :3] - lp[:, 3:4] * eye[None, :]) @ R            # R^T (l - w eye), one row per light
+    lp = cp.get("lights.pos", leaves["lights.pos"])
+    lcc = (lp[..., :3] - lp[..., 3:4] * eye) @ R                 # R^T (l - w eye), one row per light
     cidx = torch.as_tensor(np.asarray(_np(scene["lights"]["color_idx"]), dtype=np.int64), device=dev)
-    colors = leaves["colors"][cidx]
-    att = leaves["lights.attenuation"]
-    alb = leaves["materials.albedo"][mat]
-    cf = leaves["materials.coeffs"][mat]
+    colors = cp["colors"] if "colors" in cp else leaves["colors"][cidx]
+    att = cp.get("lights.attenuation", leaves["lights.attenuation"])
+    alb = up(cp["materials.albedo"]) if "materials.albedo" in cp else leaves["materials.albedo"][mat]
+    cf = up(cp["materials.coeffs"]) if "materials.coeffs" in cp else leaves["materials.coeffs"][mat]
+    amb = up(cp["lights.ambient"]) if "lights.ambient" in cp else leaves["lights.ambient"]
+    vis = cp.get("disk.light_vis", vis)
     cdir = -_unit(pos)
     im = torch.zeros((H, W, 3), dtype=dt, device=dev)
-    for l in range(lp.shape[0]):
-        v = lcc[l] - pos
+    for l in range(lp.shape[-2]):
+        v = lcc[..., l, :] - pos
         dist = torch.sqrt(torch.sum(v * v, dim=-1))
         lh = v / torch.where(dist > 0, dist, torch.ones_like(dist))[..., None]
-        den = att[l, 0] + dist * att[l, 1] + dist ** (4 if use_quartic else 2) * att[l, 2]
+        den = att[..., l, 0] + dist * att[..., l, 1] + dist ** (4 if use_quartic else 2) * att[..., l, 2]
         afac = 1.0 / torch.where(den.abs() > 0, den, torch.ones_like(den))
         ldn = torch.sum(lh * N, dim=-1)
         nd = torch.relu(afac * ldn)
         refl = 2 * ldn[..., None] * N - lh
-        rd = torch.relu(torch.sum(cdir * refl, dim=-1))
+        rdot = torch.sum(cdir * refl, dim=-1)
+        rd = torch.relu(rdot)
         wgt = cf[..., 0] * nd + cf[..., 1] * rd ** cf[..., 2]
-        term = wgt[..., None] * colors[l] * alb
+        term = wgt[..., None] * colors[..., l, :] * alb
         if vis is not None:
             term = term * vis[l][..., None]
-        im = im + term + leaves["lights.ambient"] * alb
+        im = im + term + amb * alb
+        if _probe is not None:
+            _probe.setdefault("afac * ldn", []).append(afac * ldn)
+            _probe.setdefault("reflection", []).append(rdot)
+            _probe.setdefault("den", []).append(den)
+    if _probe is not None:
+        _probe["light sum"] = im
     return {"image": torch.relu(im), "depth": depth, "pos": pos, "normal": N}
 
 
@@ -173,6 +190,135 @@ def gradients(scene: Dict[str, Any], upstream: Dict[str, np.ndarray], **params):
     loss.backward()
     grads = {k: (t.grad.numpy() if t.grad is not None else np.zeros(tuple(t.shape))) for k, t in leaves.items()}
     return {k: v.detach().numpy() for k, v in out.items()}, grads
+
+
+def clamped_color_idx(scene: Dict[str, Any]) -> np.ndarray:
+    """lights.color_idx as the kernels read it: clamped to the rows of `colors`."""
+    return np.clip(np.asarray(_np(scene["lights"]["color_idx"]), dtype=np.int64), 0, len(_np(scene["colors"])) - 1)
+
+
+def material_idx(scene: Dict[str, Any], n: int) -> np.ndarray:
+    """objects.disk.material_idx as the kernels read it: (n,), clamped to the rows of materials.albedo, 0 if absent."""
+    mat = scene["objects"]["disk"].get("material_idx")
+    if mat is None:
+        return np.zeros(n, dtype=np.int64)
+    return np.clip(np.asarray(_np(mat), dtype=np.int64).reshape(-1), 0, len(_np(scene["materials"]["albedo"])) - 1)
+
+
+def per_output_gradients(scene: Dict[str, Any], upstream: Dict[str, np.ndarray], **params):
+    """{output: {leaf: d sum(output * upstream[output]) / d leaf}}: one backward pass per output of the loss."""
+    return {k: gradients(scene, {k: g}, **params)[1] for k, g in upstream.items()}
+
+
+def gradient_terms(scene: Dict[str, Any], upstream: Dict[str, np.ndarray], _raw: Dict[str, np.ndarray] = None, **params):
+    """(total, absolute) per leaf: `total` is what gradients() returns; `absolute` the sum of the |terms| that
+    k_splat_bwd (csrc/srh_splat.h) adds in fp32 on the way to the entry, in the kernel's own grouping:
+      lights.pos[l], lights.attenuation[l], colors[color_idx[l]]   one term per (output pixel, light): wave_add sits inside
+                                                                   the sub-pixel and the light loop; a colour row shared by
+                                                                   several lights takes the terms of each of them
+      lights.ambient, materials.albedo[m], materials.coeffs[m]     one term per base pixel (sub-pixels and lights are summed
+                                                                   in fp64 registers first)
+      disk.light_vis[l, n]                                         one term per sub-pixel of splat n (written once at K = 1,
+                                                                   an fp32 read-modify-write chain over K^2 at K > 1)
+      disk.pos, disk.normal                                        written once from fp64: the |gradient| per output of the
+                                                                   loss (image, depth, normal, pos), added -- within one
+                                                                   output the paths may cancel, between them they need not
+    All terms of the shading leaves come from ONE backward pass over per-pixel copies of the leaves (render's _copies);
+    disk.pos and disk.normal take one more pass per output (per_output_gradients), a non-finite entry of which (the
+    oracle's sqrt'(0) * 0 through the depth of an origin splat) counts as 0.  `_raw` receives the copies' gradients."""
+    leaves = make_leaves(scene)
+    x, y, f, w, h, W, H = grid(scene["camera"])
+    K = int(params.get("samples", 1))
+    KH, KW = K * H, K * W
+    L = leaves["lights.pos"].shape[0]
+    cidx, mat = clamped_color_idx(scene), material_idx(scene, H * W)
+    shade = not params.get("norm_depth_image_only", False)
+
+    def copies(t, *lead):
+        return t.detach().expand(*lead, *t.shape).clone().requires_grad_(True)
+    cp = {}
+    if shade:
+        cp = {"lights.pos": copies(leaves["lights.pos"], KH, KW),
+              "lights.attenuation": copies(leaves["lights.attenuation"], KH, KW),
+              "colors": copies(leaves["colors"].detach()[torch.as_tensor(cidx)], KH, KW),
+              "lights.ambient": copies(leaves["lights.ambient"], H, W),
+              "materials.albedo": leaves["materials.albedo"].detach()[torch.as_tensor(mat)].view(H, W, 3).clone().requires_grad_(True),
+              "materials.coeffs": leaves["materials.coeffs"].detach()[torch.as_tensor(mat)].view(H, W, 3).clone().requires_grad_(True)}
+        if "disk.light_vis" in leaves:
+            v = leaves["disk.light_vis"].detach().view(L, H, W)
+            cp["disk.light_vis"] = v.repeat_interleave(K, 1).repeat_interleave(K, 2).clone().requires_grad_(True)
+    out = render(scene, leaves, _copies=cp, **params)
+    loss = sum(torch.sum(out[k] * torch.as_tensor(np.asarray(g, dtype=np.float64))) for k, g in upstream.items())
+    loss.backward()
+    g = {k: (t.grad.numpy() if t.grad is not None else np.zeros(tuple(t.shape))) for k, t in cp.items()}
+    if _raw is not None:
+        _raw.update(g)
+    total, absolute = {}, {}
+    for k in ("disk.pos", "disk.normal"):
+        if k in leaves:
+            t = leaves[k]
+            total[k] = t.grad.numpy() if t.grad is not None else np.zeros(tuple(t.shape))
+    parts = per_output_gradients(scene, upstream, **params)
+    for k in total:
+        absolute[k] = sum(np.where(np.isfinite(p[k]), np.abs(p[k]), 0.0) for p in parts.values())
+    for k, t in leaves.items():
+        if k in total:
+            continue
+        shape = tuple(t.shape)
+        total[k], absolute[k] = np.zeros(shape), np.zeros(shape)
+        if k not in g:
+            continue
+        for fn, dst in ((lambda a: a, total[k]), (np.abs, absolute[k])):
+            a = fn(g[k])
+            if k in ("lights.pos", "lights.attenuation"):
+                dst += a.sum(axis=(0, 1))
+            elif k == "colors":
+                np.add.at(dst, cidx, a.sum(axis=(0, 1)))
+            elif k == "lights.ambient":
+                dst += a.sum(axis=(0, 1))
+            elif k in ("materials.albedo", "materials.coeffs"):
+                np.add.at(dst, mat, a.reshape(H * W, 3))
+            else:                                             # disk.light_vis: (L, KH, KW) -> the K x K block of a splat
+                dst += a.reshape(L, H, K, W, K).sum(axis=(2, 4)).reshape(shape)
+    return total, absolute
+
+
+def light_vis_terms(scene: Dict[str, Any], upstream: Dict[str, np.ndarray], **params) -> np.ndarray:
+    """(L, N, K^2): the terms of disk.light_vis[l, n] in the order k_splat_bwd adds them, sub = c K + r for the sub-pixel
+    at output (i K + c, j K + r)."""
+    raw = {}
+    gradient_terms(scene, upstream, _raw=raw, **params)
+    x, y, f, w, h, W, H = grid(scene["camera"])
+    K = int(params.get("samples", 1))
+    a = raw["disk.light_vis"]
+    return a.reshape(a.shape[0], H, K, W, K).transpose(0, 1, 3, 2, 4).reshape(a.shape[0], H * W, K * K)
+
+
+def decision_margin(scene: Dict[str, Any], **params):
+    """{relu: (margin, zeros)} for every relu of the restatement -- '-z', 'afac * ldn' and 'reflection' (per light), 'light
+    sum' (per channel) -- with margin the smallest non-zero |argument| over the largest, and zeros the sorted indices of
+    the base splats at which an argument is exactly 0.  A comparison in fp64 on the GPU decides as the oracle does as long
+    as the margin is far above the chains' rounding (1e-13 of the largest argument and less)."""
+    probe = {}
+    render(scene, make_leaves(scene, requires_grad=False), _probe=probe, **params)
+    x, y, f, w, h, W, H = grid(scene["camera"])
+    K = int(params.get("samples", 1))
+    out = {}
+    for name in ("-z", "afac * ldn", "reflection", "light sum"):
+        if name not in probe:
+            continue
+        a = probe[name]
+        a = (torch.stack(a, dim=-1) if isinstance(a, list) else a).numpy()
+        if name == "-z":
+            a = a.reshape(H, 1, W, 1, 1)
+        else:
+            a = a.reshape(H, K, W, K, -1)
+        mag = np.abs(a)
+        nonzero = mag[mag > 0]
+        margin = float(nonzero.min() / mag.max()) if nonzero.size else np.inf
+        zeros = np.where((mag == 0).any(axis=(1, 3, 4)).reshape(-1))[0]
+        out[name] = (margin, zeros)
+    return out
 
 
 # --- golden files (tests/golden/p1_*.npz) ----------------------------------------------------------------------------
