@@ -482,6 +482,73 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
                   const SrhSplatGrads* grads, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's NDC splat renderer, render_splats_NDC (diffrend/torch/renderer.py:358-474): one splat per pixel of a
+ * W x H grid, given by its position in normalised device coordinates and a normal.  With m00 = 1 / (aspect tan(fovy/2)),
+ * m11 = 1 / tan(fovy/2), m22 = (near + far) / (far - near), m23 = -2 near far / (far - near), aspect = W / H:
+ *   q = (x / m00, y / m11, -w, (z - m22 w) / m23),  P = q.xyz / q.w,  depth = |P|
+ * (w = 1 for three-column positions).  The normal is used as given, neither transformed nor normalised.  Shading is the
+ * torch backend's Phong in camera coordinates with the view direction -P NOT normalised, double_sided honoured (the sign
+ * of view . normal multiplies the diffuse and the specular dot before their relus), the ambient term once per light, a
+ * relu over the light sum, no near / far mask and no tonemap.  Many views per call: positions, normals, the eye and the
+ * light positions may differ per view, everything else is shared.  These entry points were added without an ABI version
+ * change: no existing struct or signature changed.  Conventions as above: caller-owned device buffers, enqueue only, no
+ * synchronisation or allocation, argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhSplatNdcParams {
+  int32_t n_views;              /* B >= 1 */
+  int32_t width, height;        /* the grid W x H (camera viewport); N = W * H splats per view, row-major */
+  int32_t pos_cols;             /* 3: pos is (N,3), w = 1; 4: pos is (N,4) */
+  int32_t use_quartic;          /* attenuation uses d^4 instead of d^2 */
+  int32_t double_sided;         /* flip the shading to the side of the normal the camera is on */
+  int32_t shade;                /* 1: shade the image; 0: geometry only (depth, pos; norm_depth_image_only) */
+  int32_t reserved;
+  double fovy;                  /* radians, in (0, pi) */
+  double near_clip, far_clip;   /* 0 < near < far */
+  double at[3], up[3];          /* camera.at / camera.up (shared by all views; w dropped as the reference does) */
+} SrhSplatNdcParams;
+
+/* Device inputs.  A view stride of 0 shares the array between all views. */
+typedef struct SrhSplatNdcInputs {
+  const float* pos;             /* (B, N, pos_cols) with pos_view_stride elements between views */
+  int64_t pos_view_stride;
+  const float* normal;          /* (N,3) per view, used as given; read only when shade = 1 (may be NULL otherwise) */
+  int64_t normal_view_stride;
+  const float* eye;             /* (3) per view: camera.eye[:3] */
+  int64_t eye_view_stride;
+  int64_t lights_pos_view_stride; /* SrhLights.pos is (n_lights,4) per view with this stride */
+  const int32_t* material_idx;  /* (N) shared; NULL: material 0 everywhere */
+} SrhSplatNdcInputs;
+
+/* Gradients.  pos (B, N, pos_cols: every column) and normal (B, N, 3) are WRITTEN, each element by the lane that owns
+ * the splat (no atomics, no zero-fill, no workspace: identical from run to run).  The scene parameters are ADDED with
+ * fp32 atomics (zero-fill them first) in their input layouts, as SrhSplatGrads: lights_pos (n_lights,4) per view at
+ * lights_pos_view_stride, colors, attenuation, ambient, albedo, coeffs.  NULL = not wanted.  The camera has no
+ * gradient.  A geometry-only frame (shade = 0) depends on none of the lights, colours and materials:
+ * srh_splat_ndc_bwd refuses those gradient buffers then (SRH_E_TYPE). */
+typedef struct SrhSplatNdcGrads {
+  float* pos;
+  float* normal;
+  float* lights_pos;
+  float* colors;
+  float* attenuation;
+  float* ambient;
+  float* albedo;
+  float* coeffs;
+} SrhSplatNdcGrads;
+
+/* image (B,H,W,3) (may be NULL when params->shade == 0), depth (B,H,W), pos (B,H,W,3): every element is written.
+ * lights / materials as for srh_splat_fwd (attenuation, ambient and coeffs optional), n_lights in 1..SRH_MAX_LIGHTS. */
+int srh_splat_ndc_fwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                      const SrhMaterials* materials, float* image, float* depth, float* pos, void* stream);
+
+/* Vector-Jacobian product of srh_splat_ndc_fwd for the upstream gradients of its three outputs (same layouts; any may
+ * be NULL, not all; grad_image must be NULL when shade = 0).  Relus and the sign of double_sided are constants (no
+ * gradient through them); at a point at the origin the depth has no gradient. */
+int srh_splat_ndc_bwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                      const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
+                      const float* grad_pos, const SrhSplatNdcGrads* grads, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * The geometric regularisers the reference's trainers put on every rendered splat view (diffrend/torch/GAN/gan.py:
  * 601-640 with diffrend/torch/utils.py:731-851), for B views per call.  Inputs are what srh_splat_fwd writes: pos,
  * normal, image (B, H, W, 3) and depth (B, H, W), dense, with H x W the OUTPUT grid (K H x K W at samples = K).

@@ -13,12 +13,13 @@ _RENDERER = ("render", "render_views", "ResidentScene", "CapturedStep", "ViewSce
              "generate_rays")
 _SCENE = ("load_scene", "load_model", "load_obj", "load_splat", "obj_to_triangle_spec")
 _SPLATS = ("render_splats_along_ray", "render_splats_along_ray_batch")
+_SPLATS_NDC = ("render_splats_NDC", "render_splats_NDC_batch")
 _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 _PROJECTION = ("projection_renderer_differentiable_fast",)
 _REVERSE_PROJECTION = ("projection_reverse_renderer",)
 _DENSE_PROJECTION = ("projection_renderer_differentiable",)
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION]
 
 
 def __getattr__(name):
@@ -28,6 +29,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".scene", __name__), name)
     if name in _SPLATS:
         return getattr(importlib.import_module(".splats", __name__), name)
+    if name in _SPLATS_NDC:
+        return getattr(importlib.import_module(".splats_ndc", __name__), name)
     if name in _REGULARIZERS:
         return getattr(importlib.import_module(".regularizers", __name__), name)
     if name in _PROJECTION:

@@ -92,6 +92,24 @@ class SrhSplatGrads(C.Structure):
                                           "ambient", "albedo", "coeffs")]
 
 
+class SrhSplatNdcParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pos_cols", C.c_int32),
+                ("use_quartic", C.c_int32), ("double_sided", C.c_int32), ("shade", C.c_int32), ("reserved", C.c_int32),
+                ("fovy", C.c_double), ("near_clip", C.c_double), ("far_clip", C.c_double), ("at", C.c_double * 3),
+                ("up", C.c_double * 3)]
+
+
+class SrhSplatNdcInputs(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("pos_view_stride", C.c_int64), ("normal", C.c_void_p),
+                ("normal_view_stride", C.c_int64), ("eye", C.c_void_p), ("eye_view_stride", C.c_int64),
+                ("lights_pos_view_stride", C.c_int64), ("material_idx", C.c_void_p)]
+
+
+class SrhSplatNdcGrads(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pos", "normal", "lights_pos", "colors", "attenuation", "ambient", "albedo",
+                                          "coeffs")]
+
+
 class SrhRegularizerParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32),
                 ("z_min", C.c_double), ("z_max", C.c_double), ("z_scale", C.c_double),
@@ -138,6 +156,7 @@ _V, _I, _Z = C.c_void_p, C.c_int32, C.c_size_t
 # what the single-frame entry points start with, and the batched ones after their n_views
 _FRAME = [_p(SrhCamera), _p(SrhObjects), _p(SrhLights), _p(SrhMaterials), _p(SrhParams), _V, _Z]
 _SPLAT = [_p(SrhSplatParams), _p(SrhSplatInputs), _p(SrhLights), _p(SrhMaterials)]
+_SPLAT_NDC = [_p(SrhSplatNdcParams), _p(SrhSplatNdcInputs), _p(SrhLights), _p(SrhMaterials)]
 
 # name -> (restype, argtypes): every entry point of include/srh.h, in its order (tests/test_abi.py compares the two)
 SIGNATURES = {
@@ -166,6 +185,8 @@ SIGNATURES = {
     "srh_splat_workspace_bytes": (_Z, _SPLAT[:2]),
     "srh_splat_fwd": (C.c_int, _SPLAT + [_V] * 5),
     "srh_splat_bwd": (C.c_int, _SPLAT + [_V, _Z] + [_V] * 4 + [_p(SrhSplatGrads), _V]),
+    "srh_splat_ndc_fwd": (C.c_int, _SPLAT_NDC + [_V] * 4),
+    "srh_splat_ndc_bwd": (C.c_int, _SPLAT_NDC + [_V] * 3 + [_p(SrhSplatNdcGrads), _V]),
     "srh_regularizers_workspace_bytes": (_Z, [_I, _I, _I]),
     "srh_regularizers_fwd": (C.c_int, [_p(SrhRegularizerParams)] + [_V] * 5 + [_Z] + [_V] * 3),
     "srh_regularizers_bwd": (C.c_int, [_p(SrhRegularizerParams)] + [_V] * 11),

@@ -1,7 +1,7 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
-// srh_reverse_projection.h, srh_dense_projection.h.
+// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -26,6 +26,7 @@
 #include "srh_backward.h"
 #include "srh_shadow.h"
 #include "srh_splat.h"
+#include "srh_splat_ndc.h"
 #include "srh_regularizers.h"
 #include "srh_projection.h"
 #include "srh_reverse_projection.h"
@@ -1357,6 +1358,95 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
   hipLaunchKernelGGL(k_splat_bwd, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws);
   if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
   return launch_status("splat backward launch");
+}
+
+}  // extern "C"
+
+// ---- the NDC splat renderer (srh_splat_ndc.h) --------------------------------------------------------------------
+namespace {
+
+// argument checks (no HIP call) and the device view of an NDC splat launch
+int splat_ndc_setup(const SrhSplatNdcParams* p, const SrhSplatNdcInputs* in, const SrhLights* lights,
+                    const SrhMaterials* mats, SplatNdcDev* D) {
+  if (!p || !in) return fail(SRH_E_NULL, "params / inputs is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "grid")) return rc;
+  if (p->pos_cols != 3 && p->pos_cols != 4) return fail(SRH_E_RANGE, "pos_cols = %d, expected 3 or 4", p->pos_cols);
+  if (!(p->fovy > 0.0) || !(p->fovy < M_PI)) return fail(SRH_E_RANGE, "fovy = %g, expected a value in (0, pi)", p->fovy);
+  if (!(p->near_clip > 0.0) || !(p->near_clip < p->far_clip) || !(p->far_clip < HUGE_VAL))
+    return fail(SRH_E_RANGE, "near_clip = %g, far_clip = %g, expected 0 < near_clip < far_clip", p->near_clip, p->far_clip);
+  if (!in->pos || !in->eye) return fail(SRH_E_NULL, "inputs.pos / inputs.eye is NULL");
+  if (p->shade && !in->normal) return fail(SRH_E_NULL, "inputs.normal is NULL");
+  if (in->pos_view_stride < 0 || in->normal_view_stride < 0 || in->eye_view_stride < 0 || in->lights_pos_view_stride < 0)
+    return fail(SRH_E_RANGE, "negative view stride");
+  if (!lights || !mats) return fail(SRH_E_NULL, "lights / materials is NULL");
+  if (p->shade) {
+    if (lights->n_lights < 1 || lights->n_lights > SRH_MAX_LIGHTS)
+      return fail(SRH_E_RANGE, "n_lights = %d, expected 1..%d", lights->n_lights, SRH_MAX_LIGHTS);
+    if (int rc = check_lights_materials(lights, mats)) return rc;
+  }
+  const double up2 = p->up[0] * p->up[0] + p->up[1] * p->up[1] + p->up[2] * p->up[2];
+  if (!(up2 > 0.0)) return fail(SRH_E_CAMERA, "degenerate camera: camera.up is zero");
+  memset(D, 0, sizeof(*D));
+  SplatDev* S = &D->S;
+  S->B = p->n_views; S->W = p->width; S->H = p->height; S->K = 1; S->N = p->width * p->height;
+  S->pos_cols = p->pos_cols; S->use_quartic = p->use_quartic != 0; S->shade = p->shade != 0;
+  S->nlights = p->shade ? lights->n_lights : 0;
+  S->ncolors = lights->n_colors; S->nmat = mats->n_materials;
+  const double ui = 1.0 / eps_len(p->up);
+  for (int k = 0; k < 3; ++k) { S->at[k] = p->at[k]; S->up[k] = p->up[k] * ui; }
+  S->pos = in->pos; S->pos_vs = in->pos_view_stride;
+  S->normal = in->normal; S->nrm_vs = in->normal_view_stride;
+  S->eye = in->eye; S->eye_vs = in->eye_view_stride;
+  S->lpos = lights->pos; S->lpos_vs = in->lights_pos_view_stride;
+  S->lcidx = lights->color_idx; S->colors = lights->colors; S->latt = lights->attenuation; S->amb = lights->ambient;
+  S->mat = in->material_idx; S->albedo = mats->albedo; S->coeffs = mats->coeffs;
+  D->double_sided = p->double_sided != 0;
+  // perspective_NO_params (diffrend/torch/ops.py:6-20) with the reference's true division for the aspect
+  const double aspect = (double)p->width / (double)p->height, t = tan(p->fovy / 2.0);
+  D->m00 = 1.0 / (aspect * t);
+  D->m11 = 1.0 / t;
+  D->m22 = (p->near_clip + p->far_clip) / (p->far_clip - p->near_clip);
+  D->m23 = -2.0 * p->near_clip * p->far_clip / (p->far_clip - p->near_clip);
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srh_splat_ndc_fwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                      const SrhMaterials* materials, float* image, float* depth, float* pos, void* stream) {
+  SplatNdcDev D;
+  int rc = splat_ndc_setup(params, inputs, lights, materials, &D);
+  if (rc) return rc;
+  if (!depth || !pos || (D.S.shade && !image)) return fail(SRH_E_NULL, "an output buffer is NULL");
+  const dim3 grid((D.S.N + 255) / 256, D.S.B);
+  hipLaunchKernelGGL(k_splat_ndc_fwd, grid, dim3(256), 0, (hipStream_t)stream, D, image, depth, pos);
+  return launch_status("k_splat_ndc_fwd launch");
+}
+
+int srh_splat_ndc_bwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                      const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
+                      const float* grad_pos, const SrhSplatNdcGrads* grads, void* stream) {
+  SplatNdcDev D;
+  int rc = splat_ndc_setup(params, inputs, lights, materials, &D);
+  if (rc) return rc;
+  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
+  if (!grad_image && !grad_depth && !grad_pos)
+    return fail(SRH_E_NULL, "grad_image, grad_depth and grad_pos are all NULL");
+  if (!grads->pos && !grads->normal && !grads->lights_pos && !grads->colors && !grads->attenuation && !grads->ambient &&
+      !grads->albedo && !grads->coeffs)
+    return fail(SRH_E_NULL, "the gradient buffers of grads are all NULL");
+  if (!D.S.shade && (grad_image || grads->lights_pos || grads->colors || grads->attenuation || grads->ambient ||
+                     grads->albedo || grads->coeffs))
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image or shading gradients");
+  SplatGradsDev G;
+  memset(&G, 0, sizeof(G));
+  G.pos = grads->pos; G.normal = grads->normal; G.lpos = grads->lights_pos; G.colors = grads->colors;
+  G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo; G.coeffs = grads->coeffs;
+  const dim3 grid((D.S.N + 255) / 256, D.S.B);
+  hipLaunchKernelGGL(k_splat_ndc_bwd, grid, dim3(256), 0, (hipStream_t)stream, D, G, grad_image, grad_depth, grad_pos);
+  return launch_status("k_splat_ndc_bwd launch");
 }
 
 }  // extern "C"
