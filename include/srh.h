@@ -771,6 +771,73 @@ int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const doubl
                              void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
                              float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The depth-map-to-surfels front end of the reference's re-projection loops (diffrend/torch/projection_layer.py:749-750:
+ * cam_to_world_batched(z_to_pcl_CC_batched(-depth, camera), None, camera)['pos']), for B views per call.  Pixel
+ * q = i W + j of a view with depth d = max(depth, 0) (positive in front of the camera) becomes
+ *   P_cc = (d x_j / f, d y_i / f, -d),  x_j = fp32(linspace(-1, 1, W)_j w / 2),  y_i = fp32(linspace(1, -1, H)_i h / 2)
+ * (numpy's linspace, the grid of srh_splat_fwd), and in the world frame P_wc = R P_cc + eye.  fp64 arithmetic, one fp32
+ * store per element, no atomic, every element written once.  The camera is not differentiable.  Added without an ABI
+ * version change.  Conventions as above: caller-owned device buffers, enqueue only, no synchronisation or allocation,
+ * argument checks before any HIP call.  No workspace.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_SURFELS_FRAME_CAMERA 0      /* P_cc */
+#define SRH_SURFELS_FRAME_WORLD 1       /* P_wc */
+
+typedef struct SrhSurfelsParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24; N = W H pixels per view */
+  int32_t frame;                /* SRH_SURFELS_FRAME_* */
+  double fovy, focal_length;    /* shared by the views: 0 < fovy < pi, focal_length > 0 */
+} SrhSurfelsParams;
+
+/* view (B, 12) fp64: each view's camera-to-world matrix [R | eye], 3 rows of 4 -- needed for the world frame, not looked
+ * at for the camera frame; depth (B, N) fp32; out (B, N, 3) fp32 is written. */
+int srh_depth_to_surfels_fwd(const SrhSurfelsParams* params, const double* view, const float* depth, float* out,
+                             void* stream);
+
+/* Vector-Jacobian product: g_out (B, N, 3) fp32; grad_depth (B, N) fp32 is WRITTEN, every element once, exactly 0 where
+ * depth <= 0. */
+int srh_depth_to_surfels_bwd(const SrhSurfelsParams* params, const double* view, const float* depth, const float* g_out,
+                             float* grad_depth, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's hard scatter-mean projection, projection_renderer (diffrend/torch/projection_layer.py:88-106), for B
+ * views per call: each of the N = W H surfels of a view lands on the pixel nearest to its projection (round half to
+ * even; outside the frame, NaN or beyond an int: dropped), and a pixel gets the mean of the values that land on it, 0
+ * where none does.  Restated as a gather: no float atomic, fp64 sums in ascending surfel index, fp32 results, values and
+ * gradients identical from run to run.  mask is 1 WHERE NOTHING LANDED -- the reference's sense, the opposite of the
+ * soft masks of the other projection layers.  Only rgb is differentiable.
+ *
+ * One forward is three steps, because the ordering is the caller's, as for srh_projection_*:
+ *   srh_hard_projection_keys   keys (B, N) int32: the surfel's pixel y W + x, N for a dropped surfel
+ *   the caller                 order (B, N) int32: per view a STABLE ASCENDING permutation of that view's keys
+ *   srh_hard_projection_fwd    the rest.
+ * Added without an ABI version change.  Conventions as above: caller-owned device buffers, enqueue only, no
+ * synchronisation or allocation, argument checks before any HIP call.  No workspace.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhHardProjectionParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24; N = W H surfels per view */
+  int32_t channels;             /* D in 1..SRH_PROJ_MAX_CHANNELS */
+  double fovy, focal_length;    /* shared by the views: 0 < fovy < pi, focal_length > 0 */
+} SrhHardProjectionParams;
+
+/* view (B, 12) fp64: each view's world-to-camera matrix, 3 rows of 4; surfels (B, N, 3) fp32; keys (B, N) int32 out */
+int srh_hard_projection_keys(const SrhHardProjectionParams* params, const double* view, const float* surfels,
+                             int32_t* keys, void* stream);
+
+/* rgb (B, N, D) fp32; keys as srh_hard_projection_keys left them; order: per view a stable ascending permutation of the
+ * keys (an entry outside 0..N-1 is skipped).  out (B, N, D) fp32, mask (B, N) bytes (1 = no surfel landed) and count
+ * (B, N) int32 (kept for the backward) are written, every element once. */
+int srh_hard_projection_fwd(const SrhHardProjectionParams* params, const float* rgb, const int32_t* keys,
+                            const int32_t* order, float* out, uint8_t* mask, int32_t* count, void* stream);
+
+/* Vector-Jacobian product: keys and count as the forward left them, g_out (B, N, D) fp32; grad_rgb (B, N, D) fp32 is
+ * WRITTEN, every element once, 0 for a dropped surfel. */
+int srh_hard_projection_bwd(const SrhHardProjectionParams* params, const int32_t* keys, const int32_t* count,
+                            const float* g_out, float* grad_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

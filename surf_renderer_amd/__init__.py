@@ -18,8 +18,11 @@ _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 _PROJECTION = ("projection_renderer_differentiable_fast",)
 _REVERSE_PROJECTION = ("projection_reverse_renderer",)
 _DENSE_PROJECTION = ("projection_renderer_differentiable",)
+_SURFELS = ("depth_to_surfels",)
+_HARD_PROJECTION = ("projection_renderer",)
 
-__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION]
+__all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION,
+           *_SURFELS, *_HARD_PROJECTION]
 
 
 def __getattr__(name):
@@ -39,6 +42,10 @@ def __getattr__(name):
         return getattr(importlib.import_module(".reverse_projection", __name__), name)
     if name in _DENSE_PROJECTION:
         return getattr(importlib.import_module(".dense_projection", __name__), name)
+    if name in _SURFELS:
+        return getattr(importlib.import_module(".surfels", __name__), name)
+    if name in _HARD_PROJECTION:
+        return getattr(importlib.import_module(".hard_projection", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -28,6 +28,15 @@ def view_matrices(eye: torch.Tensor, at: torch.Tensor, up: torch.Tensor) -> torc
     return torch.linalg.inv(inv)[:, :3, :]
 
 
+def inverse_view_matrices(eye: torch.Tensor, at: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
+    """The first three rows [B, 3, 4] of the reference's lookat_inv(eye, at, up) (torch/utils.py:385-427) of [B, 3]
+    float64 triples: [x y z | eye], which takes a camera-space point to world coordinates."""
+    z = _normalize(eye - at)
+    x = _normalize(torch.cross(_normalize(up), z, dim=-1))
+    y = torch.cross(z, x, dim=-1)
+    return torch.cat((torch.stack((x, y, z), dim=-1), eye[..., None]), dim=-1)
+
+
 def _host(v):
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
@@ -51,10 +60,11 @@ def camera_frame(name: str, camera: Mapping, label: str = "camera") -> Tuple[int
     return W, H
 
 
-def camera_views(name: str, camera: Mapping, B: int, label: str = "camera") -> Tuple[float, float, torch.Tensor]:
+def camera_views(name: str, camera: Mapping, B: int, label: str = "camera",
+                 to_world: bool = False) -> Tuple[float, float, torch.Tensor]:
     """The second half, once the batch size is known: fovy and focal_length in range, eye / at / up finite [B, 3] or
     [B, 4] under the reference's w conventions and not degenerate.  Returns (fovy, focal_length, the per-view matrices
-    [B, 3, 4] float64 on the host)."""
+    [B, 3, 4] float64 on the host): world to camera, or with `to_world` camera to world."""
     fovy, focal = float(_host(camera["fovy"]).reshape(-1)[0]), float(_host(camera["focal_length"]).reshape(-1)[0])
     if not 0 < fovy < math.pi:
         raise ValueError(f"{name}: {label}['fovy'] = {fovy}, expected 0 < fovy < pi")
@@ -75,4 +85,4 @@ def camera_views(name: str, camera: Mapping, B: int, label: str = "camera") -> T
         raise ValueError(f"{name}: {label}['eye'] == {label}['at']")
     if torch.any(torch.linalg.cross(cam["up"], cam["eye"] - cam["at"]).abs().amax(-1) == 0):
         raise ValueError(f"{name}: {label}['up'] is zero or parallel to eye - at")
-    return fovy, focal, view_matrices(cam["eye"], cam["at"], cam["up"])
+    return fovy, focal, (inverse_view_matrices if to_world else view_matrices)(cam["eye"], cam["at"], cam["up"])

@@ -148,6 +148,19 @@ class SrhDenseProjectionParams(C.Structure):
                 ("focal_length", C.c_double)]
 
 
+SURFELS_FRAME = {"camera": 0, "world": 1}
+
+
+class SrhSurfelsParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("frame", C.c_int32),
+                ("fovy", C.c_double), ("focal_length", C.c_double)]
+
+
+class SrhHardProjectionParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("fovy", C.c_double), ("focal_length", C.c_double)]
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -201,6 +214,11 @@ SIGNATURES = {
     "srh_dense_projection_workspace_bytes": (_Z, [_p(SrhDenseProjectionParams), _I]),
     "srh_dense_projection_fwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 3),
     "srh_dense_projection_bwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 6),
+    "srh_depth_to_surfels_fwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 4),
+    "srh_depth_to_surfels_bwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 5),
+    "srh_hard_projection_keys": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 4),
+    "srh_hard_projection_fwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 7),
+    "srh_hard_projection_bwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 5),
 }
 EXPORTS = tuple(SIGNATURES)
 

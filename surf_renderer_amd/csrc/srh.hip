@@ -1,7 +1,7 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
-// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h.
+// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -31,6 +31,8 @@
 #include "srh_projection.h"
 #include "srh_reverse_projection.h"
 #include "srh_dense_projection.h"
+#include "srh_surfels.h"
+#include "srh_hard_projection.h"
 
 using namespace srh;
 
@@ -1959,6 +1961,113 @@ int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const doubl
     });
   }
   return launch_status("dense projection backward launch");
+}
+
+}  // extern "C"
+
+// ---- the depth lift (srh_surfels.h) ------------------------------------------------------------------------------
+namespace {
+
+static_assert(kSurfFrameCamera == SRH_SURFELS_FRAME_CAMERA && kSurfFrameWorld == SRH_SURFELS_FRAME_WORLD,
+              "srh.h and srh_surfels.h");
+
+// argument checks (no HIP call) and the device view of a lift; the view table is needed for the world frame only
+int surf_setup(const SrhSurfelsParams* p, const double* view, SurfDev* S) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_batch_grid(p->n_views, p->width, p->height, "width x height =")) return rc;
+  if (p->frame != SRH_SURFELS_FRAME_CAMERA && p->frame != SRH_SURFELS_FRAME_WORLD)
+    return fail(SRH_E_TYPE, "frame = %d, expected SRH_SURFELS_FRAME_CAMERA or _WORLD", p->frame);
+  if (int rc = check_pinhole("", p->fovy, p->focal_length)) return rc;
+  if (p->frame == SRH_SURFELS_FRAME_WORLD && !view) return fail(SRH_E_NULL, "view is NULL");
+  memset(S, 0, sizeof(*S));
+  S->B = p->n_views; S->W = p->width; S->H = p->height; S->N = p->width * p->height; S->frame = p->frame;
+  S->nblk = (S->N + kSurfBlock - 1) / kSurfBlock;
+  const FrameSize fs = frame_size(p->fovy, p->focal_length, p->width, p->height);
+  S->f = p->focal_length; S->half_w = fs.w / 2; S->half_h = fs.h / 2;
+  S->step_x = p->width > 1 ? 2.0 / (p->width - 1) : 0.0;
+  S->step_y = p->height > 1 ? -2.0 / (p->height - 1) : 0.0;
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srh_depth_to_surfels_fwd(const SrhSurfelsParams* params, const double* view, const float* depth, float* out,
+                             void* stream) {
+  SurfDev S;
+  int rc = surf_setup(params, view, &S);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"depth", depth}, {"out", out}}))) return rc;
+  hipLaunchKernelGGL(k_surfels_fwd, dim3(S.nblk, S.B), dim3(kSurfBlock), 0, (hipStream_t)stream, S, view, depth, out);
+  return launch_status("k_surfels_fwd launch");
+}
+
+int srh_depth_to_surfels_bwd(const SrhSurfelsParams* params, const double* view, const float* depth, const float* g_out,
+                             float* grad_depth, void* stream) {
+  SurfDev S;
+  int rc = surf_setup(params, view, &S);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"depth", depth}, {"g_out", g_out}, {"grad_depth", grad_depth}}))) return rc;
+  hipLaunchKernelGGL(k_surfels_bwd, dim3(S.nblk, S.B), dim3(kSurfBlock), 0, (hipStream_t)stream, S, view, depth, g_out,
+                     grad_depth);
+  return launch_status("k_surfels_bwd launch");
+}
+
+}  // extern "C"
+
+// ---- the hard scatter-mean projection (srh_hard_projection.h) ----------------------------------------------------
+namespace {
+
+// argument checks (no HIP call) and the device view of a hard projection launch
+int hproj_setup(const SrhHardProjectionParams* p, HProjDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_proj_frame(p->n_views, p->width, p->height, p->channels)) return rc;
+  if (int rc = check_pinhole("", p->fovy, p->focal_length)) return rc;
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->W = p->width; P->H = p->height; P->N = p->width * p->height; P->D = p->channels;
+  P->nblk = (P->N + kProjBlock - 1) / kProjBlock;
+  const PixelScales s = pixel_scales(p->fovy, p->focal_length, P->W, P->H);
+  P->fsx = s.fsx; P->fsy = s.fsy; P->cx0 = s.cx0; P->cy0 = s.cy0;
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srh_hard_projection_keys(const SrhHardProjectionParams* params, const double* view, const float* surfels,
+                             int32_t* keys, void* stream) {
+  HProjDev P;
+  int rc = hproj_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"keys", keys}}))) return rc;
+  hipLaunchKernelGGL(k_hproj_keys, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, view, surfels, keys);
+  return launch_status("k_hproj_keys launch");
+}
+
+int srh_hard_projection_fwd(const SrhHardProjectionParams* params, const float* rgb, const int32_t* keys,
+                            const int32_t* order, float* out, uint8_t* mask, int32_t* count, void* stream) {
+  HProjDev P;
+  int rc = hproj_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"rgb", rgb}, {"keys", keys}, {"order", order}, {"out", out}, {"mask", mask},
+                            {"count", count}})))
+    return rc;
+  hipLaunchKernelGGL(k_hproj_gather, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, keys, order, rgb,
+                     out, mask, count);
+  return launch_status("k_hproj_gather launch");
+}
+
+int srh_hard_projection_bwd(const SrhHardProjectionParams* params, const int32_t* keys, const int32_t* count,
+                            const float* g_out, float* grad_rgb, void* stream) {
+  HProjDev P;
+  int rc = hproj_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"keys", keys}, {"count", count}, {"g_out", g_out}, {"grad_rgb", grad_rgb}}))) return rc;
+  hipLaunchKernelGGL(k_hproj_bwd, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, keys, count, g_out,
+                     grad_rgb);
+  return launch_status("k_hproj_bwd launch");
 }
 
 }  // extern "C"
