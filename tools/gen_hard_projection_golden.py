@@ -6,7 +6,9 @@ its project_image_coordinates gives every surfel in both precisions.
 
 Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by hand -- no test reads
 the reference.  A case of exactly three views is recorded view by view (ref_harness.run_views).  The generator asserts
-the kink condition of every case, and that the float32 and the float64 indices are equal.
+the kink condition of every case, and that the float32 and the float64 indices are equal.  hp2_tie_*.npz are the two tie
+cases of tests/hard_projection_edge_cases.py: surfels placed on exact rounding ties, where the record pins torch.round's
+ties-to-even to the reference itself.
 
 Stored per fixture: in/{surfels, rgb}, in/camera/{eye, at, up, viewport, fovy, focal_length}, grad_in/out (the case's
 upstream gradient), and for P in (ref64, ref32): P/out (like rgb), P/mask (bool, like rgb: True where no surfel landed),
@@ -25,6 +27,7 @@ from oracle import ref_harness as R  # noqa: E402
 
 sys.path.insert(0, os.path.join(R.REPO, "tests"))
 import hard_projection_cases as cases  # noqa: E402
+import hard_projection_edge_cases as edges  # noqa: E402
 import hard_projection_oracle as ho  # noqa: E402
 
 with contextlib.redirect_stdout(io.StringIO()):
@@ -56,9 +59,14 @@ def record(c, dtype):
     return flat
 
 
-def emit(name):
-    c = cases.case(name)
-    assert ho.kink_margin(c["surfels"], c["camera"]) >= 1.0, name
+def emit(name, edge=False):
+    """hp1_<name> for a seeded case; hp2_<name> for a case of tests/hard_projection_edge_cases.py, whose named surfels
+    sit on a rounding tie on purpose and whose other surfels are held to the kink condition."""
+    c = edges.case(name) if edge else cases.case(name)
+    if edge:
+        assert edges.margin(c, c["named"]) >= 1.0, name
+    else:
+        assert ho.kink_margin(c["surfels"], c["camera"]) >= 1.0, name
     flat = {}
     for prefix, dtype in (("ref64", torch.float64), ("ref32", torch.float32)):
         for k, v in record(c, dtype).items():
@@ -68,10 +76,12 @@ def emit(name):
                 flat[k] = v
     assert np.array_equal(flat["ref64/index"], flat["ref32/index"]), name
     assert np.array_equal(flat["ref64/mask"], flat["ref32/mask"]), name
-    R.write("hp1_" + name, flat)
+    R.write(("hp2_" if edge else "hp1_") + name, flat)
 
 
 if __name__ == "__main__":
     R.OUT = R.fixture_dir("hard_projection")
     for n in cases.NAMES:
         emit(n)
+    for n in edges.RECORDED:                   # a list of their own: the seeded fixtures above stay as they are
+        emit(n, edge=True)

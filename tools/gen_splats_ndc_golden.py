@@ -9,8 +9,9 @@ camera scalars as float64), kwargs, grad_in/<output> (upstreams in (-1, 1)), ref
 ref32/<output> (float32) and grad32/<leaf>, and meta: the largest |ref32 - ref64| per array, with its tolerance.  Before
 anything is written the generator asserts the cases' kink margins and both-sides coverage, and that for every array the
 reference's own float32-float64 disagreement is at most a quarter of the float32 tolerance the GPU tests use (outputs
-2e-5 max(max|want|, 1); gradients 3e-3 max(max|want|, 1e-6)).  The subfolder keeps the fixtures out of the top-level
-globs (the golden drift check, conftest.golden_cases)."""
+2e-5 max(max|want|, 1); gradients 3e-3 max(max|want|, 1e-6)).  sn2_*.npz are the edge cases of tests/
+splats_ndc_edge_cases.py (wave-uniform materials, zero normals), recorded the same way.  The subfolder keeps the
+fixtures out of the top-level globs (the golden drift check, conftest.golden_cases)."""
 import json
 import os
 import sys
@@ -23,6 +24,7 @@ from oracle import ref_harness as R  # noqa: E402
 
 sys.path.insert(0, os.path.join(R.REPO, "tests"))
 import splats_ndc_cases as cases  # noqa: E402
+import splats_ndc_edge_cases as edges  # noqa: E402
 import splats_ndc_oracle as oracle  # noqa: E402
 
 
@@ -59,6 +61,20 @@ def emit(name, all_margins):
     assert all(v[0] >= cases.MARGIN for v in m.values()), (name, m)
     cases.check_special(c)
     all_margins.append(m)
+    record("sn1_" + name, c)
+
+
+def emit_edge(name):
+    """sn2_<name>: a case of tests/splats_ndc_edge_cases.py.  Its at_kink splats sit on a kink on purpose -- where a
+    restatement can drift from the function it restates -- and every other splat is held to the margins."""
+    c = edges.case(name)
+    m = edges.margins(c)
+    assert all(v[0] >= cases.MARGIN for v in m.values()), (name, m)
+    record("sn2_" + name, c)
+
+
+def record(fixture, c):
+    name = c["name"]
     ref64, grad64 = reference(c, torch.float64)
     ref32, grad32 = reference(c, torch.float32)
     out = oracle.pack(c["scene"])
@@ -78,7 +94,9 @@ def emit(name, all_margins):
         meta["grad/" + k] = {"err": err, "tol": tol, "max": float(np.abs(grad64[k]).max())}
         assert err <= tol / 4, (name, k, err, tol)
     out["meta"] = np.asarray(json.dumps(meta, sort_keys=True))
-    R.write("sn1_" + name, out)
+    for k, v in out.items():
+        assert v.dtype.kind not in "fc" or np.all(np.isfinite(v)), (name, k)
+    R.write(fixture, out)
 
 
 if __name__ == "__main__":
@@ -88,3 +106,5 @@ if __name__ == "__main__":
         emit(n, seen)
     cov = cases.coverage(seen)
     assert all(cov.values()), cov
+    for n in edges.RECORDED:                   # a list of their own: the seeded fixtures above stay as they are
+        emit_edge(n)
