@@ -838,6 +838,33 @@ int srh_hard_projection_fwd(const SrhHardProjectionParams* params, const float* 
 int srh_hard_projection_bwd(const SrhHardProjectionParams* params, const int32_t* keys, const int32_t* count,
                             const float* g_out, float* grad_rgb, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's constrained plane fit as a layer of its own, estimate_surface_normals_plane_fit_batched
+ * (diffrend/torch/utils.py:926-963), for B views per call: a grid of N = W H arbitrary points per view, row by row, to
+ * one unit normal per point with nz > 0.  At centre c, over the 8 neighbours k of the reflected 3 x 3 stencil (dy-major),
+ *   u_k = (P_k - P_c) / sqrt(|P_k - P_c|^2 + 3e-10),  a = sum ux^2, b = sum ux uy, d = sum uy^2, r = -(sum ux uz, sum uy uz)
+ *   (nx, ny) = adj([[a, b], [b, d]]) r / (a d - b^2 + 1e-12),  n = (nx, ny, 1) / sqrt(nx^2 + ny^2 + 1 + 3e-10).
+ * rot (B, 9) fp64, row-major: each view's orthonormal lookat basis R = [x y z]; the stored normal is then R n, the value
+ * of cam_to_world_batched(None, n, camera)['normal'].  rot = NULL: the camera frame, n as it is.  The rotation is not
+ * differentiable.  fp64 arithmetic, one fp32 store per element, no atomic, every element written once, results
+ * identical from run to run, and a view's result does not depend on its batch.  Reflection cannot pad a side of 1:
+ * W, H >= 2.  Added without an ABI version change.  Conventions as above: caller-owned device buffers, enqueue only, no
+ * synchronisation or allocation, argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+/* Bytes of the backward's workspace (five fp64 per point: the gradients of the fit's moments), never 0 for valid sizes;
+ * 0 and srh_last_error for n_views outside 1..65535, a side below 2 or W H > 2^24. */
+size_t srh_normals_workspace_bytes(int32_t n_views, int32_t width, int32_t height);
+
+/* pos (B, N, 3) fp32; out (B, N, 3) fp32 is written.  No workspace. */
+int srh_normals_fwd(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos, float* out,
+                    void* stream);
+
+/* Vector-Jacobian product: g_out (B, N, 3) fp32 (with rot, taken back through R^T first); grad_pos (B, N, 3) fp32 is
+ * WRITTEN, every element once, all three components.  workspace: 8-byte aligned, srh_normals_workspace_bytes, contents
+ * immaterial before and after. */
+int srh_normals_bwd(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos,
+                    const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,9 +20,10 @@ _REVERSE_PROJECTION = ("projection_reverse_renderer",)
 _DENSE_PROJECTION = ("projection_renderer_differentiable",)
 _SURFELS = ("depth_to_surfels",)
 _HARD_PROJECTION = ("projection_renderer",)
+_NORMALS = ("estimate_surface_normals_plane_fit_batched", "estimate_surface_normals_plane_fit", "estimate_surface_normals")
 
 __all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION,
-           *_SURFELS, *_HARD_PROJECTION]
+           *_SURFELS, *_HARD_PROJECTION, *_NORMALS]
 
 
 def __getattr__(name):
@@ -46,6 +47,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".surfels", __name__), name)
     if name in _HARD_PROJECTION:
         return getattr(importlib.import_module(".hard_projection", __name__), name)
+    if name in _NORMALS:
+        return getattr(importlib.import_module(".normals", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

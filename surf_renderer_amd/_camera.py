@@ -44,13 +44,23 @@ def _host(v):
 def camera_frame(name: str, camera: Mapping, label: str = "camera") -> Tuple[int, int]:
     """The first half of the camera checks (ValueError, prefixed `name`, the camera called `label`): every entry is
     there, none requires grad, and the viewport is a frame.  Returns (W, H)."""
-    for k in ("eye", "at", "up", "viewport", "fovy", "focal_length"):
+    camera_entries(name, camera, ("eye", "at", "up", "viewport", "fovy", "focal_length"), label)
+    return camera_viewport(name, camera, label)
+
+
+def camera_entries(name: str, camera: Mapping, keys, label: str = "camera") -> None:
+    """Every entry among `keys` is there and no entry requires grad (ValueError)."""
+    for k in keys:
         if k not in camera or camera[k] is None:
             raise ValueError(f"{name}: {label}['{k}'] is missing")
     for k, v in camera.items():
         if isinstance(v, torch.Tensor) and v.requires_grad:
             raise ValueError(f"{name}: {label}['{k}'] requires grad, but the camera is not differentiable on this "
                              "path (detach it)")
+
+
+def camera_viewport(name: str, camera: Mapping, label: str = "camera") -> Tuple[int, int]:
+    """(W, H) of the camera's viewport, which must be a frame (ValueError)."""
     vp = _host(camera["viewport"]).reshape(-1)
     if vp.size != 4:
         raise ValueError(f"{name}: {label}['viewport']: expected 4 values, got {vp.size}")
@@ -70,6 +80,13 @@ def camera_views(name: str, camera: Mapping, B: int, label: str = "camera",
         raise ValueError(f"{name}: {label}['fovy'] = {fovy}, expected 0 < fovy < pi")
     if not (math.isfinite(focal) and focal > 0):
         raise ValueError(f"{name}: {label}['focal_length'] = {focal}, expected positive and finite")
+    cam = camera_vectors(name, camera, B, label)
+    return fovy, focal, (inverse_view_matrices if to_world else view_matrices)(cam["eye"], cam["at"], cam["up"])
+
+
+def camera_vectors(name: str, camera: Mapping, B: int, label: str = "camera") -> Mapping[str, torch.Tensor]:
+    """eye / at / up as [B, 3] float64 on the host: finite [B, 3] or [B, 4] under the reference's w conventions and not
+    degenerate (ValueError)."""
     cam = {}
     for k in ("eye", "at", "up"):
         v = np.asarray(_host(camera[k]), dtype=np.float64)
@@ -85,4 +102,4 @@ def camera_views(name: str, camera: Mapping, B: int, label: str = "camera",
         raise ValueError(f"{name}: {label}['eye'] == {label}['at']")
     if torch.any(torch.linalg.cross(cam["up"], cam["eye"] - cam["at"]).abs().amax(-1) == 0):
         raise ValueError(f"{name}: {label}['up'] is zero or parallel to eye - at")
-    return fovy, focal, (inverse_view_matrices if to_world else view_matrices)(cam["eye"], cam["at"], cam["up"])
+    return cam

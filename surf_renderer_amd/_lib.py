@@ -219,6 +219,9 @@ SIGNATURES = {
     "srh_hard_projection_keys": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 4),
     "srh_hard_projection_fwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 7),
     "srh_hard_projection_bwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 5),
+    "srh_normals_workspace_bytes": (_Z, [_I, _I, _I]),
+    "srh_normals_fwd": (C.c_int, [_I, _I, _I] + [_V] * 4),
+    "srh_normals_bwd": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1,7 +1,7 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
-// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h.
+// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h, srh_normals.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -33,6 +33,7 @@
 #include "srh_dense_projection.h"
 #include "srh_surfels.h"
 #include "srh_hard_projection.h"
+#include "srh_normals.h"
 
 using namespace srh;
 
@@ -2068,6 +2069,60 @@ int srh_hard_projection_bwd(const SrhHardProjectionParams* params, const int32_t
   hipLaunchKernelGGL(k_hproj_bwd, dim3(P.nblk, P.B), dim3(kProjBlock), 0, (hipStream_t)stream, P, keys, count, g_out,
                      grad_rgb);
   return launch_status("k_hproj_bwd launch");
+}
+
+}  // extern "C"
+
+// ---- normals from a grid of points (srh_normals.h) ---------------------------------------------------------------
+namespace {
+
+size_t norm_ws_bytes(int32_t n_views, int32_t width, int32_t height) {
+  return (size_t)n_views * width * height * kNormMoments * sizeof(double);
+}
+
+// argument checks (no HIP call) and the device view of a plane-fit launch.  Every index in srh_normals.h is a size_t
+// built from q < W H <= 2^24 and b < 65536, so check_batch_grid's limits are the 32-bit limits too.
+int norm_setup(int32_t n_views, int32_t width, int32_t height, NormDev* S) {
+  if (int rc = check_batch_grid(n_views, width, height, "width x height =")) return rc;
+  if (width < 2 || height < 2)
+    return fail(SRH_E_RANGE, "width x height = %d x %d: the reflected 3 x 3 stencil needs both sides >= 2", width, height);
+  S->B = n_views; S->W = width; S->H = height; S->N = width * height;
+  S->nblk = (S->N + kNormBlock - 1) / kNormBlock;
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t srh_normals_workspace_bytes(int32_t n_views, int32_t width, int32_t height) {
+  NormDev S;
+  if (norm_setup(n_views, width, height, &S)) return 0;
+  return norm_ws_bytes(n_views, width, height);
+}
+
+int srh_normals_fwd(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos, float* out,
+                    void* stream) {
+  NormDev S;
+  int rc = norm_setup(n_views, width, height, &S);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"pos", pos}, {"out", out}}))) return rc;
+  hipLaunchKernelGGL(k_normals_fwd, dim3(S.nblk, S.B), dim3(kNormBlock), 0, (hipStream_t)stream, S, rot, pos, out);
+  return launch_status("k_normals_fwd launch");
+}
+
+int srh_normals_bwd(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos,
+                    const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, void* stream) {
+  NormDev S;
+  int rc = norm_setup(n_views, width, height, &S);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"pos", pos}, {"g_out", g_out}, {"grad_pos", grad_pos}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, norm_ws_bytes(S.B, S.W, S.H)))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_normals_bwd, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, rot, pos, g_out, (double*)workspace);
+  hipLaunchKernelGGL(k_normals_gather, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, pos, (const double*)workspace,
+                     grad_pos);
+  return launch_status("normals backward launch");
 }
 
 }  // extern "C"
