@@ -31,11 +31,12 @@ __device__ __forceinline__ int segment_of(const FrameDev& F, int gidx) {
 // ---- tile range of one primitive (called from k_prep) ------------------------------------------------
 struct TileBox { int tx0, ty0, tx1, ty1; };        // inclusive; tx0 > tx1: not binned (no pixel, or on the large list)
 
-__device__ inline TileBox bin_primitive(const FrameDev& F, int seg, int type, const float* rec32, int gidx,
-                                        uint32_t set, bool force_large = false) {
+// `conic`: the half extents of a disc's or a sphere's stored shape, as its record function left them (conic_record)
+__device__ inline TileBox bin_primitive(const FrameDev& F, int seg, int type, const float* rec32, const ConicExtent& conic,
+                                        int gidx, uint32_t set, bool force_large = false) {
   BBox b = bbox_full();
   if (force_large) { /* keep the full box */ }
-  else if (type == SRH_PRIM_DISK || type == SRH_PRIM_SPHERE) b = conic_bbox(rec32);
+  else if (type == SRH_PRIM_DISK || type == SRH_PRIM_SPHERE) b = conic_bbox(rec32, conic);
   else if (type == SRH_PRIM_TRIANGLE) b = triangle_bbox(rec32);
   uint16_t* tr = F.tilerange + 4 * (size_t)gidx;
   tr[0] = 1; tr[1] = 0; tr[2] = 0; tr[3] = 0;                    // default: not binned

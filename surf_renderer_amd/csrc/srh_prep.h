@@ -107,7 +107,8 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S.count) return;
   // which set of frame-wide list lengths this frame counts into (srh_device.h: kLargeNext); stable for the whole binning
-  const uint32_t set = F.tilerange ? (F.counters[kLargeNext] & 1u) : 0u;
+  // (the same word for every lane: kept in a scalar register, the vector ones are all taken while the record is built)
+  const uint32_t set = F.tilerange ? ((uint32_t)__builtin_amdgcn_readfirstlane((int)F.counters[kLargeNext]) & 1u) : 0u;
   if (s == 0 && i == 0) {
     if (F.tilerange) F.counters[kLargeNow] = set;          // ... and the render kernel reads the same one
     // per-frame fp64 copy of the lights for the fragment stage: position, colour looked up through color_idx
@@ -132,8 +133,9 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
   float Q[N32];
   const PixelBasis B = pixel_basis(F);
   const bool near_pos = F.near_clip > 0.0;
-  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q);
-  else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q);
+  ConicExtent conic = no_extent();
+  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q, &conic);
+  else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q, &conic);
   else if (TYPE == SRH_PRIM_TRIANGLE) triangle_reject_record(R, F.o, B, F.W, F.H, near_pos, Q);
   else plane_reject_record(R, B, F.W, F.H, Q);
   {
@@ -183,7 +185,7 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
       const float nd = (TYPE != SRH_PRIM_PLANE && dmin > 0.0 && dmin < 1.0e30) ? (float)dmin * 0.999999f : 0.0f;
       F.neardist[S.first + i] = nd;
     }
-    const TileBox box = bin_primitive(F, s, TYPE, Q, S.first + i, set, near_eye);
+    const TileBox box = bin_primitive(F, s, TYPE, Q, conic, S.first + i, set, near_eye);
     if (box.tx0 <= box.tx1) bin_place(F, s, TYPE, S.first, Q, S.first + i, box.tx0, box.ty0, box.tx1, box.ty1, set);
   }
 }

@@ -54,6 +54,30 @@ __device__ inline void rec_zero(float* out, int n) {
   for (int i = 0; i < n; ++i) out[i] = 0.0f;
 }
 
+// ---- cheap reciprocals and roots ---------------------------------------------------------------------
+// An IEEE fp64 division costs k_prep about 11 vector instructions and a square root about 15; rcp_newton and
+// rsqrt_newton (srh_device.h) cost 3 and 5.  Nothing below needs a correctly rounded result: the values feed fp32 records
+// whose margins are 2^-22 and wider.  kFastEps = 2^-44 is the relative error every comment below grants ONE of these
+// operations, the product formed with it included.  tools/ubench_newton.hip measures them against the IEEE results
+// over the whole exponent range (profiles/prep_div_ubench.txt): the largest error found is 2^-47.7, a factor of 13
+// inside kFastEps, and each margin cited below covers kFastEps itself with room to spare.
+// Outside the positive normal range the refined value is NaN where the IEEE one is 0 or inf (x = 0, inf, a result that
+// over- or underflows).  Where the surrounding code already sends a NaN down its "no record" branch (every test there
+// is written !(x > ...)) the bare functions are used; the *_fast forms below return the hardware seed's IEEE special
+// value instead.
+__device__ __forceinline__ double rcp_fast(double x) {          // 1 / x
+  const double y = rcp_newton(x);
+  return (y == y) ? y : __builtin_amdgcn_rcp(x);
+}
+__device__ __forceinline__ double rsqrt_fast(double x) {        // 1 / sqrt(x)
+  const double y = rsqrt_newton(x);
+  return (y == y) ? y : __builtin_amdgcn_rsq(x);
+}
+__device__ __forceinline__ double sqrt_fast(double x) {         // sqrt(x); +-0 and +inf come back as they are
+  const double y = x * rsqrt_newton(x);
+  return __builtin_amdgcn_class(x, 0x260) ? x : y;
+}
+
 // Depth-estimate fields of a planar primitive with unit normal n and plane offset k (see the file header):
 //   u_j = w_j / K  with  w0 = s v0 + E, w1 = s v1, w2 = s v2,  s = sign(k),  K = |k| (1 - 2^-20),  and lo_u, hi_u.
 // The kernel evaluates den = u0 + c u1 + r u2 = (s (n^.D) + E) / K up to an fp32 error below E / K, where
@@ -82,7 +106,12 @@ __device__ inline void plane_estimate_record(const double n[3], double k, const 
   const double e = 1.9073486328125e-6 * (fabs(a) + fabs(b) * W + fabs(c) * H) +
                    3.552713678800501e-15 * (abs_dot3(n, B.D0) + abs_dot3(n, B.Dc) * W + abs_dot3(n, B.Dr) * H);
   const double K = fabs(k) * (1.0 - 9.5367431640625e-7);
-  const double big = (fabs(a) + e + fabs(b) * W + fabs(c) * H) / K, lo = 1025.0 * e / K;
+  // ONE reciprocal of K for the six quotients (kFastEps each; K = 0, denormal or inf makes it NaN or inf and the
+  // estimate is withdrawn below, as with the division).  u0, u1, u2: together they move den by at most
+  // kFastEps (|w0| + W |w1| + H |w2|) / K < 2^-24 E / K, and E = 32 x 2^-24 (...) spends 5 of its 32 units on the
+  // vector path.  lo_u may be ANY positive number; hi_u has 1023 units of E / K where it needs 2.
+  const double iK = rcp_newton(K);
+  const double big = (fabs(a) + e + fabs(b) * W + fabs(c) * H) * iK, lo = 1025.0 * e * iK;
   *unused = 0.0f;
   if (!(K > 0.0) || !isfinite(big) || !(big < 1.0e30) || !(lo > 1.0e-30)) {
     *u0 = 1.0e30f;
@@ -91,14 +120,14 @@ __device__ inline void plane_estimate_record(const double n[3], double k, const 
     *hi_u = -3.0e38f;
     return;
   }
-  *u0 = (float)((sg * a + e) / K); *u1 = (float)(sg * b / K); *u2 = (float)(sg * c / K);
+  *u0 = (float)((sg * a + e) * iK); *u1 = (float)(sg * b * iK); *u2 = (float)(sg * c * iK);
   *lo_u = (float)lo * 1.0000002f;
-  *hi_u = (float)(-1023.0 * e / K) * 1.0000002f;
+  *hi_u = (float)(-1023.0 * e * iK) * 1.0000002f;
 }
 
 // Conic x^T T x <= 0, x = (1, c, r)  ->  inflated, normalised ellipse record out[0..4] (out[11] = 0: the quadratic form
 //   dc (A11 dc + 2A12 dr) + A22 dr^2 - 1 <= 0,  dc = c - c0, dr = r - r0).
-// Returns the major semi-axis in pixels, or -1 (record = "always a candidate") when the conic is not a
+// Returns false (record = "always a candidate") when the conic is not a
 // well-conditioned ellipse: not positive definite, centre or size beyond 2^20 pixels, or axis ratio > 512
 // (a disc seen edge-on; its parameters are then numerical noise).
 //
@@ -120,41 +149,68 @@ __device__ inline void plane_estimate_record(const double n[3], double k, const 
 // rel + 2^-22 of evaluation error, the centre moves by at most delta, and what is left shrinks the radius by another
 // (grow - 1) + 2^-10 of itself for the fp64 path's own roundings (twice the position slack the outward margin grants
 // them, plus 2^-10).  -1e30 when nothing is provably inside.
-__device__ inline double conic_record(double T00, double T01, double T02, double T11, double T12, double T22,
-                                      int W, int H, float* out, double* sure_in = nullptr) {
+// Half extents, in pixels, of the box of a stored ellipse record around its centre (rec[0], rec[1]); hc < 0: the record
+// is "always a candidate", no box.  conic_record has them at hand, conic_bbox makes the box of them.  (fp32, rounded
+// up: they wait in registers while the rest of the record is built, and k_prep has none to spare.)
+struct ConicExtent { float hc, hr; };
+__device__ inline ConicExtent no_extent() { return ConicExtent{-1.0f, -1.0f}; }
+
+// n / d from id = rcp_newton(d): one residual step on the quotient leaves 2^-52 (kFastEps^2 and one rounding), so
+// several quotients share one reciprocal and still carry no more than an IEEE division and one further rounding
+__device__ __forceinline__ double quot_refined(double n, double d, double id) {
+  const double q = n * id;
+  return __builtin_fma(__builtin_fma(-d, q, n), id, q);
+}
+
+// `ext` receives the half extents of the stored record's box (none when there is no record): see the end.
+__device__ inline bool conic_record(double T00, double T01, double T02, double T11, double T12, double T22,
+                                    int W, int H, float* out, ConicExtent* ext, double* sure_in = nullptr) {
   if (sure_in) *sure_in = -1.0e30;
   rec_zero(out, 5);
   out[11] = 0.0f;
+  *ext = no_extent();
   const double det = T11 * T22 - T12 * T12;
-  if (!(T11 > 0.0) || !(det > 0.0) || !isfinite(T00 + T01 + T02 + T11 + T12 + T22)) return -1.0;
-  const double c0 = -(T22 * T01 - T12 * T02) / det;
-  const double r0 = -(T11 * T02 - T12 * T01) / det;
+  if (!(T11 > 0.0) || !(det > 0.0) || !isfinite(T00 + T01 + T02 + T11 + T12 + T22)) return false;
+  // Centre: F0 below is first-order sensitive to it, so the two quotients keep 2^-52 (quot_refined) -- one rounding more
+  // than the products of F0 commit on the same terms.  det denormal or inf: NaN, no record.
+  const double idet = rcp_newton(det);
+  const double c0 = quot_refined(-(T22 * T01 - T12 * T02), det, idet);
+  const double r0 = quot_refined(-(T11 * T02 - T12 * T01), det, idet);
   const double F0 = T00 + T01 * c0 + T02 * r0;                 // value at the centre, < 0 inside
-  if (!(F0 < 0.0)) return -1.0;
-  const double iF = -1.0 / F0;
+  if (!(F0 < 0.0)) return false;
+  // iF and `it` below scale the whole form: kFastEps each, against the 1.4 x 2^-20 Tm that rel keeps spare (see above)
+  const double iF = -rcp_newton(F0);
   const double A11 = T11 * iF, A12 = T12 * iF, A22 = T22 * iF;
+  // IEEE root: lmin cancels, and the two limits below decide whether the disc keeps this record
   const double mean = 0.5 * (A11 + A22), dev = sqrt(0.25 * (A11 - A22) * (A11 - A22) + A12 * A12);
   const double lmax = mean + dev, lmin = mean - dev;
-  if (!(lmin > 0.0) || !isfinite(lmax)) return -1.0;
-  const double smin = 1.0 / sqrt(lmax);
-  const double smax = 1.0 / sqrt(lmin);
+  if (!(lmin > 0.0) || !isfinite(lmax)) return false;
+  // semi-axes smin = 1 / sqrt(lmax) <= smax = 1 / sqrt(lmin): the limits smax < 2^20 and smax <= 512 smin are taken
+  // on the eigenvalues themselves (powers of two: exact), no root and no quotient
   const double far_lim = 1048576.0;
-  if (!(fabs(c0) < far_lim) || !(fabs(r0) < far_lim) || !(smax < far_lim)) return -1.0;
-  if (!(smax <= 512.0 * smin)) return -1.0;
+  if (!(fabs(c0) < far_lim) || !(fabs(r0) < far_lim) || !(lmin > 9.094947017729282e-13)) return false;
+  if (!(lmax <= 262144.0 * lmin)) return false;
   const double dA = A11 * A22 - A12 * A12;
-  if (!(dA > 0.0)) return -1.0;
-  const double idA = 1.0 / dA;
-  const double X = sqrt(A22 * idA) + 34.0, Y = sqrt(A11 * idA) + 34.0;
+  if (!(dA > 0.0)) return false;
+  // half extents of the un-inflated ellipse: kFastEps on each of idA and the two roots, 2^-42 of Tm together -- rel's
+  // spare again.  (An underflowing operand gives NaN, thr is then NaN too: no record.)
+  const double idA = rcp_newton(dA);
+  const double hx2 = A22 * idA, hy2 = A11 * idA;
+  const double hx = hx2 * rsqrt_newton(hx2), hy = hy2 * rsqrt_newton(hy2);
+  const double X = hx + 34.0, Y = hy + 34.0;
   const double Tm = A11 * X * X + 2.0 * fabs(A12) * X * Y + A22 * Y * Y + 1.0;
   // Position: c0, r0 are rounded to fp32 (2^-24 |c0|) and so is c - c0 (2^-24 (W + |c0|)), together
   // < 2^-23 (|c0| + |r0| + W + H) pixels; delta doubles that and adds 2^-12 px.
   const double pos_err = 2.384185791015625e-7 * (fabs(c0) + fabs(r0) + W + H);
   const double delta = 0.000244140625 + pos_err;
   const double rel = 3.814697265625e-6 * Tm;
-  const double grow = 1.0 + delta / smin;
+  // 1 / smin = sqrt(lmax), lmax in [2^-40, inf): kFastEps of grow - 1, which holds twice the position error it needs
+  const double grow = 1.0 + delta * (lmax * rsqrt_newton(lmax));
   const double thr = grow * grow * (1.0 + rel);
-  if (!(thr < 1.0e6)) return -1.0;
-  const double it = 1.0 / thr;
+  // (a convention, not a bound: a form inflated a million-fold rejects nothing worth its test, and the record is
+  // conservative on either side of the limit -- thr's own kFastEps needs no cover here)
+  if (!(thr < 1.0e6)) return false;
+  const double it = rcp_newton(thr);
   out[0] = (float)c0;
   out[1] = (float)r0;
   out[2] = (float)(A11 * it);
@@ -162,7 +218,20 @@ __device__ inline double conic_record(double T00, double T01, double T02, double
   out[4] = (float)(A22 * it);
   const double shrink = 1.0 - 2.0 * (grow - 1.0) - 9.765625e-4;
   if (sure_in && shrink > 0.0) *sure_in = shrink * shrink * it - 1.0 - rel - 4.76837158203125e-7;
-  return smax * sqrt(thr);
+  // Box of the STORED form, from the half extents at hand: those of the inflated fp64 form are sqrt(thr) (hx, hy).  The
+  // stored coefficients are that form's rounded to fp32 (2^-24 each; they are normal numbers: lmin / thr > 2^-60), so
+  // with p = A11 A22, q = A12^2 the stored determinant is at least (p - q) (1 - x), x = 2.0000002 x 2^-24 (p + q) / (p - q),
+  // and its half extents are at most sqrt((1 + 2^-24) / (1 - x)) <= (1 + 2^-24) (1 + x) times those (x <= 0.6;
+  // here (p + q) / (p - q) <= 2 lmax / lmin <= 2^19, x <= 2^-4).  The factor below holds x with 1.001 for the 2^-33 that
+  // dA's own cancellation and idA leave on it, and 2^-22 for the 2^-24, the three kFastEps and every fp64 rounding on
+  // either side: the extents are at least those of the stored coefficients (what conic_bbox computed from the record
+  // until they were handed over), whose box contains every pixel the record can pass.  Round ellipses pay 2^-21 of
+  // their size.  (A12 alone may round to a denormal fp32: 2^-150 absolute, nothing against p - q > 2^-120.)
+  const double x = 1.1933e-7 * ((A11 * A22 + A12 * A12) * idA);
+  const double widen = (thr * rsqrt_newton(thr)) * (1.0 + 2.384185791015625e-7 + x);
+  const double hc = hx * widen, hr = hy * widen;
+  if (hc < 1.0e30 && hr < 1.0e30) *ext = ConicExtent{(float)hc * 1.0000002f, (float)hr * 1.0000002f};
+  return true;
 }
 
 // Upper bound of 1 / t for every hit inside the ball of radius r around the point at eye-relative position -oc:
@@ -170,12 +239,24 @@ __device__ inline double conic_record(double T00, double T01, double T02, double
 // fp64 side: |oc| - r cancels when the eye is close to the ball's surface relative to its size, and the exact path's
 // own distance (q = oc + t d against r^2, or the sphere's root -b - sqrt(b^2 - 4 a c)) is then off by up to
 // 2^-24 (|oc| + r) (square root of 2^-51 of the squared terms): the bound gives up 2^-22 (|oc| + r), four times that.
-__device__ inline float ball_inverse_depth_bound(const double oc[3], double r) {
-  const double l = sqrt(dot3(oc, oc));
+// l = |oc| and r may come from sqrt_fast: kFastEps (l + r) is 2^-20 of the three parts of 2^-24 (l + r) left over.
+// The reciprocal carries kFastEps under the outward factor 1 + 2^-20 in front of it (the cast and the last product are
+// covered by the 1.0000002f, as before); a denormal tmin makes it NaN, which is "no estimate".
+__device__ inline float ball_inverse_depth_bound(double l, double r) {
   const double tmin = (l - r) - 2.384185791015625e-7 * (l + fabs(r));
   if (!(tmin > 0.0) || !isfinite(tmin)) return 1.0e30f;
-  const double inv = (1.0 + 9.5367431640625e-7) / tmin;
+  const double inv = (1.0 + 9.5367431640625e-7) * rcp_newton(tmin);
   return (inv < 1.0e30) ? (float)inv * 1.0000002f : 1.0e30f;
+}
+
+// is[j] = 1 / |P_j| (0 for a zero or non-finite column): the units conic_trusted compares in.  tmax and emax carry the
+// SAME factors is[i] is[j], so their kFastEps moves each maximum by 2^-43 of itself at most -- against the factor 4
+// between the 2^-26 the margins cover and the 2^-24 the test asks for.
+__device__ inline void inverse_lengths(const double* const P[3], double is[3]) {
+  for (int j = 0; j < 3; ++j) {
+    const double l2 = dot3(P[j], P[j]);
+    is[j] = (l2 > 0.0) ? rsqrt_fast(l2) : 0.0;
+  }
 }
 
 // Can the six fp64 coefficients of a conic be trusted?  `tmax` = largest |T_ij|, `emax` = largest sum of the absolute
@@ -191,13 +272,13 @@ __device__ inline bool conic_trusted(double tmax, double emax) {
 }
 
 // sphere silhouette  cq (Pi.Pj) - (oc.Pi)(oc.Pj)  with the trust test; `sq` = magnitude of the terms cq was formed from
+// `ext`: see conic_record
 __device__ inline void sphere_conic_record(const double oc[3], double cq, double sq, const double* const P[3], int W, int H,
-                                           float* out) {
+                                           float* out, ConicExtent* ext) {
   double w[3], mw[3], is[3];
+  inverse_lengths(P, is);                                  // entries are compared in units of |Pi| |Pj| (see below)
   for (int j = 0; j < 3; ++j) {
     w[j] = dot3(oc, P[j]); mw[j] = abs_dot3(oc, P[j]);
-    const double l = sqrt(dot3(P[j], P[j]));
-    is[j] = (l > 0.0) ? 1.0 / l : 0.0;                    // entries are compared in units of |Pi| |Pj| (see below)
   }
   double t[6], tmax = 0.0, emax = 0.0;
   int q = 0;
@@ -208,8 +289,8 @@ __device__ inline void sphere_conic_record(const double oc[3], double cq, double
       emax = fmax(emax, (sq * abs_dot3(P[i], P[j]) + mw[i] * fabs(w[j]) + mw[j] * fabs(w[i]) + fabs(w[i] * w[j])) *
                             (is[i] * is[j]));
     }
-  if (!conic_trusted(tmax, emax)) { rec_zero(out, 5); out[11] = 0.0f; return; }
-  (void)conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out);
+  if (!conic_trusted(tmax, emax)) { rec_zero(out, 5); out[11] = 0.0f; *ext = no_extent(); return; }
+  (void)conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out, ext);
 }
 
 // disc: | oc (n.D) + k D |^2 <= r^2 (n.D)^2   (numpy/renderer.py:69,85-88 with t = k / (n.D))
@@ -218,8 +299,9 @@ __device__ inline void sphere_conic_record(const double oc[3], double cq, double
 //   [11] s_in: a pixel whose fp32 value q (pair_bounds) is < s_in is a CERTAIN valid hit (conic_record's sure_in) --
 //        only for a trusted, non-degenerate ellipse with finite, moderate coefficients whose whole ball lies inside
 //        [near, far] with margin; -1e30 (never) otherwise.  Its depth is then bounded through den (see sure_den_shift).
+// `ext`: the half extents of the stored shape's box (conic_record), none when the record is "always a candidate".
 __device__ inline void disk_reject_record(const double* R, const double o[3], const PixelBasis& B, int W, int H,
-                                          double near_clip, double far_clip, float* out) {
+                                          double near_clip, double far_clip, float* out, ConicExtent* ext) {
   const double* n = R;
   const double k = R[3];
   const double oc[3] = {o[0] - R[4], o[1] - R[5], o[2] - R[6]};
@@ -230,12 +312,11 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
   // is |eye| |n.P| + |k| |P| -- so |eye| joins the terms, and a camera 1e10 away from the origin makes the record
   // untrusted instead of wrong
   double nu[3], u[3][3], mu[3], au[3], is[3];
+  inverse_lengths(P, is);
   const double ol1 = fabs(o[0]) + fabs(o[1]) + fabs(o[2]);
   for (int j = 0; j < 3; ++j) {
     nu[j] = dot3(n, P[j]);
     mu[j] = au[j] = 0.0;
-    const double l = sqrt(dot3(P[j], P[j]));
-    is[j] = (l > 0.0) ? 1.0 / l : 0.0;
     for (int a = 0; a < 3; ++a) {
       u[j][a] = oc[a] * nu[j] + k * P[j][a];
       mu[j] += fabs(oc[a] * nu[j]) + fabs(k * P[j][a]);
@@ -256,36 +337,41 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
   }
   bool degenerate = true;
   double sure_in = -1.0e30;
+  *ext = no_extent();
   if (conic_trusted(tmax, emax))
-    degenerate = conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out, &sure_in) < 0.0;
+    degenerate = !conic_record(t[0], t[1], t[2], t[3], t[4], t[5], W, H, out, ext, &sure_in);
+  // ONE |oc| and ONE radius for the stand-in below, the occlusion bound and the certain hits (sqrt_fast: see
+  // ball_inverse_depth_bound and `slack`)
+  const double oo = dot3(oc, oc);
+  const double l = sqrt_fast(oo), r = sqrt_fast(r2);
   if (degenerate) {
     // The disc's own image is not a usable ellipse (seen edge-on: axis ratio beyond 512, parameters are noise).
     // Every hit lies on the disc, hence inside the sphere around its centre with its radius, and that sphere's
     // silhouette is a robust, well-conditioned ellipse.  Rare (|cos| < 2e-3), so the extra work is off the common path.
-    const double oo = dot3(oc, oc);
-    sphere_conic_record(oc, oo - r2, oo + fabs(r2) + 2.0 * sqrt(dot3(o, o) * oo), P, W, H, out);
+    sphere_conic_record(oc, oo - r2, oo + fabs(r2) + 2.0 * sqrt(dot3(o, o) * oo), P, W, H, out, ext);
   }
   plane_estimate_record(n, k, B, W, H, out + 5, out + 6, out + 7, out + 8, out + 9, out + 10);
   // A stand-in shape passes pixels the disc does not cover, and the plane-distance estimate means nothing there:
   // replace it by the bounding ball's (every hit lies in the ball, so t >= |oc| - r).  The kernel multiplies den by
   // 1 / |D|, so the constant is scaled by the largest |D| of the image (|D| is convex: a corner) -- a little weak, valid.
   if (degenerate) {
-    double dmax = 0.0;
+    double dmax2 = 0.0;
     for (int i = 0; i < 4; ++i) {
       const double c = (i & 1) ? (double)(W - 1) : 0.0, rr = (i & 2) ? (double)(H - 1) : 0.0;
       const double D[3] = {B.D0[0] + c * B.Dc[0] + rr * B.Dr[0], B.D0[1] + c * B.Dc[1] + rr * B.Dr[1],
                            B.D0[2] + c * B.Dc[2] + rr * B.Dr[2]};
-      dmax = fmax(dmax, sqrt(dot3(D, D)));
+      dmax2 = fmax(dmax2, dot3(D, D));
     }
-    const double u = (double)ball_inverse_depth_bound(oc, sqrt(r2)) * dmax * 1.000001;
+    // (the root is monotone: one of the largest square; its kFastEps is under the 1.000001)
+    const double u = (double)ball_inverse_depth_bound(l, r) * sqrt_fast(dmax2) * 1.000001;
     out[5] = (u < 1.0e30 && isfinite(u)) ? (float)u * 1.0000002f : 1.0e30f;
     out[6] = out[7] = 0.0f; out[9] = 3.0e38f; out[10] = -3.0e38f;
   }
-  const double r = sqrt(r2);
-  out[8] = ball_inverse_depth_bound(oc, r);
+  out[8] = ball_inverse_depth_bound(l, r);
   // certain hits: every point of the ball (hence every fp64 hit, whose distance ball_inverse_depth_bound's 2^-22 covers)
-  // lies in [near, far], and the record's values stay finite at every pixel (no inf - inf, no NaN sign bit to read)
-  const double l = sqrt(dot3(oc, oc)), slack = 9.5367431640625e-7 * (l + r);
+  // lies in [near, far], and the record's values stay finite at every pixel (no inf - inf, no NaN sign bit to read).
+  // `slack` is 2^-20 (l + r) where 2^-22 (l + r) is needed: the kFastEps of l and r is 2^-24 of what is left.
+  const double slack = 9.5367431640625e-7 * (l + r);
   bool sure = !degenerate && near_clip > 0.0 && (l - r) - slack > near_clip && (l + r) + slack < far_clip &&
               sure_in > -1.0 && out[9] < 1.0e30f;
   for (int i = 0; i < 11; ++i) sure = sure && fabsf(out[i]) < 1.0e30f;
@@ -296,9 +382,10 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
 // sphere: the ray's line meets it iff (oc.D)^2 - |D|^2 (|oc|^2 - r^2) >= 0   (numpy/renderer.py:20-25).
 // With near <= 0 a missed line yields the valid t = 0 (Q2), so nothing may be rejected.
 __device__ inline void sphere_reject_record(const double* R, const PixelBasis& B, int W, int H, bool near_positive,
-                                            bool tch, float* out) {
+                                            bool tch, float* out, ConicExtent* ext) {
   rec_zero(out, 12);
   out[5] = 1.0e30f;
+  *ext = no_extent();
   if (!near_positive) return;
   const double* oc = R;
   const double cq = R[3];
@@ -306,14 +393,14 @@ __device__ inline void sphere_reject_record(const double* R, const PixelBasis& B
   double w[3];
   for (int j = 0; j < 3; ++j) w[j] = dot3(oc, P[j]);
   // cq = |oc|^2 - r^2 comes from the exact record: the terms it was formed from are at most 2 |oc|^2 + |cq|
-  sphere_conic_record(oc, cq, 2.0 * dot3(oc, oc) + fabs(cq), P, W, H, out);
+  const double oo = dot3(oc, oc);
+  sphere_conic_record(oc, cq, 2.0 * oo + fabs(cq), P, W, H, out, ext);
   // Depth bound.  Eye outside the sphere (cq > 0): both roots have the sign of (pos - eye).D = -oc.D.  Positive roots
   // give t = t1 >= |oc| - r.  Negative roots are a miss under the torch semantics, but the numpy backend's sentinel
   // turns them into t = 1.0 (Q2) -- so there the bound holds only if -oc.D > 0 on the whole image (affine: its
   // minimum is at a corner); otherwise it is capped at t >= min(|oc| - r, 1).
   if (cq > 0.0) {
-    const double r = sqrt(fmax(dot3(oc, oc) - cq, 0.0));
-    float inv = ball_inverse_depth_bound(oc, r);
+    float inv = ball_inverse_depth_bound(sqrt_fast(oo), sqrt_fast(fmax(oo - cq, 0.0)));
     if (!tch) {
       double front = 1e300;
       for (int i = 0; i < 4; ++i) {
@@ -360,11 +447,14 @@ __device__ inline void triangle_reject_record(const double* R, const double o[3]
     const double as = (fabs(o[0]) + fabs(v[0])) * am[0] + (fabs(o[1]) + fabs(v[1])) * am[1] + (fabs(o[2]) + fabs(v[2])) * am[2];
     const double w[3] = {sg * (s * n[0] + k * m[0]), sg * (s * n[1] + k * m[1]), sg * (s * n[2] + k * m[2])};
     double a = dot3(w, B.Dc), b = dot3(w, B.Dr), g = dot3(w, B.D0);
-    const double len = sqrt(a * a + b * b);
-    if (!(len > 0.0) || !isfinite(len) || !isfinite(g)) continue;
-    const double err = 3.552713678800501e-15 * (2.0 * as + fabs(k) * (am[0] + am[1] + am[2])) * dsum / len;   // pixels
+    const double len2 = a * a + b * b;
+    if (!(len2 > 0.0) || !isfinite(len2) || !isfinite(g)) continue;
+    // ONE reciprocal length for the four quotients: kFastEps of a, b and g against the 1.7 x 3 x 2^-24 (|g| + W + H)
+    // that the margin below keeps spare, and of `err`, whose constant is 32x the rounding it stands for
+    const double ilen = rsqrt_newton(len2);
+    const double err = 3.552713678800501e-15 * (2.0 * as + fabs(k) * (am[0] + am[1] + am[2])) * dsum * ilen;   // pixels
     if (!(err < 0.25)) continue;
-    a /= len; b /= len; g /= len;                             // signed distance to the edge line, pixels
+    a *= ilen; b *= ilen; g *= ilen;                          // signed distance to the edge line, pixels
     if (!(fabs(g) < 1.0e9)) continue;
     // fp32 evaluation of a*c + b*r + g with rounded a, b, g: error < 3 * 2^-24 (|g| + W + H); margin 2.7x that
     g += 0.000244140625 + 4.76837158203125e-7 * (fabs(g) + W + H) + err;
@@ -401,15 +491,12 @@ struct BBox {
 
 __device__ inline BBox bbox_full() { return BBox{0, 0, 0, 0, true}; }
 
-// Box of the stored ellipse record (either form), one pixel of slack.
-__device__ inline BBox conic_bbox(const float* rec) {
-  const double A11 = rec[2], A12 = 0.5 * (double)rec[3], A22 = rec[4];
-  const double det = A11 * A22 - A12 * A12;
-  if (!(A11 > 0.0) || !(det > 0.0)) return bbox_full();
-  const double hc = sqrt(A22 / det), hr = sqrt(A11 / det);
-  if (!isfinite(hc) || !isfinite(hr)) return bbox_full();
-  return BBox{(double)rec[0] - hc - 1.0, (double)rec[0] + hc + 1.0, (double)rec[1] - hr - 1.0,
-              (double)rec[1] + hr + 1.0, false};
+// Box of the stored ellipse record from the extents its record function handed over, one pixel of slack.
+__device__ inline BBox conic_bbox(const float* rec, const ConicExtent& e) {
+  if (!(e.hc >= 0.0f)) return bbox_full();
+  const double hc = e.hc, hr = e.hr;
+  return BBox{(double)rec[0] - hc - 1.0, (double)rec[0] + hc + 1.0, (double)rec[1] - hr - 1.0, (double)rec[1] + hr + 1.0,
+              false};
 }
 
 // Box of the triangle cut out by the three stored (inflated) edge half-planes, if it is bounded.
@@ -469,8 +556,10 @@ struct RectTest {
     } else if (type == SRH_PRIM_DISK || type == SRH_PRIM_SPHERE) {
       A11 = rec[2]; A12 = 0.5 * (double)rec[3]; A22 = rec[4];
       ellipse = (A11 > 0.0) && (A22 > 0.0);                    // else "always a candidate"
-      i11 = ellipse ? 1.0 / A11 : 0.0;
-      i22 = ellipse ? 1.0 / A22 : 0.0;
+      // only the clamped vertices of `reaches` use them: a vertex off by kFastEps of itself raises the form's value
+      // there by 2^-88 A v^2 <= 2^-69 (the form is about 1 where it matters, A v^2 <= 2^19 of that) -- under the 1e-6
+      i11 = ellipse ? rcp_newton(A11) : 0.0;
+      i22 = ellipse ? rcp_newton(A22) : 0.0;
       x0 = rec[0]; y0 = rec[1];
       if (type == SRH_PRIM_DISK) { u0 = rec[5]; u1 = rec[6]; u2 = rec[7]; hi = rec[10]; behind = near_positive; }
     }
