@@ -662,6 +662,22 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
                        size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
                        const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
 
+/* The camera gradient of the depth lift and of the two warps, up to the per-view matrix: each *_bwd_view entry point is
+ * its layer's *_bwd plus grad_view (B, 12) fp64, the gradient with respect to the `view` table the layer was handed,
+ * WRITTEN with every element once (the chain from the matrix to eye / at / up is the caller's).  The other grad_*
+ * outputs may then all be NULL.  view_workspace: srh_view_grad_workspace_bytes bytes, 8-byte aligned, one set of
+ * partial sums per workgroup; they are added without atomics in an order that depends only on width x height, so the
+ * result is identical from run to run and a view of a batch gets the bits of the same view alone.  Added without an
+ * ABI version change. */
+size_t srh_view_grad_workspace_bytes(int32_t n_views, int32_t width, int32_t height);
+
+int srh_projection_bwd_view(const SrhProjectionParams* params, const double* view, const float* surfels,
+                            const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                            void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                            const float* g_image1, const float* g_depth, float* grad_surfels, float* grad_rgb,
+                            float* grad_rotated, double* grad_view, void* view_workspace, size_t view_workspace_bytes,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * The reference's backward-warp ("pull") re-projection, projection_reverse_renderer (diffrend/torch/
  * projection_layer.py:281-333), for B views per call.  Each of the N = W H pixels of the target view has a surfel
@@ -723,6 +739,17 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
                                const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
                                const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
                                float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream);
+
+/* srh_reverse_projection_bwd plus the gradients of the two view tables (see srh_projection_bwd_view): grad_view1,
+ * grad_view2 (B, 12) fp64, either may be NULL = not wanted, not both.  Camera 2 reaches the results through the values
+ * of the new depth alone, so rows 0 and 1 of grad_view2 are exactly 0, and grad_view2 needs keys, order and workspace
+ * like grad_in_pos. */
+int srh_reverse_projection_bwd_view(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                                    const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
+                                    const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
+                                    const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
+                                    float* grad_in_pos, float* grad_out_pos, float* grad_rotated, double* grad_view1,
+                                    double* grad_view2, void* view_workspace, size_t view_workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The reference's dense Gaussian re-projection, projection_renderer_differentiable (diffrend/torch/projection_layer.py:
@@ -800,6 +827,13 @@ int srh_depth_to_surfels_fwd(const SrhSurfelsParams* params, const double* view,
  * depth <= 0. */
 int srh_depth_to_surfels_bwd(const SrhSurfelsParams* params, const double* view, const float* depth, const float* g_out,
                              float* grad_depth, void* stream);
+
+/* srh_depth_to_surfels_bwd plus the gradient of the view table (see srh_projection_bwd_view), for the world frame only:
+ * grad_view (B, 12) fp64; grad_depth may be NULL = not wanted.  A pixel with depth <= 0 still contributes to column 3:
+ * the point is the eye. */
+int srh_depth_to_surfels_bwd_view(const SrhSurfelsParams* params, const double* view, const float* depth,
+                                  const float* g_out, float* grad_depth, double* grad_view, void* view_workspace,
+                                  size_t view_workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The reference's hard scatter-mean projection, projection_renderer (diffrend/torch/projection_layer.py:88-106), for B

@@ -207,15 +207,20 @@ SIGNATURES = {
     "srh_projection_keys": (C.c_int, [_p(SrhProjectionParams), _V, _V, _V, _Z, _V, _V]),
     "srh_projection_fwd": (C.c_int, [_p(SrhProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 5),
     "srh_projection_bwd": (C.c_int, [_p(SrhProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 8),
+    "srh_view_grad_workspace_bytes": (_Z, [_I, _I, _I]),
+    "srh_projection_bwd_view": (C.c_int, [_p(SrhProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 9 + [_Z, _V]),
     "srh_reverse_projection_workspace_bytes": (_Z, [_p(SrhReverseProjectionParams), _I]),
     "srh_reverse_projection_fwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 8 + [_Z] + [_V] * 5),
     "srh_reverse_projection_keys": (C.c_int, [_p(SrhReverseProjectionParams), _V, _V, _V, _Z, _V, _V]),
     "srh_reverse_projection_bwd": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 9 + [_Z] + [_V] * 8),
+    "srh_reverse_projection_bwd_view": (C.c_int, [_p(SrhReverseProjectionParams)] + [_V] * 9 + [_Z] + [_V] * 10
+                                        + [_Z, _V]),
     "srh_dense_projection_workspace_bytes": (_Z, [_p(SrhDenseProjectionParams), _I]),
     "srh_dense_projection_fwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 3),
     "srh_dense_projection_bwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 6),
     "srh_depth_to_surfels_fwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 4),
     "srh_depth_to_surfels_bwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 5),
+    "srh_depth_to_surfels_bwd_view": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 6 + [_Z, _V]),
     "srh_hard_projection_keys": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 4),
     "srh_hard_projection_fwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 7),
     "srh_hard_projection_bwd": (C.c_int, [_p(SrhHardProjectionParams)] + [_V] * 5),

@@ -28,12 +28,14 @@ def rotated_like(name: str, rotated_image, rgb: torch.Tensor) -> Optional[torch.
     return rotated_image
 
 
-def validate_surfels(name: str, surfels, rgb, camera: Mapping, rotated_image, blur_size, why: str):
+def validate_surfels(name: str, surfels, rgb, camera: Mapping, rotated_image, blur_size, why: str,
+                     camera_grad: Optional[bool] = None):
     """The checks of (surfels, rgb, camera's frame, rotated_image, blur_size) of the layer `name` (ValueError), before
     anything reaches the GPU; `why` ends the message for N != W H.  The caller goes on with its own blur and with
-    camera_views.  Returns the tensors, (B, H, W, D) and blur_size as a float."""
+    camera_views.  `camera_grad` is given by the layer that has the keyword (camera_frame).  Returns the tensors,
+    (B, H, W, D) and blur_size as a float."""
     surfels, rgb = as_float_tensor("surfels", surfels, name), as_float_tensor("rgb", rgb, name)
-    W, H = camera_frame(name, camera)
+    W, H = camera_frame(name, camera, camera_grad=camera_grad)
     if surfels.dim() != 3 or surfels.shape[-1] != 3:
         raise ValueError(f"{name}: surfels is {list(surfels.shape)}, expected [B, N, 3]")
     B, N = surfels.shape[:2]

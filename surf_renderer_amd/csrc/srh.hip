@@ -1553,6 +1553,25 @@ struct Regions {
   }
 };
 
+// ---- the camera gradient of the lift and the two warps (srh_view_grad.h): what the *_bwd_view entry points share ----
+static_assert(kViewBlock == kProjBlock && kViewBlock == kSurfBlock, "view_block_reduce's workgroup is the layers'");
+static_assert(kRProjView2First + kRProjView2Sums == kViewSums, "row 2 of the 3 x 4 matrix");
+
+// the partials of one kView launch: 12 fp64 sums per workgroup (a launch that brings fewer uses the head)
+size_t view_ws_bytes(int B, int nblk) { return (size_t)B * nblk * kViewSums * sizeof(double); }
+
+int check_grad_view(const char* name, const double* g) {
+  if (!g) return fail(SRH_E_NULL, "%s is NULL", name);
+  if ((uintptr_t)g % sizeof(double)) return fail(SRH_E_WORKSPACE, "%s: %p is not 8-byte aligned", name, (const void*)g);
+  return SRH_OK;
+}
+
+// the K sums per workgroup a kView kernel left in `part` -> entries [first, first + K) of grad_view (B, 12), 0 elsewhere
+void launch_view_finish(int B, int nblk, int K, int first, const void* part, double* grad_view, hipStream_t st) {
+  hipLaunchKernelGGL(k_view_finish, dim3(1, B), dim3(kViewRows * kViewSums), 0, st, nblk, K, first, (const double*)part,
+                     grad_view);
+}
+
 // argument checks (no HIP call) and the device view of a projection launch
 int proj_setup(const SrhProjectionParams* p, bool has_rotated, ProjDev* P) {
   if (!p) return fail(SRH_E_NULL, "params is NULL");
@@ -1660,24 +1679,31 @@ int srh_projection_fwd(const SrhProjectionParams* params, const float* rgb, cons
   return launch_status("projection forward launch");
 }
 
-int srh_projection_bwd(const SrhProjectionParams* params, const double* view, const float* surfels, const float* rgb,
-                       const float* rotated, const void* saved, size_t saved_bytes, void* workspace,
-                       size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
-                       const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+// srh_projection_bwd, and with `with_view` srh_projection_bwd_view
+static int projection_bwd(bool with_view, const SrhProjectionParams* params, const double* view, const float* surfels,
+                          const float* rgb, const float* rotated, const void* saved, size_t saved_bytes, void* workspace,
+                          size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
+                          const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated,
+                          double* grad_view, void* view_workspace, size_t view_workspace_bytes, void* stream) {
   ProjDev P;
   int rc = proj_setup(params, rotated != nullptr, &P);
   if (rc) return rc;
   if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"rgb", rgb}}))) return rc;
   if (!g_out && !g_mask && !g_image1 && !g_depth)
     return fail(SRH_E_NULL, "g_out, g_mask, g_image1 and g_depth are all NULL");
-  if (!grad_surfels && !grad_rgb && !grad_rotated)
+  if (!with_view && !grad_surfels && !grad_rgb && !grad_rotated)
     return fail(SRH_E_NULL, "grad_surfels, grad_rgb and grad_rotated are all NULL");
   if (grad_rotated && !rotated) return fail(SRH_E_NULL, "grad_rotated without rotated");
   if ((rc = check_scratch("saved", saved, saved_bytes, proj_ws_bytes(P, SRH_PROJ_WS_SAVED)))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, proj_ws_bytes(P, SRH_PROJ_WS_BWD)))) return rc;
+  if (with_view) {
+    if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+    if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(P.B, P.nblk))))
+      return rc;
+  }
   hipStream_t st = (hipStream_t)stream;
   const ProjWs s = proj_ws(P, SRH_PROJ_WS_SAVED, saved), w = proj_ws(P, SRH_PROJ_WS_BWD, workspace);
-  double* gcor = (grad_surfels || grad_rgb) ? w.gcor : nullptr;
+  double* gcor = (with_view || grad_surfels || grad_rgb) ? w.gcor : nullptr;
   const int nb = (grad_rotated && (P.flags & kProjBlurRotated)) ? 2 * P.D + 1 : P.D + 1;
   const dim3 grid(P.nblk, P.B), block(kProjBlock);
   hipLaunchKernelGGL(k_proj_merge_bwd, grid, block, 0, st, P, (const double*)s.blr, g_out, g_mask, g_image1, g_depth,
@@ -1686,10 +1712,34 @@ int srh_projection_bwd(const SrhProjectionParams* params, const double* view, co
                      (const double*)w.gpl, w.gtmp);
   hipLaunchKernelGGL(k_proj_blur_v_corner, grid, block, 0, st, P, nb, (const double*)w.gtmp, (const double*)w.gpl,
                      (const double*)s.cor, gcor, grad_rotated);
-  if (gcor)
-    hipLaunchKernelGGL(k_proj_surfel_bwd, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
-                       grad_surfels);
+  if (with_view) {
+    hipLaunchKernelGGL(k_proj_surfel_bwd<true>, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
+                       grad_surfels, (double*)view_workspace);
+    launch_view_finish(P.B, P.nblk, kViewSums, 0, view_workspace, grad_view, st);
+  } else if (gcor) {
+    hipLaunchKernelGGL(k_proj_surfel_bwd<false>, grid, block, 0, st, P, view, surfels, rgb, (const double*)gcor, grad_rgb,
+                       grad_surfels, (double*)nullptr);
+  }
   return launch_status("projection backward launch");
+}
+
+int srh_projection_bwd(const SrhProjectionParams* params, const double* view, const float* surfels, const float* rgb,
+                       const float* rotated, const void* saved, size_t saved_bytes, void* workspace,
+                       size_t workspace_bytes, const float* g_out, const float* g_mask, const float* g_image1,
+                       const float* g_depth, float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+  return projection_bwd(false, params, view, surfels, rgb, rotated, saved, saved_bytes, workspace, workspace_bytes, g_out,
+                        g_mask, g_image1, g_depth, grad_surfels, grad_rgb, grad_rotated, nullptr, nullptr, 0, stream);
+}
+
+int srh_projection_bwd_view(const SrhProjectionParams* params, const double* view, const float* surfels,
+                            const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                            void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                            const float* g_image1, const float* g_depth, float* grad_surfels, float* grad_rgb,
+                            float* grad_rotated, double* grad_view, void* view_workspace, size_t view_workspace_bytes,
+                            void* stream) {
+  return projection_bwd(true, params, view, surfels, rgb, rotated, saved, saved_bytes, workspace, workspace_bytes, g_out,
+                        g_mask, g_image1, g_depth, grad_surfels, grad_rgb, grad_rotated, grad_view, view_workspace,
+                        view_workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -1797,11 +1847,14 @@ int srh_reverse_projection_keys(const SrhReverseProjectionParams* params, const 
   return launch_status("reverse projection k_proj_keys launch");
 }
 
-int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
-                               const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
-                               const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
-                               const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
-                               float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream) {
+// srh_reverse_projection_bwd, and with `with_view` srh_reverse_projection_bwd_view
+static int reverse_projection_bwd(bool with_view, const SrhReverseProjectionParams* params, const double* view1,
+                                  const double* view2, const float* rgb, const float* in_pos, const float* out_pos,
+                                  const float* mask, const int32_t* keys, const int32_t* order, void* workspace,
+                                  size_t workspace_bytes, const float* g_out, const float* g_image1, const float* g_depth,
+                                  float* grad_rgb, float* grad_in_pos, float* grad_out_pos, float* grad_rotated,
+                                  double* grad_view1, double* grad_view2, void* view_workspace,
+                                  size_t view_workspace_bytes, void* stream) {
   RProjDev R;
   int rc = rproj_setup(params, &R);
   if (rc) return rc;
@@ -1809,9 +1862,16 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
                             {"mask", mask}})))
     return rc;
   if (!g_out && !g_image1 && !g_depth) return fail(SRH_E_NULL, "g_out, g_image1 and g_depth are all NULL");
-  if (!grad_rgb && !grad_in_pos && !grad_out_pos && !grad_rotated)
+  if (!with_view && !grad_rgb && !grad_in_pos && !grad_out_pos && !grad_rotated)
     return fail(SRH_E_NULL, "grad_rgb, grad_in_pos, grad_out_pos and grad_rotated are all NULL");
-  const bool walk = grad_rgb || grad_in_pos;
+  if (with_view) {
+    if (!grad_view1 && !grad_view2) return fail(SRH_E_NULL, "grad_view1 and grad_view2 are both NULL");
+    if (grad_view1 && (rc = check_grad_view("grad_view1", grad_view1))) return rc;
+    if (grad_view2 && (rc = check_grad_view("grad_view2", grad_view2))) return rc;
+    if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(R.B, R.nblk))))
+      return rc;
+  }
+  const bool walk = grad_rgb || grad_in_pos || grad_view2;
   if (walk) {
     if ((rc = check_not_null({{"keys", keys}, {"order", order}}))) return rc;
     if ((rc = check_scratch("workspace", workspace, workspace_bytes, rproj_ws_bytes(R, SRH_RPROJ_WS_BWD)))) return rc;
@@ -1824,12 +1884,46 @@ int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const d
       return hip_fail(e, "reverse projection cell ranges memset");
     hipLaunchKernelGGL(k_proj_mark, grid, block, 0, st, rproj_as_proj(R), keys, order, w.range);
   }
-  hipLaunchKernelGGL(k_rproj_pixel_bwd, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, mask, g_out, g_image1,
-                     g_depth, w.gpl, grad_out_pos, grad_rotated);
-  if (walk)
-    hipLaunchKernelGGL(k_rproj_texel_bwd, grid, block, 0, st, R, view2, (const double*)w.rec, order,
-                       (const int32_t*)w.range, (const double*)w.gpl, grad_rgb, grad_in_pos);
+  // the two kView kernels share view_workspace: the stream orders camera 1's finish before the texel kernel's stores
+  if (grad_view1) {
+    hipLaunchKernelGGL(k_rproj_pixel_bwd<true>, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, mask, g_out,
+                       g_image1, g_depth, w.gpl, grad_out_pos, grad_rotated, (double*)view_workspace);
+    launch_view_finish(R.B, R.nblk, kViewSums, 0, view_workspace, grad_view1, st);
+  } else {
+    hipLaunchKernelGGL(k_rproj_pixel_bwd<false>, grid, block, 0, st, R, view1, view2, rgb, in_pos, out_pos, mask, g_out,
+                       g_image1, g_depth, w.gpl, grad_out_pos, grad_rotated, (double*)nullptr);
+  }
+  if (grad_view2) {
+    hipLaunchKernelGGL(k_rproj_texel_bwd<true>, grid, block, 0, st, R, view2, (const double*)w.rec, order,
+                       (const int32_t*)w.range, (const double*)w.gpl, grad_rgb, grad_in_pos, in_pos,
+                       (double*)view_workspace);
+    launch_view_finish(R.B, R.nblk, kRProjView2Sums, kRProjView2First, view_workspace, grad_view2, st);
+  } else if (walk) {
+    hipLaunchKernelGGL(k_rproj_texel_bwd<false>, grid, block, 0, st, R, view2, (const double*)w.rec, order,
+                       (const int32_t*)w.range, (const double*)w.gpl, grad_rgb, grad_in_pos, in_pos, (double*)nullptr);
+  }
   return launch_status("reverse projection backward launch");
+}
+
+int srh_reverse_projection_bwd(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                               const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
+                               const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
+                               const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
+                               float* grad_in_pos, float* grad_out_pos, float* grad_rotated, void* stream) {
+  return reverse_projection_bwd(false, params, view1, view2, rgb, in_pos, out_pos, mask, keys, order, workspace,
+                                workspace_bytes, g_out, g_image1, g_depth, grad_rgb, grad_in_pos, grad_out_pos,
+                                grad_rotated, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int srh_reverse_projection_bwd_view(const SrhReverseProjectionParams* params, const double* view1, const double* view2,
+                                    const float* rgb, const float* in_pos, const float* out_pos, const float* mask,
+                                    const int32_t* keys, const int32_t* order, void* workspace, size_t workspace_bytes,
+                                    const float* g_out, const float* g_image1, const float* g_depth, float* grad_rgb,
+                                    float* grad_in_pos, float* grad_out_pos, float* grad_rotated, double* grad_view1,
+                                    double* grad_view2, void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  return reverse_projection_bwd(true, params, view1, view2, rgb, in_pos, out_pos, mask, keys, order, workspace,
+                                workspace_bytes, g_out, g_image1, g_depth, grad_rgb, grad_in_pos, grad_out_pos,
+                                grad_rotated, grad_view1, grad_view2, view_workspace, view_workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -2010,9 +2104,32 @@ int srh_depth_to_surfels_bwd(const SrhSurfelsParams* params, const double* view,
   int rc = surf_setup(params, view, &S);
   if (rc) return rc;
   if ((rc = check_not_null({{"depth", depth}, {"g_out", g_out}, {"grad_depth", grad_depth}}))) return rc;
-  hipLaunchKernelGGL(k_surfels_bwd, dim3(S.nblk, S.B), dim3(kSurfBlock), 0, (hipStream_t)stream, S, view, depth, g_out,
-                     grad_depth);
+  hipLaunchKernelGGL(k_surfels_bwd<false>, dim3(S.nblk, S.B), dim3(kSurfBlock), 0, (hipStream_t)stream, S, view, depth,
+                     g_out, grad_depth, (double*)nullptr);
   return launch_status("k_surfels_bwd launch");
+}
+
+size_t srh_view_grad_workspace_bytes(int32_t n_views, int32_t width, int32_t height) {
+  if (check_batch_grid(n_views, width, height, "width x height =")) return 0;
+  return view_ws_bytes(n_views, (width * height + kViewBlock - 1) / kViewBlock);
+}
+
+int srh_depth_to_surfels_bwd_view(const SrhSurfelsParams* params, const double* view, const float* depth,
+                                  const float* g_out, float* grad_depth, double* grad_view, void* view_workspace,
+                                  size_t view_workspace_bytes, void* stream) {
+  SurfDev S;
+  int rc = surf_setup(params, view, &S);
+  if (rc) return rc;
+  if (S.frame != kSurfFrameWorld)
+    return fail(SRH_E_TYPE, "frame = %d: grad_view exists only for SRH_SURFELS_FRAME_WORLD", S.frame);
+  if ((rc = check_not_null({{"depth", depth}, {"g_out", g_out}}))) return rc;
+  if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+  if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(S.B, S.nblk)))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_surfels_bwd<true>, dim3(S.nblk, S.B), dim3(kSurfBlock), 0, st, S, view, depth, g_out, grad_depth,
+                     (double*)view_workspace);
+  launch_view_finish(S.B, S.nblk, kViewSums, 0, view_workspace, grad_view, st);
+  return launch_status("depth_to_surfels backward (view) launch");
 }
 
 }  // extern "C"

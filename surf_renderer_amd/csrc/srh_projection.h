@@ -27,6 +27,7 @@
 // The per-element arithmetic (proj_point, proj_surfel, proj_merge_fwd, proj_merge_bwd) is host-callable.
 #pragma once
 #include "srh_device.h"   // as_constant
+#include "srh_view_grad.h"
 
 namespace srh {
 
@@ -431,14 +432,22 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_blur_v_corner(ProjDev P, in
 
 // Backward 4: one lane per surfel reads the rows of its four destination pixels and writes g_rgb (B, N, D) and
 // g_surfels (B, N, 3), each element once (zeros for a surfel outside the frame); either may be NULL.
+// kView: also the gradient of the view's matrix: cc = M [p, 1], so g_M = sum_s g_cc (x) [p_s, 1] with g_cc = (g_X, g_Y,
+// g_Z) below, zeros for a surfel outside the frame.  The lane keeps g_cc and the point (vg, vp), each workgroup stores
+// the sums of their 12 products to view_part (srh_view_grad.h), and g_rgb and g_surfels may then both be NULL.  Without
+// kView the trailing argument is unused and the code is what it was without it.
+template <bool kView>
 __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const double* __restrict__ view,
                                                                 const float* __restrict__ surfels,
                                                                 const float* __restrict__ rgb,
                                                                 const double* __restrict__ gcor,
-                                                                float* __restrict__ g_rgb, float* __restrict__ g_surfels) {
+                                                                float* __restrict__ g_rgb, float* __restrict__ g_surfels,
+                                                                double* __restrict__ view_part) {
   const int s = blockIdx.x * kProjBlock + threadIdx.x;
   const int b = blockIdx.y;
-  if (s >= P.N) return;
+  double vg[3] = {0.0, 0.0, 0.0}, vp[3] = {0.0, 0.0, 0.0};      // kView: g_cc and the point; zeros bring zeros
+  do {                                  // a lane that is done leaves by `break`: with kView every lane reaches the reduce
+  if (s >= P.N) break;
   const size_t base = (size_t)b * P.N, o = base + s;
   double M[12];
   proj_load_view(view, b, M);
@@ -479,7 +488,7 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const
     for (int c = 0; c < kProjMaxD; ++c)
       if (c < P.D) g_rgb[o * P.D + c] = (float)gc[c];
   }
-  if (!g_surfels) return;
+  if (!kView && !g_surfels) break;
   if (P.flags & kProjUseCenterDist) {
     const double g_alpha = g_a * S.w;
     g_fx -= g_alpha * 4.0 * S.fx * S.alpha;
@@ -492,7 +501,15 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const
   }
   const double g_X = g_fx * P.fsx / S.Zd, g_Y = g_fy * P.fsy / S.Zd;
   const double g_Z = (S.Z != 0.0 ? -(g_X * S.X + g_Y * S.Y) / S.Zd : 0.0) - g_z;
+  if (kView && S.live) {
+    vg[0] = g_X; vg[1] = g_Y; vg[2] = g_Z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vp[c] = (double)surfels[3 * o + c];
+  }
+  if (kView && !g_surfels) break;
 #pragma unroll
   for (int j = 0; j < 3; ++j) g_surfels[3 * o + j] = (float)((M[j] * g_X + M[4 + j] * g_Y) + M[8 + j] * g_Z);
+  } while (false);
+  if (kView) view_block_reduce<kViewSums>([&](int k) { return view_outer_term(vg, vp, k); }, view_part);
 }
 }  // namespace srh

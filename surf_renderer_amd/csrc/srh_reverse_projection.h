@@ -130,6 +130,12 @@ __global__ __launch_bounds__(kProjBlock) void k_rproj_fwd(RProjDev R, const doub
 
 // Backward 1: one lane per pixel.  Upstream gradients fp32, NULL = none (g_out only with a rotated image: without one
 // `out` is image1).  gpl (G planes), g_out_pos (B, N, 3) and g_rot (B, N, D) may be NULL = not wanted.
+// kView: also the gradient of camera 1's matrix, which reaches the results through the sample coordinates alone (d,
+// d_in and d_out feed only the mask): g_M1 = sum_q g_cc1 (x) [out_pos_q, 1] with g_cc1 = (g_X, g_Y, g_Z) below, zeros
+// for a sample outside the frame.  The lane keeps g_cc1 and the point (vg, vp), and each workgroup stores the sums of
+// their 12 products to view_part (srh_view_grad.h).  Without kView the trailing argument is unused and the code is what
+// it was without it.
+template <bool kView>
 __global__ __launch_bounds__(kProjBlock) void k_rproj_pixel_bwd(RProjDev R, const double* __restrict__ view1,
                                                                 const double* __restrict__ view2,
                                                                 const float* __restrict__ rgb,
@@ -140,10 +146,13 @@ __global__ __launch_bounds__(kProjBlock) void k_rproj_pixel_bwd(RProjDev R, cons
                                                                 const float* __restrict__ g_image1,
                                                                 const float* __restrict__ g_depth,
                                                                 double* __restrict__ gpl, float* __restrict__ g_out_pos,
-                                                                float* __restrict__ g_rot) {
+                                                                float* __restrict__ g_rot,
+                                                                double* __restrict__ view_part) {
   const int q = blockIdx.x * kProjBlock + threadIdx.x;
   const int b = blockIdx.y;
-  if (q >= R.N) return;
+  double vg[3] = {0.0, 0.0, 0.0}, vp[3] = {0.0, 0.0, 0.0};      // kView: g_cc and the point; zeros bring zeros
+  do {                                  // a lane that is done leaves by `break`: with kView every lane reaches the reduce
+  if (q >= R.N) break;
   const size_t base = (size_t)b * R.N, o = base + q;
   const double m = (double)mask[o];
   double G[kProjMaxD];
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(kProjBlock) void k_rproj_pixel_bwd(RProjDev R, cons
   }
   const double gd = g_depth ? (double)g_depth[o] : 0.0;
   if (gpl) gpl[rproj_plane(R, b, R.D, q)] = gd;
-  if (!g_out_pos) return;
+  if (!kView && !g_out_pos) break;
   double M1[12], M2[12];
   proj_load_view(view1, b, M1);
   proj_load_view(view2, b, M2);
@@ -178,22 +187,42 @@ __global__ __launch_bounds__(kProjBlock) void k_rproj_pixel_bwd(RProjDev R, cons
   }
   const double g_X = g_u * R.fsx[0] / S.Zd, g_Y = g_v * R.fsy[0] / S.Zd;
   const double g_Z = S.Z != 0.0 ? -(g_X * S.X + g_Y * S.Y) / S.Zd : 0.0;
+  if (kView && S.live) {
+    vg[0] = g_X; vg[1] = g_Y; vg[2] = g_Z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vp[c] = (double)out_pos[3 * o + c];
+  }
+  if (kView && !g_out_pos) break;
 #pragma unroll
   for (int j = 0; j < 3; ++j) g_out_pos[3 * o + j] = (float)((M1[j] * g_X + M1[4 + j] * g_Y) + M1[8 + j] * g_Z);
+  } while (false);
+  if (kView) view_block_reduce<kViewSums>([&](int k) { return view_outer_term(vg, vp, k); }, view_part);
 }
+
+constexpr int kRProjView2Sums = 4, kRProjView2First = 8;     // what camera 2 gets: row 2 of the 3 x 4 matrix
 
 // Backward 2: one lane per source texel t walks the lists of its four cells -- t is corner k of the cell at t - (dx, dy)
 // -- and accumulates in list order.  rec (B, N, 4) fp64 as k_proj_keys wrote it (fx, fy first), order and range as for
 // k_proj_gather.  g_rgb (B, N, D) and g_in_pos (B, N, 3) are written, each element once; either may be NULL.
+// kView: also the gradient of camera 2's matrix, which reaches the results through the values of the new depth alone,
+// c2.z = -(row 2 of M2) . [in_pos, 1]: row 2 of g_M2 = -sum_t g_z(t) [in_pos_t, 1] with g_z(t) the depth channel
+// accumulated below; rows 0 and 1 are exactly 0 (k_view_finish writes them).  The lane's 4 products go to cs, and each
+// workgroup stores its sums to view_part (srh_view_grad.h); g_rgb and g_in_pos may then both be NULL.  Without kView
+// in_pos and the trailing argument are unused and the code is what it was without them.
+template <bool kView>
 __global__ __launch_bounds__(kProjBlock) void k_rproj_texel_bwd(RProjDev R, const double* __restrict__ view2,
                                                                 const double* __restrict__ rec,
                                                                 const int32_t* __restrict__ order,
                                                                 const int32_t* __restrict__ range,
                                                                 const double* __restrict__ gpl,
-                                                                float* __restrict__ g_rgb, float* __restrict__ g_in_pos) {
+                                                                float* __restrict__ g_rgb, float* __restrict__ g_in_pos,
+                                                                const float* __restrict__ in_pos,
+                                                                double* __restrict__ view_part) {
   const int t = blockIdx.x * kProjBlock + threadIdx.x;
   const int b = blockIdx.y;
-  if (t >= R.N) return;
+  double cs[kRProjView2Sums] = {0.0, 0.0, 0.0, 0.0};
+  do {                                  // with kView every lane reaches the reduce
+  if (t >= R.N) break;
   const int ty = t / R.W, tx = t - ty * R.W;
   const size_t base = (size_t)b * R.N;
   double acc[kProjMaxD + 1];
@@ -226,5 +255,13 @@ __global__ __launch_bounds__(kProjBlock) void k_rproj_texel_bwd(RProjDev R, cons
 #pragma unroll
     for (int j = 0; j < 3; ++j) g_in_pos[3 * (base + t) + j] = (float)(-m2[8 + j] * acc[kProjMaxD]);
   }
+  if (kView) {
+    const float* p = in_pos + 3 * (base + t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) cs[c] = -acc[kProjMaxD] * (double)p[c];
+    cs[3] = -acc[kProjMaxD];
+  }
+  } while (false);
+  if (kView) view_block_reduce<kRProjView2Sums>([&](int k) { return cs[k]; }, view_part);
 }
 }  // namespace srh

@@ -16,6 +16,7 @@
 // contiguous.
 #pragma once
 #include "srh_projection.h"   // proj_load_view
+#include "srh_view_grad.h"
 
 namespace srh {
 
@@ -67,29 +68,57 @@ __global__ __launch_bounds__(kSurfBlock) void k_surfels_fwd(SurfDev S, const dou
   for (int r = 0; r < 3; ++r) out[3 * o + r] = (float)P[r];
 }
 
-// g_out (B, N, 3) fp32 -> g_depth (B, N) fp32, every element written
+// g_out (B, N, 3) fp32 -> g_depth (B, N) fp32, every element written.
+// kView (world frame only): also the gradient of the view's matrix M = [R | eye].  P_wc = R P_cc + eye, so columns 0-2
+// are sum_q g_P (x) P_cc and column 3 is sum_q g_P; a pixel with depth <= 0 has P_cc = 0 and still moves with the eye.
+// Each workgroup stores its 12 sums to view_part (srh_view_grad.h); g_depth may then be NULL = not wanted.  Without
+// kView the trailing argument is unused and the code is what it was without it.
+template <bool kView>
 __global__ __launch_bounds__(kSurfBlock) void k_surfels_bwd(SurfDev S, const double* __restrict__ view,
                                                             const float* __restrict__ depth,
                                                             const float* __restrict__ g_out,
-                                                            float* __restrict__ g_depth) {
+                                                            float* __restrict__ g_depth,
+                                                            double* __restrict__ view_part) {
   const int q = blockIdx.x * kSurfBlock + threadIdx.x;
   const int b = blockIdx.y;
-  if (q >= S.N) return;
-  const size_t o = (size_t)b * S.N + q;
-  if ((double)depth[o] <= 0.0) {
-    g_depth[o] = 0.0f;
-    return;
-  }
-  double G[3] = {(double)g_out[3 * o], (double)g_out[3 * o + 1], (double)g_out[3 * o + 2]};
-  if (S.frame == kSurfFrameWorld) {            // R^T g
-    double M[12];
-    proj_load_view(view, b, M);
-    const double gx = G[0], gy = G[1], gz = G[2];
+  if (!kView) {
+    if (q >= S.N) return;
+    const size_t o = (size_t)b * S.N + q;
+    if ((double)depth[o] <= 0.0) {
+      g_depth[o] = 0.0f;
+      return;
+    }
+    double G[3] = {(double)g_out[3 * o], (double)g_out[3 * o + 1], (double)g_out[3 * o + 2]};
+    if (S.frame == kSurfFrameWorld) {            // R^T g
+      double M[12];
+      proj_load_view(view, b, M);
+      const double gx = G[0], gy = G[1], gz = G[2];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) G[c] = (M[c] * gx + M[4 + c] * gy) + M[8 + c] * gz;
+      for (int c = 0; c < 3; ++c) G[c] = (M[c] * gx + M[4 + c] * gy) + M[8 + c] * gz;
+    }
+    double dir[3];
+    surf_dir(S, q, dir);
+    g_depth[o] = (float)((G[0] * (dir[0] / S.f) + G[1] * (dir[1] / S.f)) - G[2]);
+  } else {
+    double g[3] = {0.0, 0.0, 0.0}, P[3] = {0.0, 0.0, 0.0};      // a lane past N brings zeros
+    if (q < S.N) {
+      const size_t o = (size_t)b * S.N + q;
+      const double z = (double)depth[o];
+      const double d = (z <= 0.0) ? 0.0 : z;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) g[r] = (double)g_out[3 * o + r];
+      double dir[3];
+      surf_dir(S, q, dir);
+      P[0] = (d * dir[0]) / S.f; P[1] = (d * dir[1]) / S.f; P[2] = -d;      // the forward's P_cc
+      if (g_depth) {
+        double M[12], G[3];
+        proj_load_view(view, b, M);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[c] = (M[c] * g[0] + M[4 + c] * g[1]) + M[8 + c] * g[2];
+        g_depth[o] = (z <= 0.0) ? 0.0f : (float)((G[0] * (dir[0] / S.f) + G[1] * (dir[1] / S.f)) - G[2]);
+      }
+    }
+    view_block_reduce<kViewSums>([&](int k) { return view_outer_term(g, P, k); }, view_part);
   }
-  double dir[3];
-  surf_dir(S, q, dir);
-  g_depth[o] = (float)((G[0] * (dir[0] / S.f) + G[1] * (dir[1] / S.f)) - G[2]);
 }
 }  // namespace srh

@@ -10,7 +10,8 @@ is sampled there bilinearly.  Pixels that leave the frame, or that a nearer surf
 by camera2) hides, are masked out, and rotated_image fills the holes.  Forward and backward are HIP kernels
 (surf_renderer_amd/csrc/srh_reverse_projection.h): fp64 arithmetic, fp32 results, no float atomics, so values and
 gradients are identical from run to run.  Differentiable in rgb, rotated_image, out_pos_wc (through the sample
-coordinates) and in_pos_wc (through the values of the new depth); the mask and the cameras are not differentiable.
+coordinates) and in_pos_wc (through the values of the new depth), and with camera_grad=True in both cameras' eye, at
+and up; the mask is not differentiable.
 """
 from __future__ import annotations
 
@@ -21,8 +22,9 @@ from typing import Dict, Mapping, Tuple
 import torch
 
 from . import _lib
-from ._camera import camera_frame, camera_views
-from ._layer import as_float_tensor, fill_grads, gpu_device, grad_buffers, ptr, scratch, stream, upstreams
+from ._camera import camera_frame, camera_views, check_camera_grad
+from ._layer import (as_float_tensor, fill_grads, gpu_device, grad_buffers, ptr, scratch, stream, upstreams,
+                     view_grad_buffers)
 from ._projection import check_channels, flat, rotated_like, shaped_like, sorted_order, upload_view
 
 _NAME = "projection_reverse_renderer"
@@ -49,7 +51,7 @@ class _ReverseFunction(torch.autograd.Function):
         ctx.params = params
         ctx.set_materialize_grads(False)
         # the kernels keep nothing of their own: the backward reads the inputs and the mask
-        if any(ctx.needs_input_grad[5:]):
+        if any(ctx.needs_input_grad[1:3]) or any(ctx.needs_input_grad[5:]):
             ctx.save_for_backward(view1, view2, rgb, in_pos, out_pos, mask)
         return out, mask, image1, depth
 
@@ -58,30 +60,36 @@ class _ReverseFunction(torch.autograd.Function):
         view1, view2, rgb, in_pos, out_pos, mask = ctx.saved_tensors
         grads = grad_buffers((rgb, in_pos, out_pos, rgb), ctx.needs_input_grad[5:])
         ups = upstreams((g_out, g_image1, g_depth))
+        vgrads, vws = view_grad_buffers(_lib.load(), (view1, view2), ctx.needs_input_grad[1:3], ctx.params.width,
+                                        ctx.params.height)
 
         def launch():
             lib = _lib.load()
             st = stream(rgb.device)
             keys = order = ws = None
-            if grads[0] is not None or grads[1] is not None:
-                # grad rgb and grad in_pos gather over the pixels that sampled each texel: key, order, walk
+            if grads[0] is not None or grads[1] is not None or vgrads[1] is not None:
+                # grad rgb, grad in_pos and grad view2 gather over the pixels that sampled each texel: key, order, walk
                 ws = scratch(lib.srh_reverse_projection_workspace_bytes(C.byref(ctx.params), _lib.RPROJ_WS_BWD),
                              rgb.device)
                 keys = torch.empty(mask.shape, dtype=torch.int32, device=rgb.device)
                 _lib.check(lib.srh_reverse_projection_keys(C.byref(ctx.params), view1.data_ptr(), out_pos.data_ptr(),
                                                            ws.data_ptr(), ws.numel(), keys.data_ptr(), st))
                 order = sorted_order(keys)
-            _lib.check(lib.srh_reverse_projection_bwd(
-                C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
-                out_pos.data_ptr(), mask.data_ptr(), ptr(keys), ptr(order), ptr(ws), 0 if ws is None else ws.numel(),
-                *[ptr(u) for u in ups], *[ptr(g) for g in grads], st))
+            args = (C.byref(ctx.params), view1.data_ptr(), view2.data_ptr(), rgb.data_ptr(), in_pos.data_ptr(),
+                    out_pos.data_ptr(), mask.data_ptr(), ptr(keys), ptr(order), ptr(ws), 0 if ws is None else ws.numel(),
+                    *[ptr(u) for u in ups], *[ptr(g) for g in grads])
+            if vws is None:
+                _lib.check(lib.srh_reverse_projection_bwd(*args, st))
+            else:
+                _lib.check(lib.srh_reverse_projection_bwd_view(*args, *[ptr(g) for g in vgrads], vws.data_ptr(),
+                                                               vws.numel(), st))
 
-        fill_grads(grads, ups, launch)
-        return (None, None, None, None, None, *grads)
+        fill_grads(grads + vgrads, ups, launch)
+        return (None, *vgrads, None, None, *grads)
 
 
 def _validate(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, rotated_image, depth_epsilon,
-              mask_dropout):
+              mask_dropout, camera_grad=False):
     """Everything the kernels index by, checked on the host before anything reaches the GPU (ValueError)."""
     rgb = as_float_tensor("rgb", rgb, _NAME)
     pos = {k: as_float_tensor(k, v, _NAME) for k, v in (("in_pos_wc", in_pos_wc), ("out_pos_wc", out_pos_wc))}
@@ -97,9 +105,9 @@ def _validate(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, ro
     rotated_image = rotated_like(_NAME, rotated_image, rgb)
     cams = []
     for label, camera in (("camera1", camera1), ("camera2", camera2)):
-        if camera_frame(_NAME, camera, label) != (W, H):
+        if camera_frame(_NAME, camera, label, camera_grad) != (W, H):
             raise ValueError(f"{_NAME}: {label}['viewport'] is not the {W} x {H} (W x H) frame of rgb")
-        cams.append(camera_views(_NAME, camera, B, label))
+        cams.append(camera_views(_NAME, camera, B, label, camera_grad=camera_grad))
     depth_epsilon, mask_dropout = float(depth_epsilon), float(mask_dropout)
     if not math.isfinite(depth_epsilon):
         raise ValueError(f"{_NAME}: depth_epsilon = {depth_epsilon}, expected finite")
@@ -109,16 +117,21 @@ def _validate(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, ro
 
 
 def projection_reverse_renderer(rgb, in_pos_wc, out_pos_wc, camera1: Mapping, camera2: Mapping, rotated_image=None,
-                                compute_new_depth: bool = False, depth_epsilon: float = 1e-1,
-                                mask_dropout: float = 0) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                                compute_new_depth: bool = False, depth_epsilon: float = 1e-1, mask_dropout: float = 0,
+                                *, camera_grad: bool = False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """The reference's call.  rgb [B, H, W, D], D in 1..4: the source view; in_pos_wc, out_pos_wc [B, H W, 3]: the world
     positions of the source and of the target view's pixels; camera1 the source camera, camera2 the target camera (eye /
     at / up [B, 3] or [B, 4], a viewport of W x H, fovy and focal_length each); rotated_image like rgb or None.  With
     mask_dropout > 0 the mask is multiplied by F.dropout(ones, mask_dropout, training=True), drawn with torch on the
     GPU, so it follows torch.manual_seed.  Returns (out, {'mask': [B, H, W, 1], 'image1': like rgb, and with
-    compute_new_depth 'depth': [B, H, W, 1]}), float32 on the GPU; without a rotated image out is image1."""
+    compute_new_depth 'depth': [B, H, W, 1]}), float32 on the GPU; without a rotated image out is image1.
+    camera_grad=True lets eye, at and up of both cameras require grad (they are refused otherwise) and gives them their
+    gradient, in their own shape, dtype and device: camera1 through the sample coordinates, camera2 through the values of
+    the new depth (zero without compute_new_depth); values and the other gradients are bit for bit those of the same call
+    with the cameras detached."""
     rgb, in_pos, out_pos, rotated_image, cams, depth_epsilon, mask_dropout = _validate(
-        rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image, depth_epsilon, mask_dropout)
+        rgb, in_pos_wc, out_pos_wc, camera1, camera2, rotated_image, depth_epsilon, mask_dropout,
+        check_camera_grad(_NAME, camera_grad))
     dev = gpu_device(_NAME, (rgb, in_pos, out_pos, rotated_image))
     B, H, W, D = rgb.shape
     x = flat((rgb, in_pos, out_pos, rotated_image), B, H * W, dev)
