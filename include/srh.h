@@ -768,6 +768,8 @@ int srh_reverse_projection_bwd_view(const SrhReverseProjectionParams* params, co
 #define SRH_DPROJ_WS_FWD 0              /* scratch of srh_dense_projection_fwd */
 #define SRH_DPROJ_WS_SAVED 1            /* written by srh_dense_projection_fwd, read by srh_dense_projection_bwd */
 #define SRH_DPROJ_WS_BWD 2              /* scratch of srh_dense_projection_bwd */
+#define SRH_DPROJ_WS_VIEW 4             /* view_workspace of srh_dense_projection_bwd_view: B ceil(N / 64) 96 bytes
+                                           (3 stays refused, as before this value existed) */
 
 typedef struct SrhDenseProjectionParams {
   int32_t n_views;              /* B in 1..65535 */
@@ -797,6 +799,18 @@ int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const doubl
                              const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
                              void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
                              float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream);
+
+/* srh_dense_projection_bwd plus the gradient of the view table (see srh_projection_bwd_view): grad_view (B, 12) fp64,
+ * WRITTEN with every element once; grad_surfels, grad_rgb and grad_rotated may then all be NULL.  Every surfel
+ * contributes, those outside the frame and behind the camera too.  view_workspace: SRH_DPROJ_WS_VIEW bytes, 8-byte
+ * aligned -- this layer's surfel kernel runs one wave per workgroup, so the size is not srh_view_grad_workspace_bytes.
+ * Without a camera gradient to form, call srh_dense_projection_bwd: it launches nothing more than before.  Added without
+ * an ABI version change. */
+int srh_dense_projection_bwd_view(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                                  const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                                  void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                                  float* grad_surfels, float* grad_rgb, float* grad_rotated, double* grad_view,
+                                  void* view_workspace, size_t view_workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The depth-map-to-surfels front end of the reference's re-projection loops (diffrend/torch/projection_layer.py:749-750:
@@ -898,6 +912,15 @@ int srh_normals_fwd(int32_t n_views, int32_t width, int32_t height, const double
  * immaterial before and after. */
 int srh_normals_bwd(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos,
                     const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, void* stream);
+
+/* srh_normals_bwd plus the gradient of the rotations, for the world frame (rot must be given): out = R n, so
+ * d loss / d R = sum_q g_out[q] (x) n[q].  grad_rot (B, 12) fp64, WRITTEN with every element once: entries 0..8 of a
+ * view are its 3 x 3 gradient row-major like rot, entries 9..11 exactly 0 (the layout srh_view_grad.h's finish kernel
+ * writes for every layer).  grad_pos may be NULL = not wanted, and workspace is then not read.  view_workspace:
+ * srh_view_grad_workspace_bytes bytes, 8-byte aligned.  Added without an ABI version change. */
+int srh_normals_bwd_view(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos,
+                         const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, double* grad_rot,
+                         void* view_workspace, size_t view_workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ _SPLATS_NDC = ("render_splats_NDC", "render_splats_NDC_batch")
 _REGULARIZERS = ("splat_regularizers", "REGULARIZER_TERMS")
 _PROJECTION = ("projection_renderer_differentiable_fast",)
 _REVERSE_PROJECTION = ("projection_reverse_renderer",)
-_DENSE_PROJECTION = ("projection_renderer_differentiable",)
+_DENSE_PROJECTION = ("projection_renderer_differentiable", "projection_renderer_differentiable_camera")
 _SURFELS = ("depth_to_surfels",)
 _HARD_PROJECTION = ("projection_renderer",)
 _NORMALS = ("estimate_surface_normals_plane_fit_batched", "estimate_surface_normals_plane_fit", "estimate_surface_normals")

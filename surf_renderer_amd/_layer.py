@@ -50,14 +50,18 @@ def grad_buffers(inputs: Sequence[Optional[torch.Tensor]], needed: Sequence[bool
     return [torch.empty_like(t) if t is not None and need else None for t, need in zip(inputs, needed)]
 
 
-def view_grad_buffers(lib, views: Sequence[torch.Tensor], needed: Sequence[bool], width: int, height: int):
-    """The extra output of a layer's backward under camera_grad: per view table [B, 12] float64 that requires grad a
-    buffer like it (the *_bwd_view entry point writes every element), else None; and the partials workspace those entry
-    points share -- None when no table requires grad, and the backward is then the plain one."""
-    grads = [torch.empty_like(v) if need else None for v, need in zip(views, needed)]
+def view_grad_buffers(lib, views: Sequence[torch.Tensor], needed: Sequence[bool], width: int, height: int,
+                      n_bytes: Optional[Callable[[], int]] = None):
+    """The extra output of a layer's backward under camera_grad: per view table float64 that requires grad a [B, 12]
+    buffer (the *_bwd_view entry point writes every element), else None; and the partials workspace those entry points
+    share -- None when no table requires grad, and the backward is then the plain one.  `n_bytes` gives the workspace's
+    size where the layer's kernel does not run srh_view_grad_workspace_bytes' 256-lane workgroups."""
+    grads = [torch.empty((v.shape[0], 12), dtype=v.dtype, device=v.device) if need else None
+             for v, need in zip(views, needed)]
     if all(g is None for g in grads):
         return grads, None
-    return grads, scratch(lib.srh_view_grad_workspace_bytes(views[0].shape[0], width, height), views[0].device)
+    size = n_bytes() if n_bytes else lib.srh_view_grad_workspace_bytes(views[0].shape[0], width, height)
+    return grads, scratch(size, views[0].device)
 
 
 def upstreams(grads: Iterable[Optional[torch.Tensor]]) -> List[Optional[torch.Tensor]]:

@@ -139,7 +139,7 @@ class SrhReverseProjectionParams(C.Structure):
                 ("focal_length2", C.c_double), ("depth_epsilon", C.c_double)]
 
 
-DPROJ_WS_FWD, DPROJ_WS_SAVED, DPROJ_WS_BWD = 0, 1, 2
+DPROJ_WS_FWD, DPROJ_WS_SAVED, DPROJ_WS_BWD, DPROJ_WS_VIEW = 0, 1, 2, 4
 
 
 class SrhDenseProjectionParams(C.Structure):
@@ -218,6 +218,8 @@ SIGNATURES = {
     "srh_dense_projection_workspace_bytes": (_Z, [_p(SrhDenseProjectionParams), _I]),
     "srh_dense_projection_fwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 3),
     "srh_dense_projection_bwd": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 6),
+    "srh_dense_projection_bwd_view": (C.c_int, [_p(SrhDenseProjectionParams)] + [_V] * 5 + [_Z, _V, _Z] + [_V] * 7
+                                      + [_Z, _V]),
     "srh_depth_to_surfels_fwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 4),
     "srh_depth_to_surfels_bwd": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 5),
     "srh_depth_to_surfels_bwd_view": (C.c_int, [_p(SrhSurfelsParams)] + [_V] * 6 + [_Z, _V]),
@@ -227,6 +229,7 @@ SIGNATURES = {
     "srh_normals_workspace_bytes": (_Z, [_I, _I, _I]),
     "srh_normals_fwd": (C.c_int, [_I, _I, _I] + [_V] * 4),
     "srh_normals_bwd": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V]),
+    "srh_normals_bwd_view": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V, _V, _Z, _V]),
 }
 EXPORTS = tuple(SIGNATURES)
 

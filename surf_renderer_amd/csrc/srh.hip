@@ -1961,6 +1961,7 @@ int dproj_check_rotated(const DProjDev& P, const float* rotated) {
 // SRH_DPROJ_WS_FWD: uv (B, N, 2) fp64
 // SRH_DPROJ_WS_SAVED: sm = S, m (B, D + 1, N) fp64
 // SRH_DPROJ_WS_BWD: gt (B, H, Wp, D + 1) fp64
+// SRH_DPROJ_WS_VIEW: the partials of k_dproj_surfel_bwd<D, true, true>, 12 fp64 per one-wave workgroup (view_ws_bytes)
 struct DProjWs {
   double *uv, *sm, *gt;
   size_t bytes;
@@ -1976,7 +1977,10 @@ DProjWs dproj_ws(const DProjDev& P, int which, const void* base = nullptr) {
   w.bytes = r.bytes;
   return w;
 }
-size_t dproj_ws_bytes(const DProjDev& P, int which) { return dproj_ws(P, which).bytes; }
+int dproj_bwd_groups(const DProjDev& P) { return (P.N + kDProjBwdBlock - 1) / kDProjBwdBlock; }
+size_t dproj_ws_bytes(const DProjDev& P, int which) {
+  return which == SRH_DPROJ_WS_VIEW ? view_ws_bytes(P.B, dproj_bwd_groups(P)) : dproj_ws(P, which).bytes;
+}
 
 // f(std::integral_constant<int, D>) for the channel count D (validated by dproj_setup)
 template <class Fn>
@@ -1996,8 +2000,8 @@ extern "C" {
 size_t srh_dense_projection_workspace_bytes(const SrhDenseProjectionParams* params, int32_t which) {
   DProjDev P;
   if (dproj_setup(params, &P)) return 0;
-  if (which < SRH_DPROJ_WS_FWD || which > SRH_DPROJ_WS_BWD) {
-    fail(SRH_E_TYPE, "which = %d, expected SRH_DPROJ_WS_FWD, _SAVED or _BWD", which);
+  if ((which < SRH_DPROJ_WS_FWD || which > SRH_DPROJ_WS_BWD) && which != SRH_DPROJ_WS_VIEW) {
+    fail(SRH_E_TYPE, "which = %d, expected SRH_DPROJ_WS_FWD, _SAVED, _BWD or _VIEW", which);
     return 0;
   }
   return dproj_ws_bytes(P, which);
@@ -2024,38 +2028,68 @@ int srh_dense_projection_fwd(const SrhDenseProjectionParams* params, const doubl
   return launch_status("dense projection forward launch");
 }
 
-int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
-                             const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
-                             void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
-                             float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+// srh_dense_projection_bwd, and with `with_view` srh_dense_projection_bwd_view
+static int dense_projection_bwd(bool with_view, const SrhDenseProjectionParams* params, const double* view,
+                                const float* surfels, const float* rgb, const float* rotated, const void* saved,
+                                size_t saved_bytes, void* workspace, size_t workspace_bytes, const float* g_out,
+                                const float* g_mask, float* grad_surfels, float* grad_rgb, float* grad_rotated,
+                                double* grad_view, void* view_workspace, size_t view_workspace_bytes, void* stream) {
   DProjDev P;
   int rc = dproj_setup(params, &P);
   if (rc || (rc = dproj_check_rotated(P, rotated))) return rc;
   if ((rc = check_not_null({{"view", view}, {"surfels", surfels}, {"rgb", rgb}}))) return rc;
   if (!g_out && !g_mask) return fail(SRH_E_NULL, "g_out and g_mask are both NULL");
-  if (!grad_surfels && !grad_rgb && !grad_rotated)
+  if (!with_view && !grad_surfels && !grad_rgb && !grad_rotated)
     return fail(SRH_E_NULL, "grad_surfels, grad_rgb and grad_rotated are all NULL");
   if (grad_rotated && !rotated) return fail(SRH_E_NULL, "grad_rotated without rotated");
   if ((rc = check_scratch("saved", saved, saved_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_SAVED)))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, dproj_ws_bytes(P, SRH_DPROJ_WS_BWD)))) return rc;
+  if (with_view) {
+    if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+    if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes,
+                            dproj_ws_bytes(P, SRH_DPROJ_WS_VIEW))))
+      return rc;
+  }
   hipStream_t st = (hipStream_t)stream;
   const double* sm = dproj_ws(P, SRH_DPROJ_WS_SAVED, saved).sm;
   double* gt = dproj_ws(P, SRH_DPROJ_WS_BWD, workspace).gt;
   hipLaunchKernelGGL(k_dproj_pixel_bwd, dim3((P.H * P.Wp + kDProjBlock - 1) / kDProjBlock, P.B), dim3(kDProjBlock), 0, st,
                      P, sm, rotated, g_out, g_mask, gt, grad_rotated);
-  if (grad_surfels || grad_rgb) {
-    const dim3 grid((P.N + kDProjBwdBlock - 1) / kDProjBwdBlock, P.B), block(kDProjBwdBlock);
+  if (with_view || grad_surfels || grad_rgb) {
+    const dim3 grid(dproj_bwd_groups(P), P.B), block(kDProjBwdBlock);
     with_channels(P.D, [&](auto d) {
       constexpr int D = decltype(d)::value;
-      if (grad_surfels)
-        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, true>), grid, block, 0, st, P, view, surfels, rgb, (const double*)gt,
-                           grad_rgb, grad_surfels);
+      if (with_view)
+        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, true, true>), grid, block, 0, st, P, view, surfels, rgb,
+                           (const double*)gt, grad_rgb, grad_surfels, (double*)view_workspace);
+      else if (grad_surfels)
+        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, true, false>), grid, block, 0, st, P, view, surfels, rgb,
+                           (const double*)gt, grad_rgb, grad_surfels, (double*)nullptr);
       else
-        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, false>), grid, block, 0, st, P, view, surfels, rgb, (const double*)gt,
-                           grad_rgb, grad_surfels);
+        hipLaunchKernelGGL((k_dproj_surfel_bwd<D, false, false>), grid, block, 0, st, P, view, surfels, rgb,
+                           (const double*)gt, grad_rgb, grad_surfels, (double*)nullptr);
     });
+    if (with_view) launch_view_finish(P.B, grid.x, kViewSums, 0, view_workspace, grad_view, st);
   }
   return launch_status("dense projection backward launch");
+}
+
+int srh_dense_projection_bwd(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                             const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                             void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                             float* grad_surfels, float* grad_rgb, float* grad_rotated, void* stream) {
+  return dense_projection_bwd(false, params, view, surfels, rgb, rotated, saved, saved_bytes, workspace, workspace_bytes,
+                              g_out, g_mask, grad_surfels, grad_rgb, grad_rotated, nullptr, nullptr, 0, stream);
+}
+
+int srh_dense_projection_bwd_view(const SrhDenseProjectionParams* params, const double* view, const float* surfels,
+                                  const float* rgb, const float* rotated, const void* saved, size_t saved_bytes,
+                                  void* workspace, size_t workspace_bytes, const float* g_out, const float* g_mask,
+                                  float* grad_surfels, float* grad_rgb, float* grad_rotated, double* grad_view,
+                                  void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  return dense_projection_bwd(true, params, view, surfels, rgb, rotated, saved, saved_bytes, workspace, workspace_bytes,
+                              g_out, g_mask, grad_surfels, grad_rgb, grad_rotated, grad_view, view_workspace,
+                              view_workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -2236,10 +2270,32 @@ int srh_normals_bwd(int32_t n_views, int32_t width, int32_t height, const double
   if ((rc = check_not_null({{"pos", pos}, {"g_out", g_out}, {"grad_pos", grad_pos}}))) return rc;
   if ((rc = check_scratch("workspace", workspace, workspace_bytes, norm_ws_bytes(S.B, S.W, S.H)))) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_normals_bwd, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, rot, pos, g_out, (double*)workspace);
+  hipLaunchKernelGGL(k_normals_bwd<false>, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, rot, pos, g_out,
+                     (double*)workspace, (double*)nullptr);
   hipLaunchKernelGGL(k_normals_gather, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, pos, (const double*)workspace,
                      grad_pos);
   return launch_status("normals backward launch");
+}
+
+int srh_normals_bwd_view(int32_t n_views, int32_t width, int32_t height, const double* rot, const float* pos,
+                         const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, double* grad_rot,
+                         void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  static_assert(kViewBlock == kNormBlock, "view_block_reduce's workgroup is the plane fit's");
+  NormDev S;
+  int rc = norm_setup(n_views, width, height, &S);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"rot", rot}, {"pos", pos}, {"g_out", g_out}}))) return rc;
+  if (grad_pos && (rc = check_scratch("workspace", workspace, workspace_bytes, norm_ws_bytes(S.B, S.W, S.H)))) return rc;
+  if ((rc = check_grad_view("grad_rot", grad_rot))) return rc;
+  if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(S.B, S.nblk)))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_normals_bwd<true>, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, rot, pos, g_out,
+                     grad_pos ? (double*)workspace : nullptr, (double*)view_workspace);
+  launch_view_finish(S.B, S.nblk, 9, 0, view_workspace, grad_rot, st);
+  if (grad_pos)
+    hipLaunchKernelGGL(k_normals_gather, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, pos, (const double*)workspace,
+                       grad_pos);
+  return launch_status("normals backward (view) launch");
 }
 
 }  // extern "C"

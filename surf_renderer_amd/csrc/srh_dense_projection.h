@@ -13,7 +13,7 @@
 // the view's surfels in chunks of kDProjChunk: per chunk it fills LDS with ex for the tile's columns, ey for its rows and
 // the values as fp64 -- six exp per surfel and tile, the rest by recurrence -- and every lane adds the chunk to the
 // D + 1 fp64 sums of its eight pixels).  Backward: k_dproj_pixel_bwd (per pixel: the effective upstream row
-// gt[p, 0..D] and the rotated image's gradient) -> k_dproj_surfel_bwd<D, POS> (one lane per surfel sweeps the frame in strips of kDProjStrip columns,
+// gt[p, 0..D] and the rotated image's gradient) -> k_dproj_surfel_bwd<D, POS, kView> (one lane per surfel sweeps the frame in strips of kDProjStrip columns,
 // ex of the strip in registers, one exp per row and strip; gt is the same for every lane: scalar loads) with the chain
 // rule through the projection.  fp64 arithmetic, fp32 results, no atomic, every sum in a fixed order, every output
 // element written once: values and gradients are identical from run to run, and a batch equals its views.
@@ -190,13 +190,21 @@ __global__ __launch_bounds__(kDProjBlock) void k_dproj_pixel_bwd(DProjDev P, con
 //   g_u = sum_j ey[j] sum_c c_c Rx_c[j] / sigma^2,  g_v = sum_j ey[j] (j - v) sum_c c_c R_c[j] / sigma^2
 // summed over the strips in ascending order.  POS: grad_surfels is wanted (else the Rx sums are not formed).  g_rgb
 // (B, N, D) and g_surfels (B, N, 3) are written, each element once; g_rgb may be NULL.
-template <int D, bool POS>
+// kView (with POS: it needs the Rx sums): also the gradient of the view's matrix: cc = M [p, 1], so g_M = sum_s g_cc (x)
+// [p_s, 1] with g_cc = (g_X, g_Y, g_Z) below -- every surfel counts, and one at Z = 0 brings (g_X, g_Y, 0) as its
+// g_surfels does.  The lane keeps g_cc and re-reads its point (vg, vp); a lane past N stays for the butterfly and brings
+// zeros; each workgroup -- one wave -- stores the sums of the 12 products to view_part (view_wave_reduce,
+// srh_view_grad.h), and g_rgb and g_surfels may then both be NULL.  Without kView the trailing argument is unused and
+// the code is what it was without it.
+template <int D, bool POS, bool kView>
 __global__ __launch_bounds__(kDProjBwdBlock) void k_dproj_surfel_bwd(DProjDev P, const double* __restrict__ view,
                                                                      const float* __restrict__ surfels,
                                                                      const float* __restrict__ rgb,
                                                                      const double* __restrict__ gt,
                                                                      float* __restrict__ g_rgb,
-                                                                     float* __restrict__ g_surfels) {
+                                                                     float* __restrict__ g_surfels,
+                                                                     double* __restrict__ view_part) {
+  static_assert(POS || !kView, "the view's gradient needs the Rx sums");
   constexpr int K = kDProjStrip, CH = D + 1;
   const int b = blockIdx.y;
   // a lane past the end repeats the last surfel and stores nothing: the loops below stay uniform
@@ -252,17 +260,27 @@ __global__ __launch_bounds__(kDProjBwdBlock) void k_dproj_surfel_bwd(DProjDev P,
       }
     }
   }
-  if (!live) return;
+  double vg[3] = {0.0, 0.0, 0.0}, vp[3] = {0.0, 0.0, 0.0};      // kView: g_cc and the point; zeros bring zeros
+  do {                                  // a lane that is done leaves by `break`: with kView every lane reaches the reduce
+  if (!live) break;
   if (g_rgb) {
 #pragma unroll
     for (int d = 0; d < D; ++d) g_rgb[o * D + d] = (float)gc[d];
   }
-  if (!POS) return;
+  if (!POS) break;
   gu *= 2.0 * P.h;
   gv *= 2.0 * P.h;
   const double g_X = gu * P.fsx / Q.Zd, g_Y = gv * P.fsy / Q.Zd;
   const double g_Z = Q.Z != 0.0 ? -(g_X * Q.X + g_Y * Q.Y) / Q.Zd : 0.0;
+  if (kView) {
+    vg[0] = g_X; vg[1] = g_Y; vg[2] = g_Z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vp[c] = (double)surfels[3 * o + c];
+    if (!g_surfels) break;
+  }
 #pragma unroll
   for (int j = 0; j < 3; ++j) g_surfels[3 * o + j] = (float)((M[j] * g_X + M[4 + j] * g_Y) + M[8 + j] * g_Z);
+  } while (false);
+  if (kView) view_wave_reduce<kViewSums>([&](int k) { return view_outer_term(vg, vp, k); }, view_part);
 }
 }  // namespace srh

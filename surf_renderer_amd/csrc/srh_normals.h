@@ -25,6 +25,7 @@
 // are linear in.  fp64 arithmetic, one fp32 store per element; neighbours are read through the cache, no LDS.
 #pragma once
 #include "srh_splat.h"   // reflect_idx, unit_inv3
+#include "srh_view_grad.h"
 
 namespace srh {
 
@@ -96,18 +97,30 @@ __global__ __launch_bounds__(kNormBlock) void k_normals_fwd(NormDev S, const dou
   for (int r = 0; r < 3; ++r) out[3 * (base + q) + r] = (float)n[r];
 }
 
-// Backward, pass 1: g_out (B, N, 3) fp32 -> ws (B, N, 5) fp64, d loss / d (a, b, d, r0, r1) of every centre
+// Backward, pass 1: g_out (B, N, 3) fp32 -> ws (B, N, 5) fp64, d loss / d (a, b, d, r0, r1) of every centre.
+// kView (with rot): also the gradient of the view's rotation: out = R n, so g_R = sum_q g_out[q] (x) n[q] with n the
+// unit camera-space normal formed below.  The lane keeps g_out and n (vg, vn), a lane past N brings zeros, and each
+// workgroup stores its 9 sums to view_part (srh_view_grad.h); ws may then be NULL = grad_pos is not wanted.  Without
+// kView the trailing argument is unused and the code is what it was without it.
+template <bool kView>
 __global__ __launch_bounds__(kNormBlock) void k_normals_bwd(NormDev S, const double* __restrict__ rot,
                                                             const float* __restrict__ pos,
-                                                            const float* __restrict__ g_out, double* __restrict__ ws) {
+                                                            const float* __restrict__ g_out, double* __restrict__ ws,
+                                                            double* __restrict__ view_part) {
   const int q = blockIdx.x * kNormBlock + threadIdx.x;
   const int b = blockIdx.y;
-  if (q >= S.N) return;
+  double vg[3] = {0.0, 0.0, 0.0}, vn[3] = {0.0, 0.0, 0.0};      // kView: g_out and n; zeros bring zeros
+  do {                                  // a lane that is done leaves by `break`: with kView every lane reaches the reduce
+  if (q >= S.N) break;
   const size_t base = (size_t)b * S.N;
   const int i = q / S.W, j = q - i * S.W;
   double Pc[3], g_n[3];
   norm_load(pos, base + q, Pc);
   norm_load(g_out, base + q, g_n);
+  if (kView) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vg[c] = g_n[c];
+  }
   if (rot) {                                   // R^T g
     double R[9];
     norm_load_rot(rot, b, R);
@@ -118,6 +131,11 @@ __global__ __launch_bounds__(kNormBlock) void k_normals_bwd(NormDev S, const dou
   NormFit F;
   norm_fit(S, pos, base, i, j, Pc, F);
   const double n[3] = {F.nx * F.s_inv, F.ny * F.s_inv, F.s_inv};
+  if (kView) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vn[c] = n[c];
+    if (!ws) break;
+  }
   const double proj = (n[0] * g_n[0] + n[1] * g_n[1]) + n[2] * g_n[2];
   const double g_nx = (g_n[0] - n[0] * proj) * F.s_inv, g_ny = (g_n[1] - n[1] * proj) * F.s_inv;
   const double g_D = -(F.nx * g_nx + F.ny * g_ny) / F.D;
@@ -127,6 +145,8 @@ __global__ __launch_bounds__(kNormBlock) void k_normals_bwd(NormDev S, const dou
   w[2] = (F.r0 * g_nx) / F.D + g_D * F.a;                                  // g_d
   w[3] = (F.d * g_nx - F.b * g_ny) / F.D;                                  // g_r0
   w[4] = (F.a * g_ny - F.b * g_nx) / F.D;                                  // g_r1
+  } while (false);
+  if (kView) view_block_reduce<9>([&](int k) { return vg[k / 3] * vn[k % 3]; }, view_part);
 }
 
 // how many of the offsets -1, 0, 1 from `from` reflection lands on `to`, along an axis of n samples

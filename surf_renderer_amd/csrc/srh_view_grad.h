@@ -1,5 +1,5 @@
-// The camera gradient of the depth lift and of the two surfel warps (srh_surfels.h, srh_projection.h,
-// srh_reverse_projection.h), up to the per-view 3 x 4 matrix the layer is handed: the kView variants of the layers'
+// The camera gradient of the depth lift, of the three surfel warps and of the world-frame normals (srh_surfels.h,
+// srh_projection.h, srh_reverse_projection.h, srh_dense_projection.h, srh_normals.h), up to the per-view 3 x 4 matrix the layer is handed: the kView variants of the layers'
 // backward kernels form, per lane, the products that sum to d loss / d matrix, and this header holds the one copy of
 // the reduction.  The chain from the matrix to eye / at / up is the host's.  See DESIGN.md "Differentiable cameras for
 // the depth lift and the two warps".
@@ -9,6 +9,8 @@
 //                       part[b][workgroup][K].  A workgroup with no lane in range stores zeros.  The lane hands its
 //                       terms over as a function of k, so that the 12 products of an outer product g (x) [p, 1] are
 //                       formed one at a time from 6 values and never live together (view_outer_term).
+//   view_wave_reduce    the same for a workgroup that is one wave (the dense projection's surfel kernel): the butterfly
+//                       alone, no LDS and no barrier; lane k keeps sum k and K lanes store.
 //   k_view_finish       one workgroup per view adds the view's partials: row j of kViewRows takes the workgroups j,
 //                       j + kViewRows, ... in that order, then the rows are halved log2(kViewRows) times through LDS.
 //                       The order depends only on the number of workgroups, i.e. on N.
@@ -51,6 +53,20 @@ __device__ __forceinline__ void view_block_reduce(Term term, double* __restrict_
   if (threadIdx.x < K)
     part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * K + threadIdx.x] =
         ((lds[0][threadIdx.x] + lds[1][threadIdx.x]) + lds[2][threadIdx.x]) + lds[3][threadIdx.x];
+}
+
+// The one-wave form: called by EVERY lane of a one-dimensional 64-thread workgroup.  Every lane gets every sum (the
+// butterfly), lane k keeps the k-th, and lanes 0 .. K - 1 store them: part (gridDim.y, gridDim.x, K) fp64 as above.
+template <int K, class Term>
+__device__ __forceinline__ void view_wave_reduce(Term term, double* __restrict__ part) {
+  static_assert(K >= 1 && K <= kViewSums, "at most a 3 x 4 matrix");
+  double mine = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double sum = view_wave_sum(term(k));
+    if ((int)threadIdx.x == k) mine = sum;
+  }
+  if (threadIdx.x < K) part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * K + threadIdx.x] = mine;
 }
 
 // part (B, ngroups, K) fp64 -> grad_view (B, 12) fp64, every element written: entries [first, first + K) get the sums,
