@@ -81,14 +81,65 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
   // pass 1, arithmetic only: bit k of `mask` = tile k of the box (row-major) is reached
   const uint32_t inv_nx = 65536u / (uint32_t)nx + 1u;            // k / nx == (k * inv_nx) >> 16 for k < 64, nx <= 64
   uint64_t mask = 0;
-  for (int k = 0; k < n; ++k) {
-    const int dy = (int)(((uint32_t)k * inv_nx) >> 16);
-    const int tx = tx0 + (k - dy * nx), ty = ty0 + dy;
-    const double pc0 = tx * kTile - F.bin_pad, pr0 = F.row0 + ty * kTile - F.bin_pad;
-    const double pc1 = fmin(tx * kTile + kTile - 1, (double)(F.W - 1)) + F.bin_pad;
-    const double pr1 = fmin(F.row0 + ty * kTile + kTile - 1, (double)(F.row1 - 1)) + F.bin_pad;
-    if (T.reaches(pc0, pc1, pr0, pr1)) mask |= 1ull << k;
+  bool by_rows = false;
+#if SRH_BIN_ROW_SPANS
+  // discs and spheres: per tile ROW the run of columns the stored ellipse reaches (ConicSpans, srh_reject.h) -- two roots
+  // per row where `reaches` minimises the form over four edges per tile.  A lane whose record has no closed form takes
+  // the tile loop below (divergent; an ordinary scene has none: a record without an ellipse has no box either).
+  if (type == SRH_PRIM_DISK || type == SRH_PRIM_SPHERE) {
+    const ConicSpans S(T);
+    if (S.usable) {
+      by_rows = true;
+      const double wlast = (double)(F.W - 1);
+      const auto row_term = [&](int ty) {
+        return fmax(T.u2 * (F.row0 + ty * kTile - F.bin_pad),
+                    T.u2 * (fmin(F.row0 + ty * kTile + kTile - 1, (double)(F.row1 - 1)) + F.bin_pad));
+      };
+      const auto behind = [&](int tx, double rterm) {
+        return T.den_max(tx * kTile - F.bin_pad, fmin(tx * kTile + kTile - 1, wlast) + F.bin_pad, rterm) <= T.hi;
+      };
+      // den_max = (u0 + column term) + row term, and every operation rounds monotonically: it rises with tx for u1 >= 0
+      // and falls otherwise, likewise with ty and u2.  Its smallest value over the box sits at one corner; where that
+      // corner is not behind the eye no tile is (nearly every disc), and the rows below skip the test.
+      // (spheres have no estimate: u0 .. hi are read under T.behind only)
+      bool rising = false, hides = false;
+      if (T.behind) {
+        rising = T.u1 >= 0.0;
+        hides = behind(rising ? tx0 : tx1, row_term(T.u2 >= 0.0 ? ty0 : ty1));
+      }
+      for (int ty = ty0, bit0 = 0; ty <= ty1; ++ty, bit0 += nx) {
+        const double pr0 = F.row0 + ty * kTile - F.bin_pad;
+        const double pr1 = fmin(F.row0 + ty * kTile + kTile - 1, (double)(F.row1 - 1)) + F.bin_pad;
+        double lo, hi;
+        if (!S.row(pr0 - T.y0, pr1 - T.y0, &lo, &hi)) continue;
+        // pc0(tx) = 16 tx - pad <= hi  and  pc1(tx) = min(16 tx + 15, W - 1) + pad >= lo, clamped to the box; only the
+        // image's last column has its pc1 below 16 tx + 15 + pad, and it is then the run's first tile or outside it
+        int ta = (int)fmin(fmax(ceil((lo - F.bin_pad - (kTile - 1)) * (1.0 / kTile)), (double)tx0), (double)(tx1 + 1));
+        int tb = (int)fmax(fmin(floor((hi + F.bin_pad) * (1.0 / kTile)), (double)tx1), (double)(tx0 - 1));
+        if (ta * kTile + kTile - 1 > F.W - 1 && !(wlast + F.bin_pad >= lo)) continue;
+        if (ta > tb) continue;
+        if (hides) {
+          // the tiles den_max leaves in the row are a run that keeps the `best` end: decided at the two ends, and tile by
+          // tile from the worst end only where they disagree -- the decisions of `reaches`, tile for tile
+          const double rterm = row_term(ty);
+          if (behind(rising ? tb : ta, rterm)) continue;
+          if (rising) { while (behind(ta, rterm)) ++ta; }
+          else { while (behind(tb, rterm)) --tb; }
+        }
+        mask |= (~0ull >> (63 - (tb - ta))) << (bit0 + (ta - tx0));
+      }
+    }
   }
+#endif
+  if (!by_rows)
+    for (int k = 0; k < n; ++k) {
+      const int dy = (int)(((uint32_t)k * inv_nx) >> 16);
+      const int tx = tx0 + (k - dy * nx), ty = ty0 + dy;
+      const double pc0 = tx * kTile - F.bin_pad, pr0 = F.row0 + ty * kTile - F.bin_pad;
+      const double pc1 = fmin(tx * kTile + kTile - 1, (double)(F.W - 1)) + F.bin_pad;
+      const double pr1 = fmin(F.row0 + ty * kTile + kTile - 1, (double)(F.row1 - 1)) + F.bin_pad;
+      if (T.reaches(pc0, pc1, pr0, pr1)) mask |= 1ull << k;
+    }
   // pass 2: the slot claimed in a bin's counter is the entry's place in the bin's fixed-capacity list.  kClaims claims
   // at a time, so that their round trips overlap instead of adding up (a thread owns ~6 bins on average).
   const uint32_t cap = (uint32_t)F.bin_cap;

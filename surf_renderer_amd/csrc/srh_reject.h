@@ -587,6 +587,85 @@ struct RectTest {
     }
     return !(qmin > 1.000001);
   }
+
+  // the `behind` expression of `reaches`, operation for operation, with the row term handed in:
+  // rterm = fmax(u2 * r0, u2 * r1)
+  __device__ __forceinline__ double den_max(double c0, double c1, double rterm) const {
+    return u0 + fmax(u1 * c0, u1 * c1) + rterm;
+  }
+};
+
+// ---- row spans of a stored ellipse (bin_place) --------------------------------------------------------------------------
+// SRH_BIN_ROW_SPANS is a MEASUREMENT switch: 1 (the default) picks a conic's tiles row by row from the closed form
+// below, 0 compiles RectTest::reaches once per tile of the box for conics too, as triangles have it -- so that one
+// tree builds both criteria for an A/B (tools/ab.sh) and for the per-tile count comparison.
+#ifndef SRH_BIN_ROW_SPANS
+#define SRH_BIN_ROW_SPANS 1
+#endif
+
+// The candidate region q(dc, dr) = A11 dc^2 + 2 A12 dc dr + A22 dr^2 <= lambda (lambda = 1.000001, the threshold of
+// `reaches`) is convex: over the band dr in [a, b] of one tile row its columns are ONE interval [lo, hi], and a tile of
+// that row is reached iff its own column interval meets it.  For a fixed dr the region is
+//   dc in (-A12 dr -+ sqrt(lambda A11 - det dr^2)) / A11,      det = A11 A22 - A12^2,
+// empty beyond |dr| > dr_max = sqrt(lambda A11 / det).  The upper branch is concave in dr with its maximum
+// dc_max = sqrt(lambda A22 / det) at dr* = -A12 dc_max / A22, the lower one is its mirror image (convex, minimum at
+// -dr*): hi is the upper branch at clamp(dr*, a, b), lo the lower one at clamp(-dr*, a, b).  Every column between lo and
+// hi has a dr in the band with q <= lambda, so the tiles found are exactly those whose exact minimum of q is <= lambda.
+//
+// Rounding.  A11, A12, A22 are fp32 values: the products of det are exact in fp64, det carries one rounding.  An error
+// eta A11 on the radicand is the same as lambda moved by eta (a few 2^-52: one fma on terms <= lambda A11).  The
+// reciprocals and roots are the Newton forms (kFastEps each, see above): with |A12 dr| / A11 and the root / A11 both
+// <= dc_max they move lo and hi by less than 2^-42 dc_max; dr* is a stationary point of either branch, its error enters
+// squared.  The sums with the centre (|x0| < 2^20 (1 + 2^-24): conic_record's far_lim and the fp32 store) and with the pad
+// and the tile edge round three times, half an ulp each: 3 x 2^-53 (2^20 + dc_max + 32) = 0.375 x 2^-30 + 3 x 2^-53 dc_max
+// pixels.  The span is widened OUTWARD by
+//   m = 2^-30 (1 + dc_max) pixels                               (folded into the centre: xl = x0 - m, xh = x0 + m):
+// its constant part is 2.6 times the roundings' at the 2^20-pixel limit (1300 times at |x0| = 2048), its dc_max part 4000
+// times that of the fast forms and the roundings together; dr_max takes the factor 1 + 2^-30.  lambda itself stands 1e-6
+// above the 1 a true hit can reach (conic_record's inflation is not touched), so the result is a superset of the tiles whose exact
+// minimum is <= 1; the widening raises q at the span's ends by 2 sqrt(lambda A11) m at most (|dq / ddc| <= 2 sqrt(A11 q)),
+// that is 2^-29 (sqrt(A11) + sqrt(A11 A22 / det)): 1e-6 for an ellipse 1/512 pixel thin, 2^-20 for axis ratio 512.
+// The floor / ceil that turn lo and hi into tile indices are monotone and tile edges are integers: they only err outward.
+//
+// `usable` is false -- the caller keeps the per-tile loop -- when the record is no ellipse, det is not safely positive
+// (below 2^-30 A11 A22; conic_record's axis-ratio limit keeps stored forms above 2^-17) or an extent is not finite.
+struct ConicSpans {
+  bool usable;
+  double det, lam11, nA12, i11, dr_max, dr_star, xl, xh;
+
+  __device__ inline explicit ConicSpans(const RectTest& T) : usable(false) {
+    if (!T.ellipse) return;
+    const double p = T.A11 * T.A22;
+    det = p - T.A12 * T.A12;
+    if (!(det > 9.313225746154785e-10 * p)) return;
+    const double idet = rcp_newton(det);
+    const double cx2 = 1.000001 * T.A22 * idet, ry2 = 1.000001 * T.A11 * idet;
+    const double dc_max = cx2 * rsqrt_newton(cx2), ry = ry2 * rsqrt_newton(ry2);
+    if (!(dc_max < 1.0e30) || !(ry < 1.0e30)) return;            // NaN, inf: the Newton forms over- or underflowed
+    const double m = 9.313225746154785e-10 * (1.0 + dc_max);
+    dr_star = -T.A12 * dc_max * T.i22;
+    dr_max = ry * (1.0 + 9.313225746154785e-10);
+    lam11 = 1.000001 * T.A11; nA12 = -T.A12; i11 = T.i11;
+    xl = T.x0 - m; xh = T.x0 + m;
+    usable = true;
+  }
+
+  // sqrt(max(x, 0)) for a radicand of the size of lam11 (a stored A11 is above 2^-60, conic_record): clamped at 1e-200
+  // instead of 0 -- a root of 1e-100 where it should be 0 -- which keeps the Newton form clear of rsq(0) = inf
+  static __device__ __forceinline__ double root(double x) {
+    const double xm = fmax(x, 1.0e-200);
+    return xm * rsqrt_newton(xm);
+  }
+
+  // column extent [lo, hi] (full-image pixel coordinates, widened) over the band dr in [a, b]; false: the band is empty
+  __device__ __forceinline__ bool row(double a, double b, double* lo, double* hi) const {
+    if (!(a <= dr_max) || !(b >= -dr_max)) return false;
+    const double dR = fmin(fmax(dr_star, a), b), dL = fmin(fmax(-dr_star, a), b);
+    const double sR = root(__builtin_fma(-det * dR, dR, lam11)), sL = root(__builtin_fma(-det * dL, dL, lam11));
+    *hi = __builtin_fma(__builtin_fma(nA12, dR, sR), i11, xh);
+    *lo = __builtin_fma(__builtin_fma(nA12, dL, -sL), i11, xl);
+    return true;
+  }
 };
 
 }  // namespace srh
