@@ -451,7 +451,7 @@ typedef struct SrhSplatInputs {
  * pos (B, N, pos_cols) with zeros outside column pos_cols - 1, normal (B, N, 3) (given normals only), light_vis
  * (B, n_lights, N).  The scene parameters are ADDED with fp32 atomics (zero-fill them first) in their input layouts:
  * lights_pos (n_lights,4) per view at lights_pos_view_stride, colors, attenuation, ambient, albedo, coeffs.
- * NULL = not wanted.  The camera has no gradient.  A geometry-only frame (shade = 0) depends on none of light_vis,
+ * NULL = not wanted.  The camera's gradient is srh_splat_bwd_view's.  A geometry-only frame (shade = 0) depends on none of light_vis,
  * the lights, colours and materials: srh_splat_bwd refuses those gradient buffers then (SRH_E_TYPE). */
 typedef struct SrhSplatGrads {
   float* pos;
@@ -480,6 +480,21 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
                   const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
                   const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
                   const SrhSplatGrads* grads, void* stream);
+
+/* srh_splat_bwd plus the camera's gradient up to the per-view matrix: the camera enters only through the lights'
+ * camera coordinates L = M (l_xyz, l_w), M the view's 3 x 4 world-to-camera matrix as the kernels build it from eye /
+ * at / up, and grad_view (B, 12) fp64, row-major per view, is d loss / d M = sum over pixels, sub-pixels and lights of
+ * g_L (x) (l_x, l_y, l_z, l_w), WRITTEN with every element once (the chain from the matrix to eye / at / up is the
+ * caller's).  The buffers of `grads` may then all be NULL; a geometry-only frame (shade = 0) does not depend on the
+ * camera and is refused (SRH_E_TYPE).  view_workspace: srh_view_grad_workspace_bytes(n_views, width, height) bytes of
+ * the BASE grid, 8-byte aligned; the partial sums are added without atomics in an order that depends only on width x
+ * height, so grad_view is identical from run to run and a view of a batch gets the bits of the same view alone.  The
+ * gradients of `grads` are srh_splat_bwd's.  Added without an ABI version change. */
+int srh_splat_bwd_view(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                       const SrhMaterials* materials, void* workspace, size_t workspace_bytes, const float* grad_image,
+                       const float* grad_depth, const float* grad_pos, const float* grad_normal,
+                       const SrhSplatGrads* grads, double* grad_view, void* view_workspace,
+                       size_t view_workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The reference's NDC splat renderer, render_splats_NDC (diffrend/torch/renderer.py:358-474): one splat per pixel of a
@@ -522,8 +537,8 @@ typedef struct SrhSplatNdcInputs {
 /* Gradients.  pos (B, N, pos_cols: every column) and normal (B, N, 3) are WRITTEN, each element by the lane that owns
  * the splat (no atomics, no zero-fill, no workspace: identical from run to run).  The scene parameters are ADDED with
  * fp32 atomics (zero-fill them first) in their input layouts, as SrhSplatGrads: lights_pos (n_lights,4) per view at
- * lights_pos_view_stride, colors, attenuation, ambient, albedo, coeffs.  NULL = not wanted.  The camera has no
- * gradient.  A geometry-only frame (shade = 0) depends on none of the lights, colours and materials:
+ * lights_pos_view_stride, colors, attenuation, ambient, albedo, coeffs.  NULL = not wanted.  The camera's
+ * gradient is srh_splat_ndc_bwd_view's.  A geometry-only frame (shade = 0) depends on none of the lights, colours and materials:
  * srh_splat_ndc_bwd refuses those gradient buffers then (SRH_E_TYPE). */
 typedef struct SrhSplatNdcGrads {
   float* pos;
@@ -547,6 +562,15 @@ int srh_splat_ndc_fwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* 
 int srh_splat_ndc_bwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
                       const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
                       const float* grad_pos, const SrhSplatNdcGrads* grads, void* stream);
+
+/* srh_splat_ndc_bwd plus grad_view (B, 12) fp64, the gradient with respect to the view's 3 x 4 world-to-camera matrix
+ * through the lights' camera coordinates, exactly as srh_splat_bwd_view: every element WRITTEN once (zeros without
+ * grad_image), no atomics, the buffers of `grads` may all be NULL, shade = 0 is refused (SRH_E_TYPE), view_workspace of
+ * srh_view_grad_workspace_bytes(n_views, width, height) bytes, 8-byte aligned.  Added without an ABI version change. */
+int srh_splat_ndc_bwd_view(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                           const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
+                           const float* grad_pos, const SrhSplatNdcGrads* grads, double* grad_view,
+                           void* view_workspace, size_t view_workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * The geometric regularisers the reference's trainers put on every rendered splat view (diffrend/torch/GAN/gan.py:

@@ -230,6 +230,8 @@ SIGNATURES = {
     "srh_normals_fwd": (C.c_int, [_I, _I, _I] + [_V] * 4),
     "srh_normals_bwd": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V]),
     "srh_normals_bwd_view": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V, _V, _Z, _V]),
+    "srh_splat_bwd_view": (C.c_int, _SPLAT + [_V, _Z] + [_V] * 4 + [_p(SrhSplatGrads), _V, _V, _Z, _V]),
+    "srh_splat_ndc_bwd_view": (C.c_int, _SPLAT_NDC + [_V] * 3 + [_p(SrhSplatNdcGrads), _V, _V, _Z, _V]),
 }
 EXPORTS = tuple(SIGNATURES)
 

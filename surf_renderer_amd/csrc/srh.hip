@@ -1300,6 +1300,60 @@ int splat_setup(const SrhSplatParams* p, const SrhSplatInputs* in, const SrhLigh
 
 size_t splat_ws_bytes(const SplatDev& S) { return S.estimate ? (size_t)S.B * S.N * 9 * sizeof(double) : 0; }
 
+// the host side of srh_view_grad.h, defined below with the lift and the warps
+size_t view_ws_bytes(int B, int nblk);
+int check_grad_view(const char* name, const double* g);
+void launch_view_finish(int B, int nblk, int K, int first, const void* part, double* grad_view, hipStream_t st);
+static_assert(kViewBlock == 256, "view_block_reduce's workgroup is the splat kernels'");
+
+// srh_splat_bwd (grad_view = NULL) and srh_splat_bwd_view
+int splat_bwd_any(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                  const SrhMaterials* materials, void* workspace, size_t workspace_bytes, const float* grad_image,
+                  const float* grad_depth, const float* grad_pos, const float* grad_normal, const SrhSplatGrads* grads,
+                  bool with_view, double* grad_view, void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  SplatDev S;
+  int rc = splat_setup(params, inputs, lights, materials, &S);
+  if (rc) return rc;
+  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
+  if (!grad_image && !grad_depth && !grad_pos && !grad_normal)
+    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_pos and grad_normal are all NULL");
+  if (!S.shade && (grad_image || grads->light_vis || grads->lights_pos || grads->colors || grads->attenuation ||
+                   grads->ambient || grads->albedo || grads->coeffs))
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
+  if (!S.shade && with_view)
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) does not depend on the camera: no grad_view");
+  if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
+  if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
+  const bool gather = S.estimate && grads->pos;
+  if (gather && (rc = check_scratch("workspace", workspace, workspace_bytes, splat_ws_bytes(S)))) return rc;
+  const dim3 grid((S.N + 255) / 256, S.B);
+  if (with_view) {
+    if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+    if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(S.B, grid.x)))) return rc;
+  }
+  SplatGradsDev G;
+  G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
+  G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
+  G.coeffs = grads->coeffs;
+  if (S.estimate && !gather) {
+    G.pos = nullptr;
+    if (!with_view && !G.vis && !G.lpos && !G.colors && !G.latt && !G.amb && !G.albedo && !G.coeffs) return SRH_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // without z gradients the stencil slots are not wanted: k_splat_bwd then needs no workspace
+  double* ws = gather ? (double*)workspace : nullptr;
+  if (with_view) {
+    hipLaunchKernelGGL(k_splat_bwd<true>, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws,
+                       (double*)view_workspace);
+    launch_view_finish(S.B, grid.x, kViewSums, 0, view_workspace, grad_view, st);
+  } else {
+    hipLaunchKernelGGL(k_splat_bwd<false>, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal,
+                       ws, (double*)nullptr);
+  }
+  if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
+  return launch_status(with_view ? "splat backward (view) launch" : "splat backward launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1333,34 +1387,17 @@ int srh_splat_bwd(const SrhSplatParams* params, const SrhSplatInputs* inputs, co
                   const SrhMaterials* materials, void* workspace, size_t workspace_bytes,
                   const float* grad_image, const float* grad_depth, const float* grad_pos, const float* grad_normal,
                   const SrhSplatGrads* grads, void* stream) {
-  SplatDev S;
-  int rc = splat_setup(params, inputs, lights, materials, &S);
-  if (rc) return rc;
-  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
-  if (!grad_image && !grad_depth && !grad_pos && !grad_normal)
-    return fail(SRH_E_NULL, "grad_image, grad_depth, grad_pos and grad_normal are all NULL");
-  if (!S.shade && (grad_image || grads->light_vis || grads->lights_pos || grads->colors || grads->attenuation ||
-                   grads->ambient || grads->albedo || grads->coeffs))
-    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image, light_vis or shading gradients");
-  if (grads->light_vis && !S.vis) return fail(SRH_E_NULL, "grads.light_vis without inputs.light_vis");
-  if (grads->normal && !S.normal) return fail(SRH_E_NULL, "grads.normal without inputs.normal (estimated normals)");
-  const bool gather = S.estimate && grads->pos;
-  if (gather && (rc = check_scratch("workspace", workspace, workspace_bytes, splat_ws_bytes(S)))) return rc;
-  SplatGradsDev G;
-  G.pos = grads->pos; G.normal = grads->normal; G.vis = grads->light_vis; G.lpos = grads->lights_pos;
-  G.colors = grads->colors; G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo;
-  G.coeffs = grads->coeffs;
-  if (S.estimate && !gather) {
-    G.pos = nullptr;
-    if (!G.vis && !G.lpos && !G.colors && !G.latt && !G.amb && !G.albedo && !G.coeffs) return SRH_OK;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((S.N + 255) / 256, S.B);
-  // without z gradients the stencil slots are not wanted: k_splat_bwd then needs no workspace
-  double* ws = gather ? (double*)workspace : nullptr;
-  hipLaunchKernelGGL(k_splat_bwd, grid, dim3(256), 0, st, S, G, grad_image, grad_depth, grad_pos, grad_normal, ws);
-  if (gather) hipLaunchKernelGGL(k_splat_gather, grid, dim3(256), 0, st, S, grads->pos, (const double*)ws);
-  return launch_status("splat backward launch");
+  return splat_bwd_any(params, inputs, lights, materials, workspace, workspace_bytes, grad_image, grad_depth, grad_pos,
+                       grad_normal, grads, false, nullptr, nullptr, 0, stream);
+}
+
+int srh_splat_bwd_view(const SrhSplatParams* params, const SrhSplatInputs* inputs, const SrhLights* lights,
+                       const SrhMaterials* materials, void* workspace, size_t workspace_bytes, const float* grad_image,
+                       const float* grad_depth, const float* grad_pos, const float* grad_normal,
+                       const SrhSplatGrads* grads, double* grad_view, void* view_workspace,
+                       size_t view_workspace_bytes, void* stream) {
+  return splat_bwd_any(params, inputs, lights, materials, workspace, workspace_bytes, grad_image, grad_depth, grad_pos,
+                       grad_normal, grads, true, grad_view, view_workspace, view_workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -1413,6 +1450,47 @@ int splat_ndc_setup(const SrhSplatNdcParams* p, const SrhSplatNdcInputs* in, con
   return SRH_OK;
 }
 
+// srh_splat_ndc_bwd (grad_view = NULL) and srh_splat_ndc_bwd_view
+int splat_ndc_bwd_any(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                      const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
+                      const float* grad_pos, const SrhSplatNdcGrads* grads, bool with_view, double* grad_view,
+                      void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  SplatNdcDev D;
+  int rc = splat_ndc_setup(params, inputs, lights, materials, &D);
+  if (rc) return rc;
+  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
+  if (!grad_image && !grad_depth && !grad_pos)
+    return fail(SRH_E_NULL, "grad_image, grad_depth and grad_pos are all NULL");
+  if (!with_view && !grads->pos && !grads->normal && !grads->lights_pos && !grads->colors && !grads->attenuation &&
+      !grads->ambient && !grads->albedo && !grads->coeffs)
+    return fail(SRH_E_NULL, "the gradient buffers of grads are all NULL");
+  if (!D.S.shade && (grad_image || grads->lights_pos || grads->colors || grads->attenuation || grads->ambient ||
+                     grads->albedo || grads->coeffs))
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image or shading gradients");
+  if (!D.S.shade && with_view)
+    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) does not depend on the camera: no grad_view");
+  const dim3 grid((D.S.N + 255) / 256, D.S.B);
+  if (with_view) {
+    if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+    if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(D.S.B, grid.x))))
+      return rc;
+  }
+  SplatGradsDev G;
+  memset(&G, 0, sizeof(G));
+  G.pos = grads->pos; G.normal = grads->normal; G.lpos = grads->lights_pos; G.colors = grads->colors;
+  G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo; G.coeffs = grads->coeffs;
+  hipStream_t st = (hipStream_t)stream;
+  if (with_view) {
+    hipLaunchKernelGGL(k_splat_ndc_bwd<true>, grid, dim3(256), 0, st, D, G, grad_image, grad_depth, grad_pos,
+                       (double*)view_workspace);
+    launch_view_finish(D.S.B, grid.x, kViewSums, 0, view_workspace, grad_view, st);
+    return launch_status("splat NDC backward (view) launch");
+  }
+  hipLaunchKernelGGL(k_splat_ndc_bwd<false>, grid, dim3(256), 0, st, D, G, grad_image, grad_depth, grad_pos,
+                     (double*)nullptr);
+  return launch_status("k_splat_ndc_bwd launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1431,25 +1509,16 @@ int srh_splat_ndc_fwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* 
 int srh_splat_ndc_bwd(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
                       const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
                       const float* grad_pos, const SrhSplatNdcGrads* grads, void* stream) {
-  SplatNdcDev D;
-  int rc = splat_ndc_setup(params, inputs, lights, materials, &D);
-  if (rc) return rc;
-  if (!grads) return fail(SRH_E_NULL, "grads is NULL");
-  if (!grad_image && !grad_depth && !grad_pos)
-    return fail(SRH_E_NULL, "grad_image, grad_depth and grad_pos are all NULL");
-  if (!grads->pos && !grads->normal && !grads->lights_pos && !grads->colors && !grads->attenuation && !grads->ambient &&
-      !grads->albedo && !grads->coeffs)
-    return fail(SRH_E_NULL, "the gradient buffers of grads are all NULL");
-  if (!D.S.shade && (grad_image || grads->lights_pos || grads->colors || grads->attenuation || grads->ambient ||
-                     grads->albedo || grads->coeffs))
-    return fail(SRH_E_TYPE, "a geometry-only frame (shade = 0) has no image or shading gradients");
-  SplatGradsDev G;
-  memset(&G, 0, sizeof(G));
-  G.pos = grads->pos; G.normal = grads->normal; G.lpos = grads->lights_pos; G.colors = grads->colors;
-  G.latt = grads->attenuation; G.amb = grads->ambient; G.albedo = grads->albedo; G.coeffs = grads->coeffs;
-  const dim3 grid((D.S.N + 255) / 256, D.S.B);
-  hipLaunchKernelGGL(k_splat_ndc_bwd, grid, dim3(256), 0, (hipStream_t)stream, D, G, grad_image, grad_depth, grad_pos);
-  return launch_status("k_splat_ndc_bwd launch");
+  return splat_ndc_bwd_any(params, inputs, lights, materials, grad_image, grad_depth, grad_pos, grads, false, nullptr,
+                           nullptr, 0, stream);
+}
+
+int srh_splat_ndc_bwd_view(const SrhSplatNdcParams* params, const SrhSplatNdcInputs* inputs, const SrhLights* lights,
+                           const SrhMaterials* materials, const float* grad_image, const float* grad_depth,
+                           const float* grad_pos, const SrhSplatNdcGrads* grads, double* grad_view,
+                           void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  return splat_ndc_bwd_any(params, inputs, lights, materials, grad_image, grad_depth, grad_pos, grads, true, grad_view,
+                           view_workspace, view_workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -17,9 +17,15 @@
 // neighbours: k_splat_bwd stores, per splat, d loss / d Z of each of the 9 stencil slots (fp64 workspace), and
 // k_splat_gather sums for every splat the slots of its neighbours that land on it (reflection included).  Scene
 // parameters (lights, colours, materials) are reduced over the wave and added with fp32 atomics, as srh_backward.h does.
+//
+// The camera (k_splat_bwd<true>, k_splat_ndc_bwd<true>): it enters only through the lights' camera coordinates
+// L = M (l_xyz, l_w), M = [R^T | -R^T eye] the view's 3 x 4 world-to-camera matrix, so d loss / d M[r][c] is the sum
+// over pixels, sub-pixels and lights of g_v[r] l[c] (view_light_terms).  The lane keeps the twelve sums in fp64 across
+// both loops and the workgroup reduces them once, after the loops (srh_view_grad.h): no atomics, fp64 to the end.
 #pragma once
 #include "srh_backward.h"   // wave_sum
 #include "srh_device.h"
+#include "srh_view_grad.h"
 
 namespace srh {
 
@@ -173,6 +179,13 @@ __device__ __forceinline__ void light_cc(const SplatDev& S, int b, int l, const 
   for (int k = 0; k < 3; ++k) L[k] = (R[0][k] * q[0] + R[1][k] * q[1]) + R[2][k] * q[2];
 }
 
+// kView: the lane's share of d loss / d M for light l, g_v (x) (l_x, l_y, l_z, l_w), added to its twelve running sums
+__device__ __forceinline__ void view_light_terms(const SplatDev& S, int b, int l, const double g_v[3], double vM[12]) {
+  const float* lp = S.lpos + (size_t)b * S.lpos_vs + 4 * (size_t)l;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) vM[k] += g_v[k >> 2] * (double)lp[k & 3];
+}
+
 struct SplatLight {
   double lh[3], dist, afac, ldn, nd, rd, cl, den, dp;
   bool nz, den_ok;
@@ -313,9 +326,14 @@ __device__ __forceinline__ void wave_add(float* dst, double v, bool lane0) {
 // Backward, pass 1: one lane per base pixel.  Upstream gradients (B, KH, KW, {3, 1, 3, 3}), each may be NULL.
 // Writes d loss / d light_vis (B, L, N) and, for given normals, d loss / d normal (B, N, 3) and d loss / d z; for
 // estimated normals the 9 stencil-slot gradients d loss / d Z go to ws (B, N, 9) for k_splat_gather.
+// kView: also the gradient of the view's world-to-camera matrix, twelve sums per workgroup to view_part
+// (srh_view_grad.h); every lane reaches the reduce, the dead ones with zeros.  Without kView the trailing argument is
+// unused and the code is what it was without it.
+template <bool kView>
 __global__ __launch_bounds__(256) void k_splat_bwd(SplatDev S, SplatGradsDev G, const float* __restrict__ g_image,
                                                    const float* __restrict__ g_depth, const float* __restrict__ g_pos,
-                                                   const float* __restrict__ g_normal, double* __restrict__ ws) {
+                                                   const float* __restrict__ g_normal, double* __restrict__ ws,
+                                                   double* __restrict__ view_part) {
   const int pix0 = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   const bool live = pix0 < S.N;
@@ -332,6 +350,7 @@ __global__ __launch_bounds__(256) void k_splat_bwd(SplatDev S, SplatGradsDev G, 
   const size_t view = (size_t)b * S.N * S.K * S.K;
   double gP[3] = {0, 0, 0}, gN[3] = {0, 0, 0};
   double g_alb[3] = {0, 0, 0}, g_cf[3] = {0, 0, 0}, g_amb[3] = {0, 0, 0};
+  double vM[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // kView: this lane's sums of g_v (x) l
 #pragma unroll 1
   for (int c = 0; c < S.K; ++c) {
 #pragma unroll 1
@@ -420,6 +439,7 @@ __global__ __launch_bounds__(256) void k_splat_bwd(SplatDev S, SplatGradsDev G, 
             g_v[k] = T.nz ? (g_lh[k] - T.lh[k] * proj) / T.dist + g_dist * T.lh[k] : g_lh[k];
             gp[k] -= g_v[k];
           }
+          if (kView) view_light_terms(S, b, l, g_v, vM);
           if (G.lpos) {                          // L = R^T (l_xyz - l_w eye): d/dl_xyz = R g_v, d/dl_w = -eye . R g_v
             double gl[3];
 #pragma unroll
@@ -482,6 +502,7 @@ __global__ __launch_bounds__(256) void k_splat_bwd(SplatDev S, SplatGradsDev G, 
       }
     }
   }
+  if (kView) view_block_reduce<kViewSums>([&](int k) { return vM[k]; }, view_part);   // once, after both loops
   if (!live) return;
   const double z = load_z(S, b, pix);
   const size_t zo = ((size_t)b * S.N + pix) * S.pos_cols;

@@ -115,9 +115,14 @@ __global__ __launch_bounds__(256) void k_splat_ndc_fwd(SplatNdcDev D, float* __r
 
 // Backward: one lane per splat.  Upstream gradients image (B, N, 3), depth (B, N), pos (B, N, 3), each may be NULL.
 // Writes G.pos (B, N, pos_cols) and G.normal (B, N, 3); adds the scene parameters' gradients (G.vis is not used).
+// kView: also the gradient of the view's world-to-camera matrix, as k_splat_bwd<true> forms it: twelve fp64 sums per
+// lane over the lights, one view_block_reduce after the loop (zeros without an image gradient).  Without kView the
+// trailing argument is unused and the code is what it was without it.
+template <bool kView>
 __global__ __launch_bounds__(256) void k_splat_ndc_bwd(SplatNdcDev D, SplatGradsDev G, const float* __restrict__ g_image,
                                                        const float* __restrict__ g_depth,
-                                                       const float* __restrict__ g_pos) {
+                                                       const float* __restrict__ g_pos,
+                                                       double* __restrict__ view_part) {
   const SplatDev& S = D.S;
   const int pix0 = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -128,6 +133,7 @@ __global__ __launch_bounds__(256) void k_splat_ndc_bwd(SplatNdcDev D, SplatGrads
   ndc_point(D, b, pix, U);
   const size_t o = (size_t)b * S.N + pix;
   double gp[3] = {0, 0, 0}, gN[3] = {0, 0, 0};
+  double vM[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // kView: this lane's sums of g_v (x) l
   if (live && g_pos) { gp[0] = g_pos[3 * o]; gp[1] = g_pos[3 * o + 1]; gp[2] = g_pos[3 * o + 2]; }
   if (live && g_depth) {
     const double dl = sqrt((U.P[0] * U.P[0] + U.P[1] * U.P[1]) + U.P[2] * U.P[2]);
@@ -199,6 +205,7 @@ __global__ __launch_bounds__(256) void k_splat_ndc_bwd(SplatNdcDev D, SplatGrads
         g_v[k] = T.nz ? (g_lh[k] - T.lh[k] * proj) / T.dist + g_dist * T.lh[k] : g_lh[k];
         gp[k] -= g_v[k];
       }
+      if (kView) view_light_terms(S, b, l, g_v, vM);
       if (G.lpos) {                              // L = R^T (l_xyz - l_w eye): d/dl_xyz = R g_v, d/dl_w = -eye . R g_v
         double gl[3];
 #pragma unroll
@@ -238,6 +245,7 @@ __global__ __launch_bounds__(256) void k_splat_ndc_bwd(SplatNdcDev D, SplatGrads
       }
     }
   }
+  if (kView) view_block_reduce<kViewSums>([&](int k) { return vM[k]; }, view_part);   // once, after the loop
   if (!live) return;
   if (G.normal) {
     float* dst = G.normal + 3 * o;

@@ -9,18 +9,28 @@ diffrend/torch/renderer.py:537-751, and a batched form for the GAN's per-element
 Forward and backward are HIP kernels (srh_splat_fwd / srh_splat_bwd, surf_renderer_amd/csrc/srh_splat.h): a batch is one
 forward launch and one backward pass.  Differentiable inputs: objects.disk.pos (only z), objects.disk.normal,
 objects.disk.light_vis, lights.pos, colors, lights.attenuation, lights.ambient, materials.albedo, materials.coeffs.
-The camera is not differentiable; a camera tensor that requires grad is refused.
+
+The camera enters only through the lights' camera coordinates, light_pos @ lookat(eye, at, up).T.  With
+``camera_grad=True`` camera['eye'], ['at'] and ['up'] may require grad and receive it, in their own shape, dtype and
+device (a fourth component gets 0; a leaf shared by the views of a batch gets the sum over the views, a per-view eye
+[B, 3|4] its rows): srh_splat_bwd_view sums d loss / d (the view's 3 x 4 world-to-camera matrix) in fp64 without atomics,
+and the chain from the matrix to eye / at / up is the reference's lookat in float64 on the host (camera_matrices).
+Outputs and every other gradient are those of the same call with the camera detached.  A frame without lights
+(norm_depth_image_only=True) does not depend on the camera: nothing is launched for it and the leaves' .grad stays None,
+as under the reference's autograd; a shaded frame whose loss does not use `image` gives them exact zeros.  Without the
+keyword a camera tensor that requires grad is refused, and fovy, focal_length and the viewport are refused either way.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Dict, Tuple
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._layer import f32, fill_grads, gpu_device, ptr, scratch, stream
+from ._camera import VIEW_KEYS, _host, camera_entries, check_camera_grad, differentiable_vectors, view_matrices
+from ._layer import f32, fill_grads, gpu_device, ptr, scratch, stream, view_grad_buffers
 
 _DIFF = ("pos", "normal", "light_vis", "lights_pos", "colors", "attenuation", "ambient", "albedo", "coeffs")
 
@@ -69,11 +79,14 @@ class _Splat:
 
 
 class _SplatFunction(torch.autograd.Function):
-    """(pos, normal, light_vis, lights.pos, colors, attenuation, ambient, albedo, coeffs) -> (image, depth, pos, normal),
-    all with the leading view axis B.  normal / light_vis may be None."""
+    """(pos, normal, light_vis, lights.pos, colors, attenuation, ambient, albedo, coeffs, view) -> (image, depth, pos,
+    normal), all with the leading view axis B.  normal / light_vis may be None.  `view` [B, 3, 4] float64 or None is
+    camera_matrices' table: the kernels do not read it (they build their basis from eye / at / up as ever), it is the
+    input whose gradient is srh_splat_bwd_view's grad_view."""
 
     @staticmethod
-    def forward(ctx, cfg: _Splat, *inputs):
+    def forward(ctx, cfg: _Splat, *args):
+        *inputs, view = args
         p = cfg.params
         B, K = p.n_views, p.samples
         KH, KW = K * p.height, K * p.width
@@ -86,6 +99,7 @@ class _SplatFunction(torch.autograd.Function):
         _lib.check(_lib.load().srh_splat_fwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ptr(image),
                                              depth.data_ptr(), pos.data_ptr(), normal.data_ptr(), cfg.stream()))
         ctx.cfg = cfg
+        ctx.view = None if view is None else view.detach()
         ctx.present = [t is not None for t in inputs]
         ctx.save_for_backward(*[t for t in inputs if t is not None])
         if image is None:
@@ -121,21 +135,46 @@ class _SplatFunction(torch.autograd.Function):
         if not p.shade:
             ups[0] = None
 
+        lib = _lib.load()
+        vgrads, vws = view_grad_buffers(lib, (ctx.view,), (ctx.view is not None and ctx.needs_input_grad[-1],),
+                                        p.width, p.height)
+
         def launch():
             inp, ls, ms = cfg.structs(*inputs)
-            ws = scratch(max(_lib.load().srh_splat_workspace_bytes(C.byref(p), C.byref(inp)), 8), dev)
+            ws = scratch(max(lib.srh_splat_workspace_bytes(C.byref(p), C.byref(inp)), 8), dev)
             sg = _lib.SrhSplatGrads(**{k: v.data_ptr() for k, v in grads.items()})
-            _lib.check(_lib.load().srh_splat_bwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ws.data_ptr(),
-                                                 ws.numel(), *[ptr(u) for u in ups], C.byref(sg), cfg.stream()))
+            args = (C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ws.data_ptr(), ws.numel(),
+                    *[ptr(u) for u in ups], C.byref(sg))
+            if vws is None:
+                _lib.check(lib.srh_splat_bwd(*args, cfg.stream()))
+            else:
+                _lib.check(lib.srh_splat_bwd_view(*args, vgrads[0].data_ptr(), vws.data_ptr(), vws.numel(),
+                                                  cfg.stream()))
 
-        fill_grads(grads.values(), ups, launch)
+        fill_grads(list(grads.values()) + vgrads, ups, launch)
         out = []
         for k, t in zip(_DIFF, inputs):
             g = grads.get(k)
             if g is not None and k in ("pos", "normal", "light_vis"):
                 g = g.view(t.shape) if cfg.batched[k] else g.sum(0).view(t.shape)
             out.append(g)
-        return (None, *out)
+        return (None, *out, None if vgrads[0] is None else vgrads[0].view(B, 3, 4))
+
+
+def camera_matrices(camera: Dict[str, Any], B: int, device) -> Optional[torch.Tensor]:
+    """The reference's lookat(eye, at, up) of every view, [B, 3, 4] float64 on `device`, attached to those of
+    camera['eye' | 'at' | 'up'] that require grad -- eye [3|4] or [B, 3|4], at / up [3|4]; a shared one is expanded over
+    the views, so it gets the sum, and the w column is dropped before lookat, so it gets 0.  None when none of them
+    requires grad.  What the two splat renderers pass through autograd under camera_grad=True."""
+    if not any(isinstance(camera[k], torch.Tensor) and camera[k].requires_grad for k in VIEW_KEYS):
+        return None
+    host = {k: np.asarray(_host(camera[k]), dtype=np.float64) for k in VIEW_KEYS}
+    host = {k: torch.from_numpy(np.array(np.broadcast_to(v.reshape(-1, v.shape[-1]), (B, v.shape[-1]))[:, :3]))
+            for k, v in host.items()}
+    per_view = {k: (camera[k].reshape(1, -1).expand(B, -1) if isinstance(camera[k], torch.Tensor) and camera[k].dim() == 1
+                    else camera[k]) for k in VIEW_KEYS}
+    vec = differentiable_vectors(per_view, host)
+    return view_matrices(vec["eye"], vec["at"], vec["up"]).to(device)
 
 
 def _refuse_camera_grads(camera: Dict[str, Any]) -> None:
@@ -213,12 +252,15 @@ def _validate(scene: Dict[str, Any], batched: bool) -> Tuple[int, int]:
 
 def _render(scene: Dict[str, Any], batched: bool, samples: int = 1, normal_estimation_method: str = "plane",
             normal_estimation_kernel_size: int = 3, use_quartic: bool = False, norm_depth_image_only: bool = False,
-            **_unused) -> Dict[str, torch.Tensor]:
+            camera_grad: bool = False, **_unused) -> Dict[str, torch.Tensor]:
     if normal_estimation_method != "plane":
         raise ValueError(f"render_splats_along_ray: normal_estimation_method {normal_estimation_method!r} is not "
                          "supported (only 'plane')")
     cam = scene["camera"]
-    _refuse_camera_grads(cam)
+    if check_camera_grad("render_splats_along_ray", camera_grad):
+        camera_entries("render_splats_along_ray", cam, (), camera_grad=True)
+    else:
+        _refuse_camera_grads(cam)
     W, H = _validate(scene, batched)
     disk = scene["objects"]["disk"]
     pos_in = disk["pos"]
@@ -275,8 +317,10 @@ def _render(scene: Dict[str, Any], batched: bool, samples: int = 1, normal_estim
     params.up[:] = [float(v) for v in up]
     cfg = _Splat(params, device, eye, _i32(lights["color_idx"], device), mat, flags, L, colors.shape[0],
                  albedo.shape[0])
+    # a frame without lights does not depend on the camera: no table, nothing launched for it
+    view = camera_matrices(cam, B, device) if camera_grad and not norm_depth_image_only else None
     image, depth, pos_out, normal_out = _SplatFunction.apply(cfg, pos, normal, light_vis, lpos, colors, att, amb,
-                                                             albedo, coeffs)
+                                                             albedo, coeffs, view)
     if norm_depth_image_only:
         far = float(_value(cam["far"]))
         flat = depth.view(B, -1)
@@ -296,12 +340,14 @@ def render_splats_along_ray(scene: Dict[str, Any], **params) -> Dict[str, torch.
     """The reference's render_splats_along_ray(scene, **params) on the GPU: image (KH,KW,3), depth (KH,KW),
     pos (KH,KW,3), normal (KH,KW,3); with norm_depth_image_only=True the image is the normalised depth and pos / normal
     are (KH KW, 3).  Keywords: samples, normal_estimation_method ('plane' only), normal_estimation_kernel_size (ignored,
-    as in the reference), use_quartic, norm_depth_image_only."""
+    as in the reference), use_quartic, norm_depth_image_only, and camera_grad: True lets camera['eye'], ['at'] and ['up']
+    require grad and gives them their gradient (see the module's text); its default False refuses them."""
     return _render(scene, batched=False, **params)
 
 
 def render_splats_along_ray_batch(scene: Dict[str, Any], **params) -> Dict[str, torch.Tensor]:
     """render_splats_along_ray for B views in one forward launch and one backward pass: objects.disk.pos is [B, N] or
     [B, N, 3]; objects.disk.normal [B, N, 3], objects.disk.light_vis [B, L, N], camera.eye [B, 4] and lights.pos
-    [B, L, 4] may carry the batch axis too (otherwise shared).  Every output has the leading axis B."""
+    [B, L, 4] may carry the batch axis too (otherwise shared).  Every output has the leading axis B.  camera_grad=True:
+    a per-view eye gets its rows, a shared eye, at and up the sum over the views."""
     return _render(scene, batched=True, **params)

@@ -9,7 +9,13 @@ diffrend/torch/renderer.py:358-474 (the renderer behind optimize_NDC_test), and 
 Forward and backward are HIP kernels (srh_splat_ndc_fwd / srh_splat_ndc_bwd, surf_renderer_amd/csrc/srh_splat_ndc.h):
 a batch is one forward launch and one backward launch.  Differentiable inputs: objects.disk.pos (every column),
 objects.disk.normal, lights.pos, colors, lights.attenuation, lights.ambient, materials.albedo, materials.coeffs.
-The camera is not differentiable; a camera tensor that requires grad is refused.
+
+With ``camera_grad=True`` camera['eye'], ['at'] and ['up'] may require grad and receive it through the lights' camera
+coordinates, exactly as in render_splats_along_ray (splats.py has the text): srh_splat_ndc_bwd_view sums d loss / d (the
+view's world-to-camera matrix) in fp64 without atomics, the chain to the leaves is the reference's lookat on the host.
+norm_depth_image_only=True leaves their .grad None (nothing launched), a shaded frame whose loss does not use `image`
+gives exact zeros (nothing launched for the camera either).  Without the keyword a camera tensor that requires grad is
+refused; fovy, near, far and the viewport are refused either way.
 """
 from __future__ import annotations
 
@@ -21,8 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._layer import fill_grads, gpu_device, ptr, stream
-from .splats import _f32, _i32, _shape, _value
+from ._camera import camera_entries, check_camera_grad
+from ._layer import fill_grads, gpu_device, ptr, stream, view_grad_buffers
+from .splats import _f32, _i32, _shape, _value, camera_matrices
 
 _NAME = "render_splats_NDC"
 _DIFF = ("pos", "normal", "lights_pos", "colors", "attenuation", "ambient", "albedo", "coeffs")
@@ -52,11 +59,14 @@ class _SplatNdc:
 
 
 class _SplatNdcFunction(torch.autograd.Function):
-    """(pos, normal, lights.pos, colors, attenuation, ambient, albedo, coeffs) -> (image, depth, pos), all with the
-    leading view axis B.  The `normal` output is the caller's own tensor: autograd carries its gradient."""
+    """(pos, normal, lights.pos, colors, attenuation, ambient, albedo, coeffs, view) -> (image, depth, pos), all with
+    the leading view axis B.  The `normal` output is the caller's own tensor: autograd carries its gradient.  `view`
+    [B, 3, 4] float64 or None is splats.camera_matrices' table: not read by the kernels, it is the input whose gradient
+    is srh_splat_ndc_bwd_view's grad_view."""
 
     @staticmethod
-    def forward(ctx, cfg: _SplatNdc, *inputs):
+    def forward(ctx, cfg: _SplatNdc, *args):
+        *inputs, view = args
         p = cfg.params
         B, H, W = p.n_views, p.height, p.width
         dev = cfg.device
@@ -67,6 +77,7 @@ class _SplatNdcFunction(torch.autograd.Function):
         _lib.check(_lib.load().srh_splat_ndc_fwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), ptr(image),
                                                  depth.data_ptr(), pos.data_ptr(), stream(dev)))
         ctx.cfg = cfg
+        ctx.view = None if view is None else view.detach()
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None, not zeros
         ctx.save_for_backward(*inputs)
         if image is None:
@@ -99,20 +110,30 @@ class _SplatNdcFunction(torch.autograd.Function):
         if not p.shade:
             ups[0] = None
 
+        lib = _lib.load()
+        need_view = ctx.view is not None and ctx.needs_input_grad[-1]
+        # only the image carries the camera: without its gradient the table's is zero, and nothing is launched for it
+        vgrads, vws = view_grad_buffers(lib, (ctx.view,), (need_view and ups[0] is not None,), p.width, p.height)
+
         def launch():
             inp, ls, ms = cfg.structs(*inputs)
             sg = _lib.SrhSplatNdcGrads(**{k: v.data_ptr() for k, v in grads.items()})
-            _lib.check(_lib.load().srh_splat_ndc_bwd(C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms),
-                                                     *[ptr(u) for u in ups], C.byref(sg), stream(dev)))
+            args = (C.byref(p), C.byref(inp), C.byref(ls), C.byref(ms), *[ptr(u) for u in ups], C.byref(sg))
+            if vws is None:
+                _lib.check(lib.srh_splat_ndc_bwd(*args, stream(dev)))
+            else:
+                _lib.check(lib.srh_splat_ndc_bwd_view(*args, vgrads[0].data_ptr(), vws.data_ptr(), vws.numel(),
+                                                      stream(dev)))
 
-        fill_grads(grads.values(), ups, launch)
+        fill_grads(list(grads.values()) + vgrads, ups, launch)
+        g_view = vgrads[0].view(B, 3, 4) if vgrads[0] is not None else (torch.zeros_like(ctx.view) if need_view else None)
         out = []
         for k, t in zip(_DIFF, inputs):
             g = grads.get(k)
             if g is not None and k in ("pos", "normal"):
                 g = g.view(t.shape) if cfg.batched[k] else g.sum(0).view(t.shape)
             out.append(g)
-        return (None, *out)
+        return (None, *out, g_view)
 
 
 def _refuse_camera_grads(camera: Dict[str, Any]) -> None:
@@ -192,9 +213,12 @@ def _validate(scene: Dict[str, Any], batched: bool) -> Tuple[int, int]:
 
 
 def _render(scene: Dict[str, Any], batched: bool, double_sided: bool = False, use_quartic: bool = False,
-            norm_depth_image_only: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+            norm_depth_image_only: bool = False, camera_grad: bool = False, **_unused) -> Dict[str, torch.Tensor]:
     cam = scene["camera"]
-    _refuse_camera_grads(cam)
+    if check_camera_grad(_NAME, camera_grad):
+        camera_entries(_NAME, cam, (), camera_grad=True)
+    else:
+        _refuse_camera_grads(cam)
     W, H = _validate(scene, batched)
     disk, lights = scene["objects"]["disk"], scene["lights"]
     device = gpu_device(_NAME, (disk["pos"], disk["normal"]))
@@ -234,7 +258,9 @@ def _render(scene: Dict[str, Any], batched: bool, double_sided: bool = False, us
     params.up[:] = [float(v) for v in up]
     cfg = _SplatNdc(params, device, eye, _i32(lights["color_idx"], device), mat, flags, L, colors.shape[0],
                     albedo.shape[0])
-    image, depth, pos_out = _SplatNdcFunction.apply(cfg, pos, normal, lpos, colors, att, amb, albedo, coeffs)
+    # a frame without lights does not depend on the camera: no table, nothing launched for it
+    view = camera_matrices(cam, B, device) if camera_grad and not norm_depth_image_only else None
+    image, depth, pos_out = _SplatNdcFunction.apply(cfg, pos, normal, lpos, colors, att, amb, albedo, coeffs, view)
     if norm_depth_image_only:
         flat = depth.view(B, -1)
         mn = flat.min(dim=1).values.view(B, 1, 1)
@@ -258,12 +284,14 @@ def render_splats_NDC(scene: Dict[str, Any], **params) -> Dict[str, torch.Tensor
     """The reference's render_splats_NDC(scene, **params) on the GPU: image (H,W,3), depth (H,W), pos (H,W,3), normal
     (H,W,3) -- the given normals' first three columns, as they are.  With norm_depth_image_only=True the image (H,W) is
     the normalised depth, pos the homogeneous [N,4] (last column 1) and normal the input normals untouched.  Keywords:
-    double_sided, use_quartic, norm_depth_image_only; others are ignored."""
+    double_sided, use_quartic, norm_depth_image_only, and camera_grad: True lets camera['eye'], ['at'] and ['up'] require
+    grad and gives them their gradient (see the module's text), its default False refuses them; others are ignored."""
     return _render(scene, batched=False, **params)
 
 
 def render_splats_NDC_batch(scene: Dict[str, Any], **params) -> Dict[str, torch.Tensor]:
     """render_splats_NDC for B views in one forward launch and one backward launch: objects.disk.pos is [B, N, 3] or
     [B, N, 4]; objects.disk.normal [B, N, 3|4], camera.eye [B, 3|4] and lights.pos [B, L, 4] may carry the batch axis
-    too (otherwise shared: a shared leaf's gradient is the sum over the views).  Every output has the leading axis B."""
+    too (otherwise shared: a shared leaf's gradient is the sum over the views).  Every output has the leading axis B.
+    camera_grad=True: a per-view eye gets its rows, a shared eye, at and up the sum over the views."""
     return _render(scene, batched=True, **params)
