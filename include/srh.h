@@ -395,11 +395,12 @@ int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, i
 /* Measurement helper, sibling of srh_bin_counters: where a binned frame's per-tile table lives in its workspace.  A frame
  * of ONE disc batch with camera.near_clip > 0 whose rows [row0, row1) span at least 3072 tiles (one wave per tile) carries
  * *tiles_x * *tiles_y floats at workspace + *offset_bytes, entry ty * *tiles_x + tx: the lower bound of 1 / |D| over the
- * pixels of tile (tx, ty) that the front-to-back occlusion cull of the render kernel uses, |D| being the length of a
- * pixel's un-normalised ray direction -- (float)(1 / sqrt(max |D|^2 over the tile's four corner pixels)), corners clamped
+ * pixels of tile (tx, ty), |D| being the length of a
+ * pixel's un-normalised ray direction (the front-to-back occlusion cull of the render kernel used it until it took to
+ * tracking coverage; no kernel reads the table now, it is still written) -- (float)(1 / sqrt(max |D|^2 over the tile's four corner pixels)), corners clamped
  * to the last column and the slab's last row; 0 where that is not a positive number below 1e30.  The SRH_STAGE_BIN stage
- * writes it on every call (nothing is kept from one call to the next); the render stage only reads it.  Every other
- * frame has no table (the render kernel computes the bound where it needs it): *offset_bytes = 0 and
+ * writes it on every call (nothing is kept from one call to the next).  Every other
+ * frame has no table: *offset_bytes = 0 and
  * SRH_E_NOT_APPLICABLE.  The helper sees no camera: for near_clip <= 0 it still names the place, which nobody writes
  * then.  Added without an ABI version change: no existing struct or signature changed. */
 int srh_tile_rlen(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,

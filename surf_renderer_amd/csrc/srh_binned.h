@@ -687,25 +687,33 @@ __device__ __forceinline__ void wave_lds_fence() {
 // ---- front-to-back occlusion cull (one-batch disc kernel, one wave per tile) ----------------------------------------
 // Most entries of a busy tile cannot win: the tile is covered by nearer discs.  So the tile's list is sorted by each
 // disc's upper bound U of 1 / t (rec32[8], k_prep) -- nearest possible first -- and swept in that order while every
-// pixel tracks L(p), the largest LOWER bound of 1 / t over the discs that CERTAINLY hit it (rec32[11], conic_record's
-// sure_in; the depth through den shifted down, below).  Every kOcclGroup entries the wave takes T = min over the
-// tile's pixels of L(p); the sweep stops at the first sorted entry with U < T.  Such an entry's valid hits all have
-// t > 1 / T >= the certain hit's t at EVERY pixel of the tile: strictly behind the confirmed winner, so it can neither
-// win nor tie resolve_lex, and leaving it out of the keys changes nothing (the slow path and the re-sweep still walk
-// the full lists).  A pixel without a certain hit keeps L = 0, T = 0, and nothing is skipped.
+// pixel tracks ONE BIT: has a disc that CERTAINLY hits it been swept (q < s_in: rec32[11], conic_record's sure_in)?  The
+// wave keeps Vmin = the minimum over the swept entries of V (rec32[10]: a lower bound of 1 / t over
+// every valid hit of a disc that has certain hits, 1e30 for a disc that has none; disk_reject_record).  After each pair
+// of entries the wave asks whether every pixel of the tile is covered; the first time it is, T = Vmin, the sweep stops at
+// the first sorted entry with U < T, and the question is not asked again.  Take such an entry and a valid hit of it
+// at any pixel p of the tile: 1 / t <= U < T <= V_e <= 1 / t_e (p) for the certain disc e that covers p (e was swept before
+// T was taken, so its V is in the minimum) -- strictly behind a valid hit at EVERY pixel, so it can neither win nor tie
+// resolve_lex, and leaving it out of the keys changes nothing (the slow path and the re-sweep still walk the full
+// lists).  A tile with one uncovered pixel never takes a threshold, and nothing is skipped.
+// Dead lanes and clamped pixels of an edge tile duplicate live ones (render_binned_body), so every lane votes.
 // The key fields hold the SORTED position; ordinal_to_global maps them through the sorted copy in LDS.
+// (SRH_OCCL_COVERAGE = 0, srh_reject.h: the rule this replaced -- per pixel L (p), the largest lower bound of 1 / t over
+// the certain discs through den shifted down, and every kOcclGroup entries T = min over the tile of L (p) rlen_lo.)
 #ifndef SRH_OCCLUSION_CULL
 #define SRH_OCCLUSION_CULL 1
 #endif
-constexpr uint32_t kOcclGroup = 8;                  // entries between two thresholds (even: the sweep goes in pairs)
+constexpr uint32_t kOcclGroup = 8;                  // a list has to be longer than this to be worth sorting
 constexpr uint32_t kSortCap = 128;                  // entries one wave sorts (two per lane); longer lists: the plain sweep
 constexpr uint32_t kSortLow = 0x7Fu;                // low key bits: the list position
+#if !SRH_OCCL_COVERAGE
 // den - 3 E / K <= s (n^.D) / K for the fp32 den of the vector path AND the fp64 path's own n^.d (plane_estimate_record:
 // den carries less than E / K of error and is shifted up by E / K; E covers the fp64 side too), with E / K read off
 // lo_u = 1025 E / K (rounded up there) -- the factor is 3 / 1025 rounded up by 2.4e-6.
 constexpr float kDenShiftPerLoU = 0.0029269f;
 // L (p) rlen_lo (1 - 2^-18) <= 1 / t: the (1 - 2^-20) of K, the fp32 1 / |D|, the subtraction and two products
 constexpr float kSureRound = 0.99999619f;
+#endif
 
 // ---- cross-lane exchanges in registers (no LDS round trip) -------------------------------------------------------
 // __shfl_xor is a ds_bpermute: an LDS instruction, a wait for its result and ~4 vector instructions of address
@@ -750,6 +758,7 @@ __device__ __forceinline__ void xor_pair_maxmin(int32_t v, int32_t& hi, int32_t&
   }
 }
 
+#if !SRH_OCCL_COVERAGE
 // fminf over the wave, valid in every lane (fminf is commutative and associative: the order of the steps does not
 // change the result)
 template <int CTRL>
@@ -766,6 +775,7 @@ __device__ __forceinline__ float wave_min_f32(float m) {
   const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
   return fminf(__uint_as_float(h[0]), __uint_as_float(h[1]));
 }
+#endif
 
 // Bitonic sort, DESCENDING, of NR x 64 distinct signed keys across the wave: element i = lane + 64 h is register h of
 // lane `lane`.  Stage (k, j) compares i with i ^ j; blocks of size k with (i & k) == 0 run descending, the others
@@ -828,6 +838,87 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
 
 // The sweep of a sorted list: stream_list's pipelined pairs (records by scalar loads from wave-uniform addresses), the
 // list words by v_readlane from gs[], the key update of sweep_entry, and per pixel
+//   cov |= bits(q - s_in)                                   (the sign bit: a certain hit covers the pixel)
+// with Vmin = min(Vmin, bits(V)) per wave: positive floats compare as integers, and V arrives as a scalar operand.
+#if SRH_OCCL_COVERAGE
+template <int NR>
+__device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
+                                                 const int32_t (&us)[2], QuadState& Q) {
+  constexpr int TYPE = SRH_PRIM_DISK;
+  const char* base_c = reinterpret_cast<const char*>(S.rec32) - (size_t)S.first * (size_t)(4 * kRec32Stride[TYPE]);
+  auto record = [&](int g) {
+    return reinterpret_cast<const float*>(base_c + (uint32_t)g * (uint32_t)(4 * kRec32Stride[TYPE]));
+  };
+  auto entry = [&](uint32_t k) {
+    k = min(k, n - 1);
+    return (NR == 1 || k < 64) ? __builtin_amdgcn_readlane(gs[0], (int)k) : __builtin_amdgcn_readlane(gs[1], (int)(k - 64));
+  };
+  int32_t cov[4] = {0, 0, 0, 0};
+  // bits of the smallest V swept so far, one minimum per record buffer: wave-uniform, kept in vector registers by hipcc
+  // (DESIGN.md Part II, "Coverage instead of depth")
+  int32_t vminA = 0x7fffffff, vminB = 0x7fffffff;
+  const uint32_t keep = ~Q.ordmask;
+  auto op = [&](const RejectRecord<TYPE>& R, uint32_t k, int32_t& vmin) {
+    int32_t sel[4];
+    f32x2 den[2], q[2];
+    pair_bounds<TYPE, true, false>(R, Q.cf, Q.rf, Q.rlen, sel, den, q);
+    const uint32_t field = k + 1u;                    // n + 1 <= ordmask: never saturated
+    vmin = min(vmin, __float_as_int(R[10]));
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const f32x2 qi = q[p] - splat2(R[11]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = 2 * p + h;
+        const int32_t key = pack_key(den[p][h], field, keep) & sel[j];
+        Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
+        Q.k3[j] = imed3(Q.k2[j], key, Q.k3[j]);
+        Q.k2[j] = imed3(Q.k1[j], key, Q.k2[j]);
+        Q.k1[j] = max(Q.k1[j], key);
+        cov[j] |= __float_as_int(qi[h]);
+      }
+    }
+  };
+  // first sorted position whose U lies below T (n if none)
+  auto stop_at = [&](int32_t T) -> uint32_t {
+    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(us[0] < T);
+    if (b0) return (uint32_t)__builtin_ctzll(b0);
+    if (NR == 2) {
+      const unsigned long long b1 = __builtin_amdgcn_ballot_w64(us[1] < T);
+      if (b1) return 64u + (uint32_t)__builtin_ctzll(b1);
+    }
+    return n;
+  };
+  RejectRecord<TYPE> A, B;
+  uint32_t stop = n;
+  bool closed = false;                                // wave-uniform: the threshold has been taken
+  int gA = entry(0);
+  int gB = entry(1);
+  A.load(record(gA));
+  for (uint32_t i = 0; i < stop; i += 2) {
+    B.load(record(gB));
+    gA = entry(i + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    op(A, i, vminA);
+    if (i + 1 >= stop) break;
+    __builtin_amdgcn_sched_barrier(0);
+    A.load(record(gA));
+    gB = entry(i + 3);
+    __builtin_amdgcn_sched_barrier(0);
+    op(B, i + 1, vminB);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!closed && i + 2 < stop) {
+      // every lane covered at all four pixels: the compare's mask is the wave's exec mask
+      const bool mine = (cov[0] & cov[1] & cov[2] & cov[3]) < 0;
+      if (__builtin_amdgcn_ballot_w64(mine) == __builtin_amdgcn_ballot_w64(true)) {
+        closed = true;
+        stop = min(stop, stop_at(min(vminA, vminB)));
+      }
+    }
+  }
+}
+#else
+// SRH_OCCL_COVERAGE = 0, the rule this replaced: the same sweep, and per pixel
 //   L = max(L, bits(den - shift) & (q < s_in ? ~0 : 0))      (a negative lower bound never beats the initial 0)
 // `rlen_lo` <= 1 / |D| at every pixel of the tile (the disc kernel's Q.rlen is 1: its keys are in den units).
 template <int NR>
@@ -899,6 +990,7 @@ __device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const 
     if ((i + 2) % kOcclGroup == 0 && i + 2 < stop) stop = min(stop, stop_at());
   }
 }
+#endif
 
 // Resolve the pixel of lane `src` on the slow path with the whole wave; returns the merged (t, index) minimum of
 // everything confirmed here (index 0x7fffffff = nothing), valid in every lane.
@@ -1056,6 +1148,8 @@ __device__ __forceinline__ const FrameDev& round_frame(const FrameDev& F) {
 // row slab).  0 where no usable bound exists: T = 0 then, and nothing is skipped.  It depends on the camera, the slab and
 // the tile only.  The one copy of the expression: k_prep evaluates it once per tile, one tile per lane, into
 // FrameDev::tile_rlen (fill_tile_rlen); a render kernel whose frame has no table evaluates it itself.
+// NOBODY READS THE TABLE since the sweep tracks coverage (SRH_OCCL_COVERAGE = 1): k_prep still writes it, because
+// tests/test_hip_tile_rlen.py holds it to its numpy value; taking it out is a clean-up of its own.
 __device__ __forceinline__ float tile_rlen_lo(const FrameDev& F, int tx, int ty) {
   const int px0 = tx * kTile, py0 = F.row0 + ty * kTile;
   const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
@@ -1161,14 +1255,18 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
     // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
     int32_t gs[2] = {0, 0}, us[2] = {-1, -1};   // sorted entries and their bounds (occl_sort)
+#if !SRH_OCCL_COVERAGE
     float rlen_lo = 0.0f;                       // the sorted sweep's lower bound of 1 / |D| over the tile (tile_rlen_lo)
+#endif
 #if SRH_OCCLUSION_CULL
     if (WPT == 1 && BATCH == SRH_PRIM_DISK && pretest) {
       const TileLists L{F, tile};
       if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
+#if !SRH_OCCL_COVERAGE
         // from the frame's table (k_prep wrote it, an earlier launch: as_constant's contract), one scalar load whose
         // latency the sort hides
         if (F.tile_rlen) rlen_lo = as_constant(F.tile_rlen)[tile];
+#endif
         if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         sorted = true;
@@ -1207,11 +1305,16 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     }
     const uint32_t part = WPT == 1 ? 0u : (uint32_t)wave;     // which share of the tile's entries this wave sweeps
     if (sorted) {
+#if SRH_OCCL_COVERAGE
+      if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, Q);
+      else sweep_sorted<2>(F.seg[0], listed, gs, us, Q);
+#else
       // a frame without a table (many views per launch, one wave per tile forced on a small frame): every lane computes
       // the same value here
       if (!F.tile_rlen) rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tile_rlen_lo(F, tx, ty))));
       if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, rlen_lo, Q);
       else sweep_sorted<2>(F.seg[0], listed, gs, us, rlen_lo, Q);
+#endif
     } else if (pretest) {
       sweep_tile<true, WPT, BATCH>(F, tile, Q, part);
     } else {

@@ -134,7 +134,9 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
   const PixelBasis B = pixel_basis(F);
   const bool near_pos = F.near_clip > 0.0;
   ConicExtent conic = no_extent();
-  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q, &conic);
+  // (a disc's STORED word [10] is the occlusion cull's V; Q[10] stays hi_u for bin_place below: srh_reject.h, layouts)
+  [[maybe_unused]] float stored10 = 0.0f;
+  if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q, &conic, &stored10);
   else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q, &conic);
   else if (TYPE == SRH_PRIM_TRIANGLE) triangle_reject_record(R, F.o, B, F.W, F.H, near_pos, Q);
   else plane_reject_record(R, B, F.W, F.H, Q);
@@ -144,7 +146,14 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
     for (int k = 0; k < N64 / 2; ++k) r2[k] = make_double2(R[2 * k], R[2 * k + 1]);
     float4* q4 = reinterpret_cast<float4*>(rec32 + (size_t)i * N32);
 #pragma unroll
-    for (int k = 0; k < N32 / 4; ++k) q4[k] = make_float4(Q[4 * k], Q[4 * k + 1], Q[4 * k + 2], Q[4 * k + 3]);
+    for (int k = 0; k < N32 / 4; ++k) {
+#if SRH_OCCL_COVERAGE
+      const float w2 = (TYPE == SRH_PRIM_DISK && k == 2) ? stored10 : Q[4 * k + 2];
+#else
+      const float w2 = Q[4 * k + 2];
+#endif
+      q4[k] = make_float4(Q[4 * k], Q[4 * k + 1], w2, Q[4 * k + 3]);
+    }
   }
   if (F.tilerange) {
     // light views: a primitive that comes within near_ball of the eye can block a shadow ray from BEHIND the light

@@ -18,7 +18,14 @@
 //                  (A = 0: "always a candidate" -- the disc's image is not an ellipse, etc.)
 //                  [5..7] u0 u1 u2 [9] lo_u [10] hi_u : depth estimate, see plane_estimate_record
 //                  [8] U [11] s_in : occlusion fields, see disk_reject_record
-//   sphere (12)    [0..4] as the disc; [5] upper bound of 1 / t for the whole sphere (1e30: none)
+//                  The STORED word [10] is V, the occlusion cull's lower bound of 1 / t (disk_reject_record), not hi_u:
+//                  hi_u is read by k_prep alone (RectTest, on the thread's register copy of the record), and no kernel
+//                  reads word [10] of a stored disc record -- the binned sweeps, slow path and re-sweep evaluate
+//                  [0..7] (pair_bounds), the sort [8], the sorted sweep [10] as V and [11], the fast mode [0..4]; the
+//                  shadow pass takes the light views' bins and the fp64 records, the backward pass no reject record at
+//                  all; a render-only call (SRH_STAGE_RENDER) runs the same render kernels on the stored records.
+//                  (SRH_OCCL_COVERAGE = 0: the stored word is hi_u, as before.)
+//   sphere (12)   [0..4] as the disc; [5] upper bound of 1 / t for the whole sphere (1e30: none)
 //   triangle (16)  {a_i, b_i, g_i} at [4i..4i+2], i < 3: candidate iff min_i(a_i*c + b_i*r + g_i) >= 0
 //                  [3] u0 [7] u1 [11] u2 [13] lo_u [14] hi_u
 //   plane (8)      [0..2] u0 u1 u2 [4] lo_u [5] hi_u; candidate iff den > hi_u
@@ -298,10 +305,27 @@ __device__ inline void sphere_conic_record(const double oc[3], double cq, double
 //   [8]  U = upper bound of 1 / t over every valid hit (ball_inverse_depth_bound; 1e30: none)
 //   [11] s_in: a pixel whose fp32 value q (pair_bounds) is < s_in is a CERTAIN valid hit (conic_record's sure_in) --
 //        only for a trusted, non-degenerate ellipse with finite, moderate coefficients whose whole ball lies inside
-//        [near, far] with margin; -1e30 (never) otherwise.  Its depth is then bounded through den (see sure_den_shift).
+//        [near, far] with margin; -1e30 (never) otherwise.
+//   `v_out` (the STORED record's word [10], see the layout above; out[10] itself keeps hi_u for the binning):
+//        V = lower bound of 1 / t over every valid hit of a disc that has certain hits (s_in > -1e30); 1e30 for every
+//        other disc, so that it never lowers the sweep's running minimum.  See kFarBoundMargin.
 // `ext`: the half extents of the stored shape's box (conic_record), none when the record is "always a candidate".
+//
+// SRH_OCCL_COVERAGE is a MEASUREMENT switch: 1 (the default) stores V and compiles the sorted sweep that tracks per pixel
+// only WHETHER a certain hit covers it (sweep_sorted, srh_binned.h); 0 compiles the per-pixel depth tracking it replaced
+// and leaves hi_u in the stored word, so that one tree builds both rules for an A/B and for the swept-entry count.
+#ifndef SRH_OCCL_COVERAGE
+#define SRH_OCCL_COVERAGE 1
+#endif
+// V = kFarBoundMargin / ((l + r) + slack), cast and rounded DOWN.  Every hit lies in the ball: t <= |oc| + r.  `slack` is
+// 2^-20 (l + r): the kFastEps of l and of r (2^-44 of them) and the 2^-22 (l + r) by which the fp64 path's own distance may
+// differ from the geometric one (ball_inverse_depth_bound) together stay below 2^-21.9 (l + r).  The factor 1 - 2^-20
+// stands in front of the Newton reciprocal (kFastEps), its product with it (2^-53) and the cast to fp32 (2^-24, then
+// pushed down by the 0.9999999f): 2^-23.9 of the 2^-20 are used.
+constexpr double kFarBoundMargin = 1.0 - 9.5367431640625e-7;
 __device__ inline void disk_reject_record(const double* R, const double o[3], const PixelBasis& B, int W, int H,
-                                          double near_clip, double far_clip, float* out, ConicExtent* ext) {
+                                          double near_clip, double far_clip, float* out, ConicExtent* ext,
+                                          float* v_out) {
   const double* n = R;
   const double k = R[3];
   const double oc[3] = {o[0] - R[4], o[1] - R[5], o[2] - R[6]};
@@ -377,6 +401,14 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
   for (int i = 0; i < 11; ++i) sure = sure && fabsf(out[i]) < 1.0e30f;
   sure = sure && fabsf(out[2]) < 1.0e6f && fabsf(out[3]) < 1.0e6f && fabsf(out[4]) < 1.0e6f;
   out[11] = sure ? (float)sure_in : -1.0e30f;
+#if SRH_OCCL_COVERAGE
+  // `sure` has (l + r) + slack positive and below far_clip.  A disc WITH certain hits must never keep the 1e30 of one
+  // without: a value beyond 1e30 is capped there (still a lower bound), and a NaN (denormal operand of the Newton
+  // reciprocal) becomes 0, with which the sweep skips nothing.
+  const double v = kFarBoundMargin * rcp_newton((l + r) + slack);
+  const float vf = (v < 1.0e30) ? (float)v * 0.9999999f : 1.0e30f;
+  *v_out = sure ? ((v == v) ? vf : 0.0f) : 1.0e30f;
+#endif
 }
 
 // sphere: the ray's line meets it iff (oc.D)^2 - |D|^2 (|oc|^2 - r^2) >= 0   (numpy/renderer.py:20-25).

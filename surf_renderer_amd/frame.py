@@ -181,8 +181,8 @@ def bin_statistics(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[
 def tile_rlen_table(buf: SceneBuffers, cam: _lib.SrhCamera, workspace: torch.Tensor,
                     rows: Optional[Tuple[int, int]] = None) -> Optional[np.ndarray]:
     """The per-tile table a binned frame of ``cam`` and ``rows`` left in ``workspace`` (measurement; synchronises):
-    (tile rows, tile columns) float32, the occlusion cull's lower bound of 1 / |D| over each 16 x 16-pixel tile
-    (include/srh.h: srh_tile_rlen).  None for frames that carry no table, a camera with ``near <= 0`` included: the
+    (tile rows, tile columns) float32, a lower bound of 1 / |D| over each 16 x 16-pixel tile (include/srh.h:
+    srh_tile_rlen; the occlusion cull read it until it took to tracking coverage, the binning stage still writes it).  None for frames that carry no table, a camera with ``near <= 0`` included: the
     library's helper sees no camera and would name a place that nobody wrote."""
     lib = _lib.load()
     width, height = frame_size(cam)
