@@ -947,6 +947,83 @@ int srh_normals_bwd_view(int32_t n_views, int32_t width, int32_t height, const d
                          const float* g_out, void* workspace, size_t workspace_bytes, float* grad_pos, double* grad_rot,
                          void* view_workspace, size_t view_workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's frame transforms, world_to_cam[_batched] and cam_to_world[_batched] (diffrend/torch/utils.py:539-647),
+ * for B views per call.  Per view, n_pos points (x, y, z[, w]), w = 1 for three columns, and n_normal normals, the two
+ * counts independent and either 0 = absent (not both), with one fp64 table each:
+ *   out_pos[r]    = ((P[r][0] x + P[r][1] y) + P[r][2] z) + P[r][3] w,  r = 0..2;  out_pos[3] = w      P = view_pos
+ *   out_normal[j] = (n0 A[0][j] + n1 A[1][j]) + n2 A[2][j],             j = 0..2                       A = view_normal
+ * The direction is the caller's choice of tables: world to camera is P = lookat (world-to-camera) with A = lookat_inv
+ * (camera-to-world), camera to world the other way round.  Column 3 of A is not read, and nothing is normalised.  fp64
+ * arithmetic, one fp32 store per element, no atomic, every element written once, results identical from run to run, and
+ * a view's result does not depend on its batch.  Added without an ABI version change.  Conventions as above:
+ * caller-owned device buffers, enqueue only, no synchronisation or allocation, argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhFrameParams {
+  int32_t n_views;                  /* B in 1..65535 */
+  int32_t n_pos, n_normal;          /* 0..2^24 per view, not both 0; 0 = that input is absent */
+  int32_t pos_cols, normal_cols;    /* 3 or 4, looked at where the count is not 0 */
+} SrhFrameParams;
+
+/* view_pos, view_normal (B, 12) fp64, 3 rows of 4: each NULL only where its input is absent.  pos (B, n_pos, pos_cols),
+ * normal (B, n_normal, normal_cols) fp32; out_pos (B, n_pos, 4) and out_normal (B, n_normal, 3) fp32 are written.  The
+ * pointers of an absent input are not looked at.  No workspace. */
+int srh_frame_transform_fwd(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                            const float* pos, const float* normal, float* out_pos, float* out_normal, void* stream);
+
+/* Vector-Jacobian product: g_pos (B, n_pos, 4), g_normal (B, n_normal, 3) fp32, each needed where its input is there;
+ * grad_pos (B, n_pos, pos_cols) and grad_normal (B, n_normal, normal_cols) fp32 are WRITTEN, every element once (column 3
+ * of grad_normal exactly 0).  Either may be NULL = not wanted, not both.  The transform is linear: the inputs are not
+ * read. */
+int srh_frame_transform_bwd(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                            const float* g_pos, const float* g_normal, float* grad_pos, float* grad_normal,
+                            void* stream);
+
+/* srh_frame_transform_bwd plus the gradients of the two tables (see srh_projection_bwd_view): grad_view_pos and
+ * grad_view_normal (B, 12) fp64, every element written, either NULL = not wanted (not both):
+ *   d loss / dP[r][c] = sum g_pos[r] [p, w][c],   d loss / dA[i][j] = sum n[i] g_normal[j], column 3 exactly 0.
+ * The table of an absent input gets zeros.  grad_pos and grad_normal may both be NULL.  view_workspace:
+ * 2 x srh_view_grad_workspace_bytes(n_views, max(n_pos, n_normal), 1) bytes, 8-byte aligned. */
+int srh_frame_transform_bwd_view(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                                 const float* pos, const float* normal, const float* g_pos, const float* g_normal,
+                                 float* grad_pos, float* grad_normal, double* grad_view_pos, double* grad_view_normal,
+                                 void* view_workspace, size_t view_workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The reference's project_surfels and project_image_coordinates (diffrend/torch/projection_layer.py:19-85), for B views
+ * of N free points each (N is not tied to the frame).  With (X, Y, Z) the position transform above under the view's
+ * world-to-camera table and Zd = Z != 0 ? Z : 1:
+ *   plane    = (f X / Zd, f Y / Zd, -Z)
+ *   px_coord = (plane_x (-(W - 1) / w) + W / 2, plane_y ((H - 1) / h) + H / 2, -Z),  h = 2 f tan(fovy / 2), w = h W / H
+ *   px_idx   = srh_hard_projection_keys' key of the point (the same device function): round-half-even(px_coord_y - 1/2) W
+ *              + round-half-even(px_coord_x - 1/2), and W H, the dump slot, outside the frame, for NaN or beyond an int.
+ * Same guarantees and conventions as the frame transform.  Added without an ABI version change.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhProjectCoordsParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t n_points;             /* N in 1..2^24 per view */
+  int32_t cols;                 /* 3 or 4 columns per point */
+  int32_t width, height;        /* W, H >= 1, W H <= 2^24 */
+  double fovy, focal_length;    /* shared by the views: 0 < fovy < pi, focal_length > 0 */
+} SrhProjectCoordsParams;
+
+/* view (B, 12) fp64: each view's world-to-camera matrix; surfels (B, N, cols) fp32.  plane, px_coord (B, N, 3) fp32 and
+ * px_idx (B, N) int32 are written where given: each may be NULL = not wanted, not all three.  No workspace. */
+int srh_project_coordinates_fwd(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                float* plane, float* px_coord, int32_t* px_idx, void* stream);
+
+/* Vector-Jacobian product: g_plane, g_coord (B, N, 3) fp32, the upstream gradients of plane and px_coord, either NULL =
+ * none (not both); grad_surfels (B, N, cols) fp32 is WRITTEN, every element once.  Where Z == 0 the x and y outputs
+ * have exactly zero gradient with respect to Z. */
+int srh_project_coordinates_bwd(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                const float* g_plane, const float* g_coord, float* grad_surfels, void* stream);
+
+/* srh_project_coordinates_bwd plus the gradient of the view table, grad_view (B, 12) fp64; grad_surfels may be NULL =
+ * not wanted.  view_workspace: srh_view_grad_workspace_bytes(n_views, n_points, 1) bytes, 8-byte aligned. */
+int srh_project_coordinates_bwd_view(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                     const float* g_plane, const float* g_coord, float* grad_surfels, double* grad_view,
+                                     void* view_workspace, size_t view_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,20 @@ def view_grad_buffers(lib, views: Sequence[torch.Tensor], needed: Sequence[bool]
     return grads, scratch(size, views[0].device)
 
 
+def view_grad_buffers_for_points(lib, views, needed, n_points: int, tables: int = 1):
+    """view_grad_buffers for a layer whose lanes are N free points, not the W H pixels of a frame: `views` may hold
+    None (an absent input's table, which gets no buffer), and the workspace holds `tables` sets of partials of
+    ceil(N / 256) workgroups each."""
+    there = [(v, need) for v, need in zip(views, needed) if v is not None]
+    if not there:
+        return [None] * len(views), None
+    B = there[0][0].shape[0]
+    got, ws = view_grad_buffers(lib, [v for v, _ in there], [need for _, need in there], n_points, 1,
+                                n_bytes=lambda: tables * lib.srh_view_grad_workspace_bytes(B, n_points, 1))
+    got = iter(got)
+    return [None if v is None else next(got) for v in views], ws
+
+
 def upstreams(grads: Iterable[Optional[torch.Tensor]]) -> List[Optional[torch.Tensor]]:
     return [None if g is None else g.to(torch.float32).contiguous() for g in grads]
 

@@ -161,6 +161,16 @@ class SrhHardProjectionParams(C.Structure):
                 ("fovy", C.c_double), ("focal_length", C.c_double)]
 
 
+class SrhFrameParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_pos", C.c_int32), ("n_normal", C.c_int32), ("pos_cols", C.c_int32),
+                ("normal_cols", C.c_int32)]
+
+
+class SrhProjectCoordsParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_points", C.c_int32), ("cols", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("fovy", C.c_double), ("focal_length", C.c_double)]
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -232,6 +242,12 @@ SIGNATURES = {
     "srh_normals_bwd_view": (C.c_int, [_I, _I, _I] + [_V] * 4 + [_Z, _V, _V, _V, _Z, _V]),
     "srh_splat_bwd_view": (C.c_int, _SPLAT + [_V, _Z] + [_V] * 4 + [_p(SrhSplatGrads), _V, _V, _Z, _V]),
     "srh_splat_ndc_bwd_view": (C.c_int, _SPLAT_NDC + [_V] * 3 + [_p(SrhSplatNdcGrads), _V, _V, _Z, _V]),
+    "srh_frame_transform_fwd": (C.c_int, [_p(SrhFrameParams)] + [_V] * 7),
+    "srh_frame_transform_bwd": (C.c_int, [_p(SrhFrameParams)] + [_V] * 7),
+    "srh_frame_transform_bwd_view": (C.c_int, [_p(SrhFrameParams)] + [_V] * 11 + [_Z, _V]),
+    "srh_project_coordinates_fwd": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 6),
+    "srh_project_coordinates_bwd": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 6),
+    "srh_project_coordinates_bwd_view": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 7 + [_Z, _V]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -34,6 +34,7 @@
 #include "srh_surfels.h"
 #include "srh_hard_projection.h"
 #include "srh_normals.h"
+#include "srh_frames.h"
 
 using namespace srh;
 
@@ -2365,6 +2366,171 @@ int srh_normals_bwd_view(int32_t n_views, int32_t width, int32_t height, const d
     hipLaunchKernelGGL(k_normals_gather, dim3(S.nblk, S.B), dim3(kNormBlock), 0, st, S, pos, (const double*)workspace,
                        grad_pos);
   return launch_status("normals backward (view) launch");
+}
+
+}  // extern "C"
+
+// ---- the frame transforms and the point projection (srh_frames.h) ------------------------------------------------
+namespace {
+
+static_assert(kViewBlock == kFrameBlock, "view_block_reduce's workgroup is the frame kernels'");
+
+constexpr int32_t kFrameMaxPoints = 1 << 24;
+
+// argument checks (no HIP call) and the device view of a frame transform; a table is needed where its input is there
+int frame_setup(const SrhFrameParams* p, const double* view_pos, const double* view_normal, FramesDev* F) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_n_views(p->n_views)) return rc;
+  if (p->n_pos < 0 || p->n_pos > kFrameMaxPoints) return fail(SRH_E_RANGE, "n_pos = %d, expected 0..2^24", p->n_pos);
+  if (p->n_normal < 0 || p->n_normal > kFrameMaxPoints)
+    return fail(SRH_E_RANGE, "n_normal = %d, expected 0..2^24", p->n_normal);
+  if (p->n_pos == 0 && p->n_normal == 0) return fail(SRH_E_RANGE, "n_pos and n_normal are both 0");
+  if (p->n_pos && p->pos_cols != 3 && p->pos_cols != 4)
+    return fail(SRH_E_RANGE, "pos_cols = %d, expected 3 or 4", p->pos_cols);
+  if (p->n_normal && p->normal_cols != 3 && p->normal_cols != 4)
+    return fail(SRH_E_RANGE, "normal_cols = %d, expected 3 or 4", p->normal_cols);
+  if (p->n_pos && !view_pos) return fail(SRH_E_NULL, "view_pos is NULL");
+  if (p->n_normal && !view_normal) return fail(SRH_E_NULL, "view_normal is NULL");
+  memset(F, 0, sizeof(*F));
+  F->B = p->n_views; F->n_pos = p->n_pos; F->n_normal = p->n_normal;
+  F->pos_cols = p->pos_cols; F->normal_cols = p->normal_cols;
+  F->nblk = ((p->n_pos > p->n_normal ? p->n_pos : p->n_normal) + kFrameBlock - 1) / kFrameBlock;
+  return SRH_OK;
+}
+
+// the pointers of the half that is there: `pos_*` with n_pos > 0, `normal_*` with n_normal > 0
+int frame_check_halves(const FramesDev& F, NamedPtr pos_a, NamedPtr pos_b, NamedPtr normal_a, NamedPtr normal_b) {
+  if (F.n_pos)
+    if (int rc = check_not_null({pos_a, pos_b})) return rc;
+  if (F.n_normal)
+    if (int rc = check_not_null({normal_a, normal_b})) return rc;
+  return SRH_OK;
+}
+
+// argument checks (no HIP call) and the device view of a projection of points
+int pcoord_setup(const SrhProjectCoordsParams* p, PCoordDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_n_views(p->n_views)) return rc;
+  if (p->n_points < 1 || p->n_points > kFrameMaxPoints)
+    return fail(SRH_E_RANGE, "n_points = %d, expected 1..2^24", p->n_points);
+  if (p->cols != 3 && p->cols != 4) return fail(SRH_E_RANGE, "cols = %d, expected 3 or 4", p->cols);
+  if (int rc = check_grid_size(p->width, p->height, "width x height =")) return rc;
+  if (int rc = check_pinhole("", p->fovy, p->focal_length)) return rc;
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->N = p->n_points; P->cols = p->cols; P->W = p->width; P->H = p->height;
+  P->nblk = (P->N + kFrameBlock - 1) / kFrameBlock;
+  const FrameSize fs = frame_size(p->fovy, p->focal_length, P->W, P->H);
+  P->f = p->focal_length;
+  P->sx = -(double)(P->W - 1) / fs.w; P->sy = (double)(P->H - 1) / fs.h;
+  P->hx = P->W / 2.0; P->hy = P->H / 2.0;
+  const PixelScales s = pixel_scales(p->fovy, p->focal_length, P->W, P->H);
+  P->fsx = s.fsx; P->fsy = s.fsy; P->cx0 = s.cx0; P->cy0 = s.cy0;
+  return SRH_OK;
+}
+
+int project_coordinates_bwd(bool with_view, const SrhProjectCoordsParams* params, const double* view,
+                            const float* surfels, const float* g_plane, const float* g_coord, float* grad_surfels,
+                            double* grad_view, void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  PCoordDev P;
+  int rc = pcoord_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}}))) return rc;
+  if (!g_plane && !g_coord) return fail(SRH_E_NULL, "g_plane and g_coord are both NULL");
+  const hipStream_t st = (hipStream_t)stream;
+  if (!with_view) {
+    if ((rc = check_not_null({{"grad_surfels", grad_surfels}}))) return rc;
+    hipLaunchKernelGGL(k_project_bwd<false>, dim3(P.nblk, P.B), dim3(kFrameBlock), 0, st, P, view, surfels, g_plane,
+                       g_coord, grad_surfels, (double*)nullptr);
+    return launch_status("k_project_bwd launch");
+  }
+  if ((rc = check_grad_view("grad_view", grad_view))) return rc;
+  if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, view_ws_bytes(P.B, P.nblk)))) return rc;
+  hipLaunchKernelGGL(k_project_bwd<true>, dim3(P.nblk, P.B), dim3(kFrameBlock), 0, st, P, view, surfels, g_plane,
+                     g_coord, grad_surfels, (double*)view_workspace);
+  launch_view_finish(P.B, P.nblk, kViewSums, 0, view_workspace, grad_view, st);
+  return launch_status("project_coordinates backward (view) launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int srh_frame_transform_fwd(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                            const float* pos, const float* normal, float* out_pos, float* out_normal, void* stream) {
+  FramesDev F;
+  int rc = frame_setup(params, view_pos, view_normal, &F);
+  if (rc) return rc;
+  if ((rc = frame_check_halves(F, {"pos", pos}, {"out_pos", out_pos}, {"normal", normal}, {"out_normal", out_normal})))
+    return rc;
+  hipLaunchKernelGGL(k_frames_fwd, dim3(F.nblk, F.B), dim3(kFrameBlock), 0, (hipStream_t)stream, F, view_pos,
+                     view_normal, pos, normal, out_pos, out_normal);
+  return launch_status("k_frames_fwd launch");
+}
+
+int srh_frame_transform_bwd(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                            const float* g_pos, const float* g_normal, float* grad_pos, float* grad_normal,
+                            void* stream) {
+  FramesDev F;
+  int rc = frame_setup(params, view_pos, view_normal, &F);
+  if (rc) return rc;
+  if ((rc = frame_check_halves(F, {"g_pos", g_pos}, {"g_pos", g_pos}, {"g_normal", g_normal}, {"g_normal", g_normal})))
+    return rc;
+  if (!(F.n_pos && grad_pos) && !(F.n_normal && grad_normal))
+    return fail(SRH_E_NULL, "grad_pos and grad_normal are both NULL or absent");
+  hipLaunchKernelGGL(k_frames_bwd<false>, dim3(F.nblk, F.B), dim3(kFrameBlock), 0, (hipStream_t)stream, F, view_pos,
+                     view_normal, (const float*)nullptr, (const float*)nullptr, g_pos, g_normal, grad_pos, grad_normal,
+                     (double*)nullptr, (double*)nullptr);
+  return launch_status("k_frames_bwd launch");
+}
+
+int srh_frame_transform_bwd_view(const SrhFrameParams* params, const double* view_pos, const double* view_normal,
+                                 const float* pos, const float* normal, const float* g_pos, const float* g_normal,
+                                 float* grad_pos, float* grad_normal, double* grad_view_pos, double* grad_view_normal,
+                                 void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  FramesDev F;
+  int rc = frame_setup(params, view_pos, view_normal, &F);
+  if (rc) return rc;
+  if ((rc = frame_check_halves(F, {"pos", pos}, {"g_pos", g_pos}, {"normal", normal}, {"g_normal", g_normal})))
+    return rc;
+  if (!grad_view_pos && !grad_view_normal) return fail(SRH_E_NULL, "grad_view_pos and grad_view_normal are both NULL");
+  if (grad_view_pos && (rc = check_grad_view("grad_view_pos", grad_view_pos))) return rc;
+  if (grad_view_normal && (rc = check_grad_view("grad_view_normal", grad_view_normal))) return rc;
+  const size_t half = view_ws_bytes(F.B, F.nblk);
+  if ((rc = check_scratch("view_workspace", view_workspace, view_workspace_bytes, 2 * half))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  double* part_pos = grad_view_pos ? (double*)view_workspace : nullptr;
+  double* part_normal = grad_view_normal ? (double*)((char*)view_workspace + half) : nullptr;
+  hipLaunchKernelGGL(k_frames_bwd<true>, dim3(F.nblk, F.B), dim3(kFrameBlock), 0, st, F, view_pos, view_normal, pos,
+                     normal, g_pos, g_normal, F.n_pos ? grad_pos : nullptr, F.n_normal ? grad_normal : nullptr,
+                     part_pos, part_normal);
+  if (part_pos) launch_view_finish(F.B, F.nblk, kViewSums, 0, part_pos, grad_view_pos, st);
+  if (part_normal) launch_view_finish(F.B, F.nblk, kViewSums, 0, part_normal, grad_view_normal, st);
+  return launch_status("frame_transform backward (view) launch");
+}
+
+int srh_project_coordinates_fwd(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                float* plane, float* px_coord, int32_t* px_idx, void* stream) {
+  PCoordDev P;
+  int rc = pcoord_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"view", view}, {"surfels", surfels}}))) return rc;
+  if (!plane && !px_coord && !px_idx) return fail(SRH_E_NULL, "plane, px_coord and px_idx are all NULL");
+  hipLaunchKernelGGL(k_project_fwd, dim3(P.nblk, P.B), dim3(kFrameBlock), 0, (hipStream_t)stream, P, view, surfels,
+                     plane, px_coord, px_idx);
+  return launch_status("k_project_fwd launch");
+}
+
+int srh_project_coordinates_bwd(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                const float* g_plane, const float* g_coord, float* grad_surfels, void* stream) {
+  return project_coordinates_bwd(false, params, view, surfels, g_plane, g_coord, grad_surfels, nullptr, nullptr, 0,
+                                 stream);
+}
+
+int srh_project_coordinates_bwd_view(const SrhProjectCoordsParams* params, const double* view, const float* surfels,
+                                     const float* g_plane, const float* g_coord, float* grad_surfels, double* grad_view,
+                                     void* view_workspace, size_t view_workspace_bytes, void* stream) {
+  return project_coordinates_bwd(true, params, view, surfels, g_plane, g_coord, grad_surfels, grad_view, view_workspace,
+                                 view_workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -25,6 +25,15 @@ struct HProjDev {
   double fsx, fsy, cx0, cy0;
 };
 
+// The pixel index of a surfel at (u, v), `dump` for a dropped one.  The one copy of this arithmetic: k_project_fwd
+// (srh_frames.h) takes project_image_coordinates' index from it, so the two agree bit for bit.
+__device__ __forceinline__ int32_t hproj_key(int W, int H, int dump, double u, double v) {
+  const double ru = rint(u), rv = rint(v);
+  // NaN and anything an int cannot hold fail these comparisons
+  const bool in = ru >= 0.0 && ru <= (double)(W - 1) && rv >= 0.0 && rv <= (double)(H - 1);
+  return in ? (int)rv * W + (int)ru : dump;
+}
+
 // one lane per surfel: keys (B, N) int32
 __global__ __launch_bounds__(kProjBlock) void k_hproj_keys(HProjDev P, const double* __restrict__ view,
                                                            const float* __restrict__ surfels,
@@ -36,10 +45,7 @@ __global__ __launch_bounds__(kProjBlock) void k_hproj_keys(HProjDev P, const dou
   double M[12];
   proj_load_view(view, b, M);
   const ProjPoint S = proj_point(P.fsx, P.fsy, P.cx0, P.cy0, P.W, P.H, M, surfels + 3 * o);
-  const double ru = rint(S.u), rv = rint(S.v);
-  // NaN and anything an int cannot hold fail these comparisons
-  const bool in = ru >= 0.0 && ru <= (double)(P.W - 1) && rv >= 0.0 && rv <= (double)(P.H - 1);
-  keys[o] = in ? (int)rv * P.W + (int)ru : P.N;
+  keys[o] = hproj_key(P.W, P.H, P.N, S.u, S.v);
 }
 
 // One lane per pixel q.  order (B, N): per view a stable ascending permutation of the keys; an entry outside 0..N-1
