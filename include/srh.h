@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SRH_ABI_VERSION 11
+#define SRH_ABI_VERSION 12
 #define SRH_MAX_SEGMENTS 4
 #define SRH_MAX_LIGHTS 64
 
@@ -148,8 +148,7 @@ typedef struct SrhParams {
   int32_t stages;               /* srh_render_fwd, binned mode: 0 = the whole frame; SRH_STAGE_BIN = only the per-frame
                                    records and tile bins (into the workspace); SRH_STAGE_RENDER = only the render kernel,
                                    from the bins a SRH_STAGE_BIN call with the same arguments left in the workspace --
-                                   the bin lists, the primitive records and, where the frame has one, the per-tile table
-                                   of srh_tile_rlen, which only the SRH_STAGE_BIN call writes.
+                                   the bin lists and the primitive records.
                                    Lets a caller run the latency-bound binning of frame i+1 on one stream beside the
                                    render kernel of frame i on another (surf_renderer_amd/pipeline.py) */
   int32_t counters_clean;       /* binned frames: 1 = the caller KNOWS that this workspace's bin counters are zero, so the
@@ -391,20 +390,6 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
  * *bin_cap are cut there (their primitives are on the frame-wide list instead).  The render stage zeroes them again. */
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,
                      size_t* offset_bytes, int32_t* tiles_x, int32_t* tiles_y, int32_t* ntiles_pad, int32_t* bin_cap);
-
-/* Measurement helper, sibling of srh_bin_counters: where a binned frame's per-tile table lives in its workspace.  A frame
- * of ONE disc batch with camera.near_clip > 0 whose rows [row0, row1) span at least 3072 tiles (one wave per tile) carries
- * *tiles_x * *tiles_y floats at workspace + *offset_bytes, entry ty * *tiles_x + tx: the lower bound of 1 / |D| over the
- * pixels of tile (tx, ty), |D| being the length of a
- * pixel's un-normalised ray direction (the front-to-back occlusion cull of the render kernel used it until it took to
- * tracking coverage; no kernel reads the table now, it is still written) -- (float)(1 / sqrt(max |D|^2 over the tile's four corner pixels)), corners clamped
- * to the last column and the slab's last row; 0 where that is not a positive number below 1e30.  The SRH_STAGE_BIN stage
- * writes it on every call (nothing is kept from one call to the next).  Every other
- * frame has no table: *offset_bytes = 0 and
- * SRH_E_NOT_APPLICABLE.  The helper sees no camera: for near_clip <= 0 it still names the place, which nobody writes
- * then.  Added without an ABI version change: no existing struct or signature changed. */
-int srh_tile_rlen(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,
-                  size_t* offset_bytes, int32_t* tiles_x, int32_t* tiles_y);
 
 /* measurement helpers: timing-enabled HIP events usable as SrhParams.ev_start / ev_stop.
  * srh_event_elapsed_ms waits for `stop` to complete (the only call here that blocks the host). */

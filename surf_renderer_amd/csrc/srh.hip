@@ -157,12 +157,9 @@ void with_prim_type(int type, Fn f) {
 }
 
 // k_prep of batch s: the instantiation for the batch's type
-// Batch 0 of a frame with a per-tile table (FrameDev::tile_rlen) gets one more block per 64 tiles, behind the primitives'
-// blocks, which fill it (k_prep).
 void launch_prep(const FrameDev& F, int s, hipStream_t st) {
   const SegDev& S = F.seg[s];
-  const unsigned table_blocks = (s == 0 && F.tile_rlen) ? ((unsigned)F.ntiles + kBinBlock - 1) / kBinBlock : 0u;
-  const dim3 grid((S.count + kBinBlock - 1) / kBinBlock + table_blocks), block(kBinBlock);
+  const dim3 grid((S.count + kBinBlock - 1) / kBinBlock), block(kBinBlock);
   with_prim_type(S.type, [&](auto type) {
     hipLaunchKernelGGL(k_prep<decltype(type)::value>, grid, block, 0, st, F, s, (double*)S.rec64, (float*)S.rec32);
   });
@@ -220,7 +217,7 @@ void launch_fast(const FrameDev& F, hipStream_t st, float* image, float* depth, 
 struct WsLayout {
   size_t off64[SRH_MAX_SEGMENTS];
   size_t off32[SRH_MAX_SEGMENTS];
-  size_t lights64, frame, tilerange, neardist, counters, large, entries, entries_words, tile_rlen, tile_rlen_bytes;
+  size_t lights64, frame, tilerange, neardist, counters, large, entries, entries_words;
   size_t counters_bytes;
   int tiles_x, tiles_y_max;
   size_t total;
@@ -284,13 +281,6 @@ WsLayout layout_for(const SrhObjects* ob, int width, int height) {
   L.neardist = off;                                // light views only (FrameDev::neardist); last, so that the regions a
   off = align_up(off + total * sizeof(float));     // primary frame touches keep their places
   L.total = off;
-  // FrameDev::tile_rlen: BEHIND the layout that everything else shares (DESIGN.md Part II A11), and not part of `total`:
-  // only srh_render_fwd's frames have the table, so only srh_workspace_bytes counts it -- the slices of a views
-  // workspace and the shadow workspace's regions stay where they were.  Only where a frame can have the table at all
-  // (frame_has_tile_rlen: one disc batch, and the full frame -- so perhaps a slab -- has the tiles for one wave per tile)
-  L.tile_rlen = off;
-  const bool table = ob->n_segments == 1 && ob->seg[0].type == SRH_PRIM_DISK && (size_t)L.tiles_x * L.tiles_y_max >= (size_t)kSplitTiles;
-  L.tile_rlen_bytes = table ? align_up(ntiles * sizeof(float)) : 0;
   return L;
 }
 
@@ -470,13 +460,6 @@ void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
   }
 }
 
-// Does a binned frame carry the per-tile table of the occlusion cull's 1 / |D| bound (FrameDev::tile_rlen)?  Exactly when
-// the sorted sweep can run on it (render_binned_body): one disc batch, near > 0, one wave per tile by the tile count.
-// `near_positive` = false asks about the shape alone (srh_tile_rlen knows no camera).
-bool frame_has_tile_rlen(const FrameDev& F, int type0, bool near_positive) {
-  return SRH_OCCLUSION_CULL && F.nseg == 1 && type0 == SRH_PRIM_DISK && near_positive && binned_waves_per_tile(F) == 1;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -496,7 +479,7 @@ size_t srh_workspace_bytes(const SrhObjects* objects, int32_t width, int32_t hei
     return 0;
   }
   const WsLayout L = layout_for(objects, width, height);
-  return L.total + L.tile_rlen_bytes;
+  return L.total;
 }
 
 int srh_generate_rays(const SrhCamera* camera, int32_t row0, int32_t row1, float* ray_dir, void* stream) {
@@ -538,12 +521,6 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
   if (mode == SRH_MODE_BINNED) setup_binning(F, L, workspace);
   F.keep_bins = (stages & SRH_STAGE_KEEP_BINS) ? 1 : 0;
   if (mode == SRH_MODE_BINNED) F.self = (FrameDev*)((char*)workspace + L.frame);
-  // the same in a SRH_STAGE_RENDER-only call: its SRH_STAGE_BIN call left the table in the workspace, like the bins
-  if (mode == SRH_MODE_BINNED && frame_has_tile_rlen(F, F.seg[0].type, F.near_clip > 0.0)) {
-    if (workspace_bytes < L.tile_rlen + L.tile_rlen_bytes)       // (setup_frame checked the shared layout only)
-      return fail(SRH_E_WORKSPACE, "workspace: need %zu bytes (got %zu)", L.tile_rlen + L.tile_rlen_bytes, workspace_bytes);
-    F.tile_rlen = (const float*)((char*)workspace + L.tile_rlen);
-  }
   const bool counters_clean = params->counters_clean != 0;
   if (mode == SRH_MODE_BINNED && run_binning && !counters_clean) {
     // The bin counters start every frame at zero.  The render kernel leaves them that way (render_binned_body), so
@@ -687,7 +664,7 @@ struct ViewsCall {
     W = cameras[0].viewport[2] - cameras[0].viewport[0];
     H = cameras[0].viewport[3] - cameras[0].viewport[1];
     if (!srh_workspace_bytes(objects, W, H)) return SRH_E_RANGE;   // validates, leaves the message
-    one = layout_for(objects, W, H).total;      // (a view's slice carries no per-tile table: WsLayout::tile_rlen_bytes)
+    one = layout_for(objects, W, H).total;
     if (params->per_view & ~(SRH_VIEWS_OBJECTS | SRH_VIEWS_LIGHTS | SRH_VIEWS_MATERIALS))
       return fail(SRH_E_TYPE, "unknown per_view mask %d", params->per_view);
     if (!lights || !materials) return fail(SRH_E_NULL, "lights / materials is NULL");
@@ -1197,24 +1174,6 @@ int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, i
   setup_binning(F, L, nullptr);                        // pointers relative to NULL: only the tile arithmetic is used
   *offset_bytes = L.counters;
   *tiles_x = F.tiles_x; *tiles_y = F.tiles_y; *ntiles_pad = F.ntiles_pad; *bin_cap = F.bin_cap;
-  return SRH_OK;
-}
-
-int srh_tile_rlen(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,
-                  size_t* offset_bytes, int32_t* tiles_x, int32_t* tiles_y) {
-  if (!offset_bytes || !tiles_x || !tiles_y) return fail(SRH_E_NULL, "an output pointer is NULL");
-  if (!srh_workspace_bytes(objects, width, height)) return SRH_E_RANGE;         // validates, leaves the message
-  if (row0 < 0 || row1 > height || row0 >= row1) return fail(SRH_E_RANGE, "row range [%d,%d) outside the %d image rows", row0, row1, height);
-  const WsLayout L = layout_for(objects, width, height);
-  FrameDev F;
-  memset(&F, 0, sizeof(F));
-  F.W = width; F.H = height; F.row0 = row0; F.row1 = row1; F.nseg = objects->n_segments;
-  setup_binning(F, L, nullptr);                        // pointers relative to NULL: only the tile arithmetic is used
-  *tiles_x = F.tiles_x; *tiles_y = F.tiles_y;
-  *offset_bytes = 0;
-  if (!frame_has_tile_rlen(F, objects->seg[0].type, true))
-    return fail(SRH_E_NOT_APPLICABLE, "frames of this scene and %d x %d rows [%d,%d) carry no per-tile table", width, height, row0, row1);
-  *offset_bytes = L.tile_rlen;
   return SRH_OK;
 }
 

@@ -82,7 +82,6 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
   const uint32_t inv_nx = 65536u / (uint32_t)nx + 1u;            // k / nx == (k * inv_nx) >> 16 for k < 64, nx <= 64
   uint64_t mask = 0;
   bool by_rows = false;
-#if SRH_BIN_ROW_SPANS
   // discs and spheres: per tile ROW the run of columns the stored ellipse reaches (ConicSpans, srh_reject.h) -- two roots
   // per row where `reaches` minimises the form over four edges per tile.  A lane whose record has no closed form takes
   // the tile loop below (divergent; an ordinary scene has none: a record without an ellipse has no box either).
@@ -130,7 +129,6 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
       }
     }
   }
-#endif
   if (!by_rows)
     for (int k = 0; k < n; ++k) {
       const int dy = (int)(((uint32_t)k * inv_nx) >> 16);
@@ -698,22 +696,12 @@ __device__ __forceinline__ void wave_lds_fence() {
 // lists).  A tile with one uncovered pixel never takes a threshold, and nothing is skipped.
 // Dead lanes and clamped pixels of an edge tile duplicate live ones (render_binned_body), so every lane votes.
 // The key fields hold the SORTED position; ordinal_to_global maps them through the sorted copy in LDS.
-// (SRH_OCCL_COVERAGE = 0, srh_reject.h: the rule this replaced -- per pixel L (p), the largest lower bound of 1 / t over
-// the certain discs through den shifted down, and every kOcclGroup entries T = min over the tile of L (p) rlen_lo.)
 #ifndef SRH_OCCLUSION_CULL
 #define SRH_OCCLUSION_CULL 1
 #endif
 constexpr uint32_t kOcclGroup = 8;                  // a list has to be longer than this to be worth sorting
 constexpr uint32_t kSortCap = 128;                  // entries one wave sorts (two per lane); longer lists: the plain sweep
 constexpr uint32_t kSortLow = 0x7Fu;                // low key bits: the list position
-#if !SRH_OCCL_COVERAGE
-// den - 3 E / K <= s (n^.D) / K for the fp32 den of the vector path AND the fp64 path's own n^.d (plane_estimate_record:
-// den carries less than E / K of error and is shifted up by E / K; E covers the fp64 side too), with E / K read off
-// lo_u = 1025 E / K (rounded up there) -- the factor is 3 / 1025 rounded up by 2.4e-6.
-constexpr float kDenShiftPerLoU = 0.0029269f;
-// L (p) rlen_lo (1 - 2^-18) <= 1 / t: the (1 - 2^-20) of K, the fp32 1 / |D|, the subtraction and two products
-constexpr float kSureRound = 0.99999619f;
-#endif
 
 // ---- cross-lane exchanges in registers (no LDS round trip) -------------------------------------------------------
 // __shfl_xor is a ds_bpermute: an LDS instruction, a wait for its result and ~4 vector instructions of address
@@ -757,25 +745,6 @@ __device__ __forceinline__ void xor_pair_maxmin(int32_t v, int32_t& hi, int32_t&
     lo = min(v, p);
   }
 }
-
-#if !SRH_OCCL_COVERAGE
-// fminf over the wave, valid in every lane (fminf is commutative and associative: the order of the steps does not
-// change the result)
-template <int CTRL>
-__device__ __forceinline__ float dpp_min_f32(float m) {
-  return fminf(m, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m), CTRL, 0xF, 0xF, true)));
-}
-__device__ __forceinline__ float wave_min_f32(float m) {
-  m = dpp_min_f32<0xB1>(m);                 // quad_perm [1,0,3,2]
-  m = dpp_min_f32<0x4E>(m);                 // quad_perm [2,3,0,1]: the quad's minimum in each lane
-  m = dpp_min_f32<0x124>(m);                // row_ror:4
-  m = dpp_min_f32<0x128>(m);                // row_ror:8: the row's minimum
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-  m = fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-  return fminf(__uint_as_float(h[0]), __uint_as_float(h[1]));
-}
-#endif
 
 // Bitonic sort, DESCENDING, of NR x 64 distinct signed keys across the wave: element i = lane + 64 h is register h of
 // lane `lane`.  Stage (k, j) compares i with i ^ j; blocks of size k with (i & k) == 0 run descending, the others
@@ -840,7 +809,6 @@ __device__ __forceinline__ void occl_sort(const SegDev& S, const uint32_t* __res
 // list words by v_readlane from gs[], the key update of sweep_entry, and per pixel
 //   cov |= bits(q - s_in)                                   (the sign bit: a certain hit covers the pixel)
 // with Vmin = min(Vmin, bits(V)) per wave: positive floats compare as integers, and V arrives as a scalar operand.
-#if SRH_OCCL_COVERAGE
 template <int NR>
 __device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
                                                  const int32_t (&us)[2], QuadState& Q) {
@@ -917,80 +885,6 @@ __device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const 
     }
   }
 }
-#else
-// SRH_OCCL_COVERAGE = 0, the rule this replaced: the same sweep, and per pixel
-//   L = max(L, bits(den - shift) & (q < s_in ? ~0 : 0))      (a negative lower bound never beats the initial 0)
-// `rlen_lo` <= 1 / |D| at every pixel of the tile (the disc kernel's Q.rlen is 1: its keys are in den units).
-template <int NR>
-__device__ __forceinline__ void sweep_sorted(const SegDev& S, uint32_t n, const int32_t (&gs)[2],
-                                                 const int32_t (&us)[2], float rlen_lo, QuadState& Q) {
-  constexpr int TYPE = SRH_PRIM_DISK;
-  const char* base_c = reinterpret_cast<const char*>(S.rec32) - (size_t)S.first * (size_t)(4 * kRec32Stride[TYPE]);
-  auto record = [&](int g) {
-    return reinterpret_cast<const float*>(base_c + (uint32_t)g * (uint32_t)(4 * kRec32Stride[TYPE]));
-  };
-  auto entry = [&](uint32_t k) {
-    k = min(k, n - 1);
-    return (NR == 1 || k < 64) ? __builtin_amdgcn_readlane(gs[0], (int)k) : __builtin_amdgcn_readlane(gs[1], (int)(k - 64));
-  };
-  int32_t L[4] = {0, 0, 0, 0};
-  const uint32_t keep = ~Q.ordmask;
-  auto op = [&](const RejectRecord<TYPE>& R, uint32_t k) {
-    int32_t sel[4];
-    f32x2 den[2], q[2];
-    pair_bounds<TYPE, true, false>(R, Q.cf, Q.rf, Q.rlen, sel, den, q);
-    const uint32_t field = k + 1u;                    // n + 1 <= ordmask: never saturated
-    const float shift = R[9] * kDenShiftPerLoU;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const f32x2 qi = q[p] - splat2(R[11]);
-      const f32x2 lo = den[p] - splat2(shift);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int j = 2 * p + h;
-        const int32_t key = pack_key(den[p][h], field, keep) & sel[j];
-        Q.k4[j] = imed3(Q.k3[j], key, Q.k4[j]);
-        Q.k3[j] = imed3(Q.k2[j], key, Q.k3[j]);
-        Q.k2[j] = imed3(Q.k1[j], key, Q.k2[j]);
-        Q.k1[j] = max(Q.k1[j], key);
-        L[j] = max(L[j], __float_as_int(lo[h]) & (__float_as_int(qi[h]) >> 31));
-      }
-    }
-  };
-  // first sorted position whose U lies below the tile's certain inverse depth (n if none)
-  auto stop_at = [&]() -> uint32_t {
-    const float m0 = __int_as_float(min(min(L[0], L[1]), min(L[2], L[3])));
-    const float m = wave_min_f32(m0 * rlen_lo * kSureRound);
-    const int32_t T = __builtin_amdgcn_readfirstlane(__float_as_int(m));
-    const unsigned long long b0 = __builtin_amdgcn_ballot_w64(us[0] < T);
-    if (b0) return (uint32_t)__builtin_ctzll(b0);
-    if (NR == 2) {
-      const unsigned long long b1 = __builtin_amdgcn_ballot_w64(us[1] < T);
-      if (b1) return 64u + (uint32_t)__builtin_ctzll(b1);
-    }
-    return n;
-  };
-  RejectRecord<TYPE> A, B;
-  uint32_t stop = n;
-  int gA = entry(0);
-  int gB = entry(1);
-  A.load(record(gA));
-  for (uint32_t i = 0; i < stop; i += 2) {
-    B.load(record(gB));
-    gA = entry(i + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    op(A, i);
-    if (i + 1 >= stop) break;
-    __builtin_amdgcn_sched_barrier(0);
-    A.load(record(gA));
-    gB = entry(i + 3);
-    __builtin_amdgcn_sched_barrier(0);
-    op(B, i + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    if ((i + 2) % kOcclGroup == 0 && i + 2 < stop) stop = min(stop, stop_at());
-  }
-}
-#endif
 
 // Resolve the pixel of lane `src` on the slow path with the whole wave; returns the merged (t, index) minimum of
 // everything confirmed here (index 0x7fffffff = nothing), valid in every lane.
@@ -1143,40 +1037,9 @@ __device__ __forceinline__ const FrameDev& round_frame(const FrameDev& F) {
   return *(const FrameDev*)p;
 }
 
-// The occlusion cull's `rlen_lo` of tile (tx, ty): a lower bound of 1 / |D| over the tile's pixels.  1 / |D| is smallest
-// where |D| is largest, and |D| is convex in the pixel coordinates: at a corner of the tile (clamped to the frame and the
-// row slab).  0 where no usable bound exists: T = 0 then, and nothing is skipped.  It depends on the camera, the slab and
-// the tile only.  The one copy of the expression: k_prep evaluates it once per tile, one tile per lane, into
-// FrameDev::tile_rlen (fill_tile_rlen); a render kernel whose frame has no table evaluates it itself.
-// NOBODY READS THE TABLE since the sweep tracks coverage (SRH_OCCL_COVERAGE = 1): k_prep still writes it, because
-// tests/test_hip_tile_rlen.py holds it to its numpy value; taking it out is a clean-up of its own.
-__device__ __forceinline__ float tile_rlen_lo(const FrameDev& F, int tx, int ty) {
-  const int px0 = tx * kTile, py0 = F.row0 + ty * kTile;
-  const int ca = px0, cb = min(px0 + kTile - 1, F.W - 1), ra = py0, rb = min(py0 + kTile - 1, F.row1 - 1);
-  const double m2 = fmax(fmax(pixel_len2(F, ca, ra), pixel_len2(F, cb, ra)),
-                         fmax(pixel_len2(F, ca, rb), pixel_len2(F, cb, rb)));
-  const float rl = (float)(1.0 / sqrt(m2));
-  return (rl > 0.0f && rl < 1.0e30f) ? rl : 0.0f;
-}
-
-// k_prep's blocks behind the primitives' (launch_prep): block `block` of them writes the table entries of tiles
-// 64 block .. 64 block + 63, with plain vector stores.  The render kernel is a later launch on the stream.
-__device__ __forceinline__ void fill_tile_rlen(const FrameDev& F, unsigned block) {
-  const int tile = (int)(block * kBinBlock + threadIdx.x);
-  if (!F.tile_rlen || tile >= F.ntiles) return;
-  const int ty = tile / F.tiles_x, tx = tile - ty * F.tiles_x;
-  const_cast<float*>(F.tile_rlen)[tile] = tile_rlen_lo(F, tx, ty);
-}
-
 // ---- what a finish round needs of its TILE, computed once in front of the round loop -------------------------------
-// Each part has a build switch so that it can be compiled and counted alone (0 = the per-pixel form of the round).
+// Two parts: the ray table and the tonemap's constants (tone_hint), each counted alone when it went in.
 // The output addresses are not among them: built, measured and dropped (DESIGN Part II).
-#ifndef SRH_FINISH_RAYTAB
-#define SRH_FINISH_RAYTAB 1
-#endif
-#ifndef SRH_FINISH_TONE
-#define SRH_FINISH_TONE 1
-#endif
 
 // The ray numerator of pixel_ray, v[i] = (bx[i] X(c) + by[i] Y(r)) + bz[i] Z, has one addend that depends on the column
 // only, one on the row only and one on neither, and a tile has 16 columns and 16 rows.  A wave keeps the 33 addend
@@ -1224,9 +1087,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   __shared__ int32_t front[kWaves][4][64];    // global index of each pixel's front candidate (-1: none / saturated)
   __shared__ uint8_t queue[kWaves][256];      // [wave]: ids j * 64 + lane of the pixels with a candidate, row-major
   __shared__ int32_t occl_g[kWaves][kSortCap];  // occlusion cull: the tile's list in front-to-back order
-#if SRH_FINISH_RAYTAB
   __shared__ RayTable raytab[kWaves];         // the finish rounds' ray numerator addends of this tile (ray_table_fill)
-#endif
   const int wave = kWaves == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   int tx, ty;
@@ -1255,18 +1116,10 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     // occlusion cull (sweep_sorted): the sort runs before any pixel state is live.  One disc batch with near > 0 and
     // nothing frame-wide; a list beyond the sort's capacity, or too short to reach a threshold, keeps the plain sweep.
     int32_t gs[2] = {0, 0}, us[2] = {-1, -1};   // sorted entries and their bounds (occl_sort)
-#if !SRH_OCCL_COVERAGE
-    float rlen_lo = 0.0f;                       // the sorted sweep's lower bound of 1 / |D| over the tile (tile_rlen_lo)
-#endif
 #if SRH_OCCLUSION_CULL
     if (WPT == 1 && BATCH == SRH_PRIM_DISK && pretest) {
       const TileLists L{F, tile};
       if (L.count(0, 0) == 0 && listed > kOcclGroup && listed <= kSortCap) {
-#if !SRH_OCCL_COVERAGE
-        // from the frame's table (k_prep wrote it, an earlier launch: as_constant's contract), one scalar load whose
-        // latency the sort hides
-        if (F.tile_rlen) rlen_lo = as_constant(F.tile_rlen)[tile];
-#endif
         if (listed <= 64) occl_sort<1>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         else occl_sort<2>(F.seg[0], L.list(0, 1), listed, lane, occl_g[wave], gs, us);
         sorted = true;
@@ -1305,16 +1158,8 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
     }
     const uint32_t part = WPT == 1 ? 0u : (uint32_t)wave;     // which share of the tile's entries this wave sweeps
     if (sorted) {
-#if SRH_OCCL_COVERAGE
       if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, Q);
       else sweep_sorted<2>(F.seg[0], listed, gs, us, Q);
-#else
-      // a frame without a table (many views per launch, one wave per tile forced on a small frame): every lane computes
-      // the same value here
-      if (!F.tile_rlen) rlen_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tile_rlen_lo(F, tx, ty))));
-      if (listed <= 64) sweep_sorted<1>(F.seg[0], listed, gs, us, rlen_lo, Q);
-      else sweep_sorted<2>(F.seg[0], listed, gs, us, rlen_lo, Q);
-#endif
     } else if (pretest) {
       sweep_tile<true, WPT, BATCH>(F, tile, Q, part);
     } else {
@@ -1412,12 +1257,8 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
   }
 
   // per tile, not per round: the ray table and the tonemap's constants
-#if SRH_FINISH_RAYTAB
   if (n1 > 0) ray_table_fill(F, px0, py0, lane, raytab[wave]);
-#endif
-#if SRH_FINISH_TONE
   const ToneHint tone = tone_hint(F);
-#endif
   wave_lds_fence();                           // park / queue / ray table writes of other lanes
 #pragma unroll 1
   for (int base = 0; base < n1; base += 64) {
@@ -1434,11 +1275,7 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       FrontRecord<TCH, BATCH> fr;
       fr.fetch(F, gfront);
       double d[3];
-#if SRH_FINISH_RAYTAB
       const float len = (float)ray_from_table(F, raytab[wave], 4 * (src & 3) + j, src >> 2, d);
-#else
-      const float len = (float)pixel_ray(F, c, r, d);
-#endif
       double best = __builtin_inf();
       int besti = 0x7fffffff;
       float bound = __builtin_inff();
@@ -1503,14 +1340,10 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
         if (besti == 0x7fffffff) besti = 0;   // nothing hit: np.argmin of an all-inf column
         float rgb[3], aux[6];
         const ShadeHint hint = fr.hint();
-#if SRH_FINISH_TONE
         // Lambert kernels only: in the one-wave Phong kernels the hint's register is the 97th, one more than five waves
         // per SIMD allow
         shade_pixel_t<TCH, BATCH, true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint, nullptr, ~0ull,
                                         TCH ? nullptr : &tone);
-#else
-        shade_pixel_t<TCH, BATCH, true>(F, d, best, besti, rgb, want_aux ? aux : nullptr, &hint);
-#endif
         const size_t row = (size_t)(r - F.row0);
         float* px = image + row * F.img_stride + 3 * (size_t)c;
         out_store(px, rgb[0]); out_store(px + 1, rgb[1]); out_store(px + 2, rgb[2]);

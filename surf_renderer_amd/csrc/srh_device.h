@@ -53,7 +53,7 @@ struct FrameDev {
   int32_t shading, double_sided, use_quartic;
   int32_t div_shared;                // pixel_ray may share one reciprocal between its three divisions (see there)
   int32_t ortho;                     // orthographic projection (torch semantics only; k_render_ortho)
-  int32_t slab_cull;                 // the row pre-cull below is on (in a former padding word, see tile_rlen)
+  int32_t slab_cull;                 // the row pre-cull below is on (in a former padding word)
   const float* latt;                 // (L,3) attenuation or NULL
   const float* coeffs;               // (K,3) material coefficients or NULL
   const float* ambient;              // (3) or NULL
@@ -66,11 +66,8 @@ struct FrameDev {
   // image row g / a; slab_ma / slab_mg are the rows of [D0 Dc Dr]^-1 that give a and g, slab_na / slab_ng their
   // lengths.  slab_cull = 0 switches the test off (full frame, or a singular basis).
   double slab_ma[3], slab_mg[3], slab_na, slab_ng;
-  const float* tile_rlen;            // (ntiles_pad) per tile the occlusion cull's lower bound of 1 / |D| (srh_binned.h:
-                                     // tile_rlen_lo), written by k_prep of batch 0; NULL: the frame has no table and the
-                                     // render kernel computes the bound itself.  In the 8 bytes that held slab_cull and a
-                                     // padding word: sizeof(FrameDev) -- the views' workspace header -- and every other
-                                     // field's offset stay what they were
+  uint64_t reserved0;                // unused, zero (it held a pointer to a per-tile table that is gone): keeps
+                                     // sizeof(FrameDev) -- the views' workspace header -- and every other field's offset
   uint16_t* tilerange;               // (total,4) tx0,ty0,tx1,ty1 inclusive; tx0 > tx1 = not binned
   uint32_t* counters;                // [4p + s] n_large of batch s, set p | [8] set of the NEXT frame | [9] set of this frame |
                                      // [64, 64+nbins) bin counts   (see kLargeNext below)
@@ -95,9 +92,9 @@ struct FrameDev {
   const float* albedo;
 };
 
-// tile_rlen took the place of slab_cull and a padding word: the struct's size (the views' workspace header is an array of
-// it) and the fields around it are where they were
-static_assert(sizeof(FrameDev) == 784 && offsetof(FrameDev, tile_rlen) == 376 && offsetof(FrameDev, tilerange) == 384 &&
+// The struct's size (the views' workspace header is an array of it, and F.self a byte copy) and every field's offset are
+// fixed; reserved0 holds the place of a field that is gone
+static_assert(sizeof(FrameDev) == 784 && offsetof(FrameDev, reserved0) == 376 && offsetof(FrameDev, tilerange) == 384 &&
               offsetof(FrameDev, slab_cull) + 4 == offsetof(FrameDev, latt), "FrameDev layout");
 
 // rec64 layouts
@@ -174,18 +171,6 @@ __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, dou
 // finish rounds read its three addends from a per-tile table, srh_binned.h: RayTable); returns |v|.
 __device__ __forceinline__ double ray_normalise(const FrameDev& F, const double v[3], double d[3]) {
   return pixel_ray<true>(F, 0, 0, d, v);
-}
-
-// |D|^2 of the un-normalised direction of pixel (c, r): the part of pixel_ray the fp32 sweep needs (its 1 / |D| comes
-// from one v_rsq_f32 of this, no fp64 square root or division)
-__device__ __forceinline__ double pixel_len2(const FrameDev& F, int c, int r) {
-  double X, Y;
-  pixel_plane_xy(F, c, r, X, Y);
-  const double Z = -F.focal;
-  double v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
-  return (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
 }
 
 // ---- intersections: return the reference's ray_distance for one (ray, primitive) pair ------------
@@ -360,8 +345,8 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 //     an invalidated scalar cache, so it sees that data;
 //   - the RUNNING kernel never writes it -- hipcc treats the loads as invariant, and the scalar cache is not coherent
 //     with the kernel's own vector stores.
-// So: frame inputs (lights, colours, attenuation, ambient) and what k_prep left for the render kernels (lights64,
-// tile_rlen) -- never in k_prep itself, which writes both, and never the bin counters, which the render kernel zeroes at
+// So: frame inputs (lights, colours, attenuation, ambient) and what k_prep left for the render kernels (lights64)
+// -- never in k_prep itself, which writes it, and never the bin counters, which the render kernel zeroes at
 // its end.
 template <class T>
 __device__ __forceinline__ const __attribute__((address_space(4))) T* as_constant(const T* p) {

@@ -135,7 +135,7 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
   const bool near_pos = F.near_clip > 0.0;
   ConicExtent conic = no_extent();
   // (a disc's STORED word [10] is the occlusion cull's V; Q[10] stays hi_u for bin_place below: srh_reject.h, layouts)
-  [[maybe_unused]] float stored10 = 0.0f;
+  float stored10 = 0.0f;
   if (TYPE == SRH_PRIM_DISK) disk_reject_record(R, F.o, B, F.W, F.H, F.near_clip, F.far_clip, Q, &conic, &stored10);
   else if (TYPE == SRH_PRIM_SPHERE) sphere_reject_record(R, B, F.W, F.H, near_pos, F.shading != 0, Q, &conic);
   else if (TYPE == SRH_PRIM_TRIANGLE) triangle_reject_record(R, F.o, B, F.W, F.H, near_pos, Q);
@@ -147,11 +147,7 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
     float4* q4 = reinterpret_cast<float4*>(rec32 + (size_t)i * N32);
 #pragma unroll
     for (int k = 0; k < N32 / 4; ++k) {
-#if SRH_OCCL_COVERAGE
       const float w2 = (TYPE == SRH_PRIM_DISK && k == 2) ? stored10 : Q[4 * k + 2];
-#else
-      const float w2 = Q[4 * k + 2];
-#endif
       q4[k] = make_float4(Q[4 * k], Q[4 * k + 1], w2, Q[4 * k + 3]);
     }
   }
@@ -211,15 +207,6 @@ __global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrep
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&F);
     uint32_t* dst = reinterpret_cast<uint32_t*>(F.self);
     for (unsigned i = threadIdx.x; i < sizeof(FrameDev) / 4; i += kBinBlock) dst[i] = src[i];
-  }
-  // blocks behind the primitives' (launch_prep adds them to batch 0 of a frame with a table; only a one-batch disc frame
-  // has one): the per-tile bound of the render kernel's occlusion cull, 64 tiles each
-  if constexpr (TYPE == SRH_PRIM_DISK) {
-    const unsigned prim_blocks = ((unsigned)F.seg[s].count + kBinBlock - 1) / kBinBlock;
-    if (blockIdx.x >= prim_blocks) {
-      fill_tile_rlen(F, blockIdx.x - prim_blocks);
-      return;
-    }
   }
   prep_body<TYPE>(F, s, rec64, rec32);
 }

@@ -24,7 +24,6 @@
 //                  [0..7] (pair_bounds), the sort [8], the sorted sweep [10] as V and [11], the fast mode [0..4]; the
 //                  shadow pass takes the light views' bins and the fp64 records, the backward pass no reject record at
 //                  all; a render-only call (SRH_STAGE_RENDER) runs the same render kernels on the stored records.
-//                  (SRH_OCCL_COVERAGE = 0: the stored word is hi_u, as before.)
 //   sphere (12)   [0..4] as the disc; [5] upper bound of 1 / t for the whole sphere (1e30: none)
 //   triangle (16)  {a_i, b_i, g_i} at [4i..4i+2], i < 3: candidate iff min_i(a_i*c + b_i*r + g_i) >= 0
 //                  [3] u0 [7] u1 [11] u2 [13] lo_u [14] hi_u
@@ -310,13 +309,6 @@ __device__ inline void sphere_conic_record(const double oc[3], double cq, double
 //        V = lower bound of 1 / t over every valid hit of a disc that has certain hits (s_in > -1e30); 1e30 for every
 //        other disc, so that it never lowers the sweep's running minimum.  See kFarBoundMargin.
 // `ext`: the half extents of the stored shape's box (conic_record), none when the record is "always a candidate".
-//
-// SRH_OCCL_COVERAGE is a MEASUREMENT switch: 1 (the default) stores V and compiles the sorted sweep that tracks per pixel
-// only WHETHER a certain hit covers it (sweep_sorted, srh_binned.h); 0 compiles the per-pixel depth tracking it replaced
-// and leaves hi_u in the stored word, so that one tree builds both rules for an A/B and for the swept-entry count.
-#ifndef SRH_OCCL_COVERAGE
-#define SRH_OCCL_COVERAGE 1
-#endif
 // V = kFarBoundMargin / ((l + r) + slack), cast and rounded DOWN.  Every hit lies in the ball: t <= |oc| + r.  `slack` is
 // 2^-20 (l + r): the kFastEps of l and of r (2^-44 of them) and the 2^-22 (l + r) by which the fp64 path's own distance may
 // differ from the geometric one (ball_inverse_depth_bound) together stay below 2^-21.9 (l + r).  The factor 1 - 2^-20
@@ -401,14 +393,12 @@ __device__ inline void disk_reject_record(const double* R, const double o[3], co
   for (int i = 0; i < 11; ++i) sure = sure && fabsf(out[i]) < 1.0e30f;
   sure = sure && fabsf(out[2]) < 1.0e6f && fabsf(out[3]) < 1.0e6f && fabsf(out[4]) < 1.0e6f;
   out[11] = sure ? (float)sure_in : -1.0e30f;
-#if SRH_OCCL_COVERAGE
   // `sure` has (l + r) + slack positive and below far_clip.  A disc WITH certain hits must never keep the 1e30 of one
   // without: a value beyond 1e30 is capped there (still a lower bound), and a NaN (denormal operand of the Newton
   // reciprocal) becomes 0, with which the sweep skips nothing.
   const double v = kFarBoundMargin * rcp_newton((l + r) + slack);
   const float vf = (v < 1.0e30) ? (float)v * 0.9999999f : 1.0e30f;
   *v_out = sure ? ((v == v) ? vf : 0.0f) : 1.0e30f;
-#endif
 }
 
 // sphere: the ray's line meets it iff (oc.D)^2 - |D|^2 (|oc|^2 - r^2) >= 0   (numpy/renderer.py:20-25).
@@ -628,13 +618,6 @@ struct RectTest {
 };
 
 // ---- row spans of a stored ellipse (bin_place) --------------------------------------------------------------------------
-// SRH_BIN_ROW_SPANS is a MEASUREMENT switch: 1 (the default) picks a conic's tiles row by row from the closed form
-// below, 0 compiles RectTest::reaches once per tile of the box for conics too, as triangles have it -- so that one
-// tree builds both criteria for an A/B (tools/ab.sh) and for the per-tile count comparison.
-#ifndef SRH_BIN_ROW_SPANS
-#define SRH_BIN_ROW_SPANS 1
-#endif
-
 // The candidate region q(dc, dr) = A11 dc^2 + 2 A12 dc dr + A22 dr^2 <= lambda (lambda = 1.000001, the threshold of
 // `reaches`) is convex: over the band dr in [a, b] of one tile row its columns are ONE interval [lo, hi], and a tile of
 // that row is reached iff its own column interval meets it.  For a fixed dr the region is

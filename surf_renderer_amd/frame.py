@@ -178,26 +178,6 @@ def bin_statistics(buf: SceneBuffers, cam: _lib.SrhCamera, rows: Optional[Tuple[
             "tile_row_cost": per_tile.sum(axis=1)}
 
 
-def tile_rlen_table(buf: SceneBuffers, cam: _lib.SrhCamera, workspace: torch.Tensor,
-                    rows: Optional[Tuple[int, int]] = None) -> Optional[np.ndarray]:
-    """The per-tile table a binned frame of ``cam`` and ``rows`` left in ``workspace`` (measurement; synchronises):
-    (tile rows, tile columns) float32, a lower bound of 1 / |D| over each 16 x 16-pixel tile (include/srh.h:
-    srh_tile_rlen; the occlusion cull read it until it took to tracking coverage, the binning stage still writes it).  None for frames that carry no table, a camera with ``near <= 0`` included: the
-    library's helper sees no camera and would name a place that nobody wrote."""
-    lib = _lib.load()
-    width, height = frame_size(cam)
-    r0, r1 = _rows(rows, height)
-    if not cam.near_clip > 0.0:
-        return None
-    off, tx, ty = C.c_size_t(), C.c_int32(), C.c_int32()
-    rc = lib.srh_tile_rlen(C.byref(buf.objects), width, height, r0, r1, C.byref(off), C.byref(tx), C.byref(ty))
-    if rc == _lib.E_NOT_APPLICABLE:
-        return None
-    _lib.check(rc)
-    n = tx.value * ty.value
-    return workspace[off.value:off.value + 4 * n].view(torch.float32).cpu().numpy().reshape(ty.value, tx.value)
-
-
 def generate_rays(camera: Dict[str, Any], device="cuda", rows: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """``ray_dir`` as the reference returns it: (4, N) unit directions, row-major over the image
     (numpy/renderer.py:145-169)."""

@@ -31,7 +31,7 @@ from .buffers import (_float_keys, _source_leaves, camera_leaves, camera_struct,
                       SceneBuffers)  # noqa: F401
 from .frame import (_Shade, _forward, _frame, _render_backward, generate_rays,
                     _RenderFunction, _layout_key, _ws_note, _ws_state, bin_statistics, render_buffers,
-                    shadow_pass, tile_rlen_table)  # noqa: F401
+                    shadow_pass)  # noqa: F401
 from .views import ViewScenes, render_views, render_views_buffers, render_views_bwd_buffers  # noqa: F401
 
 # keyword arguments of the torch backend's render() that callers pass routinely (torch/renderer.py:152-168, 233-245,

@@ -22,7 +22,7 @@ def _call(lib, shading, grad_image=None, grad_depth=None, grad_normal=None, grad
 
 
 def test_entry_point_is_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12
     assert "srh_render_bwd_aux" in _lib.EXPORTS
     assert len(lib.srh_render_bwd_aux.argtypes) == 15
 

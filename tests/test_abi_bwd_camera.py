@@ -29,7 +29,7 @@ def _call(lib, shading="torch", grad_image=None, grad_depth=None, scratch=None, 
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12
     assert "srh_render_bwd_camera" in _lib.EXPORTS and "srh_camera_grad_scratch_bytes" in _lib.EXPORTS
     assert len(lib.srh_render_bwd_camera.argtypes) == 18
     assert C.sizeof(_lib.SrhCameraGrads) == 24

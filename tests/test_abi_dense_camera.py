@@ -38,7 +38,7 @@ def _size(lib, which=_lib.DPROJ_WS_VIEW, **fields):
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     for name, spec, front in (("srh_dense_projection_bwd_view", DPROJ, 1), ("srh_normals_bwd_view", NORM, 3)):
         assert name in _lib.EXPORTS and hasattr(lib, name)
         assert len(getattr(lib, name).argtypes) == front + len(spec) + 1    # params or the sizes in front, the stream behind

@@ -70,7 +70,7 @@ def _refused(lib, name, spec, p, a, code, shown, **given):
 
 # ---- exported, bound, declared; refusals (no launch) -----------------------------------------------------------------
 def test_entry_points_are_exported_bound_and_declared(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     protos = declared_prototypes()
     for name, spec in TRANSFORM + PROJECT:
         assert name in _lib.EXPORTS and hasattr(lib, name) and name in protos

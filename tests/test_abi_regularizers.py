@@ -34,7 +34,7 @@ def _bwd(lib, p, a, grads=(True,) * 4, stats=True, grad_terms=True, inputs=(True
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     for name in ("srh_regularizers_workspace_bytes", "srh_regularizers_fwd", "srh_regularizers_bwd"):
         assert name in _lib.EXPORTS and hasattr(lib, name)
     assert len(lib.srh_regularizers_fwd.argtypes) == 10

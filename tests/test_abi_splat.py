@@ -31,7 +31,7 @@ def _fwd(lib, p, inp, li, ma, buf, image=True):
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     for name in ("srh_splat_workspace_bytes", "srh_splat_fwd", "srh_splat_bwd"):
         assert name in _lib.EXPORTS and hasattr(lib, name)
     assert len(lib.srh_splat_fwd.argtypes) == 9

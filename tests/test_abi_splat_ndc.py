@@ -36,7 +36,7 @@ def _bwd(lib, p, inp, li, ma, ups, grads):
 
 def test_entry_points_are_exported_and_bound(lib):
     assert hasattr(lib, "srh_splat_ndc_fwd") and hasattr(lib, "srh_splat_ndc_bwd")
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     for name in ("srh_splat_ndc_fwd", "srh_splat_ndc_bwd"):
         assert name in _lib.EXPORTS
     assert len(lib.srh_splat_ndc_fwd.argtypes) == 8

@@ -32,7 +32,7 @@ def _bwd(lib, p, a, **given):
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11           # added without a version change
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12           # added without a version change
     for name in ("srh_depth_to_surfels_fwd", "srh_depth_to_surfels_bwd"):
         assert name in _lib.EXPORTS and hasattr(lib, name)
     assert len(lib.srh_depth_to_surfels_fwd.argtypes) == 5

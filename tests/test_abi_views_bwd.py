@@ -45,7 +45,7 @@ class _Args:
 
 
 def test_entry_point_is_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12
     assert "srh_render_views_bwd" in _lib.EXPORTS
     assert len(lib.srh_render_views_bwd.argtypes) == 14
     assert lib.srh_render_views_bwd.restype is C.c_int

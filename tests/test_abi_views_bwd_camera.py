@@ -60,7 +60,7 @@ class _Args:
 
 
 def test_entry_points_are_exported_and_bound(lib):
-    assert _lib.ABI_VERSION == 11 and lib.srh_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and lib.srh_abi_version() == 12
     for name, nargs, restype in (("srh_render_views_bwd_camera", 19, C.c_int), ("srh_render_views_aux", 14, C.c_int),
                                  ("srh_camera_grad_scratch_bytes_views", 3, C.c_size_t)):
         assert name in _lib.EXPORTS

@@ -1,6 +1,8 @@
 """GPU: the front-to-back occlusion cull of the binned disc kernel (srh_binned.h, sweep_sorted) may only skip entries
 that can neither win nor tie, so the binned frame must equal the all-pairs fp64 frame bit for bit -- image, depth and
-nearest -- on scenes built to stress its certain-hit test, its depth bounds and its limits."""
+nearest -- on scenes built to stress its certain-hit test, its depth bounds and its limits, and at the smallest
+shapes that run one wave per tile by the tile count (>= 3072 tiles), where the sorted sweep runs by default: against
+the all-pairs mode (exact), with a re-used workspace and with split stages."""
 import os
 import subprocess
 import sys
@@ -9,8 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from surf_renderer_amd import _lib, renderer, synthetic
+
 pytestmark = pytest.mark.gpu
 
+DEV = "cuda:0"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -121,6 +126,101 @@ def test_config2_bunny_splats():
     from surf_renderer_amd import synthetic
     for w, h in ((512, 512), (1024, 768)):
         _binned_equals_exact(synthetic.bunny_splat_scene(w, h))
+
+
+# ---- the only shapes where the sorted sweep runs one wave per tile by the tile count (>= 3072 tiles) ------------------
+def disc_scene(width, height, eye_z=4.0, fovy_deg=45.0, n=3000, radius=0.05):
+    scene = synthetic.disk_cloud_scene(n, width, height, radius=radius)
+    scene["camera"] = dict(scene["camera"], eye=[0.0, 0.0, eye_z, 1.0], fovy=float(np.deg2rad(fovy_deg)))
+    return scene
+
+
+class Case:
+    """One shape: the scene on the GPU, the all-pairs outputs (computed once, never modified) and the binned frame with
+    the workspace it ran in."""
+
+    def __init__(self, width, height, rows, eye_z):
+        self.rows = rows
+        self.scene = disc_scene(width, height, eye_z)
+        self.buf = renderer.flatten_scene(self.scene, device=DEV)
+        self.cam = renderer.camera_struct(self.scene["camera"])
+        self.ref = renderer.render_buffers(self.buf, self.cam, rows=rows, mode="fast")
+        self.ws = self.buf.new_workspace(width, height)
+        self.got = renderer.render_buffers(self.buf, self.cam, rows=rows, mode="binned", workspace=self.ws)
+        torch.cuda.synchronize()
+
+
+# 1000 x 790: 63 x 50 = 3150 tiles, neither side a multiple of 16 (clamped corners; the linspace end-point rule in the
+# last column and the last row).  2048 wide, rows (37, 417) of 454: a slab with row0 > 0 whose last tile row is cut,
+# 128 x 24 = 3072 tiles -- the fewest that still run one wave per tile.
+SHAPES = {"frame": (1000, 790, (0, 790), 4.0), "slab": (2048, 454, (37, 417), 2.5)}
+_cases = {}
+
+
+def get_case(name):
+    if name not in _cases:
+        _cases[name] = Case(*SHAPES[name])
+    return _cases[name]
+
+
+@pytest.fixture(params=sorted(SHAPES))
+def case(request):
+    return get_case(request.param)
+
+
+def same(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_outputs_equal_all_pairs_with_the_cull_running(case):
+    st = renderer.bin_statistics(case.buf, case.cam, rows=case.rows)
+    entries = st["entries"][0]
+    culled = int(((entries >= 9) & (entries <= 128)).sum())
+    print(f"tiles with 9..128 entries: {culled} of {entries.size}, longest list {int(entries.max())}, frame-wide {st['wide']}")
+    assert int(st["wide"].sum()) == 0 and culled >= 300      # the sorted sweep runs in a few hundred tiles
+    for name, g, w in zip(("image", "depth", "nearest"), case.got, case.ref):
+        assert torch.equal(g, w), name
+
+
+def test_reused_workspace_renders_as_a_fresh_one():
+    """A workspace of 0xFF bytes renders camera A, then camera B (another eye and fovy): B's outputs are those of a
+    fresh workspace and of the all-pairs mode."""
+    width, height, rows, _ = SHAPES["frame"]
+    a = get_case("frame")
+    scene_b = disc_scene(width, height, eye_z=3.1, fovy_deg=52.0)
+    cam_b = renderer.camera_struct(scene_b["camera"])
+    ws = a.buf.new_workspace(width, height)
+    ws.fill_(0xFF)
+    renderer.render_buffers(a.buf, a.cam, rows=rows, mode="binned", workspace=ws)
+    got_b = renderer.render_buffers(a.buf, cam_b, rows=rows, mode="binned", workspace=ws)
+    fresh = renderer.render_buffers(a.buf, cam_b, rows=rows, mode="binned", workspace=a.buf.new_workspace(width, height))
+    assert same(got_b, fresh)
+    assert same(got_b, renderer.render_buffers(a.buf, cam_b, rows=rows, mode="fast"))
+
+
+def test_split_stages_give_the_single_calls_bits():
+    width, height, rows, _ = SHAPES["frame"]
+    a = get_case("frame")
+    ws = a.buf.new_workspace(width, height)
+    out = tuple(torch.zeros_like(t) for t in a.got)
+    renderer.render_buffers(a.buf, a.cam, rows=rows, mode="binned", out=out, workspace=ws, stages=_lib.STAGE_BIN)
+    renderer.render_buffers(a.buf, a.cam, rows=rows, mode="binned", out=out, workspace=ws, stages=_lib.STAGE_RENDER)
+    assert same(out, a.got)
+
+
+def test_sphere_batch_and_four_wave_disc_frame_equal_all_pairs():
+    """A sphere batch (any size) and a 512 x 512 disc frame (1024 tiles: four waves per tile), on which the sorted sweep
+    does not run, render as the all-pairs mode does."""
+    spheres = synthetic.disk_cloud_scene(400, 1000, 790, radius=0.05)
+    disk = spheres["objects"].pop("disk")
+    spheres["objects"]["sphere"] = {"pos": disk["pos"], "radius": disk["radius"], "material_idx": disk["material_idx"]}
+    for scene in (spheres, synthetic.disk_cloud_scene(3000, 512, 512, radius=0.05)):
+        buf = renderer.flatten_scene(scene, device=DEV)
+        cam = renderer.camera_struct(scene["camera"])
+        width, height = renderer.frame_size(cam)
+        ws = buf.new_workspace(width, height)
+        got = renderer.render_buffers(buf, cam, mode="binned", workspace=ws)
+        assert same(got, renderer.render_buffers(buf, cam, mode="fast"))
 
 
 _DUMP = r"""

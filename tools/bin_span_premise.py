@@ -2,7 +2,7 @@
 """How many iterations pass 1 of bin_place runs at config 5 (bench.py's workload), from a numpy restatement of the disc
 records and their tile boxes (tests/bin_spans_model.py).  No GPU.
 
-Per wave of 64 consecutive discs: the largest box in tiles (iterations of the per-tile loop, SRH_BIN_ROW_SPANS=0), the
+Per wave of 64 consecutive discs: the largest box in tiles (iterations of the parent's per-tile loop), the
 largest box in tile rows (iterations of the row loop), and the discs whose box has its worst corner behind the eye (the
 only ones whose rows take the `behind` test).  Discs without an ellipse record of their own (the sphere stand-in) are
 not modelled and count as "no box".  profiles/bin_spans_pmc.json quotes the output."""
