@@ -431,7 +431,8 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_blur_v_corner(ProjDev P, in
 }
 
 // Backward 4: one lane per surfel reads the rows of its four destination pixels and writes g_rgb (B, N, D) and
-// g_surfels (B, N, 3), each element once (zeros for a surfel outside the frame); either may be NULL.
+// g_surfels (B, N, 3), each element once; either may be NULL.  A surfel none of whose corners can be in the frame (NaN,
+// inf and huge ones among them) gets exact zeros in both, whatever its coordinates and its rgb hold.
 // kView: also the gradient of the view's matrix: cc = M [p, 1], so g_M = sum_s g_cc (x) [p_s, 1] with g_cc = (g_X, g_Y,
 // g_Z) below, zeros for a surfel outside the frame.  The lane keeps g_cc and the point (vg, vp), each workgroup stores
 // the sums of their 12 products to view_part (srh_view_grad.h), and g_rgb and g_surfels may then both be NULL.  Without
@@ -452,6 +453,18 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const
   double M[12];
   proj_load_view(view, b, M);
   const ProjSurfel S = proj_surfel(P, M, surfels + 3 * o);
+  if (!S.live) {                        // zero rows before any arithmetic on S: its alpha, w, X, Y may be inf or NaN
+    if (g_rgb) {
+#pragma unroll
+      for (int c = 0; c < kProjMaxD; ++c)
+        if (c < P.D) g_rgb[o * P.D + c] = 0.0f;
+    }
+    if (g_surfels) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) g_surfels[3 * o + j] = 0.0f;
+    }
+    break;
+  }
   const double a = S.alpha * S.w;
   double v[kProjMaxD], gc[kProjMaxD];
 #pragma unroll
@@ -460,28 +473,26 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const
     gc[c] = 0.0;
   }
   double g_fx = 0.0, g_fy = 0.0, g_a = 0.0, g_zv = 0.0;
-  if (S.live) {
 #pragma unroll 1
-    for (int k = 0; k < 4; ++k) {
-      const int qx = S.ix + (k >> 1), qy = S.iy + (k & 1);
-      if (qx < 0 || qx >= P.W || qy < 0 || qy >= P.H) continue;
-      const double* g = gcor + proj_corner(P, b, k, 0, qy * P.W + qx);      // slot s of the row: g[s N]
-      const double beta = proj_beta(k, S.fx, S.fy);
-      const double g_dep = g[(size_t)(P.D + 1) * P.N];
-      double T = g[(size_t)P.D * P.N] + S.z * g_dep;
+  for (int k = 0; k < 4; ++k) {
+    const int qx = S.ix + (k >> 1), qy = S.iy + (k & 1);
+    if (qx < 0 || qx >= P.W || qy < 0 || qy >= P.H) continue;
+    const double* g = gcor + proj_corner(P, b, k, 0, qy * P.W + qx);      // slot s of the row: g[s N]
+    const double beta = proj_beta(k, S.fx, S.fy);
+    const double g_dep = g[(size_t)(P.D + 1) * P.N];
+    double T = g[(size_t)P.D * P.N] + S.z * g_dep;
 #pragma unroll
-      for (int c = 0; c < kProjMaxD; ++c) {
-        if (c >= P.D) continue;
-        const double gvc = g[(size_t)c * P.N];
-        T += v[c] * gvc;
-        gc[c] += beta * a * gvc;
-      }
-      const double g_beta = a * T;
-      g_fx += g_beta * ((k & 2) ? 1.0 : -1.0) * ((k & 1) ? S.fy : 1.0 - S.fy);
-      g_fy += g_beta * ((k & 1) ? 1.0 : -1.0) * ((k & 2) ? S.fx : 1.0 - S.fx);
-      g_a += beta * T + g[(size_t)(P.D + 2) * P.N];
-      g_zv += beta * a * g_dep;
+    for (int c = 0; c < kProjMaxD; ++c) {
+      if (c >= P.D) continue;
+      const double gvc = g[(size_t)c * P.N];
+      T += v[c] * gvc;
+      gc[c] += beta * a * gvc;
     }
+    const double g_beta = a * T;
+    g_fx += g_beta * ((k & 2) ? 1.0 : -1.0) * ((k & 1) ? S.fy : 1.0 - S.fy);
+    g_fy += g_beta * ((k & 1) ? 1.0 : -1.0) * ((k & 2) ? S.fx : 1.0 - S.fx);
+    g_a += beta * T + g[(size_t)(P.D + 2) * P.N];
+    g_zv += beta * a * g_dep;
   }
   if (g_rgb) {
 #pragma unroll
@@ -501,7 +512,7 @@ __global__ __launch_bounds__(kProjBlock) void k_proj_surfel_bwd(ProjDev P, const
   }
   const double g_X = g_fx * P.fsx / S.Zd, g_Y = g_fy * P.fsy / S.Zd;
   const double g_Z = (S.Z != 0.0 ? -(g_X * S.X + g_Y * S.Y) / S.Zd : 0.0) - g_z;
-  if (kView && S.live) {
+  if (kView) {
     vg[0] = g_X; vg[1] = g_Y; vg[2] = g_Z;
 #pragma unroll
     for (int c = 0; c < 3; ++c) vp[c] = (double)surfels[3 * o + c];

@@ -3,7 +3,9 @@
 (diffrend/torch/projection_layer.py:108-152), imported UNMODIFIED and run on the CPU under autograd, on the seeded
 cases of tests/dense_projection_cases.py (RECORDED: every frame with rgb as [B, H, W, D], the small ones as [B, N, D]
 too), WITHOUT a rotated image: with one the reference's own line raises a broadcast error for every frame of more than
-one pixel, so that branch has no reference result to record.
+one pixel, so that branch has no reference result to record.  dp2_*.npz are the RECORDED edge cases of tests/
+dense_projection_edge_cases.py (a frame of one row; surfels 1e3 to 1e12 pixels off the frame), as grids without a rotated
+image.  The reference raised on neither.
 
 Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by hand -- no test reads
 the reference.  The function is tried in float64 first (ref_harness.precision); PRECISION below records which precision
@@ -28,6 +30,7 @@ from oracle import ref_harness as R  # noqa: E402
 
 sys.path.insert(0, os.path.join(R.REPO, "tests"))
 import dense_projection_cases as cases  # noqa: E402
+import dense_projection_edge_cases as edges  # noqa: E402
 
 with contextlib.redirect_stdout(io.StringIO()):
     import diffrend.torch.projection_layer as ref_projection  # noqa: E402
@@ -61,13 +64,12 @@ def pick_precision():
     return torch.float32
 
 
-def emit(frame, layout, dtype):
-    c = cases.case(frame, layout)
+def emit(c, fixture, dtype):
     res, leaves = run_reference(c, dtype)
     flat = R.pack_layer(c, leaves, res, dtype=dtype)
     flat["in/blur_size"] = np.asarray(c["blur_size"], dtype=np.float64)
     flat["in/precision"] = np.asarray(str(dtype).replace("torch.", ""))
-    R.write("dp1_" + cases.tag(frame, layout), flat)
+    R.write(fixture, flat)
 
 
 if __name__ == "__main__":
@@ -75,4 +77,6 @@ if __name__ == "__main__":
     PRECISION = pick_precision()
     print(f"recording in {PRECISION}")
     for f, layout in cases.RECORDED:
-        emit(f, layout, PRECISION)
+        emit(cases.case(f, layout), "dp1_" + cases.tag(f, layout), PRECISION)
+    for n, layout in edges.RECORDED:           # a list of their own: the seeded fixtures above stay as they are
+        emit(edges.case(n, layout), "dp2_" + edges.tag(n, layout), PRECISION)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Generate tests/golden/reverse_projection/rp1_*.npz: the reference's OWN projection_reverse_renderer (diffrend/torch/
 projection_layer.py:281-333), imported UNMODIFIED and run on the CPU in float32 under autograd, on the seeded cases of
-tests/reverse_projection_cases.py and the variants of its 12x16 case that change the function.
+tests/reverse_projection_cases.py and the variants of its 12x16 case that change the function; and rp2_*.npz, the same on
+the RECORDED edge cases of tests/reverse_projection_edge_cases.py (frames of one row and of one column).  The reference
+raised on neither.
 
 Test infrastructure; needs the reference checkout (oracle/ref_harness.py locates it) and is run by hand -- no test reads
 the reference.  A case of exactly three views is recorded view by view (ref_harness.run_views).  The reference's mask
@@ -25,14 +27,14 @@ from oracle import ref_harness as R  # noqa: E402
 
 sys.path.insert(0, os.path.join(R.REPO, "tests"))
 import reverse_projection_cases as cases  # noqa: E402
+import reverse_projection_edge_cases as edges  # noqa: E402
 from reverse_projection_oracle import INPUTS  # noqa: E402
 
 with contextlib.redirect_stdout(io.StringIO()):
     import diffrend.torch.projection_layer as ref_projection  # noqa: E402
 
 
-def emit(name, variant):
-    c = cases.case(name, variant)
+def emit(c, fixture):
     leaves = {k: torch.tensor(c[k], requires_grad=True) for k in INPUTS if c[k] is not None}
     cameras = [R.layer_camera(c[cam]) for cam in ("camera1", "camera2")]
 
@@ -46,10 +48,13 @@ def emit(name, variant):
 
     flat = R.pack_layer(c, leaves, R.run_views(run, c["shape"][0]), cameras=("camera1", "camera2"))
     flat["in/flags"] = np.asarray(json.dumps(c["flags"], sort_keys=True))
-    R.write("rp1_" + cases.tag(name, variant), flat)
+    R.write(fixture, flat)
 
 
 if __name__ == "__main__":
     R.OUT = R.fixture_dir("reverse_projection")
     for n, v in cases.FIXTURES:
-        emit(n, v)
+        emit(cases.case(n, v), "rp1_" + cases.tag(n, v))
+    for n in edges.RECORDED:                   # a list of their own: the seeded fixtures above stay as they are
+        assert edges.margin(edges.case(n)) >= 1.0, n
+        emit(edges.case(n), "rp2_" + n)
