@@ -391,6 +391,13 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
 int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, int32_t row0, int32_t row1,
                      size_t* offset_bytes, int32_t* tiles_x, int32_t* tiles_y, int32_t* ntiles_pad, int32_t* bin_cap);
 
+/* What the host has proved about a camera's primary rays, as the render entry points decide it for every frame
+ * (`orthonormal`: the basis of SRH_SHADING_TORCH).  *flags bit 0: the three divisions by |D| may share one reciprocal;
+ * bit 1 (only with bit 0): |D|^2 is bounded over the frame and the binned finish rounds take its square root without
+ * range guards.  Both are bit-identical to the plain forms; 0 for a camera of extreme or non-finite magnitudes.  With
+ * SRH_ROOT_GUARDS set in the environment bit 1 is never set (tests compare the two forms on one camera). */
+int srh_camera_ray_flags(const SrhCamera* camera, int32_t orthonormal, int32_t* flags);
+
 /* measurement helpers: timing-enabled HIP events usable as SrhParams.ev_start / ev_stop.
  * srh_event_elapsed_ms waits for `stop` to complete (the only call here that blocks the host). */
 int srh_event_create(void** event);

@@ -201,6 +201,7 @@ SIGNATURES = {
     "srh_shadow_workspace_bytes": (_Z, [_p(SrhObjects), _I, _I, _I]),
     "srh_shadow_shade": (C.c_int, _FRAME + [_V] * 5),
     "srh_bin_counters": (C.c_int, [_p(SrhObjects), _I, _I, _I, _I, _p(_Z), _p(_I), _p(_I), _p(_I), _p(_I)]),
+    "srh_camera_ray_flags": (C.c_int, [_p(SrhCamera), _I, _p(_I)]),
     "srh_event_create": (C.c_int, [_p(_V)]),
     "srh_event_destroy": (C.c_int, [_V]),
     "srh_event_elapsed_ms": (C.c_int, [_V, _V, _p(C.c_float)]),

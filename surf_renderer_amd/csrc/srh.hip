@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <initializer_list>
@@ -341,7 +342,27 @@ int camera_to_frame(const SrhCamera* cam, FrameDev* F, bool orthonormal = false)
   bool ok = ordinary(F->half_w) && F->half_w != 0.0 && ordinary(F->half_h) && F->half_h != 0.0 &&
             ordinary(F->focal) && F->focal != 0.0;
   for (int i = 0; i < 3; ++i) ok = ok && ordinary(F->bx[i]) && ordinary(F->by[i]) && ordinary(F->bz[i]);
-  F->div_shared = ok ? 1 : 0;
+  // Bit 1: |D|^2 is bounded over the whole frame, so the finish rounds' square root needs none of its range guards
+  // (sqrt_bounded).  D = bx X + by Y - bz focal with |X| <= half_w, |Y| <= half_h.  Above: the triangle inequality.
+  // Below: w = z - (z.y / y.y) y is orthogonal to y and (x being a cross product with z and y or their span) to x, so
+  // D.w = -focal |w|^2 and |D| >= focal |w|, less what x.w and y.w are in fp64 instead of 0.  Admitted: 1e-100 <= |D| <=
+  // 1e100 -- normal, finite, non-zero, |D|^2 far above 2^-767 -- and a lower bound no more than 1e6 below the upper
+  // one, so that the rounding of this reckoning itself (1e-15 of the upper bound) cannot matter.
+  bool bounded = ok;
+  if (bounded) {
+    auto dot = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    const double *bx = F->bx, *by = F->by, *bz = F->bz;
+    const double hw = std::fabs(F->half_w), hh = std::fabs(F->half_h), fl = std::fabs(F->focal);
+    const double yy = dot(by, by), zy = dot(bz, by);
+    double w[3];
+    for (int i = 0; i < 3; ++i) w[i] = bz[i] - (yy > 0 ? zy / yy : 0.0) * by[i];
+    const double wl = std::sqrt(dot(w, w));
+    const double hi = hw * std::sqrt(dot(bx, bx)) + hh * std::sqrt(yy) + fl * std::sqrt(dot(bz, bz));
+    const double lo = wl > 0 ? fl * wl - (hw * std::fabs(dot(bx, w)) + hh * std::fabs(dot(by, w))) / wl : 0.0;
+    bounded = lo >= 1e-100 && hi <= 1e100 && lo >= 1e-6 * hi;        // false for a NaN anywhere
+  }
+  if (bounded && getenv("SRH_ROOT_GUARDS")) bounded = false;     // tests: the guarded root on a camera that needs none
+  F->div_shared = ok ? (bounded ? 1 | kRootBounded : 1) : 0;
   F->ortho = cam->ortho ? 1 : 0;
   return SRH_OK;
 }
@@ -1174,6 +1195,16 @@ int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, i
   setup_binning(F, L, nullptr);                        // pointers relative to NULL: only the tile arithmetic is used
   *offset_bytes = L.counters;
   *tiles_x = F.tiles_x; *tiles_y = F.tiles_y; *ntiles_pad = F.ntiles_pad; *bin_cap = F.bin_cap;
+  return SRH_OK;
+}
+
+int srh_camera_ray_flags(const SrhCamera* camera, int32_t orthonormal, int32_t* flags) {
+  if (!flags) return fail(SRH_E_NULL, "flags is NULL");
+  FrameDev F;
+  memset(&F, 0, sizeof(F));
+  const int rc = camera_to_frame(camera, &F, orthonormal != 0);
+  if (rc) return rc;
+  *flags = F.div_shared;
   return SRH_OK;
 }
 

@@ -1075,7 +1075,7 @@ __device__ __forceinline__ double ray_from_table(const FrameDev& F, const RayTab
   double v[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) v[i] = (T[kRayCols + kc][i] + T[kRayRows + kr][i]) + T[kRayZ][i];
-  return ray_normalise(F, v, d);
+  return ray_normalise<true>(F, v, d);
 }
 
 template <bool TCH, int WPT, int BATCH = -1>
@@ -1281,42 +1281,66 @@ __device__ __forceinline__ void render_binned_body(const FrameDev& __restrict__ 
       float bound = __builtin_inff();
       int g1 = -1, g2 = -1;
       bool slow = false;
-      if (live) {
-        // Confirm the front candidates in key order while their bound still reaches the confirmed depth (the
-        // first one always; the next ones after a near miss at an ellipse edge or for nearly coplanar primitives).
-        // A saturated ordinal does not identify its primitive: such a pixel confirms everything on the slow path.
-        const int32_t keys[3] = {p.k1, p.k2, p.k3};
-        const int32_t sentinel = p.k4;
-        bool saturated = false;
-        // a key still "reaches" the confirmed depth iff its inverse-depth bound is >= reach_of(bound)
-        // (one reciprocal per confirmation instead of one per key; 0 while nothing is confirmed).  Keys in den units
-        // (den_keys): den = inv |D|, so the threshold is scaled by |D| -- rounded DOWN (len is the fp32 of the fp64
-        // length; 1 - 2^-21 covers that and the product), clamped again so that a key without an estimate still
-        // reaches everything.
-        const float key_unit = den_keys(BATCH) ? len * 0.9999995f : 1.0f;
-        float reach = 0.0f;
+      // Confirm the front candidates in key order while their bound still reaches the confirmed depth (the
+      // first one always; the next ones after a near miss at an ellipse edge or for nearly coplanar primitives).
+      // A saturated ordinal does not identify its primitive: such a pixel confirms everything on the slow path.
+      // A key still "reaches" the confirmed depth iff its inverse-depth bound is >= reach_of(bound)
+      // (one reciprocal per confirmation instead of one per key; 0 while nothing is confirmed).  Keys in den units
+      // (den_keys): den = inv |D|, so the threshold is scaled by |D| -- rounded DOWN (len is the fp32 of the fp64
+      // length; 1 - 2^-21 covers that and the product), clamped again so that a key without an estimate still
+      // reaches everything.
+      const float key_unit = den_keys(BATCH) ? len * 0.9999995f : 1.0f;
+      // The front key, straight-line for the whole wave: a queued pixel has one (`has`), nothing is confirmed yet and
+      // reach is 0, so the loop's three tests say nothing about it.  resolve_lex against (inf, none) is the clip test
+      // alone.  A saturated front key (gfront = -1: the record is primitive 0's) and a dead lane compute a hit nobody
+      // looks at: best stays inf, so bound is inf and reach 0, as they were before any confirmation.
+      // (Four waves per tile: under `live`.  Unconditional, the Phong kernels of that shape need 98 vector registers
+      // and lose their fifth wave per SIMD.)
+      bool saturated = false;
+      float reach = 0.0f;
+      if (WPT == 1 || live) {
+        saturated = key_saturated(p.k1, ordmask);
+        const double t0 = fr.hit(F, d);
+        // (& not &&: hipcc turns the short-circuit into one exec-mask level per test, each with its own scalar load)
+        const bool ok0 = !saturated & (F.near_clip <= t0) & (t0 <= F.far_clip) & (t0 < __builtin_inf());
+        best = ok0 ? t0 : __builtin_inf();
+        besti = ok0 ? gfront : 0x7fffffff;
+        g1 = gfront;
+        bound = float_above(best);
+        reach = fminf(reach_of(bound) * key_unit, kReachMax);   // bound = inf (a miss) gives 0 again
+      }
+      // The second and third keys, behind one wave-uniform test: keys descend, so where the second does not reach
+      // neither does the third (reach only moves with a confirmation), and the round goes on to the sentinel.
+      // (one ballot per test, combined on the scalar unit: each is its compare's own mask, where a ballot of the
+      // combined bool goes through a vector register -- as does a ballot of `live`, hence the shift, which relies on
+      // the queue's slots being dense from `base`: the live lanes are exactly lanes 0 .. n1 - base - 1)
+      const unsigned long long live_lanes = n1 - base >= 64 ? ~0ull : (1ull << (n1 - base)) - 1ull;
+      const unsigned long long more = live_lanes & ~__builtin_amdgcn_ballot_w64(saturated) &
+                                      __builtin_amdgcn_ballot_w64(p.k2 != kNoKey) &
+                                      __builtin_amdgcn_ballot_w64(key_inv(p.k2, ordmask) >= reach);
+      if (more) {
+        if (live) {
+          const int32_t keys[3] = {p.k1, p.k2, p.k3};
 #pragma unroll
-        for (int q = 0; q < kKeys - 1; ++q) {
-          const int32_t key = keys[q];
-          if (key != kNoKey && !saturated && key_inv(key, ordmask) >= reach) {
-            if (key_saturated(key, ordmask)) {
-              saturated = true;
-            } else {
-              const int g = (q == 0) ? gfront : ordinal_to_global<BATCH>(F, tile, key_ordinal(key, ordmask),
-                                                                           sorted ? occl_g[wave] : nullptr);
-              if (q == 0) g1 = g;
-              if (q == 1) g2 = g;
-              if (q == 0) resolve_lex(F, fr.hit(F, d), g, best, besti);
-              else confirm_global<TCH, BATCH>(F, g, d, best, besti);
-              bound = float_above(best);
-              reach = fminf(reach_of(bound) * key_unit, kReachMax);   // bound = inf (a miss) gives 0 again
+          for (int q = 1; q < kKeys - 1; ++q) {
+            const int32_t key = keys[q];
+            if (key != kNoKey && !saturated && key_inv(key, ordmask) >= reach) {
+              if (key_saturated(key, ordmask)) {
+                saturated = true;
+              } else {
+                const int g = ordinal_to_global<BATCH>(F, tile, key_ordinal(key, ordmask), sorted ? occl_g[wave] : nullptr);
+                if (q == 1) g2 = g;
+                confirm_global<TCH, BATCH>(F, g, d, best, besti);
+                bound = float_above(best);
+                reach = fminf(reach_of(bound) * key_unit, kReachMax);
+              }
             }
           }
         }
-        // the fourth key is only a bound: if it still reaches the confirmed depth, somebody unknown might too
-        slow = saturated || (sentinel != kNoKey && key_inv(sentinel, ordmask) >= reach);
-        if (slow) { g1 = g2 = -1; }           // the slow path re-confirms; cheaper than excluding three indices
       }
+      // the fourth key is only a bound: if it still reaches the confirmed depth, somebody unknown might too
+      slow = live & (saturated | ((p.k4 != kNoKey) & (key_inv(p.k4, ordmask) >= reach)));
+      if (slow) { g1 = g2 = -1; }             // the slow path re-confirms; cheaper than excluding three indices
       unsigned long long todo = __builtin_amdgcn_ballot_w64(slow);
       if (__popcll(todo) > kSerialSlowMax) {      // several undecided pixels: all of them at once, lane-parallel
         if (slow) { best = __builtin_inf(); besti = 0x7fffffff; bound = __builtin_inff(); }   // confirm everything that passes

@@ -39,6 +39,8 @@ struct SegDev {
   const int32_t* mat;
 };
 
+constexpr int32_t kRootBounded = 2;   // FrameDev::div_shared, bit 1
+
 // Per-frame constants, passed to kernels by value.
 struct FrameDev {
   double o[3];                       // ray origin = eye[:3]
@@ -51,7 +53,8 @@ struct FrameDev {
   int64_t img_stride, depth_stride, near_stride;   // elements per output row
   // SRH_SHADING_TORCH extras (torch/renderer.py:82-125)
   int32_t shading, double_sided, use_quartic;
-  int32_t div_shared;                // pixel_ray may share one reciprocal between its three divisions (see there)
+  int32_t div_shared;                // non-zero: pixel_ray may share one reciprocal between its three divisions (see there);
+                                     // bit 1 (kRootBounded, set only with bit 0): |D|^2 is bounded, see sqrt_bounded
   int32_t ortho;                     // orthographic projection (torch semantics only; k_render_ortho)
   int32_t slab_cull;                 // the row pre-cull below is on (in a former padding word)
   const float* latt;                 // (L,3) attenuation or NULL
@@ -124,12 +127,29 @@ __device__ __forceinline__ void pixel_plane_xy(const FrameDev& F, int c, int r, 
   Y = ys * F.half_h;
 }
 
+// sqrt(x) as hipcc expands it for fp64 (v_rsq_f64 and its Newton steps), without the rescaling of x < 2^-767 and without
+// the selects that pass +-0 and +inf through: for a normal, finite, non-zero x >= 2^-767 every one of those is an
+// identity, so the result is sqrt(x) bit for bit (tools/ubench_sqrt.hip: 0 mismatches over the range the host admits).
+__device__ __forceinline__ double sqrt_bounded(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  double g = x * y, h = y * 0.5;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  const double e0 = __builtin_fma(-g, g, x);
+  g = __builtin_fma(e0, h, g);
+  const double e1 = __builtin_fma(-g, g, x);
+  return __builtin_fma(e1, h, g);
+}
+
 // numpy/renderer.py:145-169 for pixel (column c, row r) of the full W x H grid.
 // Returns |D|, the length of the un-normalised direction.
 // GIVEN: the numerator v[i] = (bx[i] X + by[i] Y) + bz[i] Z comes from the caller (`given`; c and r are unused) and only
 // the tail runs -- ray_normalise below.  The tail has one copy, and it stays in this function: with it in a function of
 // its own the per-pixel kernels (exact, fast, ortho, shadow, backward) compile to other text (commuted operands).
-template <bool GIVEN = false>
+// BOUNDED (with GIVEN only): where the host has bounded |D|^2 over the frame (bit 1 of FrameDev::div_shared,
+// camera_to_frame) the square root is sqrt_bounded.  A template flag, so that the per-pixel kernels keep their text.
+template <bool GIVEN = false, bool BOUNDED = false>
 __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, double d[3], const double* given = nullptr) {
   double v[3];
   if constexpr (GIVEN) {
@@ -142,7 +162,14 @@ __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, dou
 #pragma unroll
     for (int i = 0; i < 3; ++i) v[i] = (F.bx[i] * X + F.by[i] * Y) + F.bz[i] * Z;
   }
-  const double len = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  const double len2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+  double len;
+  if constexpr (GIVEN && BOUNDED) {
+    if (F.div_shared & kRootBounded) len = sqrt_bounded(len2);
+    else len = sqrt(len2);
+  } else {
+    len = sqrt(len2);
+  }
   if (F.div_shared) {
     // The three IEEE divisions by |D| as hipcc expands each of them (v_rcp_f64, two Newton steps, quotient, residual
     // correction), with the reciprocal refined ONCE: for operands that need no v_div_scale rescaling -- which the
@@ -169,8 +196,9 @@ __device__ __forceinline__ double pixel_ray(const FrameDev& F, int c, int r, dou
 
 // The tail of pixel_ray alone: d = v / |v| for a numerator v formed elsewhere by the same rounded operations (the binned
 // finish rounds read its three addends from a per-tile table, srh_binned.h: RayTable); returns |v|.
+template <bool BOUNDED = false>
 __device__ __forceinline__ double ray_normalise(const FrameDev& F, const double v[3], double d[3]) {
-  return pixel_ray<true>(F, 0, 0, d, v);
+  return pixel_ray<true, BOUNDED>(F, 0, 0, d, v);
 }
 
 // ---- intersections: return the reference's ray_distance for one (ray, primitive) pair ------------
