@@ -1016,6 +1016,43 @@ int srh_project_coordinates_bwd_view(const SrhProjectCoordsParams* params, const
                                      const float* g_plane, const float* g_coord, float* grad_surfels, double* grad_view,
                                      void* view_workspace, size_t view_workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Nearest points between two point sets: the building block of the reference's hausdorff(u, v)
+ * (diffrend/torch/ops.py:112-125) and of a Chamfer loss, for B views per call.  Per view u (n_u, dims) and v (n_v, dims):
+ *   d2(i, j) = sum over c, ascending, of (u_i[c] - v_j[c])^2     fp64 on the fp32 inputs: nothing overflows or underflows
+ *   idx_u[i] = the j of the smallest d2(i, j),  dist_u[i] = sqrt of it (d2 itself with `squared`);  idx_v, dist_v likewise
+ * The running best starts at +inf with index 0, candidates are visited in ascending index and one wins only when its
+ * d2 is strictly smaller: an exact tie goes to the lowest index, a NaN or +inf d2 never wins, and a query without a
+ * finite candidate gets dist = +inf, idx = 0.  No buffer grows with n_u n_v.  fp64 arithmetic, one fp32 store per
+ * element, no atomic, every element written once, results identical from run to run, and a view's result does not
+ * depend on its batch.  Added without an ABI version change.  Conventions as above: caller-owned device buffers, enqueue
+ * only, no synchronisation or allocation, argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhPointSetParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t n_u, n_v;             /* N, M in 1..2^24 per view */
+  int32_t dims;                 /* D in 1..4 columns per point */
+  int32_t squared;              /* not 0: squared distances, whose gradient is 2 (u - v) */
+} SrhPointSetParams;
+
+/* u (B, N, D), v (B, M, D) fp32.  dist_u (B, N) fp32 / idx_u (B, N) int32 and dist_v / idx_v (B, M) are written.  A side
+ * whose two outputs are both NULL is not computed (not both sides); exactly one NULL of a pair is refused. */
+int srh_nearest_points_fwd(const SrhPointSetParams* params, const float* u, const float* v, float* dist_u,
+                           int32_t* idx_u, float* dist_v, int32_t* idx_v, void* stream);
+
+/* Vector-Jacobian product.  With dir(p, o) = (p - o) / |p - o| (2 (p - o) with `squared`), exactly 0 where the fp64
+ * distance is 0 or not finite:
+ *   grad_u[i] = g_dist_u[i] dir(u_i, v_idx_u[i]) + sum over { j : idx_v[j] = i }, ascending j, of g_dist_v[j] dir(u_i, v_j)
+ * and grad_v likewise.  order_u (B, N) / order_v (B, M) int32: per view a STABLE ASCENDING permutation of idx_u / idx_v
+ * (the caller sorts, as for srh_hard_projection_fwd); an index or order entry outside its range is skipped.  g_dist_*
+ * (B, N) / (B, M) are fp64 -- the sum of several upstream gradients of one distance (hausdorff's symmetric and directed
+ * values) then reaches the kernel unrounded -- and may be NULL = a zero upstream gradient, idx_* / order_* of that side
+ * are then not read; order_* is needed only where the OTHER set's gradient is wanted.  grad_u (B, N, D) / grad_v (B, M, D) fp32 may be
+ * NULL = not wanted (not both), else WRITTEN, every element once; fp64 sums in a fixed order. */
+int srh_nearest_points_bwd(const SrhPointSetParams* params, const float* u, const float* v, const int32_t* idx_u,
+                           const int32_t* idx_v, const int32_t* order_u, const int32_t* order_v, const double* g_dist_u,
+                           const double* g_dist_v, float* grad_u, float* grad_v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

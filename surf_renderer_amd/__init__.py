@@ -23,9 +23,10 @@ _HARD_PROJECTION = ("projection_renderer",)
 _NORMALS = ("estimate_surface_normals_plane_fit_batched", "estimate_surface_normals_plane_fit", "estimate_surface_normals")
 _FRAMES = ("world_to_cam", "world_to_cam_batched", "cam_to_world", "cam_to_world_batched", "project_surfels",
            "project_image_coordinates")
+_POINTSETS = ("nearest_points", "hausdorff", "hausdorff_batched", "NearestPoints")
 
 __all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION,
-           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES]
+           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES, *_POINTSETS]
 
 
 def __getattr__(name):
@@ -53,6 +54,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".normals", __name__), name)
     if name in _FRAMES:
         return getattr(importlib.import_module(".frames", __name__), name)
+    if name in _POINTSETS:
+        return getattr(importlib.import_module(".pointsets", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

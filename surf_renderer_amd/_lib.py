@@ -171,6 +171,14 @@ class SrhProjectCoordsParams(C.Structure):
                 ("height", C.c_int32), ("fovy", C.c_double), ("focal_length", C.c_double)]
 
 
+class SrhPointSetParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_u", C.c_int32), ("n_v", C.c_int32), ("dims", C.c_int32),
+                ("squared", C.c_int32)]
+
+
+POINTSETS_MAX_DIMS, POINTSETS_MAX_POINTS = 4, 1 << 24
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -248,6 +256,8 @@ SIGNATURES = {
     "srh_project_coordinates_fwd": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 6),
     "srh_project_coordinates_bwd": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 6),
     "srh_project_coordinates_bwd_view": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 7 + [_Z, _V]),
+    "srh_nearest_points_fwd": (C.c_int, [_p(SrhPointSetParams)] + [_V] * 7),
+    "srh_nearest_points_bwd": (C.c_int, [_p(SrhPointSetParams)] + [_V] * 11),
 }
 EXPORTS = tuple(SIGNATURES)
 

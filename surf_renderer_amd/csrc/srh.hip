@@ -1,7 +1,8 @@
 // libsrh.so -- MI355X (gfx950) render(scene) backend: the host layer and the C ABI declared in include/srh.h.  The
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
-// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h, srh_normals.h.
+// srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h, srh_normals.h,
+// srh_frames.h, srh_pointsets.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -36,6 +37,7 @@
 #include "srh_hard_projection.h"
 #include "srh_normals.h"
 #include "srh_frames.h"
+#include "srh_pointsets.h"
 
 using namespace srh;
 
@@ -2521,6 +2523,87 @@ int srh_project_coordinates_bwd_view(const SrhProjectCoordsParams* params, const
                                      void* view_workspace, size_t view_workspace_bytes, void* stream) {
   return project_coordinates_bwd(true, params, view, surfels, g_plane, g_coord, grad_surfels, grad_view, view_workspace,
                                  view_workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+// ---- nearest points between two point sets (srh_pointsets.h) -----------------------------------------------------
+namespace {
+
+constexpr int32_t kPsMaxPoints = 1 << 24;
+
+// argument checks (no HIP call) and the device view of a point-set launch.  Every index in srh_pointsets.h is a size_t
+// built from a point < 2^24, a view < 65536 and a column < 4.
+int ps_setup(const SrhPointSetParams* p, const float* u, const float* v, PsDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_n_views(p->n_views)) return rc;
+  if (p->n_u < 1 || p->n_u > kPsMaxPoints) return fail(SRH_E_RANGE, "n_u = %d, expected 1..2^24", p->n_u);
+  if (p->n_v < 1 || p->n_v > kPsMaxPoints) return fail(SRH_E_RANGE, "n_v = %d, expected 1..2^24", p->n_v);
+  if (p->dims < 1 || p->dims > kPsMaxD) return fail(SRH_E_RANGE, "dims = %d, expected 1..%d", p->dims, kPsMaxD);
+  if (int rc = check_not_null({{"u", u}, {"v", v}})) return rc;
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->N = p->n_u; P->M = p->n_v; P->D = p->dims; P->squared = p->squared != 0;
+  return SRH_OK;
+}
+
+// f(std::integral_constant<int, D>) for D = `dims` (validated by ps_setup)
+template <class Fn>
+void with_ps_dims(int dims, Fn f) {
+  switch (dims) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+// the x extent of a grid over the sides `first` .. `first + count - 1` (0 = u, 1 = v), `block` points per workgroup
+unsigned ps_blocks(const PsDev& P, int first, int count, int block) {
+  int n = 0;
+  for (int s = first; s < first + count; ++s) n = std::max(n, s ? P.M : P.N);
+  return (unsigned)((n + block - 1) / block);
+}
+
+}  // namespace
+
+extern "C" {
+
+int srh_nearest_points_fwd(const SrhPointSetParams* params, const float* u, const float* v, float* dist_u,
+                           int32_t* idx_u, float* dist_v, int32_t* idx_v, void* stream) {
+  PsDev P;
+  int rc = ps_setup(params, u, v, &P);
+  if (rc) return rc;
+  if (!dist_u != !idx_u) return fail(SRH_E_NULL, "%s is NULL and its partner is not", dist_u ? "idx_u" : "dist_u");
+  if (!dist_v != !idx_v) return fail(SRH_E_NULL, "%s is NULL and its partner is not", dist_v ? "idx_v" : "dist_v");
+  if (!dist_u && !dist_v) return fail(SRH_E_NULL, "dist_u / idx_u and dist_v / idx_v are all NULL");
+  const int first = dist_u ? 0 : 1, count = (dist_u ? 1 : 0) + (dist_v ? 1 : 0);
+  const dim3 grid(ps_blocks(P, first, count, kPsQueries), P.B, count);
+  with_ps_dims(P.D, [&](auto d) {
+    hipLaunchKernelGGL(k_ps_nearest<decltype(d)::value>, grid, dim3(kPsBlock), 0, (hipStream_t)stream, P, first, u, v,
+                       dist_u, idx_u, dist_v, idx_v);
+  });
+  return launch_status("k_ps_nearest launch");
+}
+
+int srh_nearest_points_bwd(const SrhPointSetParams* params, const float* u, const float* v, const int32_t* idx_u,
+                           const int32_t* idx_v, const int32_t* order_u, const int32_t* order_v, const double* g_dist_u,
+                           const double* g_dist_v, float* grad_u, float* grad_v, void* stream) {
+  PsDev P;
+  int rc = ps_setup(params, u, v, &P);
+  if (rc) return rc;
+  if (!grad_u && !grad_v) return fail(SRH_E_NULL, "grad_u and grad_v are both NULL");
+  // what an upstream gradient needs: its side's indices, and their order where the other side's gradient is wanted
+  if (g_dist_u && !idx_u) return fail(SRH_E_NULL, "idx_u is NULL (g_dist_u is given)");
+  if (g_dist_v && !idx_v) return fail(SRH_E_NULL, "idx_v is NULL (g_dist_v is given)");
+  if (g_dist_u && grad_v && !order_u) return fail(SRH_E_NULL, "order_u is NULL (g_dist_u and grad_v are given)");
+  if (g_dist_v && grad_u && !order_v) return fail(SRH_E_NULL, "order_v is NULL (g_dist_v and grad_u are given)");
+  const int first = grad_u ? 0 : 1, count = (grad_u ? 1 : 0) + (grad_v ? 1 : 0);
+  const dim3 grid(ps_blocks(P, first, count, kPsBwdBlock), P.B, count);
+  with_ps_dims(P.D, [&](auto d) {
+    hipLaunchKernelGGL(k_ps_bwd<decltype(d)::value>, grid, dim3(kPsBwdBlock), 0, (hipStream_t)stream, P, first, u, v,
+                       idx_u, idx_v, order_u, order_v, g_dist_u, g_dist_v, grad_u, grad_v);
+  });
+  return launch_status("k_ps_bwd launch");
 }
 
 }  // extern "C"
