@@ -18,7 +18,8 @@
 // The variances are taken of p - p_0 (p_0 = the view's first pixel), which has the same variance and none of the
 // cancellation of sum p^2 - (sum p)^2 / N for a cloud that is thin against its distance from the origin.
 //
-// The per-pixel arithmetic (reg_pixel_fwd / reg_pixel_bwd) is host-callable so that it can be checked without a GPU.
+// The per-pixel arithmetic (reg_pixel_fwd / reg_finish / reg_pixel_bwd) is host-callable so that it can be checked
+// without a GPU: tests/host/regularizers_host.hip, run by tests/test_regularizers_host_cpu.py.
 #pragma once
 #include "srh_device.h"   // as_constant
 
@@ -46,6 +47,8 @@ struct RegGradsDev {
 };
 
 __host__ __device__ __forceinline__ double reg_sgn(double x) { return (double)(x > 0.0) - (double)(x < 0.0); }
+// torch.relu: a NaN stays a NaN (fmax(x, 0) would return 0)
+__host__ __device__ __forceinline__ double reg_relu(double x) { return x < 0.0 ? 0.0 : x; }
 __host__ __device__ __forceinline__ double reg_dot(const double a[3], const double b[3]) {
   return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
 }
@@ -73,11 +76,11 @@ __host__ __device__ inline void reg_pixel_fwd(const RegDev& R, int b, int i, int
   reg_load3(R.normal, c, n);
   const double grey = reg_grey(R.image, c), dep = R.depth[c];
   const double az = fabs(p[2]);
-  const double lo = R.z_scale * fmax(R.z_min - az, 0.0), hi = R.z_scale * fmax(az - R.z_max, 0.0);
+  const double lo = R.z_scale * reg_relu(R.z_min - az), hi = R.z_scale * reg_relu(az - R.z_max);
   acc[0] = lo * lo + hi * hi;
   const double e = R.n_scale * (sqrt(reg_dot(n, n)) - 1.0);
   acc[1] = e * e;
-  acc[5] = fmax(reg_dot(n, p) * reg_unit_inv(p), 0.0);
+  acc[5] = reg_relu(reg_dot(n, p) * reg_unit_inv(p));
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double q = p[k] - p0[k];
