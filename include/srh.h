@@ -1053,6 +1053,56 @@ int srh_nearest_points_bwd(const SrhPointSetParams* params, const float* u, cons
                            const int32_t* idx_v, const int32_t* order_u, const int32_t* order_v, const double* g_dist_u,
                            const double* g_dist_v, float* grad_u, float* grad_v, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Uniform surface samples of a triangle mesh: the reference's uniform_sample_mesh
+ * (diffrend/utils/sample_generator.py:157-194) for B views per call, with the gradient of the samples with respect to
+ * the vertices.  Per view v (n_vertices, 3) fp32 and f (n_faces, 3) int32; with p0, p1, p2 the vertices of a face:
+ *   n      = c / |c|, c = (p1 - p0) x (p2 - p0), the divisor 1 where |c| = 0
+ *   weight = the reference's double area where it is finite and positive, the indices are inside [0, n_vertices) and,
+ *            with an eye, n . (eye - p0) >= 0; else 0
+ *   cdf    = the running sum of the weights over the view's total, in an order that depends on n_faces alone
+ *   face   = the number of faces whose cdf is <= r0;  q = sqrt(s), bary = (1 - q, (1 - t) q, t q)
+ *   pos    = (b0 p0 + b1 p1) + b2 p2,  normal = n of the face
+ * for the sample's three uniforms (r0, s, t) in [0, 1).  A zero-weight face is never chosen.  A view without a positive
+ * weight gets face = -1 and NaN pos, normal and bary, and a zero gradient.  fp64 arithmetic on the fp32 vertices, one
+ * fp32 store per element, no atomic, every element written once, results identical from run to run, and a view's result
+ * does not depend on its batch.  Added without an ABI version change.  Conventions as above: caller-owned device
+ * buffers, enqueue only, no synchronisation or allocation, argument checks before any HIP call.  The caller guarantees
+ * 0 <= f < n_vertices and uniforms in [0, 1); a face with an index outside the range has weight 0 and is not read.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SrhMeshSampleParams {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t n_vertices;           /* V in 1..2^24 per view */
+  int32_t n_faces;              /* F in 1..2^24 */
+  int32_t n_samples;            /* S in 1..2^24 per view */
+  int32_t faces_per_view;       /* not 0: f is (B, F, 3), else (F, 3) shared by the views */
+  int32_t eye_per_view;         /* not 0: eye is (B, 3), else (3) shared by the views */
+} SrhMeshSampleParams;
+
+#define SRH_MESH_WS_FWD 0               /* scratch of srh_mesh_sample_fwd: the cdf, B F fp64, and the views' totals */
+#define SRH_MESH_WS_BWD 1               /* scratch of srh_mesh_sample_bwd: the corner gradients, 9 B F fp64 */
+
+/* Bytes of a workspace; 0 for parameters out of range.  Nothing in either outlives its call. */
+size_t srh_mesh_sample_workspace_bytes(const SrhMeshSampleParams* params, int32_t which);
+
+/* eye (3) or (B, 3) fp64, NULL = no backface cull; uniforms (B, S, 3) fp64.  pos, normal, bary (B, S, 3) fp32 and face
+ * (B, S) int32 are written. */
+int srh_mesh_sample_fwd(const SrhMeshSampleParams* params, const float* v, const int32_t* f, const double* eye,
+                        const double* uniforms, void* workspace, size_t workspace_bytes, float* pos, float* normal,
+                        int32_t* face, float* bary, void* stream);
+
+/* Vector-Jacobian product with face and bary held fixed.  face as the forward wrote it; sample_order (B, S) int32: per
+ * view a STABLE ASCENDING permutation of face; corner_order (3 F) int32, or (B, 3 F) with faces_per_view: a stable
+ * ascending permutation of the flattened f (the caller sorts, as for srh_hard_projection_fwd); an order entry outside
+ * its range is skipped.  g_pos, g_normal (B, S, 3) fp32, either NULL = a zero upstream gradient whose terms are skipped
+ * (not both).  The normal's gradient goes through c / |c| and is exactly 0 where |c| is 0 or not finite.  grad_v
+ * (B, V, 3) fp32 is WRITTEN, every element once, exactly 0 for a vertex no face references; fp64 sums in ascending
+ * sample index per face and ascending corner index 3 face + c per vertex. */
+int srh_mesh_sample_bwd(const SrhMeshSampleParams* params, const float* v, const int32_t* f, const double* uniforms,
+                        const int32_t* face, const int32_t* sample_order, const int32_t* corner_order,
+                        const float* g_pos, const float* g_normal, void* workspace, size_t workspace_bytes,
+                        float* grad_v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,9 +24,11 @@ _NORMALS = ("estimate_surface_normals_plane_fit_batched", "estimate_surface_norm
 _FRAMES = ("world_to_cam", "world_to_cam_batched", "cam_to_world", "cam_to_world_batched", "project_surfels",
            "project_image_coordinates")
 _POINTSETS = ("nearest_points", "hausdorff", "hausdorff_batched", "NearestPoints")
+_MESH_SAMPLING = ("uniform_sample_mesh", "sample_mesh_batched", "mesh_topology", "draw_uniforms", "MeshSamples",
+                  "MeshTopology")
 
 __all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION,
-           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES, *_POINTSETS]
+           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES, *_POINTSETS, *_MESH_SAMPLING]
 
 
 def __getattr__(name):
@@ -56,6 +58,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".frames", __name__), name)
     if name in _POINTSETS:
         return getattr(importlib.import_module(".pointsets", __name__), name)
+    if name in _MESH_SAMPLING:
+        return getattr(importlib.import_module(".mesh_sampling", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

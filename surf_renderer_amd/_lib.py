@@ -179,6 +179,15 @@ class SrhPointSetParams(C.Structure):
 POINTSETS_MAX_DIMS, POINTSETS_MAX_POINTS = 4, 1 << 24
 
 
+class SrhMeshSampleParams(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_vertices", C.c_int32), ("n_faces", C.c_int32), ("n_samples", C.c_int32),
+                ("faces_per_view", C.c_int32), ("eye_per_view", C.c_int32)]
+
+
+MESH_MAX = 1 << 24                      # vertices, faces and samples per view
+MESH_WS_FWD, MESH_WS_BWD = 0, 1
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -258,6 +267,9 @@ SIGNATURES = {
     "srh_project_coordinates_bwd_view": (C.c_int, [_p(SrhProjectCoordsParams)] + [_V] * 7 + [_Z, _V]),
     "srh_nearest_points_fwd": (C.c_int, [_p(SrhPointSetParams)] + [_V] * 7),
     "srh_nearest_points_bwd": (C.c_int, [_p(SrhPointSetParams)] + [_V] * 11),
+    "srh_mesh_sample_workspace_bytes": (_Z, [_p(SrhMeshSampleParams), _I]),
+    "srh_mesh_sample_fwd": (C.c_int, [_p(SrhMeshSampleParams)] + [_V] * 5 + [_Z] + [_V] * 5),
+    "srh_mesh_sample_bwd": (C.c_int, [_p(SrhMeshSampleParams)] + [_V] * 9 + [_Z] + [_V] * 2),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -2,7 +2,7 @@
 // kernels live in the headers: srh_prep.h (per-frame records and binning), srh_allpairs.h (rays, exact, ortho, fast),
 // srh_binned.h (the tile-binned render kernel), srh_backward.h, srh_shadow.h, srh_splat.h, srh_regularizers.h, srh_projection.h,
 // srh_reverse_projection.h, srh_dense_projection.h, srh_splat_ndc.h, srh_surfels.h, srh_hard_projection.h, srh_normals.h,
-// srh_frames.h, srh_pointsets.h.
+// srh_frames.h, srh_pointsets.h, srh_mesh.h.
 //
 // Launch structure of one frame (all on the caller's stream, no host sync):
 //   k_prep        one thread per primitive: per-frame records (unit normal, plane offset, eye-relative
@@ -38,6 +38,7 @@
 #include "srh_normals.h"
 #include "srh_frames.h"
 #include "srh_pointsets.h"
+#include "srh_mesh.h"
 
 using namespace srh;
 
@@ -2604,6 +2605,92 @@ int srh_nearest_points_bwd(const SrhPointSetParams* params, const float* u, cons
                        idx_u, idx_v, order_u, order_v, g_dist_u, g_dist_v, grad_u, grad_v);
   });
   return launch_status("k_ps_bwd launch");
+}
+
+}  // extern "C"
+
+// ---- uniform surface samples of a mesh (srh_mesh.h) --------------------------------------------------------------
+namespace {
+
+constexpr int32_t kMeshMax = 1 << 24;
+
+// argument checks (no HIP call) and the device view of a mesh-sampling launch.  Every index in srh_mesh.h is an int32
+// below 3 * 2^24 (a corner), or a size_t built from it, a view < 65536 and a column < 9.
+int mesh_setup(const SrhMeshSampleParams* p, MeshDev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_n_views(p->n_views)) return rc;
+  if (p->n_vertices < 1 || p->n_vertices > kMeshMax)
+    return fail(SRH_E_RANGE, "n_vertices = %d, expected 1..2^24", p->n_vertices);
+  if (p->n_faces < 1 || p->n_faces > kMeshMax) return fail(SRH_E_RANGE, "n_faces = %d, expected 1..2^24", p->n_faces);
+  if (p->n_samples < 1 || p->n_samples > kMeshMax)
+    return fail(SRH_E_RANGE, "n_samples = %d, expected 1..2^24", p->n_samples);
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->V = p->n_vertices; P->F = p->n_faces; P->S = p->n_samples;
+  P->f_per_view = p->faces_per_view != 0; P->eye_per_view = p->eye_per_view != 0;
+  return SRH_OK;
+}
+
+size_t mesh_cdf_bytes(const MeshDev& P) { return align_up((size_t)P.B * P.F * sizeof(double)); }
+
+dim3 mesh_grid(int n, const MeshDev& P) { return dim3((unsigned)((n + kMeshBlock - 1) / kMeshBlock), P.B); }
+
+}  // namespace
+
+extern "C" {
+
+size_t srh_mesh_sample_workspace_bytes(const SrhMeshSampleParams* params, int32_t which) {
+  MeshDev P;
+  if (mesh_setup(params, &P)) return 0;
+  switch (which) {
+    case SRH_MESH_WS_FWD: return mesh_cdf_bytes(P) + align_up((size_t)P.B * sizeof(double));
+    case SRH_MESH_WS_BWD: return align_up((size_t)P.B * P.F * 9 * sizeof(double));
+    default: fail(SRH_E_RANGE, "which = %d, expected SRH_MESH_WS_FWD or SRH_MESH_WS_BWD", which); return 0;
+  }
+}
+
+int srh_mesh_sample_fwd(const SrhMeshSampleParams* params, const float* v, const int32_t* f, const double* eye,
+                        const double* uniforms, void* workspace, size_t workspace_bytes, float* pos, float* normal,
+                        int32_t* face, float* bary, void* stream) {
+  MeshDev P;
+  int rc = mesh_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"v", v}, {"f", f}, {"uniforms", uniforms}, {"pos", pos}, {"normal", normal},
+                            {"face", face}, {"bary", bary}})))
+    return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes,
+                          srh_mesh_sample_workspace_bytes(params, SRH_MESH_WS_FWD))))
+    return rc;
+  double* cdf = (double*)workspace;
+  double* total = (double*)((char*)workspace + mesh_cdf_bytes(P));
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mesh_faces, mesh_grid(P.F, P), dim3(kMeshBlock), 0, s, P, v, f, eye, cdf);
+  hipLaunchKernelGGL(k_mesh_scan, dim3(P.B), dim3(kMeshScanBlock), 0, s, P, cdf, total);
+  hipLaunchKernelGGL(k_mesh_sample, mesh_grid(P.S, P), dim3(kMeshBlock), 0, s, P, v, f, uniforms, cdf, total, pos,
+                     normal, face, bary);
+  return launch_status("mesh sampling forward launch");
+}
+
+int srh_mesh_sample_bwd(const SrhMeshSampleParams* params, const float* v, const int32_t* f, const double* uniforms,
+                        const int32_t* face, const int32_t* sample_order, const int32_t* corner_order,
+                        const float* g_pos, const float* g_normal, void* workspace, size_t workspace_bytes,
+                        float* grad_v, void* stream) {
+  MeshDev P;
+  int rc = mesh_setup(params, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"v", v}, {"f", f}, {"uniforms", uniforms}, {"face", face}, {"sample_order", sample_order},
+                            {"corner_order", corner_order}, {"grad_v", grad_v}})))
+    return rc;
+  if (!g_pos && !g_normal) return fail(SRH_E_NULL, "g_pos and g_normal are both NULL");
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes,
+                          srh_mesh_sample_workspace_bytes(params, SRH_MESH_WS_BWD))))
+    return rc;
+  double* corner = (double*)workspace;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_mesh_bwd_faces, mesh_grid(P.F, P), dim3(kMeshBlock), 0, s, P, v, f, uniforms, face,
+                     sample_order, g_pos, g_normal, corner);
+  hipLaunchKernelGGL(k_mesh_bwd_vertices, mesh_grid(P.V, P), dim3(kMeshBlock), 0, s, P, f, corner_order, corner,
+                     grad_v);
+  return launch_status("mesh sampling backward launch");
 }
 
 }  // extern "C"
