@@ -7,6 +7,8 @@ have fixtures under tests/golden/mesh_sampling; their conditions (tests/test_mes
   - with a camera |n . cam_dir| >= 1e-6 on every face, so the cull is the oracle's;
   - no face is a sliver: sum |cross-product terms| / |c| <= 2^10, so that the normal's bound is its store's half ulp;
   - every case with more than one face hits at least two faces in every view.
+r0 ON the CDF -- its values, the doubles around them, the tie rule and zero-weight runs over a lane, a wave and a tile
+-- is what this gap leaves out: tests/mesh_scan_cases.py and tests/test_hip_mesh_sampling_scan.py cover it.
 
 Every case has three views with different vertices.  The shapes sit at the seams of srh_mesh.h: a wave's width in
 faces (63, 64, 65), a wave's share of a scan tile (256 + 1), the tile (1024 + 1), several tiles (the bunny), and sample
