@@ -454,11 +454,15 @@ int setup_frame(const SrhCamera* camera, const SrhObjects* objects, const SrhLig
 }
 
 // Tile-binning fields of a frame whose primitive records live in `workspace` (layout L).
-void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
+// Fails the call where the counter region is not 8-byte aligned: bin_place claims two adjacent bin counters with one
+// 64-bit atomic (srh_binned.h).
+int setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
+  if (((uintptr_t)workspace + L.counters) % 8 != 0)
+    return fail(SRH_E_WORKSPACE, "workspace: the bin counters at %p + %zu are not 8-byte aligned", workspace, L.counters);
   F.tiles_x = L.tiles_x;
   F.tiles_y = (F.row1 - F.row0 + kTile - 1) / kTile;
   F.ntiles = F.tiles_x * F.tiles_y;
-  F.ntiles_pad = (F.ntiles + 3) / 4 * 4;
+  F.ntiles_pad = (F.ntiles + 3) / 4 * 4;                         // a multiple of 4: every batch's counters start on 16 bytes
   F.nbins = F.nseg * F.ntiles_pad;
   F.bin_cap = (int32_t)std::min<size_t>(L.entries_words / (size_t)F.nbins, 1u << 20);
   char* ws = (char*)workspace;
@@ -482,6 +486,7 @@ void setup_binning(FrameDev& F, const WsLayout& L, void* workspace) {
       F.slab_cull = std::isfinite(F.slab_na) && std::isfinite(F.slab_ng) ? 1 : 0;
     }
   }
+  return SRH_OK;
 }
 
 }  // namespace
@@ -542,7 +547,7 @@ int srh_render_fwd(const SrhCamera* camera, const SrhObjects* objects, const Srh
   if ((stages & (SRH_STAGE_BIN | SRH_STAGE_RENDER)) != (SRH_STAGE_BIN | SRH_STAGE_RENDER) && mode != SRH_MODE_BINNED)
     return fail(SRH_E_TYPE, "SrhParams.stages splits binned frames only");
   const bool run_binning = (stages & SRH_STAGE_BIN) != 0, run_render = (stages & SRH_STAGE_RENDER) != 0;
-  if (mode == SRH_MODE_BINNED) setup_binning(F, L, workspace);
+  if (mode == SRH_MODE_BINNED && (rc = setup_binning(F, L, workspace))) return rc;
   F.keep_bins = (stages & SRH_STAGE_KEEP_BINS) ? 1 : 0;
   if (mode == SRH_MODE_BINNED) F.self = (FrameDev*)((char*)workspace + L.frame);
   const bool counters_clean = params->counters_clean != 0;
@@ -795,7 +800,7 @@ static int render_views(const char* who, int32_t n_views, const SrhCamera* camer
   for (int v = 0; v < n_views; ++v) {
     if (int rc = call.build_view(v, &stage[v], &L)) return rc;
     set_aux(v, stage[v]);
-    setup_binning(stage[v], L, call.slice(v));
+    if (int rc = setup_binning(stage[v], L, call.slice(v))) return rc;
   }
   const FrameDev* Fs = (const FrameDev*)ws;
   hipError_t e = hipMemcpyAsync(ws, stage, (size_t)n_views * sizeof(FrameDev), hipMemcpyHostToDevice, st);
@@ -909,7 +914,8 @@ int srh_shadow_shade(const SrhCamera* camera, const SrhObjects* objects, const S
     T.seg[s].rec64 = (const double*)(slice0 + SL.slice.off64[s]);
     T.seg[s].rec32 = (const float*)(slice0 + SL.slice.off32[s]);
   }
-  setup_binning(T, SL.slice, slice0);
+  // (light l's slice starts l * SL.slice.total further on: a multiple of 256, so its counters keep the alignment)
+  if ((rc = setup_binning(T, SL.slice, slice0))) return rc;
   T.bin_pad = 1.0;              // shadow rays cross the image plane between pixel centres
   T.near_ball = 0.1001;         // occluders up to 0.1 behind the light count (torch/renderer.py:299-306)
   const unsigned V = (unsigned)F.nlights;
@@ -1195,7 +1201,7 @@ int srh_bin_counters(const SrhObjects* objects, int32_t width, int32_t height, i
   FrameDev F;
   memset(&F, 0, sizeof(F));
   F.W = width; F.H = height; F.row0 = row0; F.row1 = row1; F.nseg = objects->n_segments;
-  setup_binning(F, L, nullptr);                        // pointers relative to NULL: only the tile arithmetic is used
+  (void)setup_binning(F, L, nullptr);                        // pointers relative to NULL: only the tile arithmetic is used
   *offset_bytes = L.counters;
   *tiles_x = F.tiles_x; *tiles_y = F.tiles_y; *ntiles_pad = F.ntiles_pad; *bin_cap = F.bin_cap;
   return SRH_OK;

@@ -72,7 +72,10 @@ constexpr int kBinBlock = 64;
 // No count kernel, and nobody reads the reject record back from another XCD.  Of the (at most 64) tiles of the box
 // keep those the reject shape really reaches and that are not provably behind the eye; bit k of the primitive's tile
 // mask = k-th tile of the box, row-major.
-constexpr int kClaims = 4;
+// Claims a lane has in flight (pass 2).  The wave waits for its busiest lane: at the flagship workload 97 % of the waves
+// have no lane with more than 6 pair words, 99 % none with more than 8 (profiles/prep_claims_premise.json) -- one round
+// trip for nearly every wave; with 4 it was two (2.34 rounds on average with a claim per tile, 2.01 with pairs).
+constexpr int kClaims = 6;
 __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, int first, const float* rec32, int gidx,
                                           int tx0, int ty0, int tx1, int ty1, uint32_t set) {
   uint32_t* count = F.counters + kCounterPad + seg * F.ntiles_pad;
@@ -139,12 +142,29 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
       if (T.reaches(pc0, pc1, pr0, pr1)) mask |= 1ull << k;
     }
   // pass 2: the slot claimed in a bin's counter is the entry's place in the bin's fixed-capacity list.  kClaims claims
-  // at a time, so that their round trips overlap instead of adding up (a thread owns ~6 bins on average).
+  // at a time, so that their round trips overlap instead of adding up.
+  // Paired claims: the counters of tiles t and t ^ 1 are adjacent words, and ONE returning 64-bit add on the aligned
+  // pair (low half: the even tile) claims a slot in each -- +1 in the half of every tile of the pair that this
+  // primitive keeps, +0 in the other, the two old halves are the two slots.  The scattered atomics are what the
+  // kernel's time goes to, and a row's run of adjacent tiles needs a quarter fewer of them ("Paired
+  // claims").  The partner of bit k (tile t) is bit k + 1 for an even t and was bit k - 1 for an odd one (taken with its
+  // even tile already, if kept), and only where that bit lies in the same box row: a partner outside the box or in
+  // another tile row (an odd tiles_x makes words straddle rows) gets +0 here and its own claim in its own row.
+  // What makes the 64-bit view legal:
+  //   - `count` is 8-byte aligned: the workspace's counter region is (checked on the host, setup_binning), kCounterPad is
+  //     even and ntiles_pad a multiple of 4 (asserted below and where the host sets it);
+  //   - the word of an odd ntiles' last tile ends at ntiles < ntiles_pad, inside the batch's counters;
+  //   - a half never carries into the other: a primitive claims a tile at most once, so a counter that starts the
+  //     frame at zero stays below the primitive count, far below 2^32.
+  // Everybody else reads and zeroes the counters as 32-bit words, as before.
+  static_assert(kCounterPad % 2 == 0, "the bin counters start on an 8-byte boundary of the counter region");
   const uint32_t cap = (uint32_t)F.bin_cap;
   uint32_t* slots = F.entries + (size_t)seg * F.ntiles_pad * cap;
+  unsigned long long* count2 = reinterpret_cast<unsigned long long*>(count);
   int over = 0;
   while (mask) {
-    uint32_t tile[kClaims], slot[kClaims];
+    uint32_t tile[kClaims], pairs = 0;
+    unsigned long long old[kClaims];
 #pragma unroll
     for (int j = 0; j < kClaims; ++j) {
       tile[j] = 0xffffffffu;
@@ -152,15 +172,25 @@ __device__ __forceinline__ void bin_place(const FrameDev& F, int seg, int type, 
         const uint32_t k = (uint32_t)__builtin_ctzll(mask);
         mask &= mask - 1;
         const uint32_t dy = (k * inv_nx) >> 16, dx = k - dy * (uint32_t)nx;
-        tile[j] = (uint32_t)(ty0 + (int)dy) * (uint32_t)F.tiles_x + (uint32_t)(tx0 + (int)dx);
-        slot[j] = atomicAdd(&count[tile[j]], 1u);
+        const uint32_t t = (uint32_t)(ty0 + (int)dy) * (uint32_t)F.tiles_x + (uint32_t)(tx0 + (int)dx);
+        // bit k is cleared: bit 1 of mask >> k is bit k + 1 (k = 63 is a box's last column: the test stops before it)
+        const bool pair = !(t & 1u) && dx + 1u < (uint32_t)nx && ((mask >> k) & 2u);
+        if (pair) { mask &= mask - 1; pairs |= 1u << j; }
+        tile[j] = t;
+        old[j] = atomicAdd(&count2[t >> 1], (t & 1u) ? (1ull << 32) : (pair ? (1ull << 32) | 1ull : 1ull));
       }
     }
 #pragma unroll
     for (int j = 0; j < kClaims; ++j)
       if (tile[j] != 0xffffffffu) {
-        if (slot[j] < cap) slots[(size_t)tile[j] * cap + slot[j]] = (uint32_t)gidx;
+        const uint32_t lo = (uint32_t)old[j], hi = (uint32_t)(old[j] >> 32);
+        const uint32_t slot = (tile[j] & 1u) ? hi : lo;
+        if (slot < cap) slots[(size_t)tile[j] * cap + slot] = (uint32_t)gidx;
         else over = 1;
+        if (pairs & (1u << j)) {                                  // the odd partner's slot is the high half
+          if (hi < cap) slots[(size_t)(tile[j] + 1u) * cap + hi] = (uint32_t)gidx;
+          else over = 1;
+        }
       }
   }
   // a full bin: the primitive joins the batch's `large` list (tested by every tile) -- once, whatever the number of

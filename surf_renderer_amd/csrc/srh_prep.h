@@ -199,6 +199,8 @@ __device__ __forceinline__ void prep_body(const FrameDev& F, int s, double* rec6
 // the disc instantiation once the fp64 trust terms of srh_reject.h went in, three waves per SIMD -- and the prep waves of
 // the frames in flight then hold their slots longer beside the render waves: config 5 went from 0.078 to 0.093 ms per
 // frame on that alone.  At 128 the compiler needs no spills.
+// The prep waves run at the render waves' issue priority.  Raised (s_setprio 1 or 3 as the kernels' first instruction) they
+// are 13 us shorter beside the render waves, which get 3-4 us longer each: the steady state loses 1 % (DESIGN Part II).
 constexpr int kPrepWaves = 4;
 template <int TYPE>
 __global__ __launch_bounds__(kBinBlock) __attribute__((amdgpu_waves_per_eu(kPrepWaves))) void k_prep(FrameDev F, int s, double* rec64, float* rec32) {

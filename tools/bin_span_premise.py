@@ -5,7 +5,10 @@ records and their tile boxes (tests/bin_spans_model.py).  No GPU.
 Per wave of 64 consecutive discs: the largest box in tiles (iterations of the parent's per-tile loop), the
 largest box in tile rows (iterations of the row loop), and the discs whose box has its worst corner behind the eye (the
 only ones whose rows take the `behind` test).  Discs without an ellipse record of their own (the sphere stand-in) are
-not modelled and count as "no box".  profiles/bin_spans_pmc.json quotes the output."""
+not modelled and count as "no box".  profiles/bin_spans_pmc.json quotes the output.
+
+--claims: pass 2 instead -- the returning atomics per disc with one claim per tile and with one per aligned pair of
+tiles, and the round trips per wave (see claims(); profiles/prep_claims_premise.json)."""
 import json
 import os
 import sys
@@ -69,5 +72,59 @@ def main():
     }, indent=1))
 
 
+def claims():
+    """Pass 2 at config 5, all discs: returning atomics per disc with one claim per tile and with one per aligned pair
+    of tiles (tests/bin_pairs_model.py), the per-wave maxima of both (the busiest lane sets a wave's pace), and the mean
+    round trips per wave with 4, 6 and 8 claims in flight.  profiles/prep_claims_premise.json is this output."""
+    import bin_pairs_model as P
+    W = H = 2048
+    scene = synthetic.disk_cloud_scene(100000, W, H)
+    cam = scene["camera"]
+    basis = pixel_basis(cam)[:4]
+    disc = scene["objects"]["disk"]
+    grid = M.Grid(W, (0, H), 0.0)
+    n = len(disc["radius"])
+    tiles, words = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    no_record = 0
+    for i in range(n):
+        try:
+            form, est, (hc, hr) = M.disc_records(basis, W, H, disc["pos"][i:i + 1], disc["normal"][i:i + 1], disc["radius"][i:i + 1])
+        except AssertionError:
+            no_record += 1
+            continue
+        box = M.tile_box(form, grid, hc, hr)
+        if not box[4][0]:
+            continue
+        # only the box's tile rows: a frame of 128 x 128 tiles per disc is what makes the vectorised form slow
+        ty0, ty1 = int(box[2][0]), int(box[3][0])
+        sub = M.Grid(W, (ty0 * M.TILE, min((ty1 + 1) * M.TILE, H)), 0.0)
+        sbox = (box[0], box[1], box[2] - ty0, box[3] - ty0, box[4])
+        ta, tb, usable = M.span_runs(form, sub, sbox)
+        if not usable[0]:
+            no_record += 1
+            continue
+        if cam.get("near", 0.0) > 0.0:
+            ta, tb, _, _ = M.behind_runs(est, sub, ta, tb, sbox)
+        # tile ids of the whole frame: row ty0 + k of the sub-grid
+        c, w = P.pair_words(grid.tiles_x, [(ty0 + k, range(int(a), int(b) + 1)) for k, (a, b) in enumerate(zip(ta[0], tb[0]))])
+        tiles[i], words[i] = c, w
+    wt, ww = per_wave_max(tiles), per_wave_max(words)
+    print(json.dumps({
+        "discs": n,
+        "not_modelled": no_record,
+        "tile_claims_total": int(tiles.sum()),
+        "pair_words_total": int(words.sum()),
+        "pair_words_over_tile_claims": float(words.sum() / tiles.sum()),
+        "mean_per_disc": {"tile_claims": float(tiles.mean()), "pair_words": float(words.mean())},
+        "max_per_disc": {"tile_claims": int(tiles.max()), "pair_words": int(words.max())},
+        "waves": len(wt),
+        "mean_per_wave_max": {"tile_claims": float(wt.mean()), "pair_words": float(ww.mean())},
+        "share_of_waves_whose_max_is_at_most": {
+            str(c): {"tile_claims": float((wt <= c).mean()), "pair_words": float((ww <= c).mean())} for c in (4, 6, 8)},
+        "mean_rounds_per_wave_in_flight": {
+            str(c): {"tile_claims": P.rounds(tiles, c, WAVE), "pair_words": P.rounds(words, c, WAVE)} for c in (4, 6, 8)},
+    }, indent=1))
+
+
 if __name__ == "__main__":
-    main()
+    claims() if "--claims" in sys.argv[1:] else main()
