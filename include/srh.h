@@ -1103,6 +1103,59 @@ int srh_mesh_sample_bwd(const SrhMeshSampleParams* params, const float* v, const
                         const float* g_pos, const float* g_normal, void* workspace, size_t workspace_bytes,
                         float* grad_v, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * SH9 environment lighting: the reference's radiance_SH9 and irradiance (diffrend/numpy/sph.py:46-138) for B views per
+ * call, with their gradients.
+ *   Projection.  envmap (B, H, W, C) fp32 -> L (B, C, 9) fp32.  Pixel (i, j), the reference's swapped scales kept:
+ *     v = (W/2 - i) / (W/2), u = (j - H/2) / (H/2), r = sqrt(u^2 + v^2), theta = pi r, phi = atan2(v, u)
+ *     domega = (2 pi / W) (2 pi / H) sin(pi theta) / (pi theta), the quotient 1 at theta = 0
+ *     L[c][k] = sum over the pixels with r <= 1 of (envmap[i][j][c] Y_k) domega, Y_k the nine real harmonics of
+ *     (cos phi sin theta, sin phi sin theta, cos theta) in the order (0,0) (1,-1) (1,0) (1,1) (2,-2) (2,-1) (2,0) (2,1) (2,2)
+ *   A pixel with r > 1 is not read: whatever it holds reaches no coefficient, and its gradient is exactly 0.
+ *   Irradiance.  M (B, 4, 4, C) fp32, or (4, 4, C) shared by the views, and normal (B, N, 3) fp32 -> E (B, N, C) fp32:
+ *     E_c = [n, 1]^T M_c [n, 1] for any M, symmetric or not; n is not normalised.
+ * fp64 arithmetic on the fp32 inputs, no atomic, every element written once, sums in an order that depends on H W or N
+ * alone: results are identical from run to run, and a view's result does not depend on its batch.  Added without an ABI
+ * version change.  Conventions as above: caller-owned device buffers, enqueue only, no synchronisation or allocation,
+ * argument checks before any HIP call.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SRH_SH9_MAX_CHANNELS 4
+
+typedef struct SrhSh9Params {
+  int32_t n_views;              /* B in 1..65535 */
+  int32_t height, width;        /* the probe's H, W, H W in 1..2^24: read by the projection's entry points only */
+  int32_t n_points;             /* N in 1..2^24 normals per view: read by the irradiance's entry points only */
+  int32_t channels;             /* C in 1..4 */
+  int32_t m_per_view;           /* not 0: M is (B, 4, 4, C), else (4, 4, C) shared by the views */
+} SrhSh9Params;
+
+#define SRH_SH9_WS_PROJECT 0            /* scratch of srh_sh9_project_fwd: 9 C fp64 per workgroup of 256 pixels */
+#define SRH_SH9_WS_IRRADIANCE_BWD 1     /* scratch of srh_sh9_irradiance_bwd with grad_M: 10 C fp64 per workgroup and view */
+
+/* Bytes of a workspace; 0 for parameters out of range.  Nothing in either outlives its call. */
+size_t srh_sh9_workspace_bytes(const SrhSh9Params* params, int32_t which);
+
+/* L (B, C, 9) fp32 is written. */
+int srh_sh9_project_fwd(const SrhSh9Params* params, const float* envmap, void* workspace, size_t workspace_bytes,
+                        float* L, void* stream);
+
+/* g_L (B, C, 9) fp32.  grad_envmap (B, H, W, C) fp32 is WRITTEN, every element once: domega sum_k Y_k g_L[c][k] inside
+ * the disc, exactly 0 outside. */
+int srh_sh9_project_bwd(const SrhSh9Params* params, const float* g_L, float* grad_envmap, void* stream);
+
+/* E (B, N, C) fp32 is written. */
+int srh_sh9_irradiance_fwd(const SrhSh9Params* params, const float* M, const float* normal, float* E, void* stream);
+
+/* Vector-Jacobian product.  g_E (B, N, C) fp32.  grad_normal (B, N, 3) fp32 and grad_M may be NULL = not wanted (not
+ * both), else WRITTEN, every element once:
+ *   grad_normal = sum_c g_E[c] ((M33_c + M33_c^T) n + M_c[:3, 3] + M_c[3, :3])
+ *   grad_M[r][s][c] = sum over the normals of g_E[c] h_r h_s, h = [n, 1]        fp64: (B, 4, 4, C), or (4, 4, C) for a shared
+ *                     M, the views' sums added in ascending view order
+ * grad_M is fp64 so that a chain behind it (the nine-to-sixteen map from L) sums unrounded values.  The workspace is
+ * needed with grad_M only; without it the kernel variant without the reduction runs. */
+int srh_sh9_irradiance_bwd(const SrhSh9Params* params, const float* M, const float* normal, const float* g_E,
+                           float* grad_normal, double* grad_M, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

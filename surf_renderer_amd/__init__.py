@@ -26,9 +26,11 @@ _FRAMES = ("world_to_cam", "world_to_cam_batched", "cam_to_world", "cam_to_world
 _POINTSETS = ("nearest_points", "hausdorff", "hausdorff_batched", "NearestPoints")
 _MESH_SAMPLING = ("uniform_sample_mesh", "sample_mesh_batched", "mesh_topology", "draw_uniforms", "MeshSamples",
                   "MeshTopology")
+_SH_LIGHTING = ("radiance_SH9", "radiance_SH9_batched", "RealSH9_ZonalMatrix", "irradiance", "irradiance_batched",
+                "irradiance_polar", "irrad_Z", "reconstruct_SH9", "RealSH9_cart", "RealSH9_polar", "load_lightprobe")
 
 __all__ = [*_RENDERER, *_SCENE, *_SPLATS, *_SPLATS_NDC, *_REGULARIZERS, *_PROJECTION, *_REVERSE_PROJECTION, *_DENSE_PROJECTION,
-           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES, *_POINTSETS, *_MESH_SAMPLING]
+           *_SURFELS, *_HARD_PROJECTION, *_NORMALS, *_FRAMES, *_POINTSETS, *_MESH_SAMPLING, *_SH_LIGHTING]
 
 
 def __getattr__(name):
@@ -60,6 +62,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".pointsets", __name__), name)
     if name in _MESH_SAMPLING:
         return getattr(importlib.import_module(".mesh_sampling", __name__), name)
+    if name in _SH_LIGHTING:
+        return getattr(importlib.import_module(".sh_lighting", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

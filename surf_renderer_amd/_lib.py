@@ -188,6 +188,15 @@ MESH_MAX = 1 << 24                      # vertices, faces and samples per view
 MESH_WS_FWD, MESH_WS_BWD = 0, 1
 
 
+class SrhSh9Params(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("n_points", C.c_int32),
+                ("channels", C.c_int32), ("m_per_view", C.c_int32)]
+
+
+SH9_MAX_CHANNELS, SH9_MAX = 4, 1 << 24  # channels; pixels of a probe and normals per view (MESH_MAX's value)
+SH9_WS_PROJECT, SH9_WS_IRRADIANCE_BWD = 0, 1
+
+
 def _p(struct):
     return C.POINTER(struct)
 
@@ -270,6 +279,11 @@ SIGNATURES = {
     "srh_mesh_sample_workspace_bytes": (_Z, [_p(SrhMeshSampleParams), _I]),
     "srh_mesh_sample_fwd": (C.c_int, [_p(SrhMeshSampleParams)] + [_V] * 5 + [_Z] + [_V] * 5),
     "srh_mesh_sample_bwd": (C.c_int, [_p(SrhMeshSampleParams)] + [_V] * 9 + [_Z] + [_V] * 2),
+    "srh_sh9_workspace_bytes": (_Z, [_p(SrhSh9Params), _I]),
+    "srh_sh9_project_fwd": (C.c_int, [_p(SrhSh9Params), _V, _V, _Z, _V, _V]),
+    "srh_sh9_project_bwd": (C.c_int, [_p(SrhSh9Params)] + [_V] * 3),
+    "srh_sh9_irradiance_fwd": (C.c_int, [_p(SrhSh9Params)] + [_V] * 4),
+    "srh_sh9_irradiance_bwd": (C.c_int, [_p(SrhSh9Params)] + [_V] * 6 + [_Z, _V]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -39,6 +39,7 @@
 #include "srh_frames.h"
 #include "srh_pointsets.h"
 #include "srh_mesh.h"
+#include "srh_sh9.h"
 
 using namespace srh;
 
@@ -2697,6 +2698,149 @@ int srh_mesh_sample_bwd(const SrhMeshSampleParams* params, const float* v, const
   hipLaunchKernelGGL(k_mesh_bwd_vertices, mesh_grid(P.V, P), dim3(kMeshBlock), 0, s, P, f, corner_order, corner,
                      grad_v);
   return launch_status("mesh sampling backward launch");
+}
+
+}  // extern "C"
+
+// ---- SH9 environment lighting (srh_sh9.h) ------------------------------------------------------------------------
+namespace {
+
+static_assert(kSh9MaxC == SRH_SH9_MAX_CHANNELS, "srh.h and srh_sh9.h");
+constexpr int32_t kSh9MaxPoints = 1 << 24;
+
+// argument checks (no HIP call) and the device view of an SH9 launch: `probe` checks the envmap's frame, else the
+// normals' count.  Every index in srh_sh9.h is a size_t built from a pixel or normal < 2^24, a view < 65536, a channel
+// < 4 and a column < 16.
+int sh9_setup(const SrhSh9Params* p, bool probe, Sh9Dev* P) {
+  if (!p) return fail(SRH_E_NULL, "params is NULL");
+  if (int rc = check_n_views(p->n_views)) return rc;
+  if (p->channels < 1 || p->channels > kSh9MaxC)
+    return fail(SRH_E_RANGE, "channels = %d, expected 1..%d", p->channels, kSh9MaxC);
+  if (probe) {
+    if (int rc = check_grid_size(p->width, p->height, "width x height =")) return rc;
+  } else if (p->n_points < 1 || p->n_points > kSh9MaxPoints) {
+    return fail(SRH_E_RANGE, "n_points = %d, expected 1..2^24", p->n_points);
+  }
+  memset(P, 0, sizeof(*P));
+  P->B = p->n_views; P->C = p->channels; P->m_per_view = p->m_per_view != 0;
+  if (probe) { P->H = p->height; P->W = p->width; }
+  else P->N = p->n_points;
+  return SRH_OK;
+}
+
+// f(std::integral_constant<int, C>) for C = `channels` (validated by sh9_setup)
+template <class Fn>
+void with_sh9_channels(int channels, Fn f) {
+  switch (channels) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+unsigned sh9_groups(int n) { return (unsigned)((n + kSh9Block - 1) / kSh9Block); }
+
+// the partials of a reducing launch, and behind them (irradiance only) the finished monomial sums (B, C, 10)
+size_t sh9_part_bytes(const Sh9Dev& P, int n, int K) {
+  return align_up((size_t)P.C * P.B * sh9_groups(n) * K * sizeof(double));
+}
+size_t sh9_mono_bytes(const Sh9Dev& P) { return align_up((size_t)P.B * P.C * kSh9Monomials * sizeof(double)); }
+
+}  // namespace
+
+extern "C" {
+
+size_t srh_sh9_workspace_bytes(const SrhSh9Params* params, int32_t which) {
+  Sh9Dev P;
+  switch (which) {
+    case SRH_SH9_WS_PROJECT:
+      if (sh9_setup(params, true, &P)) return 0;
+      return sh9_part_bytes(P, P.H * P.W, kSh9Coeffs);
+    case SRH_SH9_WS_IRRADIANCE_BWD:
+      if (sh9_setup(params, false, &P)) return 0;
+      return sh9_part_bytes(P, P.N, kSh9Monomials) + sh9_mono_bytes(P);
+    default:
+      fail(SRH_E_RANGE, "which = %d, expected SRH_SH9_WS_PROJECT or SRH_SH9_WS_IRRADIANCE_BWD", which);
+      return 0;
+  }
+}
+
+int srh_sh9_project_fwd(const SrhSh9Params* params, const float* envmap, void* workspace, size_t workspace_bytes,
+                        float* L, void* stream) {
+  Sh9Dev P;
+  int rc = sh9_setup(params, true, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"envmap", envmap}, {"L", L}}))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes, srh_sh9_workspace_bytes(params, SRH_SH9_WS_PROJECT))))
+    return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned groups = sh9_groups(P.H * P.W);
+  double* part = (double*)workspace;
+  with_sh9_channels(P.C, [&](auto c) {
+    hipLaunchKernelGGL(k_sh9_project<decltype(c)::value>, dim3(groups, P.B), dim3(kSh9Block), 0, s, P, envmap, part);
+  });
+  hipLaunchKernelGGL(k_sh9_finish<float>, dim3(P.C, P.B), dim3(kViewRows * kViewSums), 0, s, (int)groups, kSh9Coeffs,
+                     (const double*)part, L);
+  return launch_status("SH9 projection forward launch");
+}
+
+int srh_sh9_project_bwd(const SrhSh9Params* params, const float* g_L, float* grad_envmap, void* stream) {
+  Sh9Dev P;
+  int rc = sh9_setup(params, true, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"g_L", g_L}, {"grad_envmap", grad_envmap}}))) return rc;
+  with_sh9_channels(P.C, [&](auto c) {
+    hipLaunchKernelGGL(k_sh9_project_bwd<decltype(c)::value>, dim3(sh9_groups(P.H * P.W), P.B), dim3(kSh9Block), 0,
+                       (hipStream_t)stream, P, g_L, grad_envmap);
+  });
+  return launch_status("k_sh9_project_bwd launch");
+}
+
+int srh_sh9_irradiance_fwd(const SrhSh9Params* params, const float* M, const float* normal, float* E, void* stream) {
+  Sh9Dev P;
+  int rc = sh9_setup(params, false, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"M", M}, {"normal", normal}, {"E", E}}))) return rc;
+  with_sh9_channels(P.C, [&](auto c) {
+    hipLaunchKernelGGL(k_sh9_irradiance_fwd<decltype(c)::value>, dim3(sh9_groups(P.N), P.B), dim3(kSh9Block), 0,
+                       (hipStream_t)stream, P, M, normal, E);
+  });
+  return launch_status("k_sh9_irradiance_fwd launch");
+}
+
+int srh_sh9_irradiance_bwd(const SrhSh9Params* params, const float* M, const float* normal, const float* g_E,
+                           float* grad_normal, double* grad_M, void* workspace, size_t workspace_bytes, void* stream) {
+  Sh9Dev P;
+  int rc = sh9_setup(params, false, &P);
+  if (rc) return rc;
+  if ((rc = check_not_null({{"M", M}, {"normal", normal}, {"g_E", g_E}}))) return rc;
+  if (!grad_normal && !grad_M) return fail(SRH_E_NULL, "grad_normal and grad_M are both NULL");
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(sh9_groups(P.N), P.B);
+  if (!grad_M) {                        // an M that needs no gradient costs no reduction and no workspace
+    with_sh9_channels(P.C, [&](auto c) {
+      hipLaunchKernelGGL((k_sh9_irradiance_bwd<decltype(c)::value, false>), grid, dim3(kSh9Block), 0, s, P, M, normal,
+                         g_E, grad_normal, (double*)nullptr);
+    });
+    return launch_status("k_sh9_irradiance_bwd launch");
+  }
+  if ((rc = check_grad_view("grad_M", grad_M))) return rc;
+  if ((rc = check_scratch("workspace", workspace, workspace_bytes,
+                          srh_sh9_workspace_bytes(params, SRH_SH9_WS_IRRADIANCE_BWD))))
+    return rc;
+  double* part = (double*)workspace;
+  double* mono = (double*)((char*)workspace + sh9_part_bytes(P, P.N, kSh9Monomials));
+  with_sh9_channels(P.C, [&](auto c) {
+    hipLaunchKernelGGL((k_sh9_irradiance_bwd<decltype(c)::value, true>), grid, dim3(kSh9Block), 0, s, P, M, normal, g_E,
+                       grad_normal, part);
+  });
+  hipLaunchKernelGGL(k_sh9_finish<double>, dim3(P.C, P.B), dim3(kViewRows * kViewSums), 0, s, (int)grid.x,
+                     kSh9Monomials, (const double*)part, mono);
+  const size_t entries = (size_t)(P.m_per_view ? P.B : 1) * 16 * P.C;
+  hipLaunchKernelGGL(k_sh9_spread_M, dim3((unsigned)((entries + kSh9SpreadBlock - 1) / kSh9SpreadBlock)),
+                     dim3(kSh9SpreadBlock), 0, s, P, (const double*)mono, grad_M);
+  return launch_status("SH9 irradiance backward launch");
 }
 
 }  // extern "C"
