@@ -75,13 +75,14 @@ class _NormalsFunction(torch.autograd.Function):
 def _rotation(name: str, camera: Mapping, B: int, camera_grad: bool = False) -> torch.Tensor:
     """The lookat basis R = [x y z] of every view as [B, 9] float64 on the host; eye / at / up per view ([B, 3] or
     [B, 4]) or shared ([3] or [4]).  With `camera_grad` attached to those of them that require grad (a shared one is
-    expanded over the views, so it gets the sum)."""
+    expanded over the views, so it gets the sum -- widened to float64 on the host BEFORE the expansion, so that the
+    views' gradients are added in float64 and the leaf's dtype rounds the sum once, not every view's term)."""
     shared = {k: _host(camera[k]) for k in VIEW_KEYS}
     shared = {k: (np.broadcast_to(v, (B, v.shape[0])) if v.ndim == 1 else v) for k, v in shared.items()}
     cam = camera_vectors(name, shared, B)
     if camera_grad:
-        per_view = {k: (camera[k][None].expand(B, -1) if isinstance(camera[k], torch.Tensor) and camera[k].dim() == 1
-                        else camera[k]) for k in VIEW_KEYS}
+        per_view = {k: (camera[k].to(device="cpu", dtype=torch.float64)[None].expand(B, -1)
+                        if isinstance(camera[k], torch.Tensor) and camera[k].dim() == 1 else camera[k]) for k in VIEW_KEYS}
         cam = differentiable_vectors(per_view, cam)
     return inverse_view_matrices(cam["eye"], cam["at"], cam["up"])[:, :, :3].reshape(B, 9).contiguous()
 

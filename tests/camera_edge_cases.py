@@ -55,6 +55,7 @@ import frames_cases as fc
 import frames_oracle as fo
 import normals_cases as nc
 import normals_edge_cases as ne
+import normals_oracle as no
 import projection_cases as pc
 import splat_camera_oracle as sco
 import splat_edge_scenes as se
@@ -264,6 +265,25 @@ def _layer_of(layer, name):
 @functools.lru_cache(maxsize=None)
 def expected(layer, name, variant=None):
     return _gradients(_layer_of(layer, name), case(layer, name, variant), variant)
+
+
+@functools.lru_cache(maxsize=None)
+def magnitudes(layer, name, variant=None):
+    """(values, gradients, camera gradients): the restatements' sums of |terms| per entry of expected()
+    (tests/entry_checks.py), for the layers that are held per entry -- lift, normals, transform, project and their
+    poisoned batches.  The plane fit's values and pos gradient have no such sum (None: entry_checks.check_plane_fit)."""
+    import entry_checks
+    c, layer = case(layer, name, variant), _layer_of(layer, name)
+    if layer == "lift":
+        return so.magnitudes({"depth": c["depth"]}, c["camera"], c["upstream"], "world")
+    if layer == "normals":
+        return None, None, no.camera_magnitudes({"pos": c["pos"]}, c["camera"], c["upstream"], c["shape"],
+                                                entry_checks.NORMALS_C64 / entry_checks.C)
+    if layer == "transform":
+        return fo.transform_magnitudes(variant, fc.transform_inputs(c), c["camera"], c["upstream"])
+    assert layer == "project", layer
+    key = "px_coord" if variant else "plane"
+    return fo.project_magnitudes(variant, c["surfels"], c["camera"], {key: c["upstream"][key]})
 
 
 def one_view(layer, c, b):

@@ -151,3 +151,17 @@ def project_expected(name, coords):
     c = project_case(name)
     key = "px_coord" if coords else "plane"
     return fo.project_gradients(coords, c["surfels"], c["camera"], {key: c["upstream"][key]})
+
+
+@functools.lru_cache(maxsize=None)
+def transform_magnitudes(name, direction):
+    """The oracle's sums of |terms| per entry of transform_expected (tests/entry_checks.py), computed once."""
+    c = transform_case(name)
+    return fo.transform_magnitudes(direction, transform_inputs(c), c["camera"], c["upstream"])
+
+
+@functools.lru_cache(maxsize=None)
+def project_magnitudes(name, coords):
+    c = project_case(name)
+    key = "px_coord" if coords else "plane"
+    return fo.project_magnitudes(coords, c["surfels"], c["camera"], {key: c["upstream"][key]})

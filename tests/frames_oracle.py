@@ -96,6 +96,103 @@ def transform_gradients(direction, inputs, camera: Mapping, upstream, camera_wrt
     return vals, grads, cams["camera"]
 
 
+def _np_tables(camera: Mapping):
+    """(world-to-camera, camera-to-world) [B, 3, 4] as fp64 arrays."""
+    return tuple(t.numpy() for t in _tables(camera, torch.zeros(1, dtype=torch.float64)))
+
+
+def _np_homogeneous(p):
+    p = np.asarray(p, np.float64)
+    return p if p.shape[-1] == 4 else np.concatenate((p, np.ones_like(p[..., :1])), -1)
+
+
+def _w2c_table(eye, at, up):
+    return po.lookat(eye, at, up)[:, :3]
+
+
+def _c2w_table(eye, at, up):
+    R, eye = cco.camera_to_world({"eye": eye, "at": at, "up": up}, eye.dtype)
+    return torch.cat((R, eye[..., None]), dim=-1)
+
+
+def transform_magnitudes(direction, inputs, camera: Mapping, upstream):
+    """The sums of the absolute values of the terms of every entry transform_gradients returns, in the same three dicts
+    (tests/entry_checks.py's A), numpy fp64.  Only the sums are restated, not the function:
+        out_pos[r]     sum_c |P[r][c]| |v_c|,  v = [p, w];  out_pos[3] = |w|
+        out_normal[j]  sum_i |n_i| |A[i][j]|
+        grad_pos[c]    sum_r |g_r| |P[r][c]|, column 3 of a four-column input one more term, |g_3|
+        grad_normal[i] sum_j |g_j| |A[i][j]|, column 3 of a four-column input 0
+        camera         entry_checks.camera_magnitudes of d loss / dP (sum over the points of |g_r| |v_c|) and
+                       d loss / dA (sum of |n_i| |g_j|, column 3 exactly 0)"""
+    w2c, c2w = _np_tables(camera)
+    P, A = (w2c, c2w) if direction == "to_cam" else (c2w, w2c)
+    fns = (_w2c_table, _c2w_table) if direction == "to_cam" else (_c2w_table, _w2c_table)
+    vals, grads, tables = {}, {}, []
+    if inputs.get("pos") is not None:
+        v = np.abs(_np_homogeneous(inputs["pos"]))
+        vals["pos"] = np.concatenate((np.einsum("brc,bnc->bnr", np.abs(P), v), v[..., 3:]), -1)
+        if "pos" in upstream:
+            g = np.abs(np.asarray(upstream["pos"], np.float64))
+            gp = np.einsum("bnr,brc->bnc", g[..., :3], np.abs(P))
+            gp[..., 3] += g[..., 3]
+            grads["pos"] = gp[..., :np.asarray(inputs["pos"]).shape[-1]]
+            tables.append((fns[0], np.einsum("bnr,bnc->brc", g[..., :3], v)))
+        else:
+            grads["pos"] = np.zeros(np.asarray(inputs["pos"]).shape)
+    if inputs.get("normal") is not None:
+        n = np.abs(np.asarray(inputs["normal"], np.float64))
+        vals["normal"] = np.einsum("bni,bij->bnj", n[..., :3], np.abs(A[..., :3]))
+        grads["normal"] = np.zeros(n.shape)
+        if "normal" in upstream:
+            h = np.abs(np.asarray(upstream["normal"], np.float64))
+            grads["normal"][..., :3] = np.einsum("bnj,bij->bni", h, np.abs(A[..., :3]))
+            A_dA = np.zeros(A.shape)
+            A_dA[..., :3] = np.einsum("bni,bnj->bij", n[..., :3], h)
+            tables.append((fns[1], A_dA))
+    import entry_checks
+    return vals, grads, entry_checks.camera_magnitudes(tables, camera)
+
+
+def project_magnitudes(coords: bool, surfels, camera: Mapping, upstream):
+    """As transform_magnitudes, for what project_gradients returns (px_idx has no magnitude).  (X, Y, Z) are sums of
+    four products with A_X, A_Y, A_Z = sum_c |M[r][c]| |v_c|, and Z is itself a cancelling sum: its own fp64 error is
+    2^-53 A_Z and not 2^-53 |Z|, and it reaches every quotient through 1 / Zd.  So every derived A carries the forward
+    A of X, Y and Z, by the product and quotient rules on (value, A) pairs:
+        plane_x        |f| (A_X / |Zd| + |X| A_Z / Zd^2), plane_y alike;  the third component A_Z
+        px_coord_x     A_plane_x |sx| + W / 2, px_coord_y alike
+        gx, gy, gz     |g_plane| + |g_coord| |s|
+        dX             |f| (|gx| / |Zd| + |gx| A_Z / Zd^2), dY alike
+        dZ             |gz| + |f| (|gx| A_X + |gy| A_Y) / Zd^2 + 2 |f| (|gx| |X| + |gy| |Y|) A_Z / |Zd|^3; |gz| at Z == 0
+        grad_surfels   sum_r A_d[r] |M[r][c]|;   d loss / dM[r][c] = sum over the points of A_d[r] |v_c|
+    These are upper bounds on the sums of |terms|, above them by the factor (1 + A_Z / |Zd|) at the most, which on the
+    seeded cases (|Z| >= 1.5, the scene within a few units of the eye) stays far below 2^8
+    (tests/test_entry_checks_cpu.py measures it)."""
+    M = _np_tables(camera)[0]
+    v = _np_homogeneous(surfels)
+    cc = np.einsum("brc,bnc->bnr", M, v)
+    A_cc = np.einsum("brc,bnc->bnr", np.abs(M), np.abs(v))
+    X, Y, Z = (np.abs(cc[..., k]) for k in range(3))
+    A_X, A_Y, A_Z = (A_cc[..., k] for k in range(3))
+    live = cc[..., 2] != 0
+    Zd = np.where(live, Z, 1.0)
+    f = abs(float(camera["focal_length"]))
+    (sx, sy), (hx, hy) = frame_scales(camera)
+    out = "px_coord" if coords else "plane"
+    plane = [f * (A_X / Zd + X * A_Z / Zd ** 2), f * (A_Y / Zd + Y * A_Z / Zd ** 2), A_Z]
+    if coords:
+        plane = [plane[0] * abs(sx) + abs(hx), plane[1] * abs(sy) + abs(hy), A_Z]
+    vals = {out: np.stack(plane, -1)}
+    g = np.abs(np.asarray(upstream[out], np.float64))
+    gx, gy, gz = (g[..., 0] * abs(sx), g[..., 1] * abs(sy), g[..., 2]) if coords else (g[..., 0], g[..., 1], g[..., 2])
+    d = np.stack((f * (gx / Zd + gx * A_Z / Zd ** 2), f * (gy / Zd + gy * A_Z / Zd ** 2),
+                  gz + np.where(live, f * (gx * A_X + gy * A_Y) / Zd ** 2
+                                + 2 * f * (gx * X + gy * Y) * A_Z / Zd ** 3, 0.0)), -1)
+    cols = np.asarray(surfels).shape[-1]
+    grads = {"surfels": np.einsum("bnr,brc->bnc", d, np.abs(M))[..., :cols]}
+    import entry_checks
+    return vals, grads, entry_checks.camera_magnitudes([(_w2c_table, np.einsum("bnr,bnc->brc", d, np.abs(v)))], camera)
+
+
 def project_gradients(coords: bool, surfels, camera: Mapping, upstream, camera_wrt=CAMERA_KEYS):
     """project_surfels ({'plane'}) or with `coords` project_image_coordinates ({'px_coord', 'px_idx'})."""
     def fn(x, c):

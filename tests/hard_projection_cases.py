@@ -71,3 +71,10 @@ def expected(name):
     """(values {'out', 'mask', 'count', 'index'}, gradients {'rgb'}) from the fp64 oracle, computed once."""
     c = case(name)
     return ho.gradients({"surfels": c["surfels"], "rgb": c["rgb"]}, c["camera"], c["upstream"])
+
+
+@functools.lru_cache(maxsize=None)
+def magnitudes(name):
+    """({'out'}, {'rgb'}): the oracle's sums of |terms| per entry (tests/entry_checks.py), computed once."""
+    c = case(name)
+    return ho.magnitudes({"surfels": c["surfels"], "rgb": c["rgb"]}, c["camera"], c["upstream"])

@@ -55,6 +55,25 @@ def kink_margin(surfels, camera: Mapping) -> float:
     return min(float((uv - torch.round(uv)).abs().min()) / 1e-4, float(px[..., 2].abs().min()) / 1e-3)
 
 
+def magnitudes(inputs, camera: Mapping, upstream):
+    """The sums of the absolute values of the terms of every entry `gradients` returns (tests/entry_checks.py's A), numpy
+    fp64: ({'out': (sum of |v| over the pixel's surfels) / count, 0 for an empty pixel}, {'rgb': |g_out| of the surfel's
+    pixel / count -- one term --, 0 for a dropped surfel}).  The index is the oracle's own."""
+    surfels = torch.as_tensor(np.asarray(inputs["surfels"], dtype=np.float64))
+    rgb = np.abs(np.asarray(inputs["rgb"], np.float64))
+    B, N = surfels.shape[:2]
+    idx = pixel_index(surfels, camera)[0].numpy()
+    x, g = rgb.reshape(B, N, -1), np.abs(np.asarray(upstream["out"], np.float64)).reshape(B, N, -1)
+    total, count = np.zeros((B, N + 1, x.shape[-1])), np.zeros((B, N + 1))
+    for b in range(B):
+        np.add.at(total[b], idx[b], x[b])
+        np.add.at(count[b], idx[b], 1.0)
+    count[:, N] = 1.0
+    safe = np.where(count > 0, count, 1.0)
+    g_rgb = np.concatenate((g, np.zeros((B, 1, g.shape[-1]))), 1)[np.arange(B)[:, None], idx] / safe[np.arange(B)[:, None], idx, None]
+    return {"out": (total / safe[..., None])[:, :N].reshape(rgb.shape)}, {"rgb": g_rgb.reshape(rgb.shape)}
+
+
 def gradients(inputs, camera: Mapping, upstream, wrt=("rgb",)):
     """({'out', 'mask', 'count', 'index'}, {'rgb': like the input}) in fp64 for loss = sum(out * upstream['out'])."""
     return po.autograd(lambda x: project(x["surfels"], x["rgb"], camera), inputs, INPUTS, upstream, wrt)

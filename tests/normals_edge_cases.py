@@ -78,3 +78,10 @@ def expected(name):
     """(values {'normal': like pos}, gradients {'pos': like pos}) from the fp64 oracle, computed once."""
     c = case(name)
     return no.gradients({"pos": c["pos"]}, c["camera"], c["upstream"], c["frame"])
+
+
+@functools.lru_cache(maxsize=None)
+def turned(name):
+    """expected() from the map turned by 180 degrees (normals_oracle.turned_gradients), computed once."""
+    c = case(name)
+    return no.turned_gradients({"pos": c["pos"]}, c["camera"], c["upstream"], c["frame"], c["shape"])

@@ -77,3 +77,39 @@ def plane_fit(pos, camera: Optional[Mapping] = None, frame="camera"):
 def gradients(inputs, camera: Optional[Mapping], upstream, frame="camera", wrt=INPUTS):
     """({'normal': like pos}, {'pos': like pos}) in fp64 for loss = sum(normal * upstream['normal'])."""
     return po.autograd(lambda x: {"normal": plane_fit(x["pos"], camera, frame)}, inputs, INPUTS, upstream, wrt)
+
+
+def turned_gradients(inputs, camera: Optional[Mapping], upstream, frame="camera", shape=None):
+    """`gradients` evaluated on the map turned by 180 degrees and turned back: the turn maps the reflected stencil onto
+    itself, so this is the same function with every sum over the neighbours run in the reverse order.  `shape` (B, H, W)
+    is needed for points given as [B, N, 3].  Where the two evaluations differ, the difference is the restatement's own
+    fp64 rounding, amplified by the cancelling determinant (tests/entry_checks.ill_conditioned)."""
+    pos = np.asarray(inputs["pos"])
+    B, H, W = shape if shape is not None else pos.shape[:3]
+
+    def turn(a):
+        return np.ascontiguousarray(np.asarray(a).reshape(B, H, W, 3)[:, ::-1, ::-1])
+
+    cam = None if camera is None else dict(camera, viewport=[0, 0, W, H])
+    v, g = gradients({"pos": turn(pos)}, cam, {k: turn(u) for k, u in upstream.items()}, frame)
+    return {k: turn(a).reshape(pos.shape) for k, a in v.items()}, {k: turn(a).reshape(pos.shape) for k, a in g.items()}
+
+
+def camera_magnitudes(inputs, camera: Mapping, upstream, shape, carried: float):
+    """{eye, at, up: A} of the world frame's camera gradients (tests/entry_checks.py).  out = R n, so d loss / dR[r][c] is
+    the fp64 sum over the pixels of g_r n_c with n the camera-frame normal, and entry_checks.camera_magnitudes chains
+    A_R[r][c] = sum |g_r| (|n_c| + carried) to eye / at / up through lookat_inv's Jacobian.  `carried` is what the
+    forward's own floor is in units of the standing 2^-40: n is known to NORMALS_C64 max|n| = NORMALS_C64 and not to
+    2^-53 of its terms, and every derived A carries that.  A camera shared by the views ([3] vectors) gets the sum."""
+    import entry_checks
+    B, H, W = shape
+    pos = torch.as_tensor(np.asarray(inputs["pos"], np.float64)).reshape(B, H, W, 3)
+    n = plane_fit(pos).abs().numpy().reshape(B, H * W, 3)
+    g = np.abs(np.asarray(upstream["normal"], np.float64)).reshape(B, H * W, 3)
+    A_M = np.zeros((B, 3, 4))
+    A_M[..., :3] = np.einsum("bqr,bqc->brc", g, n + carried)
+    shared = np.asarray(camera["eye"]).ndim == 1
+    cam = {k: (np.tile(np.asarray(camera[k], np.float64)[:3], (B, 1)) if shared else np.asarray(camera[k], np.float64))
+           for k in ("eye", "at", "up")}
+    A = entry_checks.camera_magnitudes([(so._c2w_table, A_M)], cam)
+    return {k: (a.sum(0) if shared else a) for k, a in A.items()}

@@ -69,3 +69,11 @@ def expected(name, variant=None, grid="numpy"):
     """(values {'pos': [B, N, 3]}, gradients {'depth': like the input}) from the fp64 oracle, computed once."""
     c = case(name, variant)
     return so.gradients({"depth": c["depth"]}, c["camera"], c["upstream"], c["frame"], grid)
+
+
+@functools.lru_cache(maxsize=None)
+def magnitudes(name, variant=None, grid="numpy"):
+    """({'pos'}, {'depth'}, {eye, at, up}): the oracle's sums of |terms| per entry (tests/entry_checks.py), computed
+    once."""
+    c = case(name, variant)
+    return so.magnitudes({"depth": c["depth"]}, c["camera"], c["upstream"], c["frame"], grid)

@@ -74,6 +74,46 @@ def lift(depth, camera: Mapping, frame="world", grid="numpy"):
     return pos @ R.to(dev).transpose(-1, -2) + eye.to(dev)[:, None]
 
 
+def _c2w_table(eye, at, up):
+    z = po._normalize(eye - at)
+    x = po._normalize(torch.cross(po._normalize(up), z, dim=-1))
+    y = torch.cross(z, x, dim=-1)
+    return torch.cat((torch.stack((x, y, z), dim=-1), eye[..., None]), dim=-1)
+
+
+def magnitudes(inputs, camera: Mapping, upstream, frame="world", grid="numpy"):
+    """The sums of the absolute values of the terms of every entry `gradients` returns, and of the camera gradients of
+    camera_chain_oracle.lift_gradients (tests/entry_checks.py's A), numpy fp64: ({'pos'}, {'depth'}, {eye, at, up}).
+        P_cc           a product and a quotient, no sum: |P_cc|
+        P_wc[r]        sum_c |R[r][c]| |P_cc[c]| + |eye_r|
+        g_depth        the three-term dot product sum_c A_G[c] |dir_c| with dir = (x_j / f, y_i / f, -1) and, in the
+                       world frame, G = R^T g itself a sum, A_G[c] = sum_r |R[r][c]| |g_r|; 0 where depth <= 0
+        camera         entry_checks.camera_magnitudes of d loss / d[R | eye]: columns 0-2 sum over the pixels of
+                       |g_r| |P_cc[c]|, column 3 sum of |g_r|; zeros in the camera frame, which reads no camera"""
+    W, H = po.frame(camera)
+    depth = np.asarray(inputs["depth"], np.float64)
+    B = depth.shape[0]
+    f = float(camera["focal_length"])
+    gx, gy = pixel_grid(camera, grid)
+    dirs = np.abs(np.stack((np.tile(gx, H) / f, np.repeat(gy, W) / f, -np.ones(H * W)), -1))          # [N, 3]
+    d = np.maximum(depth.reshape(B, H * W), 0.0)
+    with np.errstate(invalid="ignore"):                      # an infinite depth on the optical axis: inf * 0
+        P_cc = d[..., None] * dirs
+    g = np.abs(np.asarray(upstream["pos"], np.float64)).reshape(B, H * W, 3)
+    cam = {k: np.zeros(np.asarray(camera[k]).shape) for k in ("eye", "at", "up")}
+    if frame == "camera":
+        A_pos, A_G = P_cc, g
+    else:
+        R, eye = (t.numpy() for t in camera_to_world(camera))
+        A_pos = np.einsum("brc,bnc->bnr", np.abs(R), P_cc) + np.abs(eye)[:, None]
+        A_G = np.einsum("brc,bnr->bnc", np.abs(R), g)
+        A_M = np.concatenate((np.einsum("bnr,bnc->brc", g, P_cc), g.sum(1)[..., None]), -1)
+        import entry_checks
+        cam = entry_checks.camera_magnitudes([(_c2w_table, A_M)], camera)
+    A_depth = np.where(depth.reshape(B, H * W) <= 0, 0.0, np.einsum("bnc,nc->bn", A_G, dirs))       # a NaN depth is not <= 0
+    return {"pos": A_pos}, {"depth": A_depth.reshape(depth.shape)}, cam
+
+
 def gradients(inputs, camera: Mapping, upstream, frame="world", grid="numpy", wrt=INPUTS):
     """({'pos': [B, N, 3]}, {'depth': like the input}) in fp64 for loss = sum(pos * upstream['pos'])."""
     return po.autograd(lambda x: {"pos": lift(x["depth"], camera, frame, grid)}, inputs, INPUTS, upstream, wrt)

@@ -3,8 +3,11 @@ in float32 (tests/golden/frames/fr1_*.npz, tools/gen_frames_golden.py):
 
     restatement against ref64      values and every gradient, the camera's included, to 1e-12 of each array's largest
                                    magnitude: the same function in the same precision
-    restatement against ref32      the layers' stated tolerance (projection_checks.RTOL / ATOL_SCALE): the reference's
-                                   own float32 result must meet what the kernels are held to
+    restatement against ref32      the array-scale tolerance (projection_checks.RTOL / ATOL_SCALE): the condition that the
+                                   seeded cases are well-posed for the reference's own float32 arithmetic.  It is NOT what
+                                   the kernels are held to: they meet one float32 rounding per entry (tests/entry_checks.py),
+                                   which this float32 record breaks on 45 % of its entries
+                                   (tests/test_entry_checks_cpu.py)
     px_idx                         equal to both runs on EVERY surfel: the seeded surfels keep 1e-3 px from every rounding
                                    boundary (frames_cases), which this also shows to hold for the committed inputs
 Also that a fixture holds its seeded case's inputs, that the unbatched functions give the batched ones' values, that a

@@ -6,7 +6,12 @@ non-finite, where exactly zero, and that no entry of a finite case is mere round
 The layers are run through the helpers of their camera suites (test_hip_camera_warp, test_hip_dense_camera,
 test_hip_splat_camera, test_hip_frames), so a case goes through the call those suites make.
 
-Tolerances: the standing ones of the camera suites, rtol 2e-6 with atol 2e-7 max|want| per array (projection_checks;
+Tolerances.  The rows of the layers that are held per entry -- lift, normals, transform, project and their poisoned
+batches -- hold every finite camera gradient entry to 2^-24 |ref| + 2^-40 A + 2^-149, A = |J|^T of the sums of magnitudes
+of the fp64 table gradients (tests/entry_checks.py, camera_edge_cases.magnitudes); the values and gradients of the cases no
+other suite holds, alike.  A non-finite camera gradient is a sum that overflowed or met a NaN, and which of the two it shows
+depends on the order of the sum, so those entries keep the rule below.  Beside that, and for the other layers, the standing
+tolerances of the camera suites: rtol 2e-6 with atol 2e-7 max|want| per array (projection_checks;
 test_hip_splat_camera's bound against the restatement is the same figures).  An array below 1e-9 of the camera's largest
 gradient, or an entry the CPU test lists as rounding noise, is held to that size.  Where the restatement is exactly 0
 the layer's entry is exactly 0; where it is non-finite the layer's entry is non-finite (NaN and inf are not told apart:
@@ -22,6 +27,7 @@ import pytest
 import torch
 
 import camera_edge_cases as ce
+import entry_checks as ec
 import frames_oracle as fo
 import test_hip_camera_warp as cw
 import test_hip_dense_camera as dcam
@@ -48,7 +54,7 @@ def _ids(items):
 
 
 def _bits(a):
-    return a.view(np.uint64) if a.dtype == np.float64 else a
+    return a.view({np.dtype(np.float64): np.uint64, np.dtype(np.float32): np.uint32}.get(a.dtype, a.dtype))
 
 
 def assert_same_bits(a, b, rows=slice(None), what=""):
@@ -85,6 +91,16 @@ def hold_camera(got, want, noise, tag):
               f"max err / |want| {np.max(err / np.maximum(np.abs(w[held]), 1e-300)) if err.size else 0.0:.3g}")
         np.testing.assert_allclose(g[held], w[held], rtol=RTOL, atol=ATOL_SCALE * scale, err_msg=f"{tag} {k}")
         assert np.all(np.abs(g[finite & by_size]) <= 1e-9 * top), (tag, k, "a noise entry is not small")
+
+
+PER_ENTRY = ("lift", "normals", "transform", "project")
+
+
+def check_camera_entries(layer, name, variant, got_cam, want_cam, tag, rows=slice(None)):
+    """`rows` of a finite camera gradient of a PER_ENTRY layer against the restatement, entry by entry; the worst ratio."""
+    A = ce.magnitudes(layer, name, variant)[2]
+    return ec.check_all({k: ec.narrowed(got_cam[k])[rows] for k in KEYS}, {k: want_cam[k][rows] for k in KEYS},
+                        {k: A[k][rows] for k in KEYS}, tag + " camera")
 
 
 def _splat(layer, c, camera_grad=True, others=True):
@@ -136,6 +152,8 @@ def test_camera_gradients_match_the_restatement(layer, name, variant):
     tag = ce.tag(layer, name, variant)
     finite = all(np.isfinite(w).all() for w in want_cam.values())
     assert finite == ((layer, name) not in ce.NONFINITE)
+    if layer in PER_ENTRY and finite:
+        check_camera_entries(layer, name, variant, got_cam, want_cam, tag)
     hold_camera(got_cam, want_cam, ce.noise(layer, name, variant) if finite else _no_noise(want_cam), tag)
     for k in ce.EXACT_ZERO.get((layer, name), ()):
         assert np.all(want_cam[k] == 0) and np.all(got_cam[k] == 0), (tag, k)
@@ -143,6 +161,10 @@ def test_camera_gradients_match_the_restatement(layer, name, variant):
         idx = {"px_idx"} & set(got)
         for k in idx:
             assert np.array_equal(got[k], want[k]), (tag, k)
+        A, A_g, _ = ce.magnitudes(layer, name, variant)
+        ec.check_all({k: ec.narrowed(v) for k, v in got.items() if k not in idx}, {k: v for k, v in want.items() if k not in idx},
+                     A, tag + " values")
+        ec.check_all({k: ec.narrowed(g) for k, g in got_g.items()}, want_g, A_g, tag + " gradients")
         compare_values({k: v for k, v in got.items() if k not in idx}, {k: v for k, v in want.items() if k not in idx}, tag)
         compare_grads(got_g, want_g, tag)
 
@@ -197,6 +219,8 @@ def test_a_non_finite_view_spoils_its_own_camera_and_leaves_its_neighbours_their
     for k in KEYS:
         assert got_cam[k].shape == (3, 3) and not np.isfinite(want_cam[k][ce.POISONED_VIEW]).any()
         assert np.isfinite(want_cam[k][[0, 2]]).all()
+    if sub in PER_ENTRY:
+        check_camera_entries(layer, name, variant, got_cam, want_cam, tag, rows=[0, 2])
     hold_camera(got_cam, want_cam, _no_noise(want_cam), tag)
     for b in (0, 2):
         alone = call(sub, ce.one_view(sub, c, b), variant)[2]
@@ -247,6 +271,8 @@ def test_the_half_with_one_lane_has_the_bits_it_has_with_the_other_input_absent(
     assert_same_bits({half: both[1][half]}, alone[1])
     assert_same_bits(both[2], alone[2])
     want_cam = fo.transform_gradients(direction, {half: c[half], other: None}, c["camera"], ups)[2]
+    ec.check_all(alone[2], want_cam, fo.transform_magnitudes(direction, {half: c[half], other: None}, c["camera"], ups)[2],
+                 f"{name} {direction} {half} alone camera")
     hold_camera(alone[2], want_cam, _no_noise(want_cam), f"{name} {direction} {half} alone")
 
 
@@ -263,12 +289,16 @@ def test_a_point_with_w_zero_gets_the_gradient_of_w_and_brings_nothing_to_the_tr
     M = (w2c if direction == "to_cam" else c2w).numpy()
     g = c["upstream"]["pos"].astype(np.float64)
     want = np.einsum("bnr,br->bn", g[..., :3], M[:, :, 3]) + g[..., 3]
+    ec.check(got_g["pos"][..., 3], want, np.einsum("bnr,br->bn", np.abs(g[..., :3]), np.abs(M[:, :, 3])) + np.abs(g[..., 3]),
+             f"w0_153 {direction} grad w")
     np.testing.assert_allclose(got_g["pos"][..., 3], want, rtol=RTOL, atol=ATOL_SCALE * np.abs(want).max())
     only = np.zeros_like(c["upstream"]["pos"])
     only[:, rows] = c["upstream"]["pos"][:, rows]
     one = dict(c, normal=None, upstream={"pos": only})
     got_cam = fr.transform(one, direction, camera_grad=True)[2]
     want_cam = fo.transform_gradients(direction, {"pos": one["pos"], "normal": None}, one["camera"], one["upstream"])[2]
+    ec.check_all(got_cam, want_cam, fo.transform_magnitudes(direction, {"pos": one["pos"], "normal": None}, one["camera"],
+                                                            one["upstream"])[2], f"w0_153 {direction} w0 rows alone camera")
     hold_camera(got_cam, want_cam, _no_noise(want_cam), f"w0_153 {direction} w0 rows alone")
 
 
@@ -284,6 +314,9 @@ def test_a_surfel_at_z_zero_brings_its_x_and_y_terms_and_no_division_by_z(coords
     got, got_g, got_cam = fr.project(one, coords, camera_grad=True)
     want, want_g, want_cam = fo.project_gradients(coords, one["surfels"], one["camera"], one["upstream"])
     assert all(np.abs(w).max() > 0 for w in (want_cam["eye"], want_cam["at"]))
+    A = fo.project_magnitudes(coords, one["surfels"], one["camera"], one["upstream"])
+    ec.check_all(got_cam, want_cam, A[2], f"zdepth_16x12 {key} named surfels alone camera")
+    ec.check_all(got_g, want_g, A[1], f"zdepth_16x12 {key} named surfels alone gradients")
     hold_camera(got_cam, want_cam, _no_noise(want_cam), f"zdepth_16x12 {key} named surfels alone")
     compare_grads(got_g, want_g, f"zdepth_16x12 {key} named surfels alone")
     assert_same_bits(fr.project(one, coords, camera_grad=False)[1], got_g)

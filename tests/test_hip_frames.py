@@ -3,17 +3,23 @@
 tests/test_frames_oracle_cpu.py ties that to the reference's own functions (tests/golden/frames/fr1_*.npz).
 
 Stated tolerances: the kernels compute the restatement's fp64 arithmetic from the same fp32 inputs and store fp32 once,
-so values match to rtol 2e-6 with atol 2e-7 max(|want|, 1) and gradients to rtol 2e-6 with atol 2e-7 max|want|
-(projection_checks; the reasoning is tests/test_hip_surfels.py's).  Camera gradients are compared the same way, an entry
-below 1e-9 of the camera's largest gradient being held to that size.  px_idx equals the oracle's on every surfel: the
-seeded surfels keep 1e-3 px from every rounding boundary (frames_cases)."""
+so every output element, every gradient entry and every camera gradient entry is held to its own bound
+|got - ref| <= 2^-24 |ref| + 2^-40 A + 2^-149, A the restatement's sum of the magnitudes of the entry's terms
+(tests/entry_checks.py, frames_oracle.transform_magnitudes / project_magnitudes; a camera entry's A is |J|^T of the table
+gradients' sums).  The same arithmetic in float32 does not meet that bound (tests/test_entry_checks_cpu.py).  The older
+array-scale comparison stays beside it: rtol 2e-6 with atol 2e-7 max(|want|, 1) for values and 2e-7 max|want| for
+gradients (projection_checks), camera gradients alike, an entry below 1e-9 of the camera's largest gradient being held
+to that size.  px_idx equals the oracle's on every surfel: the seeded surfels keep 1e-3 px from every rounding boundary
+(frames_cases)."""
 import numpy as np
 import pytest
 import torch
 
+import entry_checks as ec
 import frames_cases as cases
 import frames_oracle as fo
-from projection_checks import assert_bit_identical, compare_grads, compare_values, to_np
+from entry_checks import to_np
+from projection_checks import assert_bit_identical, compare_grads, compare_values
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,6 +36,17 @@ def compare_camera(got, want, tag):
     compare_grads({k: got[k] for k in live}, live, tag, nonzero=False)
     for k in set(want) - set(live):
         assert got[k].shape == want[k].shape and np.abs(got[k]).max() <= 1e-9 * top, (tag, k)
+
+
+def check_entries(got, want, A, tag):
+    """(values, gradients, camera gradients) from the GPU against the restatement's and its magnitudes, entry by entry
+    (entry_checks.check); an int64 px_idx has no magnitude and is compared where it is popped.  A None stands for a part
+    that is not compared.  Returns the worst ratio of an error to its bound."""
+    worst = 0.0
+    for what, g, w, a in zip(("values", "gradients", "camera"), got, want, A):
+        if g is not None:
+            worst = max(worst, ec.check_all(g, {k: v for k, v in w.items() if k in a}, a, f"{tag} {what}"))
+    return worst
 
 
 def _camera(camera, camera_grad):
@@ -100,6 +117,7 @@ def test_a_transform_matches_the_restatement(name, direction):
     values, grads, cam_grads = transform(c, direction, camera_grad=True)
     want, want_g, want_c = cases.transform_expected(name, direction)
     tag = f"{name} {direction}"
+    check_entries((values, grads, cam_grads), (want, want_g, want_c), cases.transform_magnitudes(name, direction), tag)
     compare_values(values, want, tag)
     compare_grads(grads, want_g, tag)
     compare_camera(cam_grads, want_c, tag)
@@ -125,6 +143,7 @@ def test_a_projection_matches_the_restatement(name, coords):
         W, H = c["frame"]
         assert np.array_equal(values.pop("px_idx"), want["px_idx"])            # every surfel
         assert want["px_idx"].size < 16 or ((want["px_idx"] == W * H).any() and (want["px_idx"] < W * H).any())
+    check_entries((values, grads, cam_grads), (want, want_g, want_c), cases.project_magnitudes(name, coords), tag)
     compare_values(values, {k: v for k, v in want.items() if k != "px_idx"}, tag)
     compare_grads(grads, want_g, tag)
     compare_camera(cam_grads, want_c, tag)
@@ -133,6 +152,8 @@ def test_a_projection_matches_the_restatement(name, coords):
 def test_nothing_requires_grad():
     c = cases.transform_case("t153_192")
     values, grads, _ = transform(c, "to_world", wrt=False)
+    ec.check_all(values, cases.transform_expected("t153_192", "to_world")[0],
+                 cases.transform_magnitudes("t153_192", "to_world")[0], "forward only")
     compare_values(values, cases.transform_expected("t153_192", "to_world")[0], "forward only")
     assert grads == {"pos": None, "normal": None}
 
@@ -145,6 +166,9 @@ def test_a_loss_on_one_output_leaves_the_other_input_a_zero_gradient():
         _, want_g, want_c = fo.transform_gradients("to_cam", cases.transform_inputs(c), c["camera"], one["upstream"])
         other = "normal" if keep == "pos" else "pos"
         assert np.all(grads[other] == 0) and np.all(want_g[other] == 0)
+        A = fo.transform_magnitudes("to_cam", cases.transform_inputs(c), c["camera"], one["upstream"])
+        assert np.all(A[1][other] == 0)
+        check_entries((None, grads, cam), (None, want_g, want_c), A, f"loss on {keep}")
         compare_grads({keep: grads[keep]}, {keep: want_g[keep]}, f"loss on {keep}")
         compare_camera(cam, want_c, f"loss on {keep}")
 
@@ -219,8 +243,8 @@ def test_px_idx_is_the_hard_projections_key(name):
 
 @pytest.mark.parametrize("direction", cases.DIRECTIONS)
 def test_a_camera_tensor_shared_by_the_views_gets_the_sum(direction):
-    """One [1, 3] leaf expanded to every view: its gradient is the sum of the per-view gradients (fp64 sum, the stated
-    tolerance)."""
+    """One [1, 3] leaf expanded to every view: its gradient is the sum of the per-view gradients (each view's an fp64
+    sum stored once as float32; the views added by torch in the leaf's float32)."""
     import surf_renderer_amd as sra
     fn = {"to_cam": sra.world_to_cam_batched, "to_world": sra.cam_to_world_batched}[direction]
     c = cases.transform_case("t153_192")
@@ -235,6 +259,12 @@ def test_a_camera_tensor_shared_by_the_views_gets_the_sum(direction):
     _, _, per_view = fo.transform_gradients(direction, cases.transform_inputs(same), same["camera"], same["upstream"])
     got = {k: to_np(t.grad) for k, t in leaves.items()}
     assert all(got[k].shape == (1, 3) for k in VIEW_KEYS)
+    # The expansion is the caller's own float32 op: torch hands every view's gradient to it as float32 -- one store per
+    # view and entry, the layer's contract -- and adds the B of them in float32.  So the leaf's entry is a float32 sum of
+    # float32 terms, 2^-24 sum_b |g_b| beside the sum's own rounding, and A carries that at 2^16 per unit of |g_b|.
+    A = fo.transform_magnitudes(direction, cases.transform_inputs(same), same["camera"], same["upstream"])[2]
+    ec.check_all(got, {k: v.sum(0, keepdims=True) for k, v in per_view.items()},
+                 {k: (A[k] + 2.0 ** 16 * np.abs(per_view[k])).sum(0, keepdims=True) for k in A}, f"shared camera {direction}")
     compare_camera(got, {k: v.sum(0, keepdims=True) for k, v in per_view.items()}, f"shared camera {direction}")
 
 
@@ -251,9 +281,16 @@ def test_other_dtypes_devices_and_layouts_are_converted_and_gradients_come_back_
     res = sra.cam_to_world_batched(pos, normal_t.permute(1, 0, 2), cam, camera_grad=True)        # not contiguous
     sum((res[k] * torch.tensor(g, device=DEV)).sum() for k, g in c["upstream"].items()).backward()
     torch.cuda.synchronize()
+    A = cases.transform_magnitudes("t153_192", "to_world")
+    ec.check_all({k: to_np(v) for k, v in res.items()}, want, A[0], "converted")
     compare_values({k: to_np(v) for k, v in res.items()}, want, "converted")
     for leaf in (pos, normal_t, cam["eye"], cam["at"]):
         assert leaf.grad.dtype == leaf.dtype and leaf.grad.device == leaf.device and leaf.grad.shape == leaf.shape
+    got_g = {"pos": ec.narrowed(to_np(pos.grad)), "normal": to_np(normal_t.grad.permute(1, 0, 2))}
+    # a float64 leaf gets the float64 sum of the host's chain unrounded: its 2^-24 |ref| term is slack, the floor holds
+    got_c = {"eye": to_np(cam["eye"].grad).astype(np.float32), "at": to_np(cam["at"].grad)}
+    ec.check_all(got_g, want_g, A[1], "converted gradients")
+    ec.check_all(got_c, {k: want_c[k] for k in ("eye", "at")}, A[2], "converted camera")
     compare_grads({"pos": to_np(pos.grad), "normal": to_np(normal_t.grad.permute(1, 0, 2))}, want_g, "converted")
     compare_camera({k: to_np(cam[k].grad) for k in ("eye", "at")}, {k: want_c[k] for k in ("eye", "at")}, "converted")
 
@@ -290,7 +327,10 @@ def test_a_splat_render_goes_to_the_world_frame_and_a_loss_there_reaches_the_sce
               "up": np.tile(scene["camera"]["up"], (B, 1))}
     pos_cc, normal_cc = res["pos"].reshape(B, H * W, 3), res["normal"].reshape(B, H * W, 3)
     world = sra.cam_to_world_batched(pos_cc, normal_cc, camera)
-    want = fo.cam_to_world_batched(torch.tensor(to_np(pos_cc)), torch.tensor(to_np(normal_cc)), camera)
+    inputs = {"pos": to_np(pos_cc).astype(np.float64), "normal": to_np(normal_cc).astype(np.float64)}
+    want = fo.cam_to_world_batched(torch.tensor(inputs["pos"]), torch.tensor(inputs["normal"]), camera)
+    ec.check_all({k: to_np(v) for k, v in world.items()}, {k: v.numpy() for k, v in want.items()},
+                 fo.transform_magnitudes("to_world", inputs, camera, {})[0], "splat to world")
     compare_values({k: to_np(v) for k, v in world.items()}, {k: v.numpy() for k, v in want.items()}, "splat to world")
     up = torch.tensor(np.random.RandomState(5).uniform(-1, 1, (B, H * W, 4)).astype(np.float32), device=DEV)
     (world["pos"] * up).sum().backward()

@@ -2,13 +2,15 @@
 hard_projection_oracle.py; tests/test_hard_projection_edge_cases_cpu.py shows that each case reaches the branch it is
 named for and pins the restatement to the reference's own record on the two tie cases.
 
-Tolerances are those of tests/test_hip_hard_projection.py (projection_checks: rtol 2e-6, atol 2e-7 max(|want|, 1) for
-values and 2e-7 max|want| for the gradient); mask, counts and the zeros of dropped surfels are decisions and compared
+Tolerances are those of tests/test_hip_hard_projection.py (every entry within 2^-24 |ref| + 2^-40 A + 2^-149 of the
+restatement, tests/entry_checks.py; beside it projection_checks: rtol 2e-6, atol 2e-7 max(|want|, 1) for values and 2e-7
+max|want| for the gradient); mask, counts and the zeros of dropped surfels are decisions and compared
 exactly.  No element is left out: the only non-finite numbers are inputs the results must not depend on (nonfinite_4x6),
 so every `want` is finite."""
 import numpy as np
 import pytest
 
+import entry_checks as ec
 import hard_projection_edge_cases as edges
 import hard_projection_oracle as ho
 from projection_checks import assert_bit_identical, compare_grads, one_view
@@ -22,7 +24,9 @@ def _check(name):
     c = edges.case(name)
     got, got_g = _hip(c)
     want, want_g = edges.expected(name)
-    _compare_values(got, want, name)
+    A, A_g = ho.magnitudes({"surfels": c["surfels"], "rgb": c["rgb"]}, c["camera"], c["upstream"])
+    _compare_values(got, want, name, A)
+    ec.check_all(got_g, want_g, A_g, name + " gradients")
     assert np.array_equal(_counts(c), want["count"]), name
     compare_grads({"rgb": got_g["rgb"]}, want_g, name, nonzero=bool(np.abs(want_g["rgb"]).max() > 0))
     assert got_g["surfels"] is None

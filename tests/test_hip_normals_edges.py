@@ -2,17 +2,22 @@
 normals_oracle.py; tests/test_normals_edge_cases_cpu.py shows that each case reaches the branch it is named for.  Then the
 chain depth -> depth_to_surfels -> normals -> a weighted sum, against the two restatements chained under autograd.
 
-Stated tolerances, those of tests/test_hip_normals.py: normals rtol 2e-6 with atol 2e-7 max(|want|, 1), pos.grad rtol 2e-6
-with atol 2e-7 max|want|, every element.  In the three cases with a special point an element is non-finite exactly where
-the restatement's is, and every other element is held to the same tolerance (max|want| over the finite elements)."""
+Stated tolerances, those of tests/test_hip_normals.py: every element within 2^-24 |ref| + NORMALS_C64 max|ref| + 2^-149
+of the restatement (entry_checks.check_plane_fit), and beside it normals rtol 2e-6 with atol 2e-7 max(|want|, 1), pos.grad
+rtol 2e-6 with atol 2e-7 max|want|.  In the three cases with a special point an element is non-finite exactly where the
+restatement's is -- a NaN where it is a NaN, the same infinity where it is one -- and every other element is held to the
+same bounds (max|want| over the finite elements).  The chain's depth gradient is a sum of the two layers' terms through a
+float32 hand-over and keeps the array-scale tolerance."""
 import numpy as np
 import pytest
 import torch
 
+import entry_checks as ec
 import normals_edge_cases as edges
 import normals_oracle as no
 import surfels_oracle as so
-from projection_checks import ATOL_SCALE, RTOL, assert_bit_identical, compare_grads, compare_values, one_view, to_np
+from entry_checks import to_np
+from projection_checks import ATOL_SCALE, RTOL, assert_bit_identical, compare_grads, compare_values, one_view
 from test_hip_normals import DEV, _hip
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +30,9 @@ def test_values_and_gradients_match_the_restatement_and_a_batch_equals_its_views
     c = edges.case(name)
     whole = _hip(c)
     want, want_g = edges.expected(name)
+    again, again_g = edges.turned(name)
+    ec.check_plane_fit(whole[0]["normal"], want["normal"], again["normal"], name + " normal")
+    ec.check_plane_fit(whole[1]["pos"], want_g["pos"], again_g["pos"], name + " grad pos")
     compare_values(whole[0], want, name)
     compare_grads(whole[1], want_g, name, nonzero=c["nonzero"])
     if c["shape"][0] > 1 and np.asarray(c["camera"]["eye"]).ndim == 2:
@@ -52,6 +60,9 @@ def test_a_special_point_spoils_its_reach_and_nothing_else(name):
     c = edges.case(name)
     got, got_g = _hip(c)
     want, want_g = edges.expected(name)
+    again, again_g = edges.turned(name)
+    ec.check_plane_fit(got["normal"], want["normal"], again["normal"], name + " normal")
+    ec.check_plane_fit(got_g["pos"], want_g["pos"], again_g["pos"], name + " grad pos")
     for tag, g, w, floor in (("normal", got["normal"], want["normal"], 1.0), ("grad pos", got_g["pos"], want_g["pos"], 0.0)):
         finite = np.isfinite(w)
         assert np.array_equal(np.isfinite(g), finite), (name, tag, np.argwhere(np.isfinite(g) != finite))
@@ -130,6 +141,11 @@ def test_a_loss_on_normals_and_positions_reaches_the_depth_map(frame):
     want, want_g = _chain_expected(c, frame)
     tag = f"depth -> surfels -> normals ({frame})"
     assert np.all(np.isfinite(to_np(normal))) and np.all(np.isfinite(to_np(depth.grad)))
+    A_pos = so.magnitudes({"depth": c["depth"]}, c["camera"], {"pos": c["w_pos"]}, "camera")[0]["pos"]
+    exact = so.lift(torch.tensor(c["depth"].astype(np.float64)), c["camera"], frame="camera").numpy()    # before the hand-over's rounding
+    ec.check_all({"pos": to_np(pos)}, {"pos": exact}, {"pos": A_pos}, tag + " pos")
+    again = no.turned_gradients({"pos": want["pos"]}, c["camera"], {"normal": c["w_normal"]}, frame, c["shape"])[0]
+    ec.check_plane_fit(to_np(normal), want["normal"], again["normal"], tag + " normal")
     compare_values({"pos": to_np(pos), "normal": to_np(normal)}, want, tag)
     assert depth.grad.shape == depth.shape
     compare_grads({"depth": to_np(depth.grad)}, want_g, tag)

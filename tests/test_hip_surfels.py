@@ -2,16 +2,20 @@
 same fp32 inputs and the same (numpy) pixel grid; tests/test_surfels_oracle_cpu.py ties that to the reference's own
 function (tests/golden/surfels/sf1_*.npz) and bounds the difference between the two grids.
 
-Stated tolerances: the kernels compute the restatement's fp64 arithmetic and store fp32 once, so values match to rtol
-2e-6 with atol 2e-7 max(|want|, 1) and the gradient to rtol 2e-6 with atol 2e-7 max|want| (projection_checks, the bounds
-of the re-projection layers for the same arithmetic regime).  Where depth <= 0 the point is the eye and the gradient
-exactly 0."""
+Stated tolerances: the kernels compute the restatement's fp64 arithmetic and store fp32 once, so every coordinate and
+every gradient entry is held to its own bound |got - ref| <= 2^-24 |ref| + 2^-40 A + 2^-149, A the restatement's sum of
+the magnitudes of the entry's terms (tests/entry_checks.py, surfels_oracle.magnitudes).  The same arithmetic in float32
+does not meet that bound (tests/test_entry_checks_cpu.py).  The older array-scale comparison stays beside it: rtol 2e-6
+with atol 2e-7 max(|want|, 1) for values and 2e-7 max|want| for the gradient (projection_checks).  Where depth <= 0 the
+point is the eye and the gradient exactly 0."""
 import numpy as np
 import pytest
 import torch
 
+import entry_checks as ec
 import surfels_cases as cases
-from projection_checks import assert_bit_identical, compare_grads, compare_values, to_np
+from entry_checks import to_np
+from projection_checks import assert_bit_identical, compare_grads, compare_values
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,6 +39,9 @@ def test_values_and_gradients_match_the_restatement(name, variant):
     c = cases.case(name, variant)
     got, got_g = _hip(c)
     want, want_g = cases.expected(name, variant)
+    A, A_g, _ = cases.magnitudes(name, variant)
+    ec.check_all(got, want, A, cases.tag(name, variant) + " values")
+    ec.check_all(got_g, want_g, A_g, cases.tag(name, variant) + " gradients")
     compare_values(got, want, cases.tag(name, variant))
     compare_grads(got_g, want_g, cases.tag(name, variant))
     dead = c["depth"] <= 0
@@ -47,6 +54,7 @@ def test_values_and_gradients_match_the_restatement(name, variant):
 
 def test_no_input_requires_grad():
     got, got_g = _hip(cases.case("17x9"), wrt=False)
+    ec.check_all(got, cases.expected("17x9")[0], cases.magnitudes("17x9")[0], "17x9 forward only")
     compare_values(got, cases.expected("17x9")[0], "17x9 forward only")
     assert got_g["depth"] is None
 
@@ -111,6 +119,9 @@ def test_float64_and_cpu_inputs_are_converted_and_the_gradient_comes_back_in_the
         assert pos.device.type == "cuda" and pos.dtype == torch.float32
         assert leaf.grad.dtype == leaf.dtype and leaf.grad.device == leaf.device and leaf.grad.shape == leaf.shape
         grad = leaf.grad.permute(0, 2, 1, 3) if leaf.dtype == torch.float32 else leaf.grad
+        A, A_g, _ = cases.magnitudes("12x16")
+        ec.check_all({"pos": to_np(pos)}, want, A, "12x16 converted values")
+        ec.check_all({"depth": ec.narrowed(to_np(grad))}, want_g, A_g, "12x16 converted gradients")
         compare_values({"pos": to_np(pos)}, want, "12x16 converted")
         compare_grads({"depth": to_np(grad)}, want_g, "12x16 converted")
 

@@ -1,8 +1,10 @@
 """GPU: depth_to_surfels on the edge inputs of tests/surfels_edge_cases.py against the fp64 restatement tests/
 surfels_oracle.py; tests/test_surfels_edge_cases_cpu.py shows that each case reaches the branch it is named for.
 
-Stated tolerances, those of tests/test_hip_surfels.py: values rtol 2e-6 with atol 2e-7 max(|want|, 1), the gradient rtol
-2e-6 with atol 2e-7 max|want|.  In the special cases one array holds 1e30 next to 2.0, so there the value bound is taken
+Stated tolerances, those of tests/test_hip_surfels.py: every coordinate and every gradient entry within its own bound
+2^-24 |ref| + 2^-40 A + 2^-149 (tests/entry_checks.py, surfels_oracle.magnitudes), a non-finite entry of the restatement
+met by the same NaN or the same infinity; beside it the older array-scale comparison, values rtol 2e-6 with atol 2e-7
+max(|want|, 1), the gradient rtol 2e-6 with atol 2e-7 max|want|.  In the special cases one array holds 1e30 next to 2.0, so there the value bound is taken
 PER PIXEL (atol 2e-7 max(max|want of that pixel|, 1)): never wider than the stated one.  The only elements compared
 otherwise are the outputs of the two pixels surfels_edge_cases.NONFINITE names (depth +inf on the centre pixel, NaN),
 which must be non-finite exactly where the restatement's are; their gradients are finite and held to the tolerance."""
@@ -10,7 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+import entry_checks as ec
 import surfels_edge_cases as edges
+import surfels_oracle as so
 from projection_checks import ATOL_SCALE, RTOL, assert_bit_identical, compare_grads, compare_values
 from test_hip_surfels import _hip
 
@@ -20,6 +24,12 @@ pytestmark = pytest.mark.gpu
 def _view(c, b):
     return dict(c, depth=c["depth"][b:b + 1], shape=(1, *c["shape"][1:]), upstream={"pos": c["upstream"]["pos"][b:b + 1]},
                 camera=dict(c["camera"], **{k: c["camera"][k][b:b + 1] for k in ("eye", "at", "up")}))
+
+
+def _check_entries(c, got, got_g, want, want_g, tag):
+    A, A_g, _ = so.magnitudes({"depth": c["depth"]}, c["camera"], c["upstream"], c["frame"])
+    ec.check_all(got, want, A, tag + " values")
+    ec.check_all(got_g, want_g, A_g, tag + " gradients")
 
 
 def _compare_special(got, want, tag):
@@ -42,6 +52,7 @@ def test_special_depths(name):
     c = edges.case(name)
     got, got_g = _hip(c)
     want, want_g = edges.expected(name)
+    _check_entries(c, got, got_g, want, want_g, name)
     _compare_special(got["pos"][0], want["pos"][0], name)
     compare_grads(got_g, want_g, name)                                  # every gradient is finite, NaN and +inf included
     rest = np.asarray(c["camera"]["eye"], np.float64)[0] if c["frame"] == "world" else np.zeros(3)
@@ -59,6 +70,7 @@ def test_values_and_gradients_match_the_restatement_and_a_batch_equals_its_views
     B, H, W = c["shape"]
     whole = _hip(c)
     want, want_g = edges.expected(name)
+    _check_entries(c, whole[0], whole[1], want, want_g, name)
     compare_values(whole[0], want, name)
     compare_grads(whole[1], want_g, name)
     dead = c["depth"] <= 0
